@@ -22,9 +22,14 @@ E-step arithmetic: the library's default, the GUARDED mode (contract of the path
 bit-exactly: include/demux_hip.h DMX_ESTEP_GUARDED); `exact_mode` = the same timed region with every logit / posterior
 / addition bit-identical to the reference.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel of the timed
-iterations, HIP-event timed on the stream it runs on, live rocprofv3 counters) and `cpu_baseline` (the numpy oracle,
-one core, on a bounded barcode sub-sample; N = 1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration of that
+region, nothing else.  `--full` adds everything beyond the headline: the same call made once more with the phase timers
+(`kernel_ms`), `roofline` (dominant kernel of the timed iterations, HIP-event timed on the stream it runs on, live
+rocprofv3 counters), `cpu_baseline` (the numpy oracle, one core, on a bounded barcode sub-sample; N = 1 only), the other
+modes, regions, hard workloads, end-to-end calls and parity checks, the `weak` region of N > 1, the sidecar file.
+
+    python bench.py --steps K --warmup W --dump-outputs DIR   # + what the timed call returns after its last step, as .npy
 """
 import argparse
 import json
@@ -545,14 +550,16 @@ def clock_warmup(ctx, spin, ms=CLOCK_WARMUP_MS):
     return n
 
 
-def timed_region(ctx, plane, steps, warmup, spin=None, idle_s=0.0, snapshot=False):
+def timed_region(ctx, plane, steps, warmup, spin=None, idle_s=0.0, snapshot=False, phase_timers=True, after_timed=None):
     """(`spin`: clock_warmup ahead of the warm-up iterations - NOT used by the headline region, which is the contract's W warm-up
     iterations and nothing else; `idle_s`: the device left idle that long ahead of them instead; `snapshot`: the end state of the
-    region - best option and its posterior of every barcode, all singlet posteriors - fetched behind both windows for parity_timed.)
+    region - best option and its posterior of every barcode, all singlet posteriors - fetched behind both windows for parity_timed;
+    `after_timed`: called right behind the timed window, before anything else runs on the device.)
     W untimed iterations, then exactly K timed ones bracketed by barrier + device synchronisation on both sides;
     the MAX over ranks of the wall time.  The timed call runs as a default call does, without the phase timers (an event record
-    is a barrier packet of its own: 6 us at each of the iteration's four phase boundaries); kernel_ms comes from the SAME call made
-    once more behind the timed window with the timers on, and its wall time is reported beside (ms_per_step_with_phase_timers)."""
+    is a barrier packet of its own: 6 us at each of the iteration's four phase boundaries); with `phase_timers`, kernel_ms comes
+    from the SAME call made once more behind the timed window with the timers on, and its wall time is reported beside
+    (ms_per_step_with_phase_timers); without, those three figures are None."""
     def barrier():
         if plane is not None:
             plane.barrier()
@@ -575,32 +582,38 @@ def timed_region(ctx, plane, steps, warmup, spin=None, idle_s=0.0, snapshot=Fals
     elapsed = time.perf_counter() - t0
     if plane is not None:
         elapsed = plane.max_float64(elapsed)
+    if after_timed is not None:
+        after_timed()
     stats = (ctx.guard_stats(), ctx.guard_levels(), ctx.mstep_incremental())
-    ctx.set_phase_timers(True)
-    ctx.reset_timings()
-    barrier()
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    ctx.run_iterations(steps, 0.01)
-    ctx.synchronize()
-    barrier()
-    elapsed_timers = time.perf_counter() - t0
-    if plane is not None:
-        elapsed_timers = plane.max_float64(elapsed_timers)
-    timers = ctx.timings()
-    ctx.set_phase_timers(False)
+    timers, elapsed_timers = None, None
+    if phase_timers:
+        ctx.set_phase_timers(True)
+        ctx.reset_timings()
+        barrier()
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        ctx.run_iterations(steps, 0.01)
+        ctx.synchronize()
+        barrier()
+        elapsed_timers = time.perf_counter() - t0
+        if plane is not None:
+            elapsed_timers = plane.max_float64(elapsed_timers)
+        timers = ctx.timings()
+        ctx.set_phase_timers(False)
     end_state = None
     if snapshot:
-        end_state = dict(best=ctx.get_assignments()[0], probs=ctx.get_block('probs', 0, ctx.B, 0, min(ctx.K, 128)), iterations=warmup + 2 * steps)
+        end_state = dict(best=ctx.get_assignments()[0], probs=ctx.get_block('probs', 0, ctx.B, 0, min(ctx.K, 128)),
+                         iterations=warmup + (2 if phase_timers else 1) * steps)
     (_redone, redone_total, rows), levels, (m_full, m_delta, m_changed) = stats
-    return {'elapsed': elapsed, 'end_state': end_state, 'ms_per_step_with_phase_timers': 1e3 * elapsed_timers / steps, 'clock_warmup_esteps': n_spin,
+    return {'elapsed': elapsed, 'end_state': end_state, 'clock_warmup_esteps': n_spin,
+            'ms_per_step_with_phase_timers': 1e3 * elapsed_timers / steps if phase_timers else None,
             'mstep_passes': ({'incremental_mstep': True, 'full': m_full, 'delta': m_delta, 'of': steps, 'barcodes_changed_in_the_last_mstep': m_changed}
                              if m_full + m_delta > 0 else {'incremental_mstep': False, 'note': 'every M-step recomputes every sum'}), 'ms_per_step': 1e3 * elapsed / steps, 'em_iterations_per_s': steps / elapsed,
             'estep_passes': {'coarse': levels['coarse_steps'], 'of': steps, 'last': {0: 'coarse', 1: 'fine', 2: 'direct'}.get(levels['level'], 'not guarded'),
                              'device_timed_ms': {'coarse_pass': levels['coarse_pass_ms'], 'fine_pass': levels['fine_pass_ms'], 'exact_kernel': abs(levels['exact_pass_ms'])},
                              'last_estep_flagged': {'fine_guard': levels['flagged_fine'], 'coarse_guard': levels['flagged_coarse']}},
-            'kernel_ms': {k: (v['ms'] / max(1, v['launches'])) for k, v in timers.items()},
-            'exchange_ms_per_step': timers['allreduce']['ms'] / max(1, steps),
+            'kernel_ms': {k: (v['ms'] / max(1, v['launches'])) for k, v in timers.items()} if phase_timers else None,
+            'exchange_ms_per_step': timers['allreduce']['ms'] / max(1, steps) if phase_timers else None,
             'guard': {'barcodes_redone_exactly': redone_total, 'barcode_rows': rows, 'fraction': redone_total / max(1, rows)}}
 
 # ---------------------------------------------------------------------------------------------------------
@@ -639,8 +652,8 @@ def compact_line(full, details_path=None):
         'kernel_ms': full.get('kernel_ms'),
         'estep_passes': {k: v for k, v in (full.get('estep_passes') or {}).items() if k in ('coarse', 'of', 'last')},
         'guard_redone_fraction': (full.get('guard') or {}).get('fraction'),
-        'roofline': {k: roof.get(k) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'algorithmic_bytes_per_launch', 'estep_ms',
-                                              'kernel_ns_under_tracer', 'valu_busy', 'iteration_frac')},
+        'roofline': ({k: roof.get(k) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'algorithmic_bytes_per_launch', 'estep_ms',
+                                               'kernel_ns_under_tracer', 'valu_busy', 'iteration_frac')} if roof else None),
         'cpu_baseline': ({k: base.get(k) for k in ('value', 'unit', 'cores', 'host_cores', 'kind', 'sample', 'speedup_vs_gpu_value')} if base else None),
         'exact_mode_ms_per_step': (full.get('exact_mode') or {}).get('ms_per_step'),
         'after_idle_ms_per_step': (full.get('after_idle') or {}).get('ms_per_step'),
@@ -669,6 +682,45 @@ def compact_line(full, details_path=None):
     if missing or len(text) >= LINE_LIMIT:
         raise AssertionError(f'bench line unusable: {len(text)} bytes (limit {LINE_LIMIT}), missing keys {missing}')
     return text
+
+
+DUMP_BUDGET = {'posteriors': 40 << 20, 'genotype_addition': 20 << 20}   # bytes per array, its row indices included: 60 MB in all
+DUMP_BLOCK = 64   # rows: a sampled array is a fixed, seeded choice of blocks of this many consecutive rows
+
+
+def _dump_blocks(n_rows, row_bytes, budget, seed):
+    """None when all rows fit `budget`; else the sorted first rows of the sampled blocks (each sampled row also costs its float64 index)."""
+    if n_rows * row_bytes <= budget:
+        return None
+    n_blocks = -(-n_rows // DUMP_BLOCK)
+    take = max(1, min(n_blocks, budget // (DUMP_BLOCK * (row_bytes + 8))))
+    return np.sort(np.random.default_rng(seed).choice(n_blocks, size=take, replace=False)) * DUMP_BLOCK
+
+
+def dump_outputs(ctx, directory, write):
+    """--dump-outputs: what the timed call leaves its caller after its last step - the posteriors [B, K] of the last E-step
+    (learn_genotypes' DataFrame; this rank's barcodes) and the last M-step's beta addition [V, G] (the learnt table is the prior
+    betas + it) - as DIR/<name>.npy, float32.  An array over its share of DUMP_BUDGET is a fixed, seeded sample of row blocks, and
+    DIR/<name>_rows.npy (float64) holds the indices of the rows kept.  The addition is fetched on every rank (a collective when the
+    M-step is sharded); only the rank with `write` writes."""
+    addition = ctx.get_addition()
+    B, K = ctx.B, ctx.K
+    starts = _dump_blocks(B, 4 * K, DUMP_BUDGET['posteriors'], seed=1)
+    if starts is None:
+        arrays = {'posteriors': (ctx.get_block('probs', 0, B), None)}
+    else:
+        blocks = [ctx.get_block('probs', int(s), int(min(B, s + DUMP_BLOCK))) for s in starts]
+        arrays = {'posteriors': (np.concatenate(blocks), np.concatenate([np.arange(s, min(B, s + DUMP_BLOCK)) for s in starts]))}
+    starts = _dump_blocks(len(addition), 4 * addition.shape[1], DUMP_BUDGET['genotype_addition'], seed=2)
+    rows = None if starts is None else np.concatenate([np.arange(s, min(len(addition), s + DUMP_BLOCK)) for s in starts])
+    arrays['genotype_addition'] = (addition if rows is None else addition[rows], rows)
+    if not write:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, (values, rows) in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(values, dtype=np.float32))
+        if rows is not None:
+            np.save(os.path.join(directory, name + '_rows.npy'), rows.astype(np.float64))
 
 
 def write_details(full, workload, world):
@@ -712,10 +764,18 @@ def main():
     ap.add_argument('--deadline', type=float, default=1500.0,
                     help='N > 1 without a launcher: seconds after which the parent kills the rank processes it started, reports every '
                          'rank\'s last phase and exits non-zero (a rank hung in a collective must not cost the caller its own limit)')
-    ap.add_argument('--timed-only', action='store_true', help='the timed region of the default mode only (profiler child runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the phase-timed re-run of the timed call (kernel_ms, roofline), the exact mode and the other '
+                         'regions, the hard workloads, predict and end-to-end timings, the CPU baseline and parity checks, the live counters, the '
+                         '`weak` region of N > 1 and the sidecar file.  A plain run times the headline region and prints its line, nothing else')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed call returned in its last step (posteriors, beta addition) as DIR/<name>.npy, '
+                         'float32, at most 64 MB (a fixed, seeded sample of rows beyond that): bench.dump_outputs')
+    ap.add_argument('--timed-only', action='store_true',
+                    help='the timed region of the default mode and its phase-timed re-run only (profiler child runs; with or without --full)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-exact-mode', action='store_true', help='skip the second timed region (bit-exact E-step and additions)')
-    ap.add_argument('--fast-mode', action='store_true', help='a third timed region: the tolerance-mode E-step without the guard')
+    ap.add_argument('--fast-mode', action='store_true', help='with --full, a third timed region: the tolerance-mode E-step without the guard')
     ap.add_argument('--no-fast-mode', action='store_true', help=argparse.SUPPRESS)  # older command lines (the region is opt-in now)
     ap.add_argument('--no-live-traffic', action='store_true', help='no rocprofv3 --pmc child runs (roofline.traffic / valu stay empty)')
     ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end timing of the drop-in calls (containers in, DataFrames out)')
@@ -730,7 +790,12 @@ def main():
                     help='the per-iteration exchange staged through host memory over the control plane instead of RCCL '
                          '(dmx_comm_init_host): several ranks on ONE GPU, hosts without a usable RCCL fabric')
     args = ap.parse_args()
-    if args.timed_only:
+    if args.fast_mode and not args.full:
+        ap.error('--fast-mode is a region of --full')
+    # plain run: the headline region alone; --timed-only: that region and its phase-timed re-run; --full: every region and figure
+    phase_timed = args.full or args.timed_only
+    extras = args.full and not args.timed_only
+    if not extras:
         args.no_cpu_baseline = args.no_exact_mode = args.no_live_traffic = args.no_e2e = args.no_hard_workload = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -852,7 +917,7 @@ def main():
 
     # ---- the timed regions: configs[3] as written first (strong: this rank's barcode range), then the workload per GPU ----
     kinds = ['strong', 'weak'] if args.scaling == 'both' else [args.scaling]
-    if world == 1:
+    if world == 1 or not extras:
         kinds = kinds[:1]
     regions, t_up = {}, 0.0
     logits0 = probs0 = best0 = None
@@ -861,7 +926,7 @@ def main():
         problem = shard_of(whole, rank, world) if (kind == 'strong' and world > 1) else whole
         phase(f'{kind}: installing the problem (set-up collectives)')
         t_up += install(problem)
-        keep_first = world == 1 and not args.timed_only
+        keep_first = world == 1 and extras
         ctx.estep(pen, with_doublets=dp > 0, fetch_logits=False, fetch_probs=False)  # fixes the options
         if keep_first:  # the first rows of the first pass (never the whole [B, K] matrices: 2 x 33 GB at 1M x 8256)
             n_keep = int(min(problem.n_barcodes, max(64, (256 << 20) // (4 * K))))
@@ -870,7 +935,11 @@ def main():
         if args.mstep == 'auto':
             ctx.set_msteps_expected(args.warmup + args.steps)
         phase(f'{kind}: warm-up + timed region (per-iteration collectives)')
-        region = timed_region(ctx, plane, args.steps, args.warmup, snapshot=world == 1 and not args.timed_only)
+        dump = None
+        if args.dump_outputs and kind == kinds[0]:
+            def dump():
+                dump_outputs(ctx, args.dump_outputs, write=rank == 0)
+        region = timed_region(ctx, plane, args.steps, args.warmup, snapshot=world == 1 and extras, phase_timers=phase_timed, after_timed=dump)
         built, build_ms = ctx.mstep_tiles_info()
         region['mstep_records_build_ms'] = build_ms if built else 0.0
         region['device_bytes'] = ctx.device_bytes()
@@ -919,7 +988,7 @@ def main():
     took_tiles = ctx_mstep_form == 'tiles'
     if plane is not None:  # every rank or none (the region has barriers)
         took_tiles = plane.all_ok(took_tiles, 'work-item M-step on this rank')[0]
-    if args.mstep != 'items' and not args.timed_only and took_tiles:
+    if args.mstep != 'items' and extras and took_tiles:
         ctx.set_mstep_tiles('never')
         ctx.set_addition(None)
         ctx.probs_from_betas(0.01, fetch=False)
@@ -930,7 +999,7 @@ def main():
         ctx.set_mstep_tiles('always' if args.mstep == 'tiles' else 'auto')
 
     incr_mstep_region = None
-    if world == 1 and not args.timed_only and not args.incremental_mstep and ctx_mstep_form == 'tiles' and default_mode != 'exact':  # (one rank: the region has barriers)
+    if world == 1 and extras and not args.incremental_mstep and ctx_mstep_form == 'tiles' and default_mode != 'exact':  # (one rank: the region has barriers)
         phase('default mode with the incremental M-step (the library default): timed region')
         ctx.set_mstep_incremental(True)
         ctx.set_addition(None)
@@ -942,7 +1011,7 @@ def main():
         ctx.set_mstep_incremental(False)
 
     fine_only_region = None
-    if world == 1 and not args.timed_only and default_mode == 'guarded' and regions[kinds[-1]]['estep_passes']['coarse'] > 0:  # (one rank: the region has barriers)
+    if world == 1 and extras and default_mode == 'guarded' and regions[kinds[-1]]['estep_passes']['coarse'] > 0:  # (one rank: the region has barriers)
         phase('default mode without the coarse pass: timed region')
         ctx.set_coarse_pass(False)
         ctx.set_addition(None)
@@ -954,7 +1023,7 @@ def main():
         ctx.set_coarse_pass(True)
 
     logits_kept_region = None
-    if world == 1 and not args.timed_only and default_mode == 'guarded':
+    if world == 1 and extras and default_mode == 'guarded':
         phase('default mode, logits of the last E-step kept: timed region')
         ctx.set_logits_needed(True)
         ctx.set_addition(None)
@@ -965,7 +1034,7 @@ def main():
         ctx.set_logits_needed(False)
 
     clocks_warm_region = None
-    if world == 1 and not args.timed_only:
+    if world == 1 and extras:
         phase('default mode behind a clock warm-up: timed region')
         ctx.set_addition(None)
         ctx.probs_from_betas(0.01, fetch=False)
@@ -977,7 +1046,7 @@ def main():
     # prior: the dictionary-form first E-step, the stream / record builds, the first guard decisions - none of which the steady-state
     # `value` contains.  One dmx_em call exactly as demuxalot_amd/demux.py makes it, three times, the median.
     cold_region = None
-    if world == 1 and not args.timed_only:
+    if world == 1 and extras:
         phase('cold start: 5-iteration calls from the prior')
         _apply_environment()   # the library's own defaults: incremental M-step, form chosen for a 5-iteration call
         ctx.set_logits_needed(False)
@@ -996,7 +1065,7 @@ def main():
         ctx.apply_environment()
 
     after_idle_region = None
-    if world == 1 and not args.timed_only:
+    if world == 1 and extras:
         phase('default mode on a device that has idled: timed region')
         ctx.set_addition(None)
         ctx.probs_from_betas(0.01, fetch=False)
@@ -1011,7 +1080,7 @@ def main():
     # case the dictionary form of the exact E-step exists for (csrc/estep_dict.hip); timed with the form on (default)
     # and off, same bits either way.
     predict = {}
-    if not args.timed_only:
+    if extras:
         n_pred = max(3, args.steps // 2)
         for mode in ('auto', 'never'):
             ctx.set_estep_dictionary(mode)
@@ -1042,7 +1111,7 @@ def main():
     # dmx_set_lean_memory (default off): the fine pass's copy of the E-step records and the dictionary form's row array released - the
     # footprint and the same timed region on what is left.  The last region on this problem: the release is for good.
     lean_region = None
-    if world == 1 and not args.timed_only and default_mode == 'guarded' and dp == 0:
+    if world == 1 and extras and default_mode == 'guarded' and dp == 0:
         phase('lean memory: timed region')
         ctx.set_addition(None)
         ctx.probs_from_betas(0.01, fetch=False)
@@ -1067,7 +1136,7 @@ def main():
 
     if rank == 0:
         ab = algorithmic_bytes(B, V, G, K, N)
-        e_ms = regions[kinds[-1]]['kernel_ms']['estep']
+        e_ms = (regions[kinds[-1]]['kernel_ms'] or {}).get('estep')   # (None in a plain run: no phase-timed re-run, no roofline)
         mode_notes = {'guarded': ': contract of the path proven per barcode and E-step, the rest redone bit-exactly (include/demux_hip.h '
                                  'DMX_ESTEP_GUARDED); E-steps whose logits nobody can read - all but the last of a call: estep_passes - may take the '
                                  'coarse pass (genotype table as binary16, dmx_set_coarse_pass), the timed region is ONE dmx_run_iterations call of '
@@ -1174,7 +1243,8 @@ def main():
                     import shutil
                     shutil.rmtree(cache, ignore_errors=True)
         passes = regions[kinds[-1]].get('estep_passes', {})
-        out['roofline'] = roofline(ab, e_ms, N, G, K, live, coarse_share=passes.get('coarse', 0) / max(1, passes.get('of', 1)), passes=passes, ms_per_step=head['ms_per_step'])
+        out['roofline'] = (roofline(ab, e_ms, N, G, K, live, coarse_share=passes.get('coarse', 0) / max(1, passes.get('of', 1)), passes=passes, ms_per_step=head['ms_per_step'])
+                           if phase_timed else None)
         if world == 1 and not args.no_e2e and not args.flat_genotypes and N > 200_000_000:
             out['e2e'] = {'skipped': 'the object form of an experiment of this size (1.3 M dictionary entries, 1 M barcode strings, 4e8 container records) is '
                                      'minutes of Python before any call is made'}
@@ -1197,7 +1267,7 @@ def main():
             out['cpu_baseline'] = None
         if isinstance(out.get('e2e'), dict) and 'split_s' in out['e2e']:
             out['default_call_5it_ms_per_iteration'] = 1e3 * out['e2e']['split_s']['em_5_iterations_fused'] / 5
-        details = write_details(out, args.workload, world)
+        details = write_details(out, args.workload, world) if phase_timed else None
         print(json.dumps(out), file=sys.stderr)   # (the whole result for a reader of the log; stdout carries the compact line only)
         sys.stdout.flush()
         sys.stderr.flush()

@@ -6,8 +6,8 @@ OUT=gpurun_out/profiles_r3
 mkdir -p $OUT
 for wl in em_200k_100k_64 em_200k_100k_32 predict_20k_20k_8 em_130k_650k_128_doublets; do
   steps=10; [ $wl = em_130k_650k_128_doublets ] && steps=3
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r3_$wl -- python3 bench.py --steps $steps --warmup 2 --no-cpu-baseline --no-e2e --no-live-traffic --workload $wl > $OUT/r3_bench_line_$wl.json 2> $OUT/bench_$wl.err
-  python3 - gpurun_out/prof_r3_$wl $OUT/r3_kernel_stats_$wl.csv <<'PY'
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_r3_$wl -- python3 bench.py --full --steps $steps --warmup 2 --no-cpu-baseline --no-e2e --no-live-traffic --workload $wl > $OUT/r3_bench_line_$wl.json 2> $OUT/bench_$wl.err
+  python3 - $OUT/prof_r3_$wl $OUT/r3_kernel_stats_$wl.csv <<'PY'
 import csv, glob, sys
 rows = []
 for f in glob.glob(sys.argv[1] + '/*/*kernel_stats.csv'):

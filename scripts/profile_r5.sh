@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/r5_prof
 mkdir -p $OUT
 for WL in "$@"; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$WL -- python3 $R/bench.py --workload $WL --steps ${STEPS:-10} --warmup ${WARMUP:-2} --no-cpu-baseline --no-e2e --no-live-traffic --no-hard-workload > $OUT/bench_line_$WL.json 2> $OUT/bench_$WL.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$WL -- python3 $R/bench.py --full --workload $WL --steps ${STEPS:-10} --warmup ${WARMUP:-2} --no-cpu-baseline --no-e2e --no-live-traffic --no-hard-workload > $OUT/bench_line_$WL.json 2> $OUT/bench_$WL.err
   f=$(find $OUT/$WL -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && python3 - "$f" > $OUT/kernel_stats_$WL.csv <<'PY'
 import csv, sys

@@ -10,7 +10,7 @@ cd $R
 WL=${1:-em_200k_100k_64}
 OUT=gpurun_out/r6_prof
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$WL -- python3 bench.py --workload $WL --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-live-traffic --no-hard-workload > $OUT/bench_line_${WL}_under_tracer.json 2> $OUT/bench_$WL.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$WL -- python3 bench.py --full --workload $WL --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-live-traffic --no-hard-workload > $OUT/bench_line_${WL}_under_tracer.json 2> $OUT/bench_$WL.err
 f=$(find $OUT/stats_$WL -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && python3 - "$f" > $OUT/kernel_stats_$WL.csv <<'PY'
 import csv, sys

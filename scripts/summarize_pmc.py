@@ -10,6 +10,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else 'r1'
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.makedirs(os.path.join(root, 'gpurun_out', 'profiles_out'), exist_ok=True)
 out_dir = os.path.join(root, 'gpurun_out', 'profiles_out')
+runs = sys.argv[2] if len(sys.argv) > 2 else os.path.dirname(out_dir)   # where the profiler runs wrote (second argument)
 
 
 def short(name):
@@ -18,13 +19,13 @@ def short(name):
 
 
 lines = []
-stats = glob.glob(os.path.join(root, 'gpurun_out', f'prof_{tag}_trace', '*', '*kernel_stats.csv')) or \
-    glob.glob(os.path.join(root, 'gpurun_out', f'prof_{tag}_em_200k_100k_64', '*', '*kernel_stats.csv'))
+stats = glob.glob(os.path.join(runs, f'prof_{tag}_trace', '*', '*kernel_stats.csv')) or \
+    glob.glob(os.path.join(runs, f'prof_{tag}_em_200k_100k_64', '*', '*kernel_stats.csv'))
 if stats:
-    lines.append('== rocprofv3 --kernel-trace --stats (python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline) ==')
+    lines.append('== rocprofv3 --kernel-trace --stats (python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline) ==')
     lines.append(open(stats[0]).read())
 counters = collections.defaultdict(dict)
-for d in sorted(glob.glob(os.path.join(root, 'gpurun_out', f'pmc_{tag}_*/'))):
+for d in sorted(glob.glob(os.path.join(runs, f'pmc_{tag}_*/'))):
     f = glob.glob(d + '/*/*counter_collection.csv')
     if not f:
         continue

@@ -346,7 +346,7 @@ def _bench_rank(rank, world, port, out, scaling, exchange=None, broken_rccl=Fals
         env['DEMUXALOT_AMD_EXCHANGE'] = exchange
     if broken_rccl:
         env['DEMUXALOT_AMD_RCCL'] = '/nonexistent/librccl.so'
-    done = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '2', '--warmup', '1',
+    done = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '2', '--warmup', '1', '--full',
                            '--workload', 'em_20k_10k_64', '--scaling', scaling, '--no-cpu-baseline', '--no-fast-mode',
                            '--no-live-traffic', '--no-e2e'] + ([] if broken_rccl else ['--host-plane']),
                           env=env, cwd=root, capture_output=True, text=True, timeout=900)
@@ -404,7 +404,7 @@ def test_bench_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items()
            if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'TORCHELASTIC_RUN_ID', 'DEMUXALOT_AMD_ESTEP')}
-    done = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+    done = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
                            '--workload', 'em_20k_10k_64', '--host-plane'], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [ln for ln in done.stdout.splitlines() if ln.strip()]
