@@ -64,36 +64,35 @@ static int finish_problem(dmx_ctx *c, const int32_t *v2snp, const std::vector<in
     const long long B = c->B, V = c->V, S = c->S;
     const int G = c->G;
     const size_t vg = (size_t)V * G;
-    DMX_TRY(dev_alloc(c, &c->d_v2snp, (size_t)V));
-    DMX_TRY(dev_alloc(c, &c->d_snp_ptr, (size_t)S + 1));
-    DMX_TRY(dev_alloc(c, &c->d_snp_vars, (size_t)V));
-    DMX_TRY(dev_alloc(c, &c->d_prior, vg));
-    DMX_TRY(dev_alloc(c, &c->d_add, vg));
-    DMX_TRY(dev_alloc(c, &c->d_add64, vg));
-    DMX_TRY(dev_alloc(c, &c->d_partial, (size_t)c->n_items * G));
-    c->cap_redo = ((size_t)c->n_items / 2 + 1) * (size_t)G;  // a variant queues at most G sums and only with >= 2 items
-    DMX_TRY(dev_alloc(c, &c->d_redo, c->cap_redo));
-    DMX_TRY(dev_alloc(c, &c->d_n_redo, (size_t)2));  // long variants, the others
-    DMX_TRY(dev_alloc(c, &c->d_nz, (size_t)B * ((G + 63) / 64)));
-    DMX_TRY(dev_alloc(c, &c->d_first, (size_t)B));
-    DMX_TRY(dev_alloc(c, &c->d_dense_calls, (size_t)1 + dmx::DENSE_SLOTS));
-    DMX_TRY(dev_alloc(c, &c->d_guard_count, (size_t)dmx::GUARD_STATE_WORDS));
-    DMX_TRY(dev_alloc(c, &c->d_guard_list, (size_t)B));
+    DMX_TRY(dev_alloc(c, c->d_v2snp, (size_t)V));
+    DMX_TRY(dev_alloc(c, c->d_snp_ptr, (size_t)S + 1));
+    DMX_TRY(dev_alloc(c, c->d_snp_vars, (size_t)V));
+    DMX_TRY(dev_alloc(c, c->d_prior, vg));
+    DMX_TRY(dev_alloc(c, c->d_add, vg));
+    DMX_TRY(dev_alloc(c, c->d_add64, vg));
+    DMX_TRY(dev_alloc(c, c->d_partial, (size_t)c->n_items * G));
+    DMX_TRY(dev_alloc(c, c->d_redo, ((size_t)c->n_items / 2 + 1) * (size_t)G));  // a variant queues at most G sums and only with >= 2 items
+    DMX_TRY(dev_alloc(c, c->d_n_redo, (size_t)2));  // long variants, the others
+    DMX_TRY(dev_alloc(c, c->d_nz, (size_t)B * ((G + 63) / 64)));
+    DMX_TRY(dev_alloc(c, c->d_first, (size_t)B));
+    DMX_TRY(dev_alloc(c, c->d_dense_calls, (size_t)1 + dmx::DENSE_SLOTS));
+    DMX_TRY(dev_alloc(c, c->d_guard_count, (size_t)dmx::GUARD_STATE_WORDS));
+    DMX_TRY(dev_alloc(c, c->d_guard_list, (size_t)B));
     c->guard_sub_cap = (unsigned)((B + dmx::GUARD_QUEUES - 1) / dmx::GUARD_QUEUES);
-    DMX_TRY(dev_alloc(c, &c->d_guard_sub, (size_t)dmx::GUARD_QUEUES * c->guard_sub_cap));
-    HIP_TRY(hipMemsetAsync(c->d_guard_count, 0, dmx::GUARD_STATE_WORDS * sizeof(unsigned), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_dense_calls, 0, sizeof(unsigned long long) * (1 + dmx::DENSE_SLOTS), c->stream));
-    DMX_TRY(dev_alloc(c, &c->d_best, (size_t)B));
-    DMX_TRY(dev_alloc(c, &c->d_bestp, (size_t)B));
+    DMX_TRY(dev_alloc(c, c->d_guard_sub, (size_t)dmx::GUARD_QUEUES * c->guard_sub_cap));
+    HIP_TRY(hipMemsetAsync(c->d_guard_count.p, 0, dmx::GUARD_STATE_WORDS * sizeof(unsigned), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_dense_calls.p, 0, sizeof(unsigned long long) * (1 + dmx::DENSE_SLOTS), c->stream));
+    DMX_TRY(dev_alloc(c, c->d_best, (size_t)B));
+    DMX_TRY(dev_alloc(c, c->d_bestp, (size_t)B));
     hipStream_t st = c->stream;
     if (V) {
-        HIP_TRY(hipMemcpyAsync(c->d_v2snp, v2snp, sizeof(int) * V, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_snp_vars, snp_vars.data(), sizeof(int) * V, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_v2snp.p, v2snp, sizeof(int) * V, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_snp_vars.p, snp_vars.data(), sizeof(int) * V, hipMemcpyHostToDevice, st));
     }
-    HIP_TRY(hipMemcpyAsync(c->d_snp_ptr, snp_ptr.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->d_add, 0, sizeof(float) * (vg ? vg : 1), st));
-    if (B) HIP_TRY(hipMemsetAsync(c->d_nz, 0, sizeof(unsigned long long) * (size_t)B * ((G + 63) / 64), st));
-    if (B) HIP_TRY(hipMemsetAsync(c->d_first, 0, sizeof(uint2) * (size_t)B, st));
+    HIP_TRY(hipMemcpyAsync(c->d_snp_ptr.p, snp_ptr.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), st));
+    if (B) HIP_TRY(hipMemsetAsync(c->d_nz.p, 0, sizeof(unsigned long long) * (size_t)B * ((G + 63) / 64), st));
+    if (B) HIP_TRY(hipMemsetAsync(c->d_first.p, 0, sizeof(uint2) * (size_t)B, st));
     HIP_TRY(hipStreamSynchronize(st));  // host staging vectors die in the caller
     DMX_TRY(build_row_segments(c));
     DMX_TRY(layout_exchange(c));        // genotype_prob table (padded when a communicator is attached)
@@ -199,13 +198,13 @@ int dmx_pack_staged_and_set_problem(dmx_ctx *c, int64_t B, int64_t V, int32_t G,
 int dmx_get_packed_calls(dmx_ctx *c, int32_t *variant_id, int32_t *cb, float *p_wrong, int64_t *count)
 {
     DMX_TRY(bind(c));
-    DMX_TRY(need(c, c->have_problem && (c->d_u_variant || c->n_u == 0) && c->n_u == c->N,
+    DMX_TRY(need(c, c->have_problem && (c->d_u_variant.p || c->n_u == 0) && c->n_u == c->N,
                  "dmx_pack_and_set_problem before dmx_get_packed_calls"));
     const size_t n = (size_t)c->n_u;
-    if (variant_id && n) HIP_TRY(hipMemcpyAsync(variant_id, c->d_u_variant, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (cb && n) HIP_TRY(hipMemcpyAsync(cb, c->d_u_cb, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (p_wrong && n) HIP_TRY(hipMemcpyAsync(p_wrong, c->d_u_p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-    if (count && n) HIP_TRY(hipMemcpyAsync(count, c->d_u_count, sizeof(long long) * n, hipMemcpyDeviceToHost, c->stream));
+    if (variant_id && n) HIP_TRY(hipMemcpyAsync(variant_id, c->d_u_variant.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (cb && n) HIP_TRY(hipMemcpyAsync(cb, c->d_u_cb.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (p_wrong && n) HIP_TRY(hipMemcpyAsync(p_wrong, c->d_u_p.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    if (count && n) HIP_TRY(hipMemcpyAsync(count, c->d_u_count.p, sizeof(long long) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -228,8 +227,8 @@ int dmx_set_estep_mode(dmx_ctx *c, int mode)
 static int read_guard_state(dmx_ctx *c, unsigned (&st)[dmx::GS_WORDS], long long *count, long long *count_fine = nullptr, long long *count_coarse = nullptr)
 {
     std::vector<unsigned> all((size_t)dmx::GUARD_STATE_WORDS, 0u);
-    if (c->d_guard_count) {
-        HIP_TRY(hipMemcpyAsync(all.data(), c->d_guard_count, all.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_guard_count.p) {
+        HIP_TRY(hipMemcpyAsync(all.data(), c->d_guard_count.p, all.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     for (int i = 0; i < dmx::GS_WORDS; i++) st[i] = all[(size_t)i];
@@ -277,8 +276,8 @@ int dmx_get_mstep_incremental(dmx_ctx *c, int64_t *full_passes, int64_t *delta_p
 {
     DMX_TRY(bind(c));
     unsigned st[3 * dmx::IS_WORDS] = {};
-    if (c->d_incr_state) {
-        HIP_TRY(hipMemcpyAsync(st, c->d_incr_state, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_incr_state.p) {
+        HIP_TRY(hipMemcpyAsync(st, c->d_incr_state.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (full_passes) *full_passes = (int64_t)st[2 * dmx::IS_WORDS];
@@ -300,8 +299,8 @@ int dmx_set_lean_memory(dmx_ctx *c, int lean)
     DMX_TRY(bind(c));
     c->lean_memory = lean != 0;
     if (c->lean_memory && c->coarse_ready) {  // the resident problem's coarse records exist: what run_estep would have released behind their build
-        dev_free(c, &c->d_tile_stream, (size_t)c->n_pairs);
-        dev_free(c, &c->d_call_rows, ((size_t)c->n_pairs + dmx::CALL_PAD_PAIRS) * 2);
+        dev_free(c, c->d_tile_stream);
+        dev_free(c, c->d_call_rows);
     }
     return 0;
 }
@@ -372,7 +371,7 @@ int dmx_get_guard_probes(dmx_ctx *c, int64_t *probes, int64_t *streak)
 int dmx_debug_set_pass_ms(dmx_ctx *c, double coarse_pass_ms, double fine_pass_ms, double exact_pass_ms)
 {
     DMX_TRY(bind(c));
-    if (!c->d_guard_count) return fail(DMX_ERR_INVALID, "call order: a guarded E-step before dmx_debug_set_pass_ms");
+    if (!c->d_guard_count.p) return fail(DMX_ERR_INVALID, "call order: a guarded E-step before dmx_debug_set_pass_ms");
     int khz = 0;
     HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
     const double ms[3] = {coarse_pass_ms, fine_pass_ms, exact_pass_ms};
@@ -381,10 +380,10 @@ int dmx_debug_set_pass_ms(dmx_ctx *c, double coarse_pass_ms, double fine_pass_ms
     for (int i = 0; i < 3; i++) {
         if (ms[i] < 0.0) continue;
         const unsigned ticks = (unsigned)std::min(ms[i] * (double)khz, 1.0e9);
-        HIP_TRY(hipMemcpy(c->d_guard_count + word[i], &ticks, sizeof(unsigned), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_guard_count.p + word[i], &ticks, sizeof(unsigned), hipMemcpyHostToDevice));
         if (i == 2) {
             const unsigned measured = ticks != 0u;
-            HIP_TRY(hipMemcpy(c->d_guard_count + dmx::GS_E_MEASURED, &measured, sizeof(unsigned), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(c->d_guard_count.p + dmx::GS_E_MEASURED, &measured, sizeof(unsigned), hipMemcpyHostToDevice));
         }
     }
     return 0;
@@ -427,8 +426,8 @@ int dmx_get_redo_count(dmx_ctx *c, int64_t *count)
     DMX_TRY(bind(c));
     if (!count) return fail(DMX_ERR_INVALID, "null argument");
     unsigned n[2] = {0, 0};
-    if (c->d_n_redo) {
-        HIP_TRY(hipMemcpyAsync(n, c->d_n_redo, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_n_redo.p) {
+        HIP_TRY(hipMemcpyAsync(n, c->d_n_redo.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     *count = (int64_t)n[0] + (int64_t)n[1];
@@ -477,7 +476,7 @@ int dmx_set_betas(dmx_ctx *c, const float *prior)
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_problem, "dmx_set_problem before dmx_set_betas"));
     if (!prior && c->V > 0) return fail(DMX_ERR_INVALID, "null betas");
-    HIP_TRY(hipMemcpyAsync(c->d_prior, prior, sizeof(float) * c->V * c->G, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_prior.p, prior, sizeof(float) * c->V * c->G, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_betas = true;
     c->have_raw = false;  // (a prior table given as such: no raw betas behind it)
@@ -495,8 +494,8 @@ int dmx_set_prior_betas(dmx_ctx *c, const float *raw_betas, double default_prior
     const size_t vg = (size_t)V * G;
     // the raw betas stay on the device: dmx_get_learnt_betas forms raw + addition there (demux.py:65)
     c->have_raw = false;
-    if (!c->d_raw) DMX_TRY(dev_alloc(c, &c->d_raw, vg));
-    float *d_raw = c->d_raw, *d_bsum = nullptr;
+    if (!c->d_raw.p) DMX_TRY(dev_alloc(c, c->d_raw, vg));
+    float *d_raw = c->d_raw.p, *d_bsum = nullptr;
     HIP_TRY(hipMalloc((void **)&d_bsum, (size_t)(V ? V : 1) * sizeof(float)));
     int rc = 0;
     do {
@@ -507,25 +506,25 @@ int dmx_set_prior_betas(dmx_ctx *c, const float *raw_betas, double default_prior
         const unsigned long long *n_mol = nullptr;
         if (add_data_prior) {
             if (mol_per_variant) {  // counts supplied by the caller (problem installed with dmx_set_problem)
-                dev_free(c, &c->d_mol, (size_t)V);
-                if ((rc = dev_alloc(c, &c->d_mol, (size_t)V)) != 0) break;
-                if (V && hipMemcpyAsync(c->d_mol, mol_per_variant, sizeof(long long) * V, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+                dev_free(c, c->d_mol);
+                if ((rc = dev_alloc(c, c->d_mol, (size_t)V)) != 0) break;
+                if (V && hipMemcpyAsync(c->d_mol.p, mol_per_variant, sizeof(long long) * V, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
                     rc = fail(DMX_ERR_HIP, "upload of the molecule counts failed");
                     break;
                 }
-            } else if (!c->d_mol) {
+            } else if (!c->d_mol.p) {
                 rc = fail(DMX_ERR_INVALID, "add_data_prior needs molecule counts: pass them or install the problem with dmx_pack_and_set_problem");
                 break;
             }
-            n_mol = c->d_mol;
+            n_mol = c->d_mol.p;
         }
-        const hipError_t e = dmx::launch_prior_betas(c->stream, d_raw, d_bsum, n_mol, c->d_v2snp, c->d_snp_ptr, c->d_snp_vars, V, G,
-                                    default_prior, c->d_prior);
+        const hipError_t e = dmx::launch_prior_betas(c->stream, d_raw, d_bsum, n_mol, c->d_v2snp.p, c->d_snp_ptr.p, c->d_snp_vars.p, V, G,
+                                    default_prior, c->d_prior.p);
         if (e != hipSuccess) {
             rc = fail(DMX_ERR_HIP, "prior betas kernel: %s", hipGetErrorString(e));
             break;
         }
-        if (prior_out && vg && hipMemcpyAsync(prior_out, c->d_prior, vg * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+        if (prior_out && vg && hipMemcpyAsync(prior_out, c->d_prior.p, vg * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
             rc = fail(DMX_ERR_HIP, "download of the prior betas failed");
             break;
         }
@@ -541,7 +540,7 @@ int dmx_get_prior_betas(dmx_ctx *c, float *out)
 {
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_problem && c->have_betas, "prior betas (dmx_set_betas / dmx_set_prior_betas) before dmx_get_prior_betas"));
-    DMX_TRY(copy_out(c, out, c->d_prior, (size_t)c->V * c->G));
+    DMX_TRY(copy_out(c, out, c->d_prior.p, (size_t)c->V * c->G));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -554,12 +553,12 @@ int dmx_get_learnt_betas(dmx_ctx *c, float *out)
     DMX_TRY(ensure_full_addition(c));  // collective when sliced
     const size_t vg = (size_t)c->V * c->G;
     if (vg == 0) return 0;
-    float *d_sum = nullptr;
-    DMX_TRY(dev_alloc(c, &d_sum, vg));
-    hipError_t e = dmx::launch_add_f32(c->stream, c->d_raw, c->d_add, d_sum, (long long)vg);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, vg * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    DevBuf<float> d_sum;
+    DMX_TRY(dev_alloc(c, d_sum, vg));
+    hipError_t e = dmx::launch_add_f32(c->stream, c->d_raw.p, c->d_add.p, d_sum.p, (long long)vg);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum.p, vg * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);
-    dev_free(c, &d_sum, vg);
+    dev_free(c, d_sum);
     if (e != hipSuccess) return fail(DMX_ERR_HIP, "learnt betas: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(DMX_ERR_HIP, "learnt betas: %s", hipGetErrorString(e2));
     return 0;
@@ -570,7 +569,7 @@ int dmx_get_logits(dmx_ctx *c, float *out)
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_post, "dmx_estep before dmx_get_logits"));
     DMX_TRY(need(c, c->logits_readable, "the last E-step ran with dmx_set_logits_needed(ctx, 0): its logits were not kept (dmx_estep computes them)"));
-    DMX_TRY(copy_out(c, out, c->d_logits, (size_t)c->B * c->K));
+    DMX_TRY(copy_out(c, out, c->d_logits.p, (size_t)c->B * c->K));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -579,7 +578,7 @@ int dmx_get_probs(dmx_ctx *c, float *out)
 {
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_post, "dmx_estep before dmx_get_probs"));
-    DMX_TRY(copy_out(c, out, c->d_post, (size_t)c->B * c->K));
+    DMX_TRY(copy_out(c, out, c->d_post.p, (size_t)c->B * c->K));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -589,7 +588,7 @@ int dmx_get_addition(dmx_ctx *c, float *out)
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_problem, "dmx_set_problem before dmx_get_addition"));
     DMX_TRY(ensure_full_addition(c));  // collective when sliced
-    DMX_TRY(copy_out(c, out, c->d_add, (size_t)c->V * c->G));
+    DMX_TRY(copy_out(c, out, c->d_add.p, (size_t)c->V * c->G));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -606,7 +605,7 @@ int dmx_get_block(dmx_ctx *c, int what, int64_t b0, int64_t b1, int64_t k0, int6
                     (long long)k0, (long long)k1, c->B, c->K);
     if (b1 == b0 || k1 == k0) return 0;
     if (!out) return fail(DMX_ERR_INVALID, "null output");
-    const float *src = (what == DMX_LOGITS ? c->d_logits : c->d_post) + (size_t)b0 * c->K + k0;
+    const float *src = (what == DMX_LOGITS ? c->d_logits.p : c->d_post.p) + (size_t)b0 * c->K + k0;
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)(k1 - k0) * 4, src, (size_t)c->K * 4, (size_t)(k1 - k0) * 4, (size_t)(b1 - b0),
                              hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -617,9 +616,9 @@ int dmx_get_assignments(dmx_ctx *c, int32_t *best, float *best_p)
 {
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_post, "dmx_estep before dmx_get_assignments"));
-    HIP_TRY(dmx::launch_assign(c->stream, c->d_post, c->B, c->K, c->d_best, c->d_bestp));
-    if (best) HIP_TRY(hipMemcpyAsync(best, c->d_best, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream));
-    if (best_p) HIP_TRY(hipMemcpyAsync(best_p, c->d_bestp, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(dmx::launch_assign(c->stream, c->d_post.p, c->B, c->K, c->d_best.p, c->d_bestp.p));
+    if (best) HIP_TRY(hipMemcpyAsync(best, c->d_best.p, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream));
+    if (best_p) HIP_TRY(hipMemcpyAsync(best_p, c->d_bestp.p, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -627,13 +626,12 @@ int dmx_get_assignments(dmx_ctx *c, int32_t *best, float *best_p)
 // ---- self tests -------------------------------------------------------------------
 static int scratch(dmx_ctx *c, size_t bytes)
 {
-    if (bytes <= c->cap_scratch) return 0;
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    c->d_scratch = nullptr;
-    c->cap_scratch = 0;
-    hipError_t e = hipMalloc(&c->d_scratch, bytes);
+    if (bytes <= c->d_scratch.n) return 0;
+    if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
+    c->d_scratch = DevBuf<unsigned char>();
+    hipError_t e = hipMalloc((void **)&c->d_scratch.p, bytes);
     if (e != hipSuccess) return fail(DMX_ERR_HIP, "hipMalloc(scratch %zu): %s", bytes, hipGetErrorString(e));
-    c->cap_scratch = bytes;
+    c->d_scratch.n = bytes;
     return 0;
 }
 
@@ -643,7 +641,7 @@ static int unary_test(dmx_ctx *c, const float *in, float *out, int64_t n, int wh
     if (n < 0 || (n > 0 && (!in || !out))) return fail(DMX_ERR_INVALID, "bad test buffers");
     if (n == 0) return 0;
     DMX_TRY(scratch(c, (size_t)n * 8));
-    float *d_in = (float *)c->d_scratch, *d_out = d_in + n;
+    float *d_in = (float *)c->d_scratch.p, *d_out = d_in + n;
     HIP_TRY(hipMemcpyAsync(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (which == 0) HIP_TRY(dmx::launch_test_log(c->stream, d_in, d_out, n));
     if (which == 1) HIP_TRY(dmx::launch_test_exp(c->stream, d_in, d_out, n));

@@ -376,12 +376,12 @@ int shard_mstep_by_variant(dmx_ctx *c, bool force)
     if (rc) return rc;
     c->rows_pad = rows_pad;
     c->rows_total = rows_pad * n;
-    DMX_TRY(dev_alloc(c, &c->d_first_g, (size_t)c->rows_total));
-    DMX_TRY(dev_alloc(c, &c->d_nz_g, (size_t)c->rows_total * W));
-    DMX_TRY(dev_alloc(c, &c->d_post_g, (size_t)c->rows_total * G));
-    HIP_TRY(hipMemsetAsync(c->d_first_g, 0, sizeof(uint2) * (size_t)c->rows_total, st));
-    HIP_TRY(hipMemsetAsync(c->d_nz_g, 0, sizeof(unsigned long long) * (size_t)c->rows_total * W, st));
-    HIP_TRY(hipMemsetAsync(c->d_post_g, 0, sizeof(float) * (size_t)c->rows_total * G, st));
+    DMX_TRY(dev_alloc(c, c->d_first_g, (size_t)c->rows_total));
+    DMX_TRY(dev_alloc(c, c->d_nz_g, (size_t)c->rows_total * W));
+    DMX_TRY(dev_alloc(c, c->d_post_g, (size_t)c->rows_total * G));
+    HIP_TRY(hipMemsetAsync(c->d_first_g.p, 0, sizeof(uint2) * (size_t)c->rows_total, st));
+    HIP_TRY(hipMemsetAsync(c->d_nz_g.p, 0, sizeof(unsigned long long) * (size_t)c->rows_total * W, st));
+    HIP_TRY(hipMemsetAsync(c->d_post_g.p, 0, sizeof(float) * (size_t)c->rows_total * G, st));
     // Compact exchange of the posterior rows (gather_posteriors): a barcode with ONE live posterior - 82 % of them on the converged 200k x 100k x 64
     // experiment - is described by its 8-byte code; only the rows of the others - and of those only the ones that differ from what
     // was sent last (d_post_sent) - travel, in a list of at most rows_pad / 4 per rank (beyond that: the whole table, as until round 6).  G <= 64 (the codes exist).
@@ -394,13 +394,13 @@ int shard_mstep_by_variant(dmx_ctx *c, bool force)
         c->post_compact_cap = (unsigned)(asked > 0 ? std::min<long long>(asked, rows_pad) : std::max<long long>(64, rows_pad / 4));
         c->post_compact_words = 4 + (size_t)c->post_compact_cap * (size_t)(1 + G);
         c->post_cap_now = c->post_compact_cap;
-        DMX_TRY(dev_alloc(c, &c->d_post_compact, c->post_compact_words * (size_t)n));
-        HIP_TRY(hipMemsetAsync(c->d_post_compact, 0, sizeof(unsigned) * (c->post_compact_words * (size_t)n), st));
-        DMX_TRY(dev_alloc(c, &c->d_post_seen, (size_t)c->rows_total));
-        HIP_TRY(hipMemsetAsync(c->d_post_seen, 0xFF, sizeof(uint2) * (size_t)c->rows_total, st));
-        DMX_TRY(dev_alloc(c, &c->d_post_sent, (size_t)std::max<long long>(1, c->B) * G));
-        DMX_TRY(dev_alloc(c, &c->d_post_sent_multi, (size_t)std::max<long long>(1, c->B)));
-        HIP_TRY(hipMemsetAsync(c->d_post_sent_multi, 0, (size_t)std::max<long long>(1, c->B), st));  // (nothing sent yet: every such row is listed)
+        DMX_TRY(dev_alloc(c, c->d_post_compact, c->post_compact_words * (size_t)n));
+        HIP_TRY(hipMemsetAsync(c->d_post_compact.p, 0, sizeof(unsigned) * (c->post_compact_words * (size_t)n), st));
+        DMX_TRY(dev_alloc(c, c->d_post_seen, (size_t)c->rows_total));
+        HIP_TRY(hipMemsetAsync(c->d_post_seen.p, 0xFF, sizeof(uint2) * (size_t)c->rows_total, st));
+        DMX_TRY(dev_alloc(c, c->d_post_sent, (size_t)std::max<long long>(1, c->B) * G));
+        DMX_TRY(dev_alloc(c, c->d_post_sent_multi, (size_t)std::max<long long>(1, c->B)));
+        HIP_TRY(hipMemsetAsync(c->d_post_sent_multi.p, 0, (size_t)std::max<long long>(1, c->B), st));  // (nothing sent yet: every such row is listed)
         HIP_TRY(hipHostMalloc((void **)&c->h_post_counts, sizeof(unsigned) * (size_t)(n + 1), hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(c->h_post_counts, 0, sizeof(unsigned) * (size_t)(n + 1));
     }
@@ -416,7 +416,7 @@ int layout_exchange(dmx_ctx *c)
     const int G = c->G, n = c->attached() ? c->nranks : 1;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(st));
-    if (c->d_prow) return fail(DMX_ERR_INVALID, "the resident problem is already laid out for a communicator: install it again");
+    if (c->d_prow.p) return fail(DMX_ERR_INVALID, "the resident problem is already laid out for a communicator: install it again");
     bool contiguous = true;
     long long rows = V;
     exchange_slices(c->h_v2snp.data(), V, n, c->cut, rows, contiguous);
@@ -435,35 +435,31 @@ int layout_exchange(dmx_ctx *c)
     }
     c->slice_rows = c->sliced ? rows : V;
     const long long new_rows = c->sliced ? rows * n : V;
-    if (new_rows != c->prob_rows || !c->d_prob) {
-        dev_free(c, &c->d_prob, (size_t)c->prob_rows * G);
+    if (new_rows != c->prob_rows || !c->d_prob.p) {
+        dev_free(c, c->d_prob);
         c->prob_rows = new_rows;
-        DMX_TRY(dev_alloc(c, &c->d_prob, (size_t)new_rows * G));
+        DMX_TRY(dev_alloc(c, c->d_prob, (size_t)new_rows * G));
     }
     c->have_probs = false;
     c->emu_table_filled = false;
-    HIP_TRY(hipMemsetAsync(c->d_prob, 0, sizeof(float) * (size_t)(new_rows ? new_rows * G : 1), st));
+    HIP_TRY(hipMemsetAsync(c->d_prob.p, 0, sizeof(float) * (size_t)(new_rows ? new_rows * G : 1), st));
     if (c->sliced) {
         std::vector<int> prow((size_t)V);
         for (int r = 0; r < n; r++)
             for (long long v = c->cut[r]; v < c->cut[r + 1]; v++) prow[v] = (int)(r * rows + (v - c->cut[r]));
-        DMX_TRY(dev_alloc(c, &c->d_prow, (size_t)V));
-        HIP_TRY(hipMemcpyAsync(c->d_prow, prow.data(), sizeof(int) * V, hipMemcpyHostToDevice, st));
+        DMX_TRY(dev_alloc(c, c->d_prow, (size_t)V));
+        HIP_TRY(hipMemcpyAsync(c->d_prow.p, prow.data(), sizeof(int) * V, hipMemcpyHostToDevice, st));
         std::vector<int> row_variant((size_t)std::max<long long>(1, c->prob_rows), 0);
         for (long long v = 0; v < V; v++) row_variant[(size_t)prow[v]] = (int)v;
-        DMX_TRY(dev_alloc(c, &c->d_row_variant, (size_t)c->prob_rows));
-        HIP_TRY(hipMemcpyAsync(c->d_row_variant, row_variant.data(), sizeof(int) * (size_t)c->prob_rows, hipMemcpyHostToDevice, st));
-        HIP_TRY(dmx::launch_remap_row_offsets(st, c->d_call_pairs, c->n_pairs, (unsigned)G * 4u, c->d_prow, c->d_call_rows));
-        if (c->d_tile_stream) HIP_TRY(dmx::launch_remap_row_offsets(st, c->d_tile_stream, c->n_pairs, (unsigned)G * 4u, c->d_prow, nullptr));
+        DMX_TRY(dev_alloc(c, c->d_row_variant, (size_t)c->prob_rows));
+        HIP_TRY(hipMemcpyAsync(c->d_row_variant.p, row_variant.data(), sizeof(int) * (size_t)c->prob_rows, hipMemcpyHostToDevice, st));
+        HIP_TRY(dmx::launch_remap_row_offsets(st, c->d_call_pairs.p, c->n_pairs, (unsigned)G * 4u, c->d_prow.p, c->d_call_rows.p));
+        if (c->d_tile_stream.p) HIP_TRY(dmx::launch_remap_row_offsets(st, c->d_tile_stream.p, c->n_pairs, (unsigned)G * 4u, c->d_prow.p, nullptr));
         release_coarse_stream(c);  // (its row offsets are the tile-major stream's: rebuilt at the next admissible E-step)
         const size_t elem = c->reduce_dtype == DMX_F64 ? 8 : 4;
-        c->exch_bytes = (size_t)new_rows * G * 8;  // float64 sums of the reduce-scatter exchange; also the float32 staging of the addition gather
-        c->recv_bytes = (size_t)rows * G * elem;
-        HIP_TRY(hipMalloc(&c->d_exch, c->exch_bytes));
-        c->bytes += (int64_t)c->exch_bytes;
-        HIP_TRY(hipMalloc(&c->d_recv, c->recv_bytes));
-        c->bytes += (int64_t)c->recv_bytes;
-        HIP_TRY(hipMemsetAsync(c->d_exch, 0, c->exch_bytes, st));  // padding rows stay zero
+        DMX_TRY(raw_alloc(c, c->d_exch, (size_t)new_rows * G * 8));  // float64 sums of the reduce-scatter exchange; also the float32 staging of the addition gather
+        DMX_TRY(raw_alloc(c, c->d_recv, (size_t)rows * G * elem));
+        HIP_TRY(hipMemsetAsync(c->d_exch.p, 0, c->d_exch.n, st));  // padding rows stay zero
         // Compact exchange of the table (run_pstep): the rows of a rank's slice that changed since it sent them, in a list of at most
         // slice_rows / 4 (beyond that: the whole slices, as until round 6).  DEMUXALOT_AMD_EXCHANGE_COMPACT=0 switches it off, =<n>: capacity n.
         {
@@ -476,9 +472,9 @@ int layout_exchange(dmx_ctx *c)
                 c->prob_list_cap = (unsigned)(asked > 0 ? std::min<long long>(asked, rows) : std::max<long long>(64, rows / 4));
                 c->prob_list_words = 4 + (size_t)c->prob_list_cap * (size_t)(1 + G);
                 c->prob_cap_now = c->prob_list_cap;
-                DMX_TRY(dev_alloc(c, &c->d_prob_list, c->prob_list_words * (size_t)n));
-                HIP_TRY(hipMemsetAsync(c->d_prob_list, 0, sizeof(unsigned) * (c->prob_list_words * (size_t)n), st));
-                DMX_TRY(dev_alloc(c, &c->d_prob_prev, (size_t)rows * G));
+                DMX_TRY(dev_alloc(c, c->d_prob_list, c->prob_list_words * (size_t)n));
+                HIP_TRY(hipMemsetAsync(c->d_prob_list.p, 0, sizeof(unsigned) * (c->prob_list_words * (size_t)n), st));
+                DMX_TRY(dev_alloc(c, c->d_prob_prev, (size_t)rows * G));
                 if (!c->h_prob_counts) {
                     HIP_TRY(hipHostMalloc((void **)&c->h_prob_counts, sizeof(unsigned) * (size_t)(n + 1), hipHostMallocMapped | hipHostMallocCoherent));
                     std::memset(c->h_prob_counts, 0, sizeof(unsigned) * (size_t)(n + 1));
@@ -512,9 +508,9 @@ int gather_posteriors(dmx_ctx *c)
     if (c->emulated && !c->emu_post_filled) {
         for (int r = 0; r < c->nranks; r++) {
             if (r == c->rank) continue;
-            HIP_TRY(hipMemcpyAsync(c->d_first_g + r * rows, c->d_first_g + c->rank * rows, sizeof(uint2) * rows, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_nz_g + r * rows * W, c->d_nz_g + c->rank * rows * W, sizeof(unsigned long long) * rows * W, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_post_g + r * rows * G, c->d_post_g + c->rank * rows * G, sizeof(float) * rows * G, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_first_g.p + r * rows, c->d_first_g.p + c->rank * rows, sizeof(uint2) * rows, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_nz_g.p + r * rows * W, c->d_nz_g.p + c->rank * rows * W, sizeof(unsigned long long) * rows * W, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_post_g.p + r * rows * G, c->d_post_g.p + c->rank * rows * G, sizeof(float) * rows * G, hipMemcpyDeviceToDevice, c->stream));
         }
         c->emu_post_filled = true;
     }
@@ -525,14 +521,14 @@ int gather_posteriors(dmx_ctx *c)
     const unsigned cap_now = compact ? std::max(1u, std::min(c->post_cap_now, c->post_compact_cap)) : 0u;
     const size_t words_now = 4 + (size_t)cap_now * (size_t)(1 + G);
     if (compact)  // this rank's rows with several live posteriors, listed (the count may run beyond the capacity: overflow)
-        HIP_TRY(dmx::launch_post_compact_build(c->stream, c->d_first_g + c->rank * rows, c->d_post_g + c->rank * rows * G, c->B, G, cap_now,
-                                               c->d_post_compact + (size_t)c->rank * words_now, c->d_post_sent, c->d_post_sent_multi,
-                                               c->emulated ? c->d_post_compact : nullptr, (unsigned long long)words_now, c->nranks, c->rank));
+        HIP_TRY(dmx::launch_post_compact_build(c->stream, c->d_first_g.p + c->rank * rows, c->d_post_g.p + c->rank * rows * G, c->B, G, cap_now,
+                                               c->d_post_compact.p + (size_t)c->rank * words_now, c->d_post_sent.p, c->d_post_sent_multi.p,
+                                               c->emulated ? c->d_post_compact.p : nullptr, (unsigned long long)words_now, c->nranks, c->rank));
     coll_group_begin(c);  // one launch for the tables
-    rc = coll_all_gather(c, (float *)c->d_first_g, rows * 2, "posterior codes");
-    if (rc == 0) rc = coll_all_gather(c, (float *)c->d_nz_g, rows * W * 2, "posterior bitmaps");
-    if (rc == 0 && compact) rc = coll_all_gather(c, (float *)c->d_post_compact, words_now, "listed posterior rows");
-    if (rc == 0 && !compact) rc = coll_all_gather(c, c->d_post_g, rows * G, "singlet posteriors");
+    rc = coll_all_gather(c, (float *)c->d_first_g.p, rows * 2, "posterior codes");
+    if (rc == 0) rc = coll_all_gather(c, (float *)c->d_nz_g.p, rows * W * 2, "posterior bitmaps");
+    if (rc == 0 && compact) rc = coll_all_gather(c, (float *)c->d_post_compact.p, words_now, "listed posterior rows");
+    if (rc == 0 && !compact) rc = coll_all_gather(c, c->d_post_g.p, rows * G, "singlet posteriors");
     int rc_end = coll_group_end(c);
     if (rc == 0) rc = rc_end;
     if (rc == 0 && compact) {
@@ -540,9 +536,9 @@ int gather_posteriors(dmx_ctx *c)
         // rank was 8 x 8 us at 8 ranks, one strided hipMemcpy2DAsync 70 us of runtime overhead) and the host polls for them (wait_counts) while
         // the rows are rebuilt: that launch does not wait for the decision - should a list have overflowed, the whole table overwrites what it wrote.
         const unsigned seq = ++c->list_seq;
-        HIP_TRY(dmx::launch_post_counts(c->stream, c->d_post_compact, (unsigned long long)words_now, c->nranks, c->h_post_counts, seq));
-        HIP_TRY(dmx::launch_post_reconstruct(c->stream, c->d_first_g, c->d_post_g, c->d_post_compact, (unsigned long long)words_now,
-                                             (long long)rows, G, c->nranks, c->rank, cap_now, c->d_post_seen));
+        HIP_TRY(dmx::launch_post_counts(c->stream, c->d_post_compact.p, (unsigned long long)words_now, c->nranks, c->h_post_counts, seq));
+        HIP_TRY(dmx::launch_post_reconstruct(c->stream, c->d_first_g.p, c->d_post_g.p, c->d_post_compact.p, (unsigned long long)words_now,
+                                             (long long)rows, G, c->nranks, c->rank, cap_now, c->d_post_seen.p));
         DMX_TRY(wait_counts(c, c->h_post_counts, c->nranks, seq));
         unsigned longest = 0;
         for (int r = 0; r < c->nranks; r++) longest = std::max(longest, c->h_post_counts[r]);
@@ -551,11 +547,11 @@ int gather_posteriors(dmx_ctx *c)
         c->post_cap_now = overflow ? c->post_compact_cap : (unsigned)std::min<unsigned long long>(c->post_compact_cap, 4ull * longest + 512ull);
         if (overflow) {  // (dense posteriors: the first E-steps of a run that starts from uninformative genotypes)
             c->post_compact_overflows++;
-            rc = coll_all_gather(c, c->d_post_g, rows * G, "singlet posteriors (the lists overflowed)");
-            HIP_TRY(hipMemsetAsync(c->d_post_seen, 0xFF, sizeof(uint2) * (size_t)c->rows_total, c->stream));  // (the rows are the senders' own now)
+            rc = coll_all_gather(c, c->d_post_g.p, rows * G, "singlet posteriors (the lists overflowed)");
+            HIP_TRY(hipMemsetAsync(c->d_post_seen.p, 0xFF, sizeof(uint2) * (size_t)c->rows_total, c->stream));  // (the rows are the senders' own now)
             if (c->B > 0) {  // ... and what everybody holds of this rank's rows is what they are
-                HIP_TRY(hipMemcpyAsync(c->d_post_sent, c->d_post_g + c->rank * rows * G, sizeof(float) * (size_t)c->B * G, hipMemcpyDeviceToDevice, c->stream));
-                HIP_TRY(hipMemsetAsync(c->d_post_sent_multi, 1, (size_t)c->B, c->stream));
+                HIP_TRY(hipMemcpyAsync(c->d_post_sent.p, c->d_post_g.p + c->rank * rows * G, sizeof(float) * (size_t)c->B * G, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(hipMemsetAsync(c->d_post_sent_multi.p, 1, (size_t)c->B, c->stream));
             }
         } else {
             c->post_compact_taken++;

@@ -100,10 +100,9 @@ int ensure_sum_plan(dmx_ctx *c, long long K)
         plan.push_back(value_of(nd[1]));
     }
     for (int r : roots) plan.push_back(value_of(r));
-    dev_free(c, &c->d_sum_plan, c->cap_sum_plan);
-    c->cap_sum_plan = plan.size();
-    DMX_TRY(dev_alloc(c, &c->d_sum_plan, plan.size()));
-    HIP_TRY(hipMemcpyAsync(c->d_sum_plan, plan.data(), sizeof(int) * plan.size(), hipMemcpyHostToDevice, c->stream));
+    dev_free(c, c->d_sum_plan);
+    DMX_TRY(dev_alloc(c, c->d_sum_plan, plan.size()));
+    HIP_TRY(hipMemcpyAsync(c->d_sum_plan.p, plan.data(), sizeof(int) * plan.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sum_plan_k = K;
     c->sum_plan_values = n_leaves + (int)inner.size();
@@ -294,6 +293,24 @@ void ctx_trim(dmx_ctx *c, size_t keep_bytes)
     (void)trim_locked(c, keep_bytes);
 }
 
+int raw_alloc(dmx_ctx *c, DevBuf<unsigned char> &b, size_t bytes)
+{
+    b = DevBuf<unsigned char>();
+    HIP_TRY(hipMalloc((void **)&b.p, bytes));
+    b.n = bytes;
+    c->bytes += (int64_t)bytes;
+    return 0;
+}
+
+void raw_free(dmx_ctx *c, DevBuf<unsigned char> &b)
+{
+    if (b.p) {
+        (void)hipFree(b.p);
+        c->bytes -= (int64_t)b.n;
+    }
+    b = DevBuf<unsigned char>();
+}
+
 namespace dmx {
 namespace host {
 
@@ -370,99 +387,118 @@ void timer_end(dmx_ctx *c, int slot, TimerSpan &ev)
 // incremental M-step: the sums, the posteriors they were formed from, the work lists (run_mstep allocates them at first use)
 void release_incremental(dmx_ctx *c)
 {
-    const size_t vg = (size_t)c->V * c->G;
-    dev_free(c, &c->d_acc64, vg);
-    const size_t rows = (size_t)(c->incr_rows > 0 ? c->incr_rows : c->B);
-    dev_free(c, &c->d_prev_post, rows * c->G);
-    dev_free(c, &c->d_prev_first, rows);
-    dev_free(c, &c->d_incr_list, rows);
-    dev_free(c, &c->d_incr_map, rows);
-    dev_free(c, &c->d_slice_rec, (size_t)c->n_slice_rec);
-    dev_free(c, &c->d_slice_ptr, rows + 1);
-    c->n_slice_rec = 0;
+    dev_free(c, c->d_acc64);
+    dev_free(c, c->d_prev_post);
+    dev_free(c, c->d_prev_first);
+    dev_free(c, c->d_incr_list);
+    dev_free(c, c->d_incr_map);
+    dev_free(c, c->d_slice_rec);
+    dev_free(c, c->d_slice_ptr);
     c->slice_index_tried = false;
     c->incr_rows = 0;
-    dev_free(c, &c->d_incr_touched, (size_t)c->V);
-    dev_free(c, &c->d_incr_state, (size_t)(3 * dmx::IS_WORDS));
+    dev_free(c, c->d_incr_touched);
+    dev_free(c, c->d_incr_state);
     c->incr_valid = false;
 }
 
 // the coarse pass's records and constants (run_estep builds them at the problem's first admissible E-step)
 void release_coarse_stream(dmx_ctx *c)
 {
-    dev_free(c, &c->d_coarse_stream, c->cap_coarse_stream);
-    c->cap_coarse_stream = 0;
-    dev_free(c, &c->d_coarse_bin_ptr, (size_t)c->n_bins + 1);
-    dev_free(c, &c->d_log2_keep, (size_t)c->B);
+    dev_free(c, c->d_coarse_stream);
+    dev_free(c, c->d_coarse_bin_ptr);
+    dev_free(c, c->d_log2_keep);
     c->coarse_ready = false;
 }
 
-void release_problem(dmx_ctx *c)
+// the repack's E-step records and schedules, the M-step records and work items
+static void release_records(dmx_ctx *c)
 {
-    // the blocks released here are handed out again at once (ctx_malloc) to work ordered on c->stream: whatever the
-    // other streams of the context still have queued on them must be done first (hipFree used to wait for the device)
-    dev_free(c, &c->d_pair_ptr, (size_t)c->B + 1);
-    dev_free(c, &c->d_call_pairs, (size_t)c->n_pairs + dmx::CALL_PAD_PAIRS);
-    dev_free(c, &c->d_call_rows, ((size_t)c->n_pairs + dmx::CALL_PAD_PAIRS) * 2);
-    dev_free(c, &c->d_tile_stream, (size_t)c->n_pairs);
-    release_coarse_stream(c);
-    release_incremental(c);
-    c->n_pairs = 0;
-    dmx::release_mstep_tiles(c);  // (its record stream is sized by n_csc)
-    dev_free(c, &c->d_csc, (size_t)c->n_csc);
-    c->n_csc = 0;
-    dev_free(c, &c->d_item_start, (size_t)c->n_items);
-    dev_free(c, &c->d_item_len, (size_t)c->n_items);
-    dev_free(c, &c->d_item_ptr, (size_t)c->V + 1);
-    dev_free(c, &c->d_item_variant, (size_t)c->n_items);
-    dev_free(c, &c->d_bc_order, (size_t)c->B);
-    dev_free(c, &c->d_bin_rows, (size_t)c->n_bins * c->bin_rows_cap);
-    dev_free(c, &c->d_bin_order, (size_t)c->n_bins);
-    dev_free(c, &c->d_bin_ptr, (size_t)c->n_bins + 1);
-    c->n_bins = 0;
+    dev_free(c, c->d_pair_ptr);
+    dev_free(c, c->d_call_pairs);
+    dev_free(c, c->d_call_rows);
+    dev_free(c, c->d_tile_stream);
+    dev_free(c, c->d_bc_order);
+    dev_free(c, c->d_bin_rows);
+    dev_free(c, c->d_bin_order);
+    dev_free(c, c->d_bin_ptr);
+    c->n_pairs = c->n_bins = 0;
     c->n_tiles = c->bin_rows_cap = 0;
-    dev_free(c, &c->d_item_order, (size_t)c->n_items);
-    dev_free(c, &c->d_v2snp, (size_t)c->V);
-    dev_free(c, &c->d_snp_ptr, (size_t)c->S + 1);
-    dev_free(c, &c->d_snp_vars, (size_t)c->V);
-    const size_t vg = (size_t)c->V * c->G;
-    dev_free(c, &c->d_prior, vg);
-    dev_free(c, &c->d_raw, vg);
-    c->have_raw = false;
-    dev_free(c, &c->d_add, vg);
-    dev_free(c, &c->d_prob_list, c->prob_list_words * (size_t)std::max(1, c->nranks));
-    dev_free(c, &c->d_prob_prev, (size_t)c->slice_rows * c->G);
+    dmx::release_mstep_tiles(c);
+    dev_free(c, c->d_csc);
+    dev_free(c, c->d_item_start);
+    dev_free(c, c->d_item_len);
+    dev_free(c, c->d_item_ptr);
+    dev_free(c, c->d_item_variant);
+    dev_free(c, c->d_item_order);
+    dev_free(c, c->d_partial);
+    dev_free(c, c->d_redo);
+    dev_free(c, c->d_n_redo);
+    c->n_csc = c->n_items = 0;
+    c->h_col_ptr.clear();
+}
+
+// the option tables (ensure_options, ensure_sum_plan) and the [B, K] tables sized by them (upload_prior_logits too)
+static void release_options(dmx_ctx *c)
+{
+    dev_free(c, c->d_pen);
+    dev_free(c, c->d_pairs);
+    dev_free(c, c->d_pair_blocks);
+    c->n_pair_blocks = 0;
+    dev_free(c, c->d_sum_plan);
+    c->sum_plan_k = -1;
+    dev_free(c, c->d_logits);
+    dev_free(c, c->d_post);
+    raw_free(c, c->d_prior_logits);
+}
+
+// dictionary form of the E-step (prepare_dictionary)
+static void release_dictionary(dmx_ctx *c)
+{
+    dev_free(c, c->d_dict);
+    dev_free(c, c->d_codes);
+    dev_free(c, c->d_dtab);
+    dev_free(c, c->d_dict_stat);
+    c->dict_candidate = false;
+    c->add_is_zero = true;
+    c->dict_distinct = 0;
+}
+
+// the guarded mode's state and queues, the split rows of the tolerance / guarded E-step (build_row_segments)
+static void release_guard(dmx_ctx *c)
+{
+    dev_free(c, c->d_guard_count);
+    dev_free(c, c->d_guard_list);
+    dev_free(c, c->d_guard_sub);
+    c->guard_sub_cap = 0;
+    c->guard_rows_total = 0;
+    c->guard_ran = false;
+    dev_free(c, c->d_segs);
+    dev_free(c, c->d_split_first);
+    dev_free(c, c->d_seg_sums);
+    c->n_segs = c->n_split = 0;
+}
+
+// multi-GPU: the padded layout, the exchange buffers and compact lists, the variant-sharded M-step's global tables
+static void release_exchange(dmx_ctx *c)
+{
+    dev_free(c, c->d_prow);
+    dev_free(c, c->d_row_variant);
+    raw_free(c, c->d_exch);
+    raw_free(c, c->d_recv);
+    dev_free(c, c->d_prob_list);
+    dev_free(c, c->d_prob_prev);
     c->prob_list_words = 0;
     c->prob_list_cap = 0;
     c->prob_prev_valid = false;
     if (c->h_prob_counts) (void)hipHostFree(c->h_prob_counts);
     c->h_prob_counts = nullptr;
-    dev_free(c, &c->d_prob, (size_t)c->prob_rows * c->G);
-    dev_free(c, &c->d_prob16, c->cap_prob16);
-    c->cap_prob16 = 0;
-    c->prob16_valid = false;
-    dev_free(c, &c->d_add64, vg);
-    dev_free(c, &c->d_prow, (size_t)c->V);
-    dev_free(c, &c->d_row_variant, (size_t)c->prob_rows);
-    if (c->d_exch) {
-        (void)hipFree(c->d_exch);
-        c->bytes -= (int64_t)c->exch_bytes;
-        c->d_exch = nullptr;
-        c->exch_bytes = 0;
-    }
-    if (c->d_recv) {
-        (void)hipFree(c->d_recv);
-        c->bytes -= (int64_t)c->recv_bytes;
-        c->d_recv = nullptr;
-        c->recv_bytes = 0;
-    }
-    dev_free(c, &c->d_first_g, (size_t)c->rows_total);
-    dev_free(c, &c->d_nz_g, (size_t)c->rows_total * ((c->G + 63) / 64));
-    dev_free(c, &c->d_post_g, (size_t)c->rows_total * c->G);
-    dev_free(c, &c->d_post_compact, c->post_compact_words * (size_t)std::max(1, c->nranks));
-    dev_free(c, &c->d_post_seen, (size_t)c->rows_total);
-    dev_free(c, &c->d_post_sent, (size_t)std::max<long long>(1, c->B) * c->G);
-    dev_free(c, &c->d_post_sent_multi, (size_t)std::max<long long>(1, c->B));
+    dev_free(c, c->d_first_g);
+    dev_free(c, c->d_nz_g);
+    dev_free(c, c->d_post_g);
+    dev_free(c, c->d_post_compact);
+    dev_free(c, c->d_post_seen);
+    dev_free(c, c->d_post_sent);
+    dev_free(c, c->d_post_sent_multi);
     if (c->h_post_counts) (void)hipHostFree(c->h_post_counts);
     c->h_post_counts = nullptr;
     c->post_compact_words = 0;
@@ -473,73 +509,63 @@ void release_problem(dmx_ctx *c)
     c->slice_rows = c->prob_rows = 0;
     c->cut.clear();
     c->h_v2snp.clear();
-    c->h_col_ptr.clear();
-    dev_free(c, &c->d_partial, (size_t)c->n_items * c->G);
-    dev_free(c, &c->d_redo, c->cap_redo);
-    dev_free(c, &c->d_n_redo, (size_t)2);
-    c->cap_redo = 0;
-    dev_free(c, &c->d_logits, (size_t)c->cap_bk);
-    dev_free(c, &c->d_post, (size_t)c->cap_bk);
-    c->cap_bk = 0;
-    dev_free(c, &c->d_nz, (size_t)c->B * ((c->G + 63) / 64));
-    dev_free(c, &c->d_first, (size_t)c->B);
-    dev_free(c, &c->d_dense_calls, (size_t)1 + dmx::DENSE_SLOTS);
-    c->dense_stat_valid = false;
-    dev_free(c, &c->d_segs, (size_t)c->n_segs);
-    dev_free(c, &c->d_split_first, (size_t)c->n_split + 1);
-    dev_free(c, &c->d_seg_sums, c->cap_seg_sums);
-    c->cap_seg_sums = 0;
-    c->n_segs = c->n_split = 0;
-    dev_free(c, &c->d_guard_count, (size_t)dmx::GUARD_STATE_WORDS);
-    dev_free(c, &c->d_guard_list, (size_t)c->B);
-    dev_free(c, &c->d_guard_sub, (size_t)dmx::GUARD_QUEUES * c->guard_sub_cap);
-    c->guard_sub_cap = 0;
-    c->guard_rows_total = 0;
-    c->guard_ran = false;
-    dev_free(c, &c->d_dict, c->cap_dict_rows * dmx::DICT_CAP);
-    dev_free(c, &c->d_codes, c->cap_dict_rows * (size_t)dmx::dict_code_pitch(c->G));
-    dev_free(c, &c->d_dtab, c->cap_dtab);
-    dev_free(c, &c->d_dict_stat, (size_t)1);
-    c->cap_dict_rows = c->cap_dtab = 0;
-    c->dict_candidate = false;
-    c->add_is_zero = true;
-    c->estep_form = DMX_FORM_NONE;
-    c->dict_distinct = 0;
-    dev_free(c, &c->d_pen, (size_t)c->cap_k);
-    dev_free(c, &c->d_pairs, (size_t)c->cap_k);
-    dev_free(c, &c->d_pair_blocks, (size_t)c->cap_pair_blocks);
-    c->cap_pair_blocks = c->n_pair_blocks = 0;
-    dev_free(c, &c->d_sum_plan, c->cap_sum_plan);
-    c->cap_sum_plan = 0;
-    c->sum_plan_k = -1;
-    c->cap_k = 0;
-    if (c->d_prior_logits) {
-        (void)hipFree(c->d_prior_logits);
-        c->bytes -= (int64_t)c->cap_prior;
-        c->d_prior_logits = nullptr;
-        c->cap_prior = 0;
-    }
-    dev_free(c, &c->d_best, (size_t)c->B);
-    dev_free(c, &c->d_bestp, (size_t)c->B);
-    dev_free(c, &c->d_u_variant, (size_t)c->n_u);
-    dev_free(c, &c->d_u_cb, (size_t)c->n_u);
-    dev_free(c, &c->d_u_p, (size_t)c->n_u);
-    dev_free(c, &c->d_u_count, (size_t)c->n_u);
-    c->n_u = 0;
-    dev_free(c, &c->d_mol, (size_t)c->V);
-    dev_free(c, &c->d_mc_variant, (size_t)c->n_mc);
-    dev_free(c, &c->d_mc_e, (size_t)c->n_mc);
-    dev_free(c, &c->d_mc_start, (size_t)c->B + 1);
-    c->n_mc = 0;
+}
+
+// aggregate_on_snps: the molecule calls grouped by (barcode, SNP) and the float64 results (snp_aggregate.hip)
+static void release_snp_groups(dmx_ctx *c)
+{
+    dev_free(c, c->d_mc_variant);
+    dev_free(c, c->d_mc_e);
+    dev_free(c, c->d_mc_start);
     c->mc_max_count = 0;
-    dev_free(c, &c->d_logits64, c->cap_bk64);
-    dev_free(c, &c->d_post64, c->cap_bk64);
-    c->cap_bk64 = 0;
+    dev_free(c, c->d_logits64);
+    dev_free(c, c->d_post64);
     c->have_post64 = false;
+}
+
+// what the device pack leaves behind: the unique calls (dmx_get_packed_calls) and the molecule calls per variant
+static void release_pack_leftovers(dmx_ctx *c)
+{
+    dev_free(c, c->d_u_variant);
+    dev_free(c, c->d_u_cb);
+    dev_free(c, c->d_u_p);
+    dev_free(c, c->d_u_count);
+    c->n_u = 0;
+    dev_free(c, c->d_mol);
+}
+
+void release_problem(dmx_ctx *c)
+{
+    // the blocks released here are handed out again at once (ctx_malloc) to work ordered on c->stream: whatever the
+    // other streams of the context still have queued on them must be done first (hipFree used to wait for the device)
+    release_records(c);
+    release_coarse_stream(c);
+    release_incremental(c);
+    release_options(c);
+    release_dictionary(c);
+    release_guard(c);
+    release_exchange(c);
+    release_snp_groups(c);
+    release_pack_leftovers(c);
+    dev_free(c, c->d_v2snp);
+    dev_free(c, c->d_snp_ptr);
+    dev_free(c, c->d_snp_vars);
+    dev_free(c, c->d_prior);
+    dev_free(c, c->d_raw);
+    dev_free(c, c->d_add);
+    dev_free(c, c->d_add64);
+    dev_free(c, c->d_prob);
+    dev_free(c, c->d_prob16);
+    dev_free(c, c->d_nz);
+    dev_free(c, c->d_first);
+    dev_free(c, c->d_dense_calls);
+    dev_free(c, c->d_best);
+    dev_free(c, c->d_bestp);
+    c->have_raw = c->prob16_valid = c->dense_stat_valid = false;
+    c->estep_form = DMX_FORM_NONE;
     c->have_problem = c->have_betas = c->have_probs = c->have_post = false;
     c->B = c->V = c->N = c->S = 0;
     c->G = c->K = 0;
-    c->n_items = 0;
 }
 
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)
@@ -608,7 +634,7 @@ int dmx_destroy(dmx_ctx *c)
     comm_destroy(c);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     release_problem(c);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
+    if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too
     ctx_retire(c);
@@ -689,9 +715,9 @@ int dmx_reset_timings(dmx_ctx *c)
     DMX_TRY(bind(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // the totals; the last E-step's own numbers stay (they decide how the next one runs: kernels.hip k_guard_begin)
-    if (c->d_guard_count) HIP_TRY(hipMemsetAsync(c->d_guard_count + dmx::GS_PENDING, 0, 4 * sizeof(unsigned), c->stream));  // GS_PENDING, GS_DIRECT_STEPS, GS_TOTAL
-    if (c->d_guard_count) HIP_TRY(hipMemsetAsync(c->d_guard_count + dmx::GS_COARSE_STEPS, 0, 2 * sizeof(unsigned), c->stream));  // + GS_PROBES
-    if (c->d_incr_state) HIP_TRY(hipMemsetAsync(c->d_incr_state + 2 * dmx::IS_WORDS, 0, sizeof(unsigned) * 3, c->stream));  // (word 3: full passes since the install, kept)
+    if (c->d_guard_count.p) HIP_TRY(hipMemsetAsync(c->d_guard_count.p + dmx::GS_PENDING, 0, 4 * sizeof(unsigned), c->stream));  // GS_PENDING, GS_DIRECT_STEPS, GS_TOTAL
+    if (c->d_guard_count.p) HIP_TRY(hipMemsetAsync(c->d_guard_count.p + dmx::GS_COARSE_STEPS, 0, 2 * sizeof(unsigned), c->stream));  // + GS_PROBES
+    if (c->d_incr_state.p) HIP_TRY(hipMemsetAsync(c->d_incr_state.p + 2 * dmx::IS_WORDS, 0, sizeof(unsigned) * 3, c->stream));  // (word 3: full passes since the install, kept)
     c->guard_rows_total = 0;
     for (int s = 0; s < DMX_T_COUNT; s++) {
         timer_flush(c, s);

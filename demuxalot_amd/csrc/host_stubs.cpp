@@ -232,60 +232,60 @@ int repack_on_device(dmx_ctx *c, const int32_t *variant, const int32_t *cb, cons
     std::stable_sort(bc_order.begin(), bc_order.end(), [&](int x, int y) {
         return row_start[(size_t)x + 1] - row_start[(size_t)x] > row_start[(size_t)y + 1] - row_start[(size_t)y];
     });
-    DMX_TRY(dev_alloc(c, &c->d_pair_ptr, (size_t)B + 1));
-    DMX_TRY(dev_alloc(c, &c->d_item_ptr, (size_t)V + 1));
-    DMX_TRY(dev_alloc(c, &c->d_bc_order, (size_t)B));
-    std::memcpy(c->d_pair_ptr, pair_ptr.data(), sizeof(long long) * ((size_t)B + 1));
-    std::memcpy(c->d_item_ptr, item_ptr.data(), sizeof(long long) * ((size_t)V + 1));
-    if (B) std::memcpy(c->d_bc_order, bc_order.data(), sizeof(int) * (size_t)B);
+    DMX_TRY(dev_alloc(c, c->d_pair_ptr, (size_t)B + 1));
+    DMX_TRY(dev_alloc(c, c->d_item_ptr, (size_t)V + 1));
+    DMX_TRY(dev_alloc(c, c->d_bc_order, (size_t)B));
+    std::memcpy(c->d_pair_ptr.p, pair_ptr.data(), sizeof(long long) * ((size_t)B + 1));
+    std::memcpy(c->d_item_ptr.p, item_ptr.data(), sizeof(long long) * ((size_t)V + 1));
+    if (B) std::memcpy(c->d_bc_order.p, bc_order.data(), sizeof(int) * (size_t)B);
     const long long padded_pairs = c->n_pairs + CALL_PAD_PAIRS;
-    DMX_TRY(dev_alloc(c, &c->d_call_pairs, (size_t)padded_pairs));
-    DMX_TRY(dev_alloc(c, &c->d_call_rows, (size_t)padded_pairs * 2));
+    DMX_TRY(dev_alloc(c, c->d_call_pairs, (size_t)padded_pairs));
+    DMX_TRY(dev_alloc(c, c->d_call_rows, (size_t)padded_pairs * 2));
     for (long long i = 0; i < padded_pairs; i++) {
-        CallPair &pr = c->d_call_pairs[i];
+        CallPair &pr = c->d_call_pairs.p[i];
         pr.row_off[0] = pr.row_off[1] = 0u;
         pr.keep[0] = pr.keep[1] = 0.0f;
         pr.floor[0] = pr.floor[1] = 1.0f;
         pr.reserved[0] = pr.reserved[1] = 0u;
     }
-    std::memset(c->d_call_rows, 0, sizeof(unsigned) * (size_t)padded_pairs * 2);
+    std::memset(c->d_call_rows.p, 0, sizeof(unsigned) * (size_t)padded_pairs * 2);
     for (long long s = 0; s < N; s++) {
         const long long i = perm_b[(size_t)s];
         const long long b = cb[i], j = s - row_start[(size_t)b];
-        CallPair &pr = c->d_call_pairs[pair_ptr[(size_t)b] + (j >> 1)];
+        CallPair &pr = c->d_call_pairs.p[pair_ptr[(size_t)b] + (j >> 1)];
         const int h = (int)(j & 1);
         pr.row_off[h] = (unsigned)variant[i] * (unsigned)G * 4u;
-        c->d_call_rows[2 * (pair_ptr[(size_t)b] + (j >> 1)) + h] = (unsigned)variant[i];
+        c->d_call_rows.p[2 * (pair_ptr[(size_t)b] + (j >> 1)) + h] = (unsigned)variant[i];
         pr.keep[h] = 1.0f - p[i];
         pr.floor[h] = p[i] > 1e-4f ? p[i] : 1e-4f;
     }
     c->n_bins = 0;
     c->n_tiles = c->bin_rows_cap = 0;
-    DMX_TRY(dev_alloc(c, &c->d_csc, (size_t)N));
+    DMX_TRY(dev_alloc(c, c->d_csc, (size_t)N));
     c->n_csc = N;
     for (long long s = 0; s < N; s++) {
         const long long i = perm_v[(size_t)s];
         const float keep = 1.0f - p[i];
         unsigned bits;
         std::memcpy(&bits, &keep, 4);
-        c->d_csc[s] = make_uint2((unsigned)cb[i], bits);
+        c->d_csc.p[s] = make_uint2((unsigned)cb[i], bits);
     }
-    DMX_TRY(dev_alloc(c, &c->d_item_start, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_len, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_order, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_variant, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_start, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_len, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_order, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_variant, (size_t)c->n_items));
     for (long long v = 0; v < V; v++) {
         long long it = item_ptr[(size_t)v];
         for (long long s = col_ptr[(size_t)v]; s < col_ptr[(size_t)v + 1]; s += c->item_calls, it++) {
-            c->d_item_variant[it] = (int)v;
-            c->d_item_start[it] = s;
-            c->d_item_len[it] = (int)std::min<long long>(c->item_calls, col_ptr[(size_t)v + 1] - s);
+            c->d_item_variant.p[it] = (int)v;
+            c->d_item_start.p[it] = s;
+            c->d_item_len.p[it] = (int)std::min<long long>(c->item_calls, col_ptr[(size_t)v + 1] - s);
         }
     }
     std::vector<int> order((size_t)c->n_items);
     std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c->d_item_len[x] > c->d_item_len[y]; });
-    if (c->n_items) std::memcpy(c->d_item_order, order.data(), sizeof(int) * (size_t)c->n_items);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c->d_item_len.p[x] > c->d_item_len.p[y]; });
+    if (c->n_items) std::memcpy(c->d_item_order.p, order.data(), sizeof(int) * (size_t)c->n_items);
     return 0;
 }
 
@@ -294,9 +294,9 @@ int wire_records_of(dmx_ctx *c, long long row_base, uint4 *out, long long capaci
 {
     std::memset(out, 0, sizeof(uint4) * (size_t)capacity);
     for (long long it = 0; it < c->n_items; it++)
-        for (int i = 0; i < c->d_item_len[it]; i++) {
-            const long long s = c->d_item_start[it] + i;
-            out[s] = make_uint4((unsigned)c->d_item_variant[it], c->d_csc[s].x + (unsigned)row_base, c->d_csc[s].y, 1u);
+        for (int i = 0; i < c->d_item_len.p[it]; i++) {
+            const long long s = c->d_item_start.p[it] + i;
+            out[s] = make_uint4((unsigned)c->d_item_variant.p[it], c->d_csc.p[s].x + (unsigned)row_base, c->d_csc.p[s].y, 1u);
         }
     return 0;
 }
@@ -332,13 +332,13 @@ int install_mstep_records(dmx_ctx *c, const uint4 *rec, long long n, long long v
         if (rec[i].w != 0u && rec[i].x >= (unsigned)v_lo && rec[i].x < (unsigned)v_hi) keep.push_back(i);
     std::stable_sort(keep.begin(), keep.end(), [&](long long x, long long y) { return rec[x].x < rec[y].x; });
     const long long m = (long long)keep.size();
-    dev_free(c, &c->d_csc, (size_t)c->n_csc);
-    dev_free(c, &c->d_item_start, (size_t)c->n_items);
-    dev_free(c, &c->d_item_len, (size_t)c->n_items);
-    dev_free(c, &c->d_item_order, (size_t)c->n_items);
-    dev_free(c, &c->d_item_variant, (size_t)c->n_items);
-    dev_free(c, &c->d_partial, (size_t)c->n_items * c->G);
-    dev_free(c, &c->d_redo, c->cap_redo);
+    dev_free(c, c->d_csc);
+    dev_free(c, c->d_item_start);
+    dev_free(c, c->d_item_len);
+    dev_free(c, c->d_item_order);
+    dev_free(c, c->d_item_variant);
+    dev_free(c, c->d_partial);
+    dev_free(c, c->d_redo);
     c->item_calls = item_calls_for(m);
     std::vector<long long> col_ptr((size_t)V + 1, 0), item_ptr((size_t)V + 1, 0);
     for (long long i : keep) col_ptr[(size_t)rec[i].x + 1]++;
@@ -347,28 +347,27 @@ int install_mstep_records(dmx_ctx *c, const uint4 *rec, long long n, long long v
         item_ptr[(size_t)v + 1] = item_ptr[(size_t)v] + (col_ptr[(size_t)v + 1] - col_ptr[(size_t)v] + c->item_calls - 1) / c->item_calls;
     c->n_items = item_ptr[(size_t)V];
     c->n_csc = m;
-    std::memcpy(c->d_item_ptr, item_ptr.data(), sizeof(long long) * ((size_t)V + 1));
-    DMX_TRY(dev_alloc(c, &c->d_csc, (size_t)m));
-    for (long long s = 0; s < m; s++) c->d_csc[s] = make_uint2(rec[keep[(size_t)s]].y, rec[keep[(size_t)s]].z);
-    DMX_TRY(dev_alloc(c, &c->d_item_start, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_len, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_order, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_variant, (size_t)c->n_items));
-    DMX_TRY(dev_alloc(c, &c->d_partial, (size_t)c->n_items * c->G));
-    c->cap_redo = ((size_t)c->n_items / 2 + 1) * (size_t)c->G;
-    DMX_TRY(dev_alloc(c, &c->d_redo, c->cap_redo));
+    std::memcpy(c->d_item_ptr.p, item_ptr.data(), sizeof(long long) * ((size_t)V + 1));
+    DMX_TRY(dev_alloc(c, c->d_csc, (size_t)m));
+    for (long long s = 0; s < m; s++) c->d_csc.p[s] = make_uint2(rec[keep[(size_t)s]].y, rec[keep[(size_t)s]].z);
+    DMX_TRY(dev_alloc(c, c->d_item_start, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_len, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_order, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_variant, (size_t)c->n_items));
+    DMX_TRY(dev_alloc(c, c->d_partial, (size_t)c->n_items * c->G));
+    DMX_TRY(dev_alloc(c, c->d_redo, ((size_t)c->n_items / 2 + 1) * (size_t)c->G));
     for (long long v = 0; v < V; v++) {
         long long it = item_ptr[(size_t)v];
         for (long long s = col_ptr[(size_t)v]; s < col_ptr[(size_t)v + 1]; s += c->item_calls, it++) {
-            c->d_item_variant[it] = (int)v;
-            c->d_item_start[it] = s;
-            c->d_item_len[it] = (int)std::min<long long>(c->item_calls, col_ptr[(size_t)v + 1] - s);
+            c->d_item_variant.p[it] = (int)v;
+            c->d_item_start.p[it] = s;
+            c->d_item_len.p[it] = (int)std::min<long long>(c->item_calls, col_ptr[(size_t)v + 1] - s);
         }
     }
     std::vector<int> order((size_t)c->n_items);
     std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c->d_item_len[x] > c->d_item_len[y]; });
-    if (c->n_items) std::memcpy(c->d_item_order, order.data(), sizeof(int) * (size_t)c->n_items);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return c->d_item_len.p[x] > c->d_item_len.p[y]; });
+    if (c->n_items) std::memcpy(c->d_item_order.p, order.data(), sizeof(int) * (size_t)c->n_items);
     return 0;
 }
 

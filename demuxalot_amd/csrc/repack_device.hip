@@ -386,12 +386,12 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
     if (V)
         hipLaunchKernelGGL(k_derive_counts, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, V, 1, c->item_calls, col_items, (unsigned *)nullptr,
                            (unsigned *)nullptr);
-    DMX_TRY(dev_alloc(c, &c->d_pair_ptr, (size_t)B + 1));
-    DMX_TRY(dev_alloc(c, &c->d_item_ptr, (size_t)V + 1));
-    DMX_TRY(dev_alloc(c, &c->d_bc_order, (size_t)B));
-    DMX_TRY(scan_with_total(sc, row_pairs, c->d_pair_ptr, (size_t)B, st));
-    DMX_TRY(scan_with_total(sc, col_items, c->d_item_ptr, (size_t)V, st));
-    DMX_TRY(sort_pairs(sc, inv, inv_sorted, ids, (unsigned *)c->d_bc_order, (size_t)B, 32, st));  // longest rows first
+    DMX_TRY(dev_alloc(c, c->d_pair_ptr, (size_t)B + 1));
+    DMX_TRY(dev_alloc(c, c->d_item_ptr, (size_t)V + 1));
+    DMX_TRY(dev_alloc(c, c->d_bc_order, (size_t)B));
+    DMX_TRY(scan_with_total(sc, row_pairs, c->d_pair_ptr.p, (size_t)B, st));
+    DMX_TRY(scan_with_total(sc, col_items, c->d_item_ptr.p, (size_t)V, st));
+    DMX_TRY(sort_pairs(sc, inv, inv_sorted, ids, (unsigned *)c->d_bc_order.p, (size_t)B, 32, st));  // longest rows first
     long long n_pairs = 0, n_items = 0;
     unsigned longest = ~0u;  // ~calls of the longest row
     if (B) HIP_TRY(hipMemcpyAsync(&longest, inv_sorted, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -410,8 +410,8 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
                            (unsigned)std::min<long long>(c->long_row_calls[1], 0xFFFFFFFEll), (unsigned)std::min<long long>(c->long_row_calls[2], 0xFFFFFFFEll), d_longer);
         HIP_TRY(hipMemcpyAsync(h_longer, d_longer, sizeof(h_longer), hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipMemcpyAsync(&n_pairs, c->d_pair_ptr + B, sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&n_items, c->d_item_ptr + V, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_pairs, c->d_pair_ptr.p + B, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_items, c->d_item_ptr.p + V, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_items >= (1LL << 31)) return fail(DMX_ERR_UNSUPPORTED, "too many M-step work items");
     c->n_pairs = n_pairs;
@@ -422,13 +422,13 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
     // barcode-major -> E-step records
     // (CALL_PAD_PAIRS neutral records behind the last row: the dictionary form reads whole super-batches)
     const long long padded_pairs = n_pairs + CALL_PAD_PAIRS;
-    DMX_TRY(dev_alloc(c, &c->d_call_pairs, (size_t)padded_pairs));
-    DMX_TRY(dev_alloc(c, &c->d_call_rows, (size_t)padded_pairs * 2));
-    hipLaunchKernelGGL(k_fill_neutral, dim3(grid_for(padded_pairs)), dim3(256), 0, st, c->d_call_pairs, padded_pairs);
-    HIP_TRY(hipMemsetAsync(c->d_call_rows, 0, sizeof(unsigned) * (size_t)padded_pairs * 2, st));
+    DMX_TRY(dev_alloc(c, c->d_call_pairs, (size_t)padded_pairs));
+    DMX_TRY(dev_alloc(c, c->d_call_rows, (size_t)padded_pairs * 2));
+    hipLaunchKernelGGL(k_fill_neutral, dim3(grid_for(padded_pairs)), dim3(256), 0, st, c->d_call_pairs.p, padded_pairs);
+    HIP_TRY(hipMemsetAsync(c->d_call_rows.p, 0, sizeof(unsigned) * (size_t)padded_pairs * 2, st));
     if (N)
         hipLaunchKernelGGL(k_build_pairs, dim3(grid_for(N)), dim3(256), 0, st, keys_b, perm_b, d_variant, d_p, row_start,
-                           c->d_pair_ptr, N, (unsigned)G, c->d_call_pairs, c->d_call_rows);
+                           c->d_pair_ptr.p, N, (unsigned)G, c->d_call_pairs.p, c->d_call_rows.p);
     // ---- tile-major E-step schedule, when the shape calls for it ----
     c->n_bins = 0;
     c->n_tiles = 0;
@@ -455,10 +455,10 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
         const size_t cells = (size_t)n_bins * n_tiles * R;
         const long long total_groups = n_pairs >> 2;
         if (total_groups >= (1LL << 32)) return fail(DMX_ERR_UNSUPPORTED, "too many call groups for the tile-major schedule");
-        DMX_TRY(dev_alloc(c, &c->d_bin_rows, (size_t)n_bins * R));
-        DMX_TRY(dev_alloc(c, &c->d_bin_order, (size_t)n_bins));
-        DMX_TRY(dev_alloc(c, &c->d_bin_ptr, (size_t)n_bins + 1));
-        DMX_TRY(dev_alloc(c, &c->d_tile_stream, (size_t)n_pairs));
+        DMX_TRY(dev_alloc(c, c->d_bin_rows, (size_t)n_bins * R));
+        DMX_TRY(dev_alloc(c, c->d_bin_order, (size_t)n_bins));
+        DMX_TRY(dev_alloc(c, c->d_bin_ptr, (size_t)n_bins + 1));
+        DMX_TRY(dev_alloc(c, c->d_tile_stream, (size_t)n_pairs));
         c->n_bins = n_bins;  // (set before any failure below so that release_problem frees with the right sizes)
         c->n_tiles = n_tiles;
         c->bin_rows_cap = R;
@@ -478,15 +478,15 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
         hipLaunchKernelGGL(k_iota, dim3(grid_for(n_bins)), dim3(256), 0, st, bin_ids, n_bins);
         for (int stratum = 0; stratum < R; stratum++) {
             DMX_TRY(sort_pairs(sc, loads, keys_tmp, bin_ids, sorted_bins, (size_t)n_bins, 32, st));  // lightest bin first (stable)
-            hipLaunchKernelGGL(k_assign_stratum, dim3(grid_for(n_bins)), dim3(256), 0, st, c->d_bc_order, sorted_bins, stratum, R, n_bins,
-                               B, c->d_pair_ptr, c->d_bin_rows, loads, row_slot);
+            hipLaunchKernelGGL(k_assign_stratum, dim3(grid_for(n_bins)), dim3(256), 0, st, c->d_bc_order.p, sorted_bins, stratum, R, n_bins,
+                               B, c->d_pair_ptr.p, c->d_bin_rows.p, loads, row_slot);
         }
         hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(n_bins)), dim3(256), 0, st, loads, n_bins, inv_l, bin_ids);
-        DMX_TRY(sort_pairs(sc, inv_l, keys_tmp, bin_ids, (unsigned *)c->d_bin_order, (size_t)n_bins, 32, st));  // heaviest bin first
+        DMX_TRY(sort_pairs(sc, inv_l, keys_tmp, bin_ids, (unsigned *)c->d_bin_order.p, (size_t)n_bins, 32, st));  // heaviest bin first
         // groups per (bin, tile, slot) cell -> position of every cell / of every row's tile run in the bin-major stream
         HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned) * cells, st));
         const dim3 row_grid((unsigned)((B + 3) / 4));
-        hipLaunchKernelGGL(k_tile_groups<0>, row_grid, dim3(256), 0, st, c->d_call_pairs, c->d_pair_ptr, row_slot, B, (unsigned)G * 4u,
+        hipLaunchKernelGGL(k_tile_groups<0>, row_grid, dim3(256), 0, st, c->d_call_pairs.p, c->d_pair_ptr.p, row_slot, B, (unsigned)G * 4u,
                            tile_rows, n_tiles, R, cnt, (const unsigned *)nullptr, (const unsigned *)nullptr, (CallPair *)nullptr);
         {
             size_t bytes = 0;
@@ -497,29 +497,29 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
         }
         hipLaunchKernelGGL(k_row_tile_starts, dim3(grid_for(n_bins * R)), dim3(256), 0, st, cnt, n_bins, n_tiles, R, row_tile_start);
         hipLaunchKernelGGL(k_bin_ptr, dim3(grid_for(n_bins + 1)), dim3(256), 0, st, cell_start, n_bins, (size_t)n_tiles * R, total_groups,
-                           c->d_bin_ptr);
-        hipLaunchKernelGGL(k_tile_groups<1>, row_grid, dim3(256), 0, st, c->d_call_pairs, c->d_pair_ptr, row_slot, B, (unsigned)G * 4u,
-                           tile_rows, n_tiles, R, (unsigned *)nullptr, cell_start, row_tile_start, c->d_tile_stream);
+                           c->d_bin_ptr.p);
+        hipLaunchKernelGGL(k_tile_groups<1>, row_grid, dim3(256), 0, st, c->d_call_pairs.p, c->d_pair_ptr.p, row_slot, B, (unsigned)G * 4u,
+                           tile_rows, n_tiles, R, (unsigned *)nullptr, cell_start, row_tile_start, c->d_tile_stream.p);
     }
 
     // variant-major -> M-step records
-    DMX_TRY(dev_alloc(c, &c->d_csc, (size_t)N));
+    DMX_TRY(dev_alloc(c, c->d_csc, (size_t)N));
     c->n_csc = N;
-    if (N) hipLaunchKernelGGL(k_build_csc, dim3(grid_for(N)), dim3(256), 0, st, perm_v, d_cb, d_p, N, c->d_csc);
+    if (N) hipLaunchKernelGGL(k_build_csc, dim3(grid_for(N)), dim3(256), 0, st, perm_v, d_cb, d_p, N, c->d_csc.p);
 
     // ---- work items and their length-sorted list ----
-    DMX_TRY(dev_alloc(c, &c->d_item_start, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_len, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_order, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_variant, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_start, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_len, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_order, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_variant, (size_t)n_items));
     unsigned *inv_i = nullptr, *ids_i = nullptr, *keys_out = nullptr;
     DMX_TRY(sc.get(&inv_i, (size_t)n_items));
     DMX_TRY(sc.get(&ids_i, (size_t)n_items));
     DMX_TRY(sc.get(&keys_out, (size_t)n_items));
     if (V)
-        hipLaunchKernelGGL(k_build_items, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, c->d_item_ptr, V, c->item_calls,
-                           c->d_item_start, c->d_item_len, inv_i, ids_i, c->d_item_variant);
-    DMX_TRY(sort_pairs(sc, inv_i, keys_out, ids_i, (unsigned *)c->d_item_order, (size_t)n_items, 32, st));
+        hipLaunchKernelGGL(k_build_items, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, c->d_item_ptr.p, V, c->item_calls,
+                           c->d_item_start.p, c->d_item_len.p, inv_i, ids_i, c->d_item_variant.p);
+    DMX_TRY(sort_pairs(sc, inv_i, keys_out, ids_i, (unsigned *)c->d_item_order.p, (size_t)n_items, 32, st));
     // the variant-major offsets stay on the host: what cuts the tiles of the tile-major M-step (build_mstep_tiles)
     c->h_col_ptr.resize((size_t)V + 1);
     HIP_TRY(hipMemcpyAsync(c->h_col_ptr.data(), col_ptr, sizeof(long long) * (V + 1), hipMemcpyDeviceToHost, st));
@@ -593,8 +593,8 @@ int wire_records_of(dmx_ctx *c, long long row_base, uint4 *d_out, long long capa
     hipStream_t st = c->stream;
     HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(uint4) * (size_t)capacity, st));
     if (c->n_items)
-        hipLaunchKernelGGL(k_wire_records, dim3(grid_for(c->n_items * 64)), dim3(256), 0, st, c->d_csc, c->d_item_start, c->d_item_len,
-                           c->d_item_variant, c->n_items, (unsigned)row_base, d_out);
+        hipLaunchKernelGGL(k_wire_records, dim3(grid_for(c->n_items * 64)), dim3(256), 0, st, c->d_csc.p, c->d_item_start.p, c->d_item_len.p,
+                           c->d_item_variant.p, c->n_items, (unsigned)row_base, d_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -626,13 +626,13 @@ int install_mstep_records(dmx_ctx *c, const uint4 *d_rec, long long n, long long
     DMX_TRY(sort_pairs(sc, variant, keys_v, iota, perm, (size_t)m, bits_for(V ? V - 1 : 0), st));
     // the old records and items go, the slice's come
     release_mstep_tiles(c);
-    dev_free(c, &c->d_csc, (size_t)c->n_csc);
-    dev_free(c, &c->d_item_start, (size_t)c->n_items);
-    dev_free(c, &c->d_item_len, (size_t)c->n_items);
-    dev_free(c, &c->d_item_order, (size_t)c->n_items);
-    dev_free(c, &c->d_item_variant, (size_t)c->n_items);
-    dev_free(c, &c->d_partial, (size_t)c->n_items * c->G);
-    dev_free(c, &c->d_redo, c->cap_redo);
+    dev_free(c, c->d_csc);
+    dev_free(c, c->d_item_start);
+    dev_free(c, c->d_item_len);
+    dev_free(c, c->d_item_order);
+    dev_free(c, c->d_item_variant);
+    dev_free(c, c->d_partial);
+    dev_free(c, c->d_redo);
     c->n_items = 0;
     c->n_csc = 0;
     c->item_calls = item_calls_for(m);
@@ -643,30 +643,29 @@ int install_mstep_records(dmx_ctx *c, const uint4 *d_rec, long long n, long long
     if (V)
         hipLaunchKernelGGL(k_derive_counts, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, V, 1, c->item_calls, col_items, (unsigned *)nullptr,
                            (unsigned *)nullptr);
-    DMX_TRY(scan_with_total(sc, col_items, c->d_item_ptr, (size_t)V, st));
+    DMX_TRY(scan_with_total(sc, col_items, c->d_item_ptr.p, (size_t)V, st));
     long long n_items = 0;
-    HIP_TRY(hipMemcpyAsync(&n_items, c->d_item_ptr + V, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_items, c->d_item_ptr.p + V, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_items >= (1LL << 31)) return fail(DMX_ERR_UNSUPPORTED, "too many M-step work items");
-    DMX_TRY(dev_alloc(c, &c->d_csc, (size_t)m));
+    DMX_TRY(dev_alloc(c, c->d_csc, (size_t)m));
     c->n_csc = m;
-    if (m) hipLaunchKernelGGL(k_permute_records, dim3(grid_for(m)), dim3(256), 0, st, perm, row_keep, m, c->d_csc);
+    if (m) hipLaunchKernelGGL(k_permute_records, dim3(grid_for(m)), dim3(256), 0, st, perm, row_keep, m, c->d_csc.p);
     c->n_items = n_items;
-    DMX_TRY(dev_alloc(c, &c->d_item_start, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_len, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_order, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_item_variant, (size_t)n_items));
-    DMX_TRY(dev_alloc(c, &c->d_partial, (size_t)n_items * c->G));
-    c->cap_redo = ((size_t)n_items / 2 + 1) * (size_t)c->G;
-    DMX_TRY(dev_alloc(c, &c->d_redo, c->cap_redo));
+    DMX_TRY(dev_alloc(c, c->d_item_start, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_len, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_order, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_item_variant, (size_t)n_items));
+    DMX_TRY(dev_alloc(c, c->d_partial, (size_t)n_items * c->G));
+    DMX_TRY(dev_alloc(c, c->d_redo, ((size_t)n_items / 2 + 1) * (size_t)c->G));
     unsigned *inv_i = nullptr, *ids_i = nullptr, *keys_out = nullptr;
     DMX_TRY(sc.get(&inv_i, (size_t)n_items));
     DMX_TRY(sc.get(&ids_i, (size_t)n_items));
     DMX_TRY(sc.get(&keys_out, (size_t)n_items));
     if (V)
-        hipLaunchKernelGGL(k_build_items, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, c->d_item_ptr, V, c->item_calls, c->d_item_start,
-                           c->d_item_len, inv_i, ids_i, c->d_item_variant);
-    DMX_TRY(sort_pairs(sc, inv_i, keys_out, ids_i, (unsigned *)c->d_item_order, (size_t)n_items, 32, st));
+        hipLaunchKernelGGL(k_build_items, dim3(grid_for(V)), dim3(256), 0, st, col_ptr, c->d_item_ptr.p, V, c->item_calls, c->d_item_start.p,
+                           c->d_item_len.p, inv_i, ids_i, c->d_item_variant.p);
+    DMX_TRY(sort_pairs(sc, inv_i, keys_out, ids_i, (unsigned *)c->d_item_order.p, (size_t)n_items, 32, st));
     c->h_col_ptr.resize((size_t)V + 1);
     HIP_TRY(hipMemcpyAsync(c->h_col_ptr.data(), col_ptr, sizeof(long long) * (V + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipGetLastError());
@@ -757,13 +756,12 @@ int sort_pairs64(Scratch &sc, const unsigned *keys_in, unsigned *keys_out, const
 
 void release_mstep_tiles(dmx_ctx *c)
 {
-    dev_free(c, (unsigned long long **)&c->d_mt_stream, (size_t)c->n_mt_stream);
-    c->n_mt_stream = 0;
-    dev_free(c, &c->d_mt_ptr, (size_t)c->n_mt + 1);
-    dev_free(c, &c->d_mt_first, (size_t)c->n_mt + 1);
-    dev_free(c, &c->d_mt_order, (size_t)c->n_mt);
-    dev_free(c, &c->d_mt_shift, (size_t)c->n_mt);
-    dev_free(c, &c->d_mt_shift_v, (size_t)c->V);
+    dev_free(c, c->d_mt_stream);
+    dev_free(c, c->d_mt_ptr);
+    dev_free(c, c->d_mt_first);
+    dev_free(c, c->d_mt_order);
+    dev_free(c, c->d_mt_shift);
+    dev_free(c, c->d_mt_shift_v);
     c->incr_valid = false;
     c->n_mt = 0;
     c->mt_tv = 0;
@@ -848,8 +846,8 @@ int upload_variant_shifts(dmx_ctx *c, const TileCut &t)
     const long long V = c->V;
     std::vector<unsigned char> shift_v((size_t)V);
     for (long long v = 0; v < V; v++) shift_v[(size_t)v] = (unsigned char)t.tile_shift[(size_t)t.tile_of[(size_t)v]];
-    if (!c->d_mt_shift_v) DMX_TRY(dev_alloc(c, &c->d_mt_shift_v, (size_t)V));
-    HIP_TRY(hipMemcpyAsync(c->d_mt_shift_v, shift_v.data(), (size_t)V, hipMemcpyHostToDevice, c->stream));
+    if (!c->d_mt_shift_v.p) DMX_TRY(dev_alloc(c, c->d_mt_shift_v, (size_t)V));
+    HIP_TRY(hipMemcpyAsync(c->d_mt_shift_v.p, shift_v.data(), (size_t)V, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (the host vector)
     return 0;
 }
@@ -880,12 +878,12 @@ __global__ __launch_bounds__(256) void k_slice_rows(const uint2 *__restrict__ cs
 // Leaves d_slice_rec null where it does not apply (the caller stays with the masked walk).
 int build_slice_row_index(dmx_ctx *c)
 {
-    if (c->d_slice_rec != nullptr || c->slice_index_tried) return 0;
+    if (c->d_slice_rec.p != nullptr || c->slice_index_tried) return 0;
     c->slice_index_tried = true;
     const char *env = std::getenv("DEMUXALOT_AMD_SLICE_INDEX");  // =0: the masked walk (tests; a rank short of memory)
     if (env && atoi(env) == 0) return 0;
     const long long m = c->n_csc, rows = c->rows_total;
-    if (!c->mshard || m == 0 || rows == 0 || m >= (1LL << 32) || c->d_item_variant == nullptr) return 0;
+    if (!c->mshard || m == 0 || rows == 0 || m >= (1LL << 32) || c->d_item_variant.p == nullptr) return 0;
     hipStream_t st = c->stream;
     Scratch sc(c);
     unsigned *keys = nullptr, *keys_out = nullptr;
@@ -893,13 +891,12 @@ int build_slice_row_index(dmx_ctx *c)
     DMX_TRY(sc.get(&keys, (size_t)m));
     DMX_TRY(sc.get(&keys_out, (size_t)m));
     DMX_TRY(sc.get(&vals, (size_t)m));
-    hipLaunchKernelGGL(k_slice_rows, dim3((unsigned)((c->n_items + 3) / 4)), dim3(256), 0, st, c->d_csc, c->d_item_start, c->d_item_len,
-                       c->d_item_variant, c->n_items, keys, vals);
-    DMX_TRY(dev_alloc(c, &c->d_slice_rec, (size_t)m));
-    c->n_slice_rec = m;
-    DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, (unsigned long long *)c->d_slice_rec, (size_t)m, bits_for((unsigned long long)(rows - 1)), st));
-    DMX_TRY(dev_alloc(c, &c->d_slice_ptr, (size_t)rows + 1));
-    hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(rows + 1)), dim3(256), 0, st, keys_out, m, rows, c->d_slice_ptr);
+    hipLaunchKernelGGL(k_slice_rows, dim3((unsigned)((c->n_items + 3) / 4)), dim3(256), 0, st, c->d_csc.p, c->d_item_start.p, c->d_item_len.p,
+                       c->d_item_variant.p, c->n_items, keys, vals);
+    DMX_TRY(dev_alloc(c, c->d_slice_rec, (size_t)m));
+    DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, (unsigned long long *)c->d_slice_rec.p, (size_t)m, bits_for((unsigned long long)(rows - 1)), st));
+    DMX_TRY(dev_alloc(c, c->d_slice_ptr, (size_t)rows + 1));
+    hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(rows + 1)), dim3(256), 0, st, keys_out, m, rows, c->d_slice_ptr.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // (scratch)
     return 0;
@@ -910,7 +907,7 @@ int build_slice_row_index(dmx_ctx *c)
 // d_mt_shift_v null when the problem does not take the tile cut (the caller then stays with the float64 item form).
 int plan_mstep_shifts(dmx_ctx *c)
 {
-    if (c->d_mt_shift_v != nullptr || c->mt_shift_tried) return 0;
+    if (c->d_mt_shift_v.p != nullptr || c->mt_shift_tried) return 0;
     c->mt_shift_tried = true;
     if (c->mshard) return 0;  // (a variant-sharded rank: the cut of its slice comes with the records, build_mstep_tiles)
     TileCut t;
@@ -949,29 +946,27 @@ int build_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi)
     // of the barcode-major E-step records by a STABLE sort on the tile alone - 11 key bits instead of tile + barcode row (29),
     // two radix passes instead of four, the records themselves as the sort's values instead of a gather behind it
     // (200k x 100k x 64: the build 4.1 -> ~1.6 ms).  A tile's lengths follow from the sorted keys.
-    if (!c->mshard && !c->sliced && c->d_call_pairs != nullptr && v_lo == 0 && v_hi == V && c->n_pairs > 0 && 2 * c->n_pairs < (1LL << 32)) {
+    if (!c->mshard && !c->sliced && c->d_call_pairs.p != nullptr && v_lo == 0 && v_hi == V && c->n_pairs > 0 && 2 * c->n_pairs < (1LL << 32)) {
         const size_t n = (size_t)(2 * c->n_pairs);
-        unsigned long long *vals = nullptr, *vals_out = nullptr;
+        unsigned long long *vals = nullptr;
         DMX_TRY(sc.get(&keys, n));
         DMX_TRY(sc.get(&keys_out, n));
         DMX_TRY(sc.get(&vals, n));
         DMX_TRY(upload_variant_shifts(c, cut));
         for (long long v = 0; v < V; v++) tile_of[(size_t)v] = (tile_of[(size_t)v] << 7) | vin_of[(size_t)v];  // (vin < 128 = MTILE_MAX_VARIANTS)
         HIP_TRY(hipMemcpyAsync(d_tile_of, tile_of.data(), sizeof(unsigned) * V, hipMemcpyHostToDevice, st));
-        DMX_TRY(dev_alloc(c, &vals_out, n));
-        c->d_mt_stream = (uint2 *)vals_out;
-        c->n_mt_stream = (long long)n;
-        hipLaunchKernelGGL(k_mtile_from_rows, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, st, c->d_call_pairs, c->d_pair_ptr, c->B,
+        DMX_TRY(dev_alloc(c, c->d_mt_stream, n));
+        hipLaunchKernelGGL(k_mtile_from_rows, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, st, c->d_call_pairs.p, c->d_pair_ptr.p, c->B,
                            (unsigned)G * 4u, d_tile_of, (unsigned)n_mt, keys, vals);
-        DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, vals_out, n, bits_for((unsigned long long)n_mt), st));
-        DMX_TRY(dev_alloc(c, &c->d_mt_ptr, (size_t)n_mt + 1));
-        hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(n_mt + 1)), dim3(256), 0, st, keys_out, (long long)n, n_mt, c->d_mt_ptr);
-        DMX_TRY(dev_alloc(c, &c->d_mt_first, (size_t)n_mt + 1));
-        DMX_TRY(dev_alloc(c, &c->d_mt_order, (size_t)n_mt));
-        DMX_TRY(dev_alloc(c, &c->d_mt_shift, (size_t)n_mt));
-        HIP_TRY(hipMemcpyAsync(c->d_mt_shift, tile_shift.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_mt_first, tile_first.data(), sizeof(int) * (n_mt + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_mt_order, order.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
+        DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, (unsigned long long *)c->d_mt_stream.p, n, bits_for((unsigned long long)n_mt), st));
+        DMX_TRY(dev_alloc(c, c->d_mt_ptr, (size_t)n_mt + 1));
+        hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(n_mt + 1)), dim3(256), 0, st, keys_out, (long long)n, n_mt, c->d_mt_ptr.p);
+        DMX_TRY(dev_alloc(c, c->d_mt_first, (size_t)n_mt + 1));
+        DMX_TRY(dev_alloc(c, c->d_mt_order, (size_t)n_mt));
+        DMX_TRY(dev_alloc(c, c->d_mt_shift, (size_t)n_mt));
+        HIP_TRY(hipMemcpyAsync(c->d_mt_shift.p, tile_shift.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_mt_first.p, tile_first.data(), sizeof(int) * (n_mt + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_mt_order.p, order.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));  // host vectors, scratch
         c->n_mt = n_mt;
@@ -987,22 +982,21 @@ int build_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi)
     DMX_TRY(sc.get(&rec, (size_t)m));
     HIP_TRY(hipMemcpyAsync(d_tile_of, tile_of.data(), sizeof(unsigned) * V, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_vin_of, vin_of.data(), sizeof(unsigned) * V, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mtile_keys, dim3((unsigned)c->n_items), dim3(256), 0, st, c->d_csc, c->d_item_start, c->d_item_len, c->d_item_variant,
+    hipLaunchKernelGGL(k_mtile_keys, dim3((unsigned)c->n_items), dim3(256), 0, st, c->d_csc.p, c->d_item_start.p, c->d_item_len.p, c->d_item_variant.p,
                        d_tile_of, d_vin_of, row_bits, keys, rec);
     hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, st, iota, m);
     const unsigned tile_bits = bits_for(n_mt > 1 ? (unsigned long long)n_mt - 1 : 0);
     DMX_TRY(sort_pairs(sc, keys, keys_out, iota, perm, (size_t)m, std::max(1u, tile_bits + row_bits), st));
-    DMX_TRY(dev_alloc(c, &c->d_mt_stream, (size_t)m));
-    c->n_mt_stream = m;
-    hipLaunchKernelGGL(k_permute_records, dim3(grid_for(m)), dim3(256), 0, st, perm, rec, m, c->d_mt_stream);
-    DMX_TRY(dev_alloc(c, &c->d_mt_ptr, (size_t)n_mt + 1));
-    DMX_TRY(dev_alloc(c, &c->d_mt_first, (size_t)n_mt + 1));
-    DMX_TRY(dev_alloc(c, &c->d_mt_order, (size_t)n_mt));
-    DMX_TRY(dev_alloc(c, &c->d_mt_shift, (size_t)n_mt));
-    HIP_TRY(hipMemcpyAsync(c->d_mt_shift, tile_shift.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->d_mt_ptr, tile_ptr.data(), sizeof(long long) * (n_mt + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->d_mt_first, tile_first.data(), sizeof(int) * (n_mt + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->d_mt_order, order.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
+    DMX_TRY(dev_alloc(c, c->d_mt_stream, (size_t)m));
+    hipLaunchKernelGGL(k_permute_records, dim3(grid_for(m)), dim3(256), 0, st, perm, rec, m, c->d_mt_stream.p);
+    DMX_TRY(dev_alloc(c, c->d_mt_ptr, (size_t)n_mt + 1));
+    DMX_TRY(dev_alloc(c, c->d_mt_first, (size_t)n_mt + 1));
+    DMX_TRY(dev_alloc(c, c->d_mt_order, (size_t)n_mt));
+    DMX_TRY(dev_alloc(c, c->d_mt_shift, (size_t)n_mt));
+    HIP_TRY(hipMemcpyAsync(c->d_mt_shift.p, tile_shift.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_mt_ptr.p, tile_ptr.data(), sizeof(long long) * (n_mt + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_mt_first.p, tile_first.data(), sizeof(int) * (n_mt + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_mt_order.p, order.data(), sizeof(int) * n_mt, hipMemcpyHostToDevice, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // host vectors, scratch
     c->n_mt = n_mt;
@@ -1179,9 +1173,9 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     // 2. match + order-preserving compaction
     int *call_variant, *bad;
     unsigned *flag, *pos_excl;
-    dev_free(c, &c->d_mol, (size_t)c->V);
-    DMX_TRY(dev_alloc(c, &c->d_mol, (size_t)V));
-    unsigned long long *d_mol = c->d_mol;
+    dev_free(c, c->d_mol);
+    DMX_TRY(dev_alloc(c, c->d_mol, (size_t)V));
+    unsigned long long *d_mol = c->d_mol.p;
     DMX_TRY(sc.get(&call_variant, (size_t)n_calls));
     DMX_TRY(sc.get(&flag, (size_t)n_calls + 1));
     DMX_TRY(sc.get(&pos_excl, (size_t)n_calls + 1));
@@ -1248,21 +1242,21 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     }
     *n_unique = n_u;
     // unique calls stay resident in the ctx (dmx_get_packed_calls) and feed the layout derivation directly
-    dev_free(c, &c->d_u_variant, (size_t)c->n_u);
-    dev_free(c, &c->d_u_cb, (size_t)c->n_u);
-    dev_free(c, &c->d_u_p, (size_t)c->n_u);
-    dev_free(c, &c->d_u_count, (size_t)c->n_u);
+    dev_free(c, c->d_u_variant);
+    dev_free(c, c->d_u_cb);
+    dev_free(c, c->d_u_p);
+    dev_free(c, c->d_u_count);
     c->n_u = n_u;
-    DMX_TRY(dev_alloc(c, &c->d_u_variant, (size_t)n_u));
-    DMX_TRY(dev_alloc(c, &c->d_u_cb, (size_t)n_u));
-    DMX_TRY(dev_alloc(c, &c->d_u_p, (size_t)n_u));
-    DMX_TRY(dev_alloc(c, &c->d_u_count, (size_t)n_u));
+    DMX_TRY(dev_alloc(c, c->d_u_variant, (size_t)n_u));
+    DMX_TRY(dev_alloc(c, c->d_u_cb, (size_t)n_u));
+    DMX_TRY(dev_alloc(c, c->d_u_p, (size_t)n_u));
+    DMX_TRY(dev_alloc(c, c->d_u_count, (size_t)n_u));
     if (m)
         hipLaunchKernelGGL(k_products, dim3(grid_for(m)), dim3(256), 0, st, keys_sorted, perm, head, seg_incl, d_cp, m,
-                           c->d_u_variant, c->d_u_cb, c->d_u_p, c->d_u_count);
+                           c->d_u_variant.p, c->d_u_cb.p, c->d_u_p.p, c->d_u_count.p);
     HIP_TRY(hipGetLastError());
     c->N = n_u;
-    return repack_core(c, sc, c->d_u_variant, c->d_u_cb, c->d_u_p);
+    return repack_core(c, sc, c->d_u_variant.p, c->d_u_cb.p, c->d_u_p.p);
 }
 
 int pack_on_device(dmx_ctx *c, long long V, const int *var_chrom, const int *var_pos, const unsigned char *var_base,

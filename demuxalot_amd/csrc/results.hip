@@ -147,8 +147,8 @@ int dmx_get_assignments_above(dmx_ctx *c, float threshold, int32_t *best, float 
             break;
         }
         if (c->B > 0) {
-            hipLaunchKernelGGL(k_top_options<1>, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, c->stream, c->d_post, c->B, c->K,
-                               threshold, c->d_best, c->d_bestp, d_n);
+            hipLaunchKernelGGL(k_top_options<1>, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, c->stream, c->d_post.p, c->B, c->K,
+                               threshold, c->d_best.p, c->d_bestp.p, d_n);
             if (hipGetLastError() != hipSuccess) {
                 rc = fail(DMX_ERR_HIP, "assignment kernel launch failed");
                 break;
@@ -156,8 +156,8 @@ int dmx_get_assignments_above(dmx_ctx *c, float threshold, int32_t *best, float 
         }
         unsigned long long n = 0;
         hipError_t e = hipSuccess;
-        if (best && c->B) e = hipMemcpyAsync(best, c->d_best, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && best_p && c->B) e = hipMemcpyAsync(best_p, c->d_bestp, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream);
+        if (best && c->B) e = hipMemcpyAsync(best, c->d_best.p, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && best_p && c->B) e = hipMemcpyAsync(best_p, c->d_bestp.p, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
@@ -188,10 +188,10 @@ int dmx_get_top_options(dmx_ctx *c, int32_t k, int32_t *options, float *probs)
     const dim3 grid((unsigned)((c->B + 3) / 4)), block(256);
     const float none = -__builtin_inff();
     switch (k) {
-    case 1: hipLaunchKernelGGL(k_top_options<1>, grid, block, 0, c->stream, c->d_post, c->B, c->K, none, d_i, d_p, nullptr); break;
-    case 2: hipLaunchKernelGGL(k_top_options<2>, grid, block, 0, c->stream, c->d_post, c->B, c->K, none, d_i, d_p, nullptr); break;
-    case 3: hipLaunchKernelGGL(k_top_options<3>, grid, block, 0, c->stream, c->d_post, c->B, c->K, none, d_i, d_p, nullptr); break;
-    default: hipLaunchKernelGGL(k_top_options<4>, grid, block, 0, c->stream, c->d_post, c->B, c->K, none, d_i, d_p, nullptr); break;
+    case 1: hipLaunchKernelGGL(k_top_options<1>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
+    case 2: hipLaunchKernelGGL(k_top_options<2>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
+    case 3: hipLaunchKernelGGL(k_top_options<3>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
+    default: hipLaunchKernelGGL(k_top_options<4>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(options, d_i, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -216,7 +216,7 @@ int dmx_get_option_sums(dmx_ctx *c, double *sums)
         return DMX_ERR_HIP;
     }
     const unsigned kb = (unsigned)((K + 255) / 256);
-    hipLaunchKernelGGL(k_option_partial, dim3(kb, SUM_SLABS), dim3(256), 0, c->stream, c->d_post, c->B, K, d_part);
+    hipLaunchKernelGGL(k_option_partial, dim3(kb, SUM_SLABS), dim3(256), 0, c->stream, c->d_post.p, c->B, K, d_part);
     hipLaunchKernelGGL(k_option_final, dim3(kb), dim3(256), 0, c->stream, d_part, K, d_sums);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(sums, d_sums, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream);

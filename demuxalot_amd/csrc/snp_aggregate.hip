@@ -522,11 +522,11 @@ void launch_m64(dmx_ctx *c, double power, double *sums)
 {
     const dim3 grid((unsigned)((c->V + 3) / 4)), block(256);
     if (power == 2.0)
-        hipLaunchKernelGGL((k_mstep_f64<A, true>), grid, block, 0, c->stream, c->d_item_ptr, c->d_item_start, c->d_item_len, c->d_csc,
-                           c->d_post64, c->V, c->G, (long long)c->K, power, c->d_add, sums);
+        hipLaunchKernelGGL((k_mstep_f64<A, true>), grid, block, 0, c->stream, c->d_item_ptr.p, c->d_item_start.p, c->d_item_len.p, c->d_csc.p,
+                           c->d_post64.p, c->V, c->G, (long long)c->K, power, c->d_add.p, sums);
     else
-        hipLaunchKernelGGL((k_mstep_f64<A, false>), grid, block, 0, c->stream, c->d_item_ptr, c->d_item_start, c->d_item_len, c->d_csc,
-                           c->d_post64, c->V, c->G, (long long)c->K, power, c->d_add, sums);
+        hipLaunchKernelGGL((k_mstep_f64<A, false>), grid, block, 0, c->stream, c->d_item_ptr.p, c->d_item_start.p, c->d_item_len.p, c->d_csc.p,
+                           c->d_post64.p, c->V, c->G, (long long)c->K, power, c->d_add.p, sums);
 }
 
 }  // namespace
@@ -538,14 +538,13 @@ namespace dmx {
 int build_snp_groups(dmx_ctx *c, const unsigned long long *vb_keys, const unsigned *src_idx, const float *src_p, long long m)
 {
     hipStream_t st = c->stream;
-    dev_free(c, &c->d_mc_variant, (size_t)c->n_mc);
-    dev_free(c, &c->d_mc_e, (size_t)c->n_mc);
-    dev_free(c, &c->d_mc_start, (size_t)c->B + 1);
-    c->n_mc = m;
+    dev_free(c, c->d_mc_variant);
+    dev_free(c, c->d_mc_e);
+    dev_free(c, c->d_mc_start);
     c->mc_max_count = 0;
-    DMX_TRY(dev_alloc(c, &c->d_mc_variant, (size_t)m));
-    DMX_TRY(dev_alloc(c, &c->d_mc_e, (size_t)m));
-    DMX_TRY(dev_alloc(c, &c->d_mc_start, (size_t)c->B + 1));
+    DMX_TRY(dev_alloc(c, c->d_mc_variant, (size_t)m));
+    DMX_TRY(dev_alloc(c, c->d_mc_e, (size_t)m));
+    DMX_TRY(dev_alloc(c, c->d_mc_start, (size_t)c->B + 1));
     int *d_v2snp = nullptr;
     unsigned long long *keys = nullptr, *keys_sorted = nullptr;
     unsigned *idx = nullptr, *perm = nullptr, *longest = nullptr;
@@ -575,10 +574,10 @@ int build_snp_groups(dmx_ctx *c, const unsigned long long *vb_keys, const unsign
             if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, bytes, keys, keys_sorted, idx, perm, (size_t)m, 0u, 64u, st);
             if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "snp groups sort: %s", hipGetErrorString(e)); break; }
             hipLaunchKernelGGL(k_pair_fill, dim3(grid_for(m)), dim3(256), 0, st, keys_sorted, perm, vb_keys, src_idx, src_p, m,
-                               c->d_mc_variant, c->d_mc_e);
-            hipLaunchKernelGGL(k_max_run, dim3(grid_for(m)), dim3(256), 0, st, c->d_mc_variant, m, longest);
+                               c->d_mc_variant.p, c->d_mc_e.p);
+            hipLaunchKernelGGL(k_max_run, dim3(grid_for(m)), dim3(256), 0, st, c->d_mc_variant.p, m, longest);
         }
-        hipLaunchKernelGGL(k_barcode_starts, dim3(grid_for(c->B + 1)), dim3(256), 0, st, keys_sorted, m, c->B, c->d_mc_start);
+        hipLaunchKernelGGL(k_barcode_starts, dim3(grid_for(c->B + 1)), dim3(256), 0, st, keys_sorted, m, c->B, c->d_mc_start.p);
         unsigned h_longest = 0;
         e = hipMemcpyAsync(&h_longest, longest, sizeof(unsigned), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -636,7 +635,7 @@ int dmx_set_molecule_calls(dmx_ctx *c, int64_t n, const int32_t *variant_id, con
 int dmx_get_max_pair_count(dmx_ctx *c, int64_t *max_count)
 {
     if (!c || !max_count) return fail(DMX_ERR_INVALID, "null argument");
-    if (!c->d_mc_start) return fail(DMX_ERR_INVALID, "call order: molecule calls (dmx_set_keep_molecule_calls + a device pack, or dmx_set_molecule_calls) first");
+    if (!c->d_mc_start.p) return fail(DMX_ERR_INVALID, "call order: molecule calls (dmx_set_keep_molecule_calls + a device pack, or dmx_set_molecule_calls) first");
     *max_count = (int64_t)c->mc_max_count;
     return 0;
 }
@@ -647,21 +646,15 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
     if (!c) return fail(DMX_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
     if (!c->have_problem || !c->have_probs) return fail(DMX_ERR_INVALID, "call order: genotype probabilities before dmx_estep_snp");
-    if (!c->d_mc_start) return fail(DMX_ERR_INVALID, "call order: molecule calls (dmx_set_keep_molecule_calls + a device pack, or dmx_set_molecule_calls) first");
+    if (!c->d_mc_start.p) return fail(DMX_ERR_INVALID, "call order: molecule calls (dmx_set_keep_molecule_calls + a device pack, or dmx_set_molecule_calls) first");
     if (!count_pow || n_count_pow <= (int64_t)c->mc_max_count) return fail(DMX_ERR_INVALID, "count_pow must cover counts 0..%u", c->mc_max_count);
     if (prior_logits && prior_dtype != DMX_F32 && prior_dtype != DMX_F64) return fail(DMX_ERR_INVALID, "prior_dtype must be DMX_F32 or DMX_F64");
     const int G = c->G;
     const long long K = with_doublets ? (long long)G * (G + 1) / 2 : G;
     if (K > SNP_MAX_OPTIONS) return fail(DMX_ERR_UNSUPPORTED, "aggregate_on_snps supports up to %d options (K=%lld)", SNP_MAX_OPTIONS, K);
     const size_t bk = (size_t)c->B * K;
-    if (bk > c->cap_bk64) {
-        dev_free(c, &c->d_logits64, c->cap_bk64);
-        dev_free(c, &c->d_post64, c->cap_bk64);
-        c->cap_bk64 = 0;
-        DMX_TRY(dev_alloc(c, &c->d_logits64, bk));
-        DMX_TRY(dev_alloc(c, &c->d_post64, bk));
-        c->cap_bk64 = bk;
-    }
+    DMX_TRY(dev_grow(c, c->d_logits64, bk));
+    DMX_TRY(dev_grow(c, c->d_post64, bk));
     std::vector<unsigned> pairs((size_t)K);
     for (int g = 0; g < G; g++) pairs[g] = (unsigned)g | ((unsigned)g << 16);
     if (with_doublets) {
@@ -683,24 +676,24 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
         if (e == hipSuccess && prior_bytes) e = hipMemcpyAsync(d_prior, prior_logits, prior_bytes, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "dmx_estep_snp uploads: %s", hipGetErrorString(e)); break; }
         SnpArgs a;
-        a.bc_start = c->d_mc_start;
-        a.variant = c->d_mc_variant;
-        a.e = c->d_mc_e;
-        a.prob = c->d_prob;
-        a.prow = c->d_prow;
+        a.bc_start = c->d_mc_start.p;
+        a.variant = c->d_mc_variant.p;
+        a.e = c->d_mc_e.p;
+        a.prob = c->d_prob.p;
+        a.prow = c->d_prow.p;
         a.opt_pairs = d_pairs;
         a.count_pow = d_pow;
         a.prior = d_prior;
         a.prior_dtype = prior_dtype;
-        a.logits = c->d_logits64;
-        a.post = c->d_post64;
+        a.logits = c->d_logits64.p;
+        a.post = c->d_post64.p;
         a.log_bad = std::log(0.01 / (double)K);
         a.sum_plan = nullptr;
         a.sum_plan_values = 0;
         if (K > 1024) {
             rc = dmx::ensure_sum_plan(c, K);
             if (rc) break;
-            a.sum_plan = c->d_sum_plan;
+            a.sum_plan = c->d_sum_plan.p;
             a.sum_plan_values = c->sum_plan_values;
         }
         a.B = c->B;
@@ -719,8 +712,8 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
         else if (K <= 256 * 24) rc = launch_snp_block<24>(c, a);
         else rc = launch_snp_block<33>(c, a);
         if (rc) break;
-        if (logits_out && bk) e = hipMemcpyAsync(logits_out, c->d_logits64, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && probs_out && bk) e = hipMemcpyAsync(probs_out, c->d_post64, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
+        if (logits_out && bk) e = hipMemcpyAsync(logits_out, c->d_logits64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && probs_out && bk) e = hipMemcpyAsync(probs_out, c->d_post64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "dmx_estep_snp: %s", hipGetErrorString(e)); break; }
         // the float32 logits / posteriors of dmx_estep (and the M-step's bitmaps) were laid out for the previous K
@@ -746,7 +739,7 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
     if (c->attached()) return fail(DMX_ERR_UNSUPPORTED, "the float64 M-step does not run the device-side exchange: barcode-sharded "
                                                        "aggregate_on_snps runs add dmx_mstep_f64_sums over ranks on the host");
     const int G = c->G;
-    double *sums = sums_out ? c->d_add64 : nullptr;
+    double *sums = sums_out ? c->d_add64.p : nullptr;
     if (G <= 64) launch_m64<1>(c, contribution_power, sums);
     else if (G <= 128) launch_m64<2>(c, contribution_power, sums);
     else if (G <= 256) launch_m64<4>(c, contribution_power, sums);
@@ -756,8 +749,8 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
     c->add_partial = false;
     c->add_is_zero = false;
     const size_t vg = (size_t)c->V * G;
-    if (addition_out && vg) HIP_TRY(hipMemcpyAsync(addition_out, c->d_add, sizeof(float) * vg, hipMemcpyDeviceToHost, c->stream));
-    if (sums_out && vg) HIP_TRY(hipMemcpyAsync(sums_out, c->d_add64, sizeof(double) * vg, hipMemcpyDeviceToHost, c->stream));
+    if (addition_out && vg) HIP_TRY(hipMemcpyAsync(addition_out, c->d_add.p, sizeof(float) * vg, hipMemcpyDeviceToHost, c->stream));
+    if (sums_out && vg) HIP_TRY(hipMemcpyAsync(sums_out, c->d_add64.p, sizeof(double) * vg, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -131,6 +131,7 @@ def run_contexts(rng, rounds):
         world = int(rng.choice([1, 1, 2, 3, 5]))
         rank = int(rng.integers(0, world))
         ctx = DeviceContext(0)
+        created = ctx.device_bytes()
         try:
             os.environ['DEMUXALOT_AMD_EXCHANGE'] = str(rng.choice(['variant', 'variant', 'reduce_scatter', 'allreduce']))
             if world > 1 or rng.random() < 0.3:
@@ -174,7 +175,9 @@ def run_contexts(rng, rounds):
             if r % 3 == 0:  # a second problem on the same context: the block cache hands the blocks out again
                 variant2, cb2, p2, v2snp2 = random_problem(rng, B + 3, V, G, 500)
                 ctx.set_problem(B + 3, V, G, variant2, cb2, p2, v2snp2)
-                ctx.release_problem()
+            ctx.release_problem()  # every buffer of the problem counted back out, whatever the run allocated
+            assert ctx.device_bytes() == created, (r, ctx.device_bytes(), created)
+            if r % 3 == 0:
                 ctx.trim_cache()
         finally:
             ctx.close()

@@ -109,6 +109,41 @@ def test_lean_memory_releases_the_fine_pass_records(separable):
     print(f'released: {saved} bytes = {saved / len(p.variant_id):.2f} per call')
 
 
+def test_release_problem_gives_back_every_counted_byte(separable, monkeypatch):
+    """dmx_release_problem: dmx_device_bytes returns to what the context held before dmx_set_problem - after a guarded lean-memory run
+    that built the coarse pass's records, the tile-major M-step records and the incremental M-step's state, and on rank 0 of two over
+    the emulated wire with the reduce-scatter exchange (its buffers outside the block cache, the compact lists of the sliced table)."""
+    from demuxalot_amd import synth
+    from demuxalot_amd.device import DeviceContext
+    p = separable
+    with DeviceContext(0) as ctx:
+        ctx.set_estep_mode('guarded')
+        ctx.set_exact_additions(False)
+        ctx.set_lean_memory(True)
+        ctx.set_mstep_tiles('always')
+        before = ctx.device_bytes()
+        _install(ctx, p)
+        ctx.em(25, 0.01, np.zeros(p.n_genotypes, dtype=np.float32), False, fetch_logits=False, fetch_probs=False)
+        levels, form, (full, _delta, _last) = ctx.guard_levels(), ctx.mstep_form(), ctx.mstep_incremental()
+        assert levels['coarse_steps'] > 0 and form == 'tiles' and full >= 1, (levels, form, full)
+        held = ctx.device_bytes()
+        ctx.release_problem()
+        assert ctx.device_bytes() == before, (before, held, ctx.device_bytes())
+    monkeypatch.setenv('DEMUXALOT_AMD_EXCHANGE', 'reduce_scatter')
+    q = synth.generate(20_000, 10_000, 16, calls_per_barcode=100, seed=4103)
+    with DeviceContext(0) as ctx:
+        ctx.comm_init_emulated(0, 2)
+        ctx.set_estep_mode('guarded')
+        ctx.set_exact_additions(False)
+        before = ctx.device_bytes()
+        _install(ctx, q)
+        ctx.em(4, 0.01, np.zeros(q.n_genotypes, dtype=np.float32), False, fetch_logits=False, fetch_probs=False)
+        assert ctx.exchange_mode() == 'reduce_scatter' and ctx.exchange_compact_table()[2] > 0, (ctx.exchange_mode(), ctx.exchange_compact_table())
+        held = ctx.device_bytes()
+        ctx.release_problem()
+        assert ctx.device_bytes() == before, (before, held, ctx.device_bytes())
+
+
 def test_coarse_pass_gives_way_where_it_proves_too_little(siblings):
     """Sibling donors, 50 calls per barcode: the coarse guard (D ~ 0.03) flags most barcodes, the fine one a fifth.  The first
     admissible E-step takes the coarse pass and finds that out; the device then prices  C + f_coarse E  against  F + f_fine E  and E
