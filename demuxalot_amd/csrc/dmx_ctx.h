@@ -262,8 +262,10 @@ struct dmx_ctx {
     bool prob_prev_valid = false;            // d_prob_prev is what every rank holds of this slice
     unsigned *h_prob_counts = nullptr;       // pinned, [nranks + 1]
     long long prob_compact_taken = 0, prob_compact_overflows = 0;
-    DevBuf<unsigned char> d_exch;         // padded send buffer of the reduce-scatter (float64 or float32 partial sums)
+    DevBuf<unsigned char> d_exch;         // padded send buffer of the reduce-scatter (float64 or float32 partial sums; the incremental
+                                          // M-step keeps them there between two M-steps, the padding rows stay zero)
     DevBuf<unsigned char> d_recv;         // this rank's reduced slice
+    DevBuf<unsigned char> d_add_stage;    // [nranks * slice_rows, G] float32: the all-gather of the addition's slices (ensure_full_addition)
 
     // flat call arrays of staged containers (dmx_stage_containers -> dmx_pack_staged_and_set_problem); n_staged < 0: none
     int *st_chrom = nullptr, *st_pos = nullptr, *st_cb = nullptr;

@@ -457,9 +457,11 @@ int layout_exchange(dmx_ctx *c)
         if (c->d_tile_stream.p) HIP_TRY(dmx::launch_remap_row_offsets(st, c->d_tile_stream.p, c->n_pairs, (unsigned)G * 4u, c->d_prow.p, nullptr));
         release_coarse_stream(c);  // (its row offsets are the tile-major stream's: rebuilt at the next admissible E-step)
         const size_t elem = c->reduce_dtype == DMX_F64 ? 8 : 4;
-        DMX_TRY(raw_alloc(c, c->d_exch, (size_t)new_rows * G * 8));  // float64 sums of the reduce-scatter exchange; also the float32 staging of the addition gather
+        DMX_TRY(raw_alloc(c, c->d_exch, (size_t)new_rows * G * elem));  // partial sums of the reduce-scatter exchange
         DMX_TRY(raw_alloc(c, c->d_recv, (size_t)rows * G * elem));
+        DMX_TRY(raw_alloc(c, c->d_add_stage, (size_t)new_rows * G * 4));
         HIP_TRY(hipMemsetAsync(c->d_exch.p, 0, c->d_exch.n, st));  // padding rows stay zero
+        HIP_TRY(hipMemsetAsync(c->d_add_stage.p, 0, c->d_add_stage.n, st));  // (the emulated wire never fills the other ranks' blocks)
         // Compact exchange of the table (run_pstep): the rows of a rank's slice that changed since it sent them, in a list of at most
         // slice_rows / 4 (beyond that: the whole slices, as until round 6).  DEMUXALOT_AMD_EXCHANGE_COMPACT=0 switches it off, =<n>: capacity n.
         {

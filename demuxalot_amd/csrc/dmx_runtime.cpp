@@ -485,6 +485,7 @@ static void release_exchange(dmx_ctx *c)
     dev_free(c, c->d_row_variant);
     raw_free(c, c->d_exch);
     raw_free(c, c->d_recv);
+    raw_free(c, c->d_add_stage);
     dev_free(c, c->d_prob_list);
     dev_free(c, c->d_prob_prev);
     c->prob_list_words = 0;

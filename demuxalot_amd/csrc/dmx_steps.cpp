@@ -156,12 +156,13 @@ int copy_prob_in(dmx_ctx *c, const float *src)
 }
 
 // sliced mode: after an M-step only this rank's slice of d_add is current; assemble the whole table (collective:
-// every rank must get here)
+// every rank must get here).  The gather has a buffer of its own: d_exch holds the partial sums the incremental M-step
+// builds on, whatever host calls come between two M-steps.
 int ensure_full_addition(dmx_ctx *c)
 {
     if (!c->add_partial) return 0;
     const int G = c->G, n = c->nranks;
-    float *stage = (float *)c->d_exch.p;
+    float *stage = (float *)c->d_add_stage.p;
     const size_t block = (size_t)c->slice_rows * G;
     const long long mine = c->cut[c->rank + 1] - c->cut[c->rank];
     if (mine) HIP_TRY(hipMemcpyAsync(stage + c->rank * block, c->d_add.p + c->cut[c->rank] * G, sizeof(float) * mine * G, hipMemcpyDeviceToDevice, c->stream));
@@ -170,8 +171,6 @@ int ensure_full_addition(dmx_ctx *c)
         const long long rows = c->cut[k + 1] - c->cut[k];
         if (rows && k != c->rank) HIP_TRY(hipMemcpyAsync(c->d_add.p + c->cut[k] * G, stage + k * block, sizeof(float) * rows * G, hipMemcpyDeviceToDevice, c->stream));
     }
-    // the exchange buffer's padding rows must be zero again before the next reduce-scatter
-    HIP_TRY(hipMemsetAsync(c->d_exch.p, 0, c->d_exch.n, c->stream));
     c->add_partial = false;
     return 0;
 }

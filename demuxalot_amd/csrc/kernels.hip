@@ -3521,8 +3521,8 @@ hipError_t launch_mcombine(hipStream_t st, const MstepArgs &a, const long long *
 }
 
 // ---- compact exchange of the posterior rows (variant-sharded M-step, G <= 64; dmx_exchange.cpp: gather_posteriors) ----
-// What the M-step reads of a barcode with ONE live posterior is in its 8-byte code (nz_code); its 256-byte row need not travel: the
-// receivers rebuild it - the code's posterior at the code's genotype, zeros elsewhere; a posterior that is not live contributes
+// What the M-step reads of a barcode with ONE live posterior - or none, a doublet's row - is in its 8-byte code (nz_code); its 256-byte
+// row need not travel: the receivers rebuild it - the code's posterior at the code's genotype, zeros elsewhere; a posterior that is not live contributes
 // exactly +0 to every sum (NZ_FLOOR_SQUARE; with another contribution_power "live" means non-zero), so the additions keep their bits.
 // Rows with several live posteriors (1 - 15 % of the barcodes) travel in a list: block = {rows listed (beyond `cap`: overflow - the
 // caller falls back to the all-gather of the whole table), 3 words of padding, cap entries of (row, G floats)}.
@@ -3550,7 +3550,7 @@ __global__ __launch_bounds__(256) void k_post_compact_build(const uint2 *__restr
     const long long b0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
     const long long b = b0 + lane;
     const bool in = lane < 16 && b < B;
-    const bool multi = in && (first[in ? b : 0].y & 127u) != 1u;
+    const bool multi = in && (first[in ? b : 0].y & 127u) > 1u;  // (as k_post_reconstruct: a row without a live posterior is rebuilt too)
     const bool was = in && sent_multi[in ? b : 0] != 0;
     if (in && !multi && was) sent_multi[b] = 0;
     const unsigned long long m = __ballot(multi), was_m = __ballot(multi && was);

@@ -748,6 +748,7 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
     HIP_TRY(hipGetLastError());
     c->add_partial = false;
     c->add_is_zero = false;
+    c->incr_valid = false;  // (the addition is no longer the sums the incremental M-step keeps: its next M-step is a full pass)
     const size_t vg = (size_t)c->V * G;
     if (addition_out && vg) HIP_TRY(hipMemcpyAsync(addition_out, c->d_add.p, sizeof(float) * vg, hipMemcpyDeviceToHost, c->stream));
     if (sums_out && vg) HIP_TRY(hipMemcpyAsync(sums_out, c->d_add64.p, sizeof(double) * vg, hipMemcpyDeviceToHost, c->stream));

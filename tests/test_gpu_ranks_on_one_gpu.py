@@ -246,11 +246,20 @@ def test_device_resident_sharded_results_against_pandas(world):
             fio.assert_bitwise(got['frame'].values, want.values, 'to_dataframe at the root')
 
 
-@pytest.mark.parametrize('aggregate', [False, True])
-def test_sharded_staged_learning(aggregate):
+@pytest.mark.parametrize('aggregate,exchange,exact_additions', [
+    pytest.param(False, None, None, id='False'), pytest.param(True, None, None, id='True'),
+    pytest.param(False, 'reduce_scatter', None, id='reduce_scatter'), pytest.param(False, 'variant', None, id='variant'),
+    pytest.param(False, 'reduce_scatter', '0', id='reduce_scatter-fixed_point')])
+def test_sharded_staged_learning(aggregate, exchange, exact_additions, monkeypatch):
     """distributed.staged_genotype_learning at world 2 against the reference's per-iteration captures: the default
-    E-step (float32, the exchange inside the library) and aggregate_on_snps (float64 posteriors; the ranks' float64
-    M-step sums added on the host)."""
+    E-step (float32, the exchange inside the library) - with the exchange the library picks, forced to the reduce-scatter of the
+    sums or to the variant-sharded M-step, and the reduce-scatter at the product's arithmetic (exact additions off: the
+    fixed-point M-step, incremental across the fetch of every iteration) - and aggregate_on_snps (float64 posteriors; the
+    ranks' float64 M-step sums added on the host)."""
+    if exchange is not None:
+        monkeypatch.setenv('DEMUXALOT_AMD_EXCHANGE', exchange)
+    if exact_additions is not None:
+        monkeypatch.setenv('DEMUXALOT_AMD_EXACT_ADDITIONS', exact_additions)
     from demuxalot_amd import Demultiplexer, distributed
     fx = fio.load('f7_aggregate_synthetic_g4.npz' if aggregate else 'f2_synthetic_g4.npz')
     inputs = fio.load(str(fx['inputs_of'])) if aggregate else fx
@@ -521,40 +530,43 @@ def test_variant_sharded_mstep_is_bit_identical_to_the_reference(world, monkeypa
         assert np.abs(probs - fx[f'em0_it{n_it - 1}_probs']).max() <= 1e-5
 
 
-@pytest.mark.parametrize('mode', ['exact', 'guarded'])
-def test_compact_exchange_of_the_posterior_rows(mode, monkeypatch):
+@pytest.mark.parametrize('mode,doublets', [pytest.param('exact', False, id='exact'), pytest.param('guarded', False, id='guarded'),
+                                           pytest.param('exact', True, id='exact-doublets')])
+def test_compact_exchange_of_the_posterior_rows(mode, doublets, monkeypatch):
     """Variant-sharded M-step, G <= 64 (include/demux_hip_debug.h: dmx_get_exchange_compact): a barcode with ONE live posterior is
     described by its 8-byte code, which travels anyway; only the rows of the others travel, in a list of bounded capacity, and the
     receivers rebuild the table.  10 000 barcodes x 3 000 SNPs x 48 genotypes on 3 ranks, 6 iterations: with the compact form
     (default), with a capacity of 16 rows (every list overflows: the whole table travels, decided alike on every rank) and with the
     compact form off - the same bits every time, equal to ONE context holding everything; and the compact form did carry the
-    exchange where it could."""
+    exchange where it could.  With doublets (6 000 barcodes x 24 genotypes): rows whose singlet posteriors are all dead (the doublets')
+    are described by their code like the rows with one live posterior - the builder and the receivers agree on that; the compact form
+    twice (with a capacity of a whole slice: no list overflows, every exchange is compact) and off, the same bits, equal to one context."""
     monkeypatch.setenv('DEMUXALOT_AMD_EXCHANGE', 'variant')
     monkeypatch.setenv('DEMUXALOT_AMD_ESTEP', mode)
-    from demuxalot_amd import distributed, synth
+    from demuxalot_amd import Demultiplexer, distributed, synth
     from demuxalot_amd.device import DeviceContext
-    G, world, n_it = 48, 3, 6
-    p = synth.generate(10_000, 3000, G, calls_per_barcode=400, seed=61)
+    G, world, n_it = (24, 3, 6) if doublets else (48, 3, 6)
+    p = synth.generate(6_000 if doublets else 10_000, 3000, G, calls_per_barcode=400, doublets=doublets, seed=62 if doublets else 61)
     betas = p.prior_betas()
-    pen = np.zeros(G, dtype=np.float32)
+    pen = Demultiplexer._doublet_penalties(G, 0.2 if doublets else 0.0)
     with DeviceContext(0) as ctx:
         ctx.set_problem(p.n_barcodes, p.n_variants, G, p.variant_id, p.compressed_cb, p.p_base_wrong, p.v2snp)
         ctx.set_betas(betas)
         ctx.set_mstep_tiles('never')           # (a rank's M-step is the work-item form: the same float64 order)
         ctx.set_mstep_incremental(False)
-        _l, want_probs, want_add = ctx.em(n_it, 0.01, pen, False, fetch_logits=False)
+        _l, want_probs, want_add = ctx.em(n_it, 0.01, pen, doublets, fetch_logits=False)
     outcomes = {}
-    for setting in (None, '16', '0'):
+    for setting in (('1000000', 'again', '0') if doublets else (None, '16', '0')):
         if setting is None:
             monkeypatch.delenv('DEMUXALOT_AMD_EXCHANGE_COMPACT', raising=False)
-        else:
+        elif setting != 'again':                # (the compact form once more, as it was)
             monkeypatch.setenv('DEMUXALOT_AMD_EXCHANGE_COMPACT', setting)
         shared = ThreadWorld(world)
 
         def rank_body(plane):
             em = distributed.ShardedEM(plane, p.n_barcodes, p.v2snp, betas, p.variant_id, p.compressed_cb, p.p_base_wrong)
             try:
-                probs, addition = em.learn(n_it, 0.01, pen, False)
+                probs, addition = em.learn(n_it, 0.01, pen, doublets)
                 return em.lo, em.hi, probs, addition, em.ctx.exchange_compact(), em.ctx.exchange_compact_table()
             finally:
                 em.ctx.close()
@@ -567,6 +579,11 @@ def test_compact_exchange_of_the_posterior_rows(mode, monkeypatch):
                 fio.assert_bitwise(addition, want_add, f'compact={setting}: addition')
             fio.assert_bitwise(probs, outcomes['0'][[r[0] for r in outcomes['0']].index(lo)][2], f'compact={setting} vs off: posterior rows')
             fio.assert_bitwise(addition, outcomes['0'][0][3], f'compact={setting} vs off: addition')
+    if doublets:
+        for setting in ('1000000', 'again'):
+            assert all(r[4][:2] == (n_it - 1, 0) for r in outcomes[setting]), [r[4] for r in outcomes[setting]]
+        assert outcomes['0'][0][4] == (0, 0, 0), outcomes['0'][0][4]
+        return
     taken, overflows, cap = outcomes[None][0][4]
     assert cap >= 64 and taken >= 2 and taken + overflows == n_it - 1, outcomes[None][0][4]   # (one exchange per M-step; the first ones may overflow)
     taken16, overflows16, cap16 = outcomes['16'][0][4]
