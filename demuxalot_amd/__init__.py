@@ -8,5 +8,7 @@ from .utils import BarcodeHandler
 from .snp_counter import CompressedSNPCalls
 from .genotypes import ProbabilisticGenotypes
 from .demux import Demultiplexer, DevicePosteriors, invalidate_resident
+from .snp_detection import detect_snps_positions_from_calls, select_snps_from_calls
 
-__all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'invalidate_resident']
+__all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'invalidate_resident',
+           'detect_snps_positions_from_calls', 'select_snps_from_calls']

@@ -87,6 +87,9 @@ SIGNATURES = {
     'dmx_set_estep_mode': (c_int, [_P, c_int]),
     'dmx_get_guard_stats': (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     'dmx_set_msteps_expected': (c_int, [_P, c_int64]),
+    'dmx_snp_count': (c_int, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, c_int32, POINTER(c_int64)]),
+    'dmx_snp_score': (c_int, [_P, c_double, _P, _P, _P, _P, _P, _P]),
+    'dmx_snp_select': (c_int, [_P, c_int64, c_int64, _P, POINTER(c_int64)]),
 }
 # every symbol include/demux_hip_debug.h declares (tests, bench.py, scripts: switches, controller read-outs, self-tests)
 DEBUG_SIGNATURES = {

@@ -202,6 +202,13 @@ struct dmx_ctx {
     DevBuf<double> d_logits64, d_post64;  // float64 results of dmx_estep_snp
     bool have_post64 = false;
     DevBuf<unsigned char> d_scratch;  // self tests
+    // SNP detection (snp_detect.hip): read and written by the dmx_snp_* entry points only; sd_P < 0: no counts
+    DevBuf<unsigned long long> d_sd_pos;  // [sd_P] chrom << 32 | (position ^ 0x80000000), ascending (the canonical order)
+    DevBuf<int> d_sd_counts;              // [sd_P, sd_D, 4]
+    DevBuf<double> d_sd_imp;              // [sd_P, sd_D] importances (dmx_snp_score)
+    long long sd_P = -1;
+    int sd_D = 0;
+    bool sd_scored = false;
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at

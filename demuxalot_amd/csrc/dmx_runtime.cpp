@@ -569,6 +569,16 @@ void release_problem(dmx_ctx *c)
     c->G = c->K = 0;
 }
 
+void release_snp_detection(dmx_ctx *c)
+{
+    dev_free(c, c->d_sd_pos);
+    dev_free(c, c->d_sd_counts);
+    dev_free(c, c->d_sd_imp);
+    c->sd_P = -1;
+    c->sd_D = 0;
+    c->sd_scored = false;
+}
+
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)
 {
     if (!dst) return 0;
@@ -635,6 +645,7 @@ int dmx_destroy(dmx_ctx *c)
     comm_destroy(c);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     release_problem(c);
+    release_snp_detection(c);
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too
@@ -662,6 +673,7 @@ int dmx_release_problem(dmx_ctx *c)
     DMX_TRY(bind(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     release_problem(c);
+    release_snp_detection(c);
     dmx::release_staged_calls(c);
     return 0;
 }

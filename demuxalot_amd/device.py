@@ -29,6 +29,7 @@ class DeviceContext:
         self.K = 0
         self._resident_key = None
         self._keep_molecule_calls = False
+        self._snp_shape = (0, 0)
         self.apply_environment()
 
     def apply_environment(self):
@@ -365,6 +366,38 @@ class DeviceContext:
         n = ctypes.c_int64(0)
         check(self._lib.dmx_get_assignments_above(self._h, float(threshold), ptr(best), ptr(prob), ctypes.byref(n)))
         return best, prob, n.value
+
+    # ---- SNP detection (include/demux_hip.h: dmx_snp_count / _score / _select; demuxalot_amd/snp_detection.py) ----
+    def snp_count(self, containers, donor_of_barcode, n_donors, p_threshold=0.01, cap=3):
+        """Counts [position, donor, base] of the calls in `containers` ([(chrom number, snp_calls, molecules)] as for
+        pack_containers_and_set_problem) on the device; returns the number of positions.  The resident problem stays."""
+        parts, _keep_alive = self._container_list(containers)
+        donor_of_barcode = as_c(donor_of_barcode, np.int32)
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_snp_count(self._h, ctypes.cast(parts, ctypes.c_void_p), len(containers), ptr(donor_of_barcode),
+                                      len(donor_of_barcode), int(n_donors), float(np.float32(p_threshold)), int(cap),
+                                      ctypes.byref(n)))
+        self._snp_shape = (n.value, int(n_donors))
+        return n.value
+
+    def snp_score(self, regularization, fetch_counts=True, fetch_importances=True):
+        """dict chrom, pos (int32[P]), counts (int32[P, D, 4]), importances (float64[P, D]), bases (uint8[P, 2]: ref, alt),
+        base_totals (int64[P, 2]) of the last snp_count; counts / importances None unless fetched."""
+        P, D = self._snp_shape
+        out = dict(chrom=np.empty(P, np.int32), pos=np.empty(P, np.int32), bases=np.empty((P, 2), np.uint8),
+                   base_totals=np.empty((P, 2), np.int64),
+                   counts=np.empty((P, D, 4), np.int32) if fetch_counts else None,
+                   importances=np.empty((P, D), np.float64) if fetch_importances else None)
+        check(self._lib.dmx_snp_score(self._h, float(regularization), ptr(out['chrom']), ptr(out['pos']), ptr(out['counts']),
+                                      ptr(out['importances']), ptr(out['bases']), ptr(out['base_totals'])))
+        return out
+
+    def snp_select(self, n_best_per_donor, n_additional):
+        """Selected position indices (int64, ascending) of the last snp_score."""
+        selected = np.empty(max(1, self._snp_shape[0]), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_snp_select(self._h, int(n_best_per_donor), int(n_additional), ptr(selected), ctypes.byref(n)))
+        return selected[:n.value].copy()
 
     def get_top_options(self, k):
         """The k (<= 4) best options per barcode, best first: (int32[B, k], float32[B, k])."""

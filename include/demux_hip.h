@@ -350,6 +350,30 @@ int dmx_mstep_f64(dmx_ctx *ctx, double contribution_power, float *addition_out);
 int dmx_mstep_f64_sums(dmx_ctx *ctx, double contribution_power, double *sums_out);
 
 /* ------------------------------------------------------------------------- *
+ * SNP detection: the compute half of the reference's detect_snps_positions (demuxalot/snp_detection.py:78-125,
+ * 218-227) on calls at candidate positions (containers as for dmx_pack_containers_and_set_problem; `chrom` >= 0 is the
+ * chromosome's number in the caller's order).  Positions are numbered in the canonical order: chrom, then position
+ * ascending.  The state sits in buffers of its own: the resident problem, its results and every other entry point are
+ * untouched; dmx_release_problem and dmx_destroy free it.
+ *   dmx_snp_count   donor_of_barcode int32[n_barcodes] (-1: unassigned, else 0 .. n_donors-1).  A call counts when
+ *                   p_base_wrong < p_threshold (float32 comparison), base_index < 4 and its barcode is assigned; every
+ *                   (barcode, position, base) adds min(calls, cap) to counts[position, donor, base] (:105-125).
+ *                   *n_positions = positions with at least one such call.
+ *   dmx_snp_score   per position (:78-97): ref = the base of the largest total, alt = the next (stable ascending
+ *                   argsort: the higher base wins a tie); float64 importances in the reference's operation order.
+ *                   Outputs, all nullable: chrom / pos int32[P], counts int32[P*D*4], importances float64[P*D],
+ *                   bases uint8[P*2] (ref, alt), base_totals int64[P*2] (ref, alt).
+ *   dmx_snp_select  _select_top_snps (:218-227) with stable rankings (ties to the earlier position): the n_best_per_donor
+ *                   best positions of every donor, and the overall ranking by numpy's pairwise row sum up to the
+ *                   (n_additional + 1)-th position not chosen for a donor; selected int64[P] (nullable) receives the union
+ *                   in ascending order, *n_selected its length. */
+int dmx_snp_count(dmx_ctx *ctx, const dmx_call_container *containers, int32_t n_containers, const int32_t *donor_of_barcode,
+                  int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions);
+int dmx_snp_score(dmx_ctx *ctx, double regularization, int32_t *chrom, int32_t *pos, int32_t *counts, double *importances,
+                  uint8_t *bases, int64_t *base_totals);
+int dmx_snp_select(dmx_ctx *ctx, int64_t n_best_per_donor, int64_t n_additional, int64_t *selected, int64_t *n_selected);
+
+/* ------------------------------------------------------------------------- *
  * Multi-GPU: one ctx per rank, barcodes sharded by the caller (every rank installs the calls of ITS barcodes, all
  * variants, the whole beta table).  E-step rows need nothing from other ranks.  The M-step (demux.py:113-118) sums over
  * the calls of a variant, i.e. over the barcodes of all ranks; it is sharded on VARIANTS (slices cut at SNP boundaries,
