@@ -5,10 +5,10 @@ Drop-in names of the reference package (demuxalot/__init__.py:3-7) that belong t
 __version__ = '0.1.0'
 
 from .utils import BarcodeHandler
-from .snp_counter import CompressedSNPCalls
+from .snp_counter import CompressedSNPCalls, DecodedReads, count_snps_from_reads
 from .genotypes import ProbabilisticGenotypes
 from .demux import Demultiplexer, DevicePosteriors, invalidate_resident
 from .snp_detection import detect_snps_positions_from_calls, select_snps_from_calls
 
 __all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'invalidate_resident',
-           'detect_snps_positions_from_calls', 'select_snps_from_calls']
+           'detect_snps_positions_from_calls', 'select_snps_from_calls', 'DecodedReads', 'count_snps_from_reads']

@@ -90,6 +90,8 @@ SIGNATURES = {
     'dmx_snp_count': (c_int, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, c_int32, POINTER(c_int64)]),
     'dmx_snp_score': (c_int, [_P, c_double, _P, _P, _P, _P, _P, _P]),
     'dmx_snp_select': (c_int, [_P, c_int64, c_int64, _P, POINTER(c_int64)]),
+    'dmx_count_reads': (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), POINTER(c_int64)]),
+    'dmx_count_reads_fetch': (c_int, [_P, _P, _P]),
 }
 # every symbol include/demux_hip_debug.h declares (tests, bench.py, scripts: switches, controller read-outs, self-tests)
 DEBUG_SIGNATURES = {
@@ -118,7 +120,18 @@ DEBUG_SIGNATURES = {
     'dmx_test_expf': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_log2_hw': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_softmax': (c_int, [_P, _P, _P, c_int64, c_int64]),
+    'dmx_get_count_reads_timings': (c_int, [_P, POINTER(c_double)]),
 }
+
+COUNT_READS_STAGES = ('upload', 'walk', 'molecules', 'duplicates', 'observations', 'fold', 'order')  # dmx_get_count_reads_timings
+
+
+class DecodedReadsStruct(ctypes.Structure):
+    """dmx_decoded_reads of include/demux_hip.h."""
+    _fields_ = [('n_reads', c_int64), ('reference_start', _P), ('compressed_cb', _P), ('compressed_ub', _P), ('p_misaligned', _P),
+                ('alignment_score', _P), ('cigar_begin', _P), ('n_cigar', _P), ('seq_begin', _P), ('l_seq', _P),
+                ('n_cigar_ops', c_int64), ('cigar', _P), ('n_bases', c_int64), ('seq', _P), ('qual', _P)]
+
 
 _lib = None
 

@@ -1,0 +1,838 @@
+// count_reads.hip -- SNP call containers from decoded reads: the compute half of the reference's count_snps
+// (demuxalot/snp_counter.py:37-69, 142-276; include/demux_hip.h "Read counting"; the contract: DESIGN.md "Read counting").
+//
+//   1 walk     one lane per read: CIGAR -> reference_end, number of observations (binary search over the positions),
+//              error bits, event flag; the events (reads that enter another 1000-base segment) are compacted
+//   2 groups   reads sorted by (cb, ub, index) with rocPRIM; a max-scan gives the reach of every (cb, ub) run up to a read
+//              (earlier molecules of a run end below the later ones, so the run's prefix maximum IS the open molecule's);
+//              one lane per read finds the event that would flush the molecule after it by binary search (thresholds are
+//              monotone) and compares it with the run's next read: molecule boundaries, flushing events
+//   3 dups     reads sorted by (molecule, start | end, score), stable: a read equal to its predecessor is a duplicate.
+//              A UMI of thousands of PCR duplicates costs its share of two sorts, no lane walks it.
+//              p_group_misaligned: one lane per molecule over its compacted non-duplicate reads, float64, in read order
+//   4 emit     observations of the non-duplicate reads (count -> scan -> emit), sorted by (molecule, position), stable
+//   5 fold     one lane per (molecule, position): float64 products per base in read order, the 1000x rule.  A position
+//              covered by thousands of molecules is thousands of independent lanes.
+//   6 order    molecules by (flushing event, first read), calls by (molecule, first read that saw the position, position);
+//              packed records of MOLECULE_DTYPE / SNP_CALL_DTYPE
+//
+// The per-molecule and per-(molecule, position) products are sequential on purpose: their order fixes the float64 bits.
+// Nothing traps: malformed input sets a flag word the host reads.  The state (the records of the last call) lives in
+// dmx_ctx::d_cr_*, which nothing else touches; dmx_release_problem and dmx_destroy free it.
+#include <climits>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
+
+#include "dmx_host.h"
+
+namespace {
+
+using dmx::host::bind;
+typedef unsigned long long ull;
+
+constexpr int MOLECULE_BYTES = 12, SNP_CALL_BYTES = 13, SEGMENT = 1000, QUALITY_CAP = 40;
+// flag word
+constexpr int F_UNSORTED = 1, F_LAYOUT = 2, F_OP = 4, F_INDEX = 8, F_LETTER = 16, F_POSITIONS = 32;
+
+struct Scratch {
+    dmx_ctx *ctx;
+    std::vector<void *> ptrs;
+    explicit Scratch(dmx_ctx *c) : ctx(c) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch()
+    {
+        // an error return leaves with kernels and copies of this call still queued: they finish before their blocks go back
+        // to the context's cache (after a call that succeeded the stream is idle already)
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : ptrs) ctx_free(ctx, p);
+    }
+    template <typename T>
+    int get(T **out, size_t count)
+    {
+        void *p = nullptr;
+        const int rc = ctx_malloc(ctx, &p, (count ? count : 1) * sizeof(T));
+        if (rc) return rc;
+        ptrs.push_back(p);
+        *out = (T *)p;
+        return 0;
+    }
+};
+
+inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+inline int bits_for(ull n)  // bits that hold the values 0 .. n-1
+{
+    int b = 0;
+    while (b < 64 && (n - 1) >> b) b++;
+    return n <= 1 ? 0 : b;
+}
+
+template <typename T>
+int upload(Scratch &sc, T **out, const T *host, size_t count, hipStream_t st)
+{
+    DMX_TRY(sc.get(out, count));
+    if (count) HIP_TRY(hipMemcpyAsync(*out, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// out[i] = op(in[0] .. in[i]); the last entry is returned through *total (synchronises)
+template <typename Op>
+int inclusive_scan_total(Scratch &sc, const ull *in, ull *out, size_t n, ull *total, Op op, hipStream_t st)
+{
+    *total = 0;
+    if (n == 0) return 0;
+    size_t bytes = 0;
+    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, in, out, n, op, st));
+    char *tmp = nullptr;
+    DMX_TRY(sc.get(&tmp, bytes));
+    HIP_TRY(rocprim::inclusive_scan(tmp, bytes, in, out, n, op, st));
+    HIP_TRY(hipMemcpyAsync(total, out + n - 1, sizeof(ull), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int sum_scan(Scratch &sc, const ull *in, ull *out, size_t n, ull *total, hipStream_t st)
+{
+    return inclusive_scan_total(sc, in, out, n, total, rocprim::plus<ull>(), st);
+}
+
+// stable (LSD radix sort): equal keys keep their input order
+template <typename K, typename V>
+int sort_pairs(Scratch &sc, const K *keys_in, K *keys_out, const V *vals_in, V *vals_out, size_t n, unsigned end_bit, hipStream_t st)
+{
+    if (n == 0) return 0;
+    if (end_bit == 0) end_bit = 1;
+    size_t bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
+    char *tmp = nullptr;
+    DMX_TRY(sc.get(&tmp, bytes));
+    HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
+    return 0;
+}
+
+int launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DMX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+// the reads and positions on the device
+struct Reads {
+    long long n, n_ops, n_bases, P;
+    const int *start, *cb, *ub, *score, *n_cigar, *l_seq;
+    const double *p_misaligned;
+    const long long *cigar_begin, *seq_begin;
+    const unsigned *cigar;
+    const unsigned char *seq, *qual;
+    const int *positions;
+};
+
+__device__ __forceinline__ long long segment_of(long long start)  // Python's start // 1000
+{
+    return start >= 0 ? start / SEGMENT : -((-start + SEGMENT - 1) / SEGMENT);
+}
+
+// first index whose position is >= x
+__device__ __forceinline__ long long lower_bound(const int *__restrict__ positions, long long P, long long x)
+{
+    long long lo = 0, hi = P;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (positions[mid] < x)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_cr_positions(const int *__restrict__ positions, long long P, int *flags)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P || i == 0) return;
+    if (positions[i] <= positions[i - 1]) atomicOr(flags, F_POSITIONS);
+}
+
+// Stage 1.  A read whose arrays do not lie inside cigar / seq is flagged and treated as empty: nothing is read out of bounds.
+__global__ __launch_bounds__(256) void k_cr_walk(Reads R, int *__restrict__ end, ull *__restrict__ n_obs, unsigned char *__restrict__ err,
+                                                 ull *__restrict__ is_event, ull *__restrict__ key, unsigned *__restrict__ idx, int *flags)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n) return;
+    const long long start = R.start[i];
+    bool event = true;
+    if (i > 0) {
+        const long long before = R.start[i - 1];
+        if (start < before) atomicOr(flags, F_UNSORTED);
+        event = segment_of(start) != segment_of(before);
+    }
+    is_event[i] = event ? 1ull : 0ull;
+    long long c0 = R.cigar_begin[i], nc = R.n_cigar[i];
+    const long long s0 = R.seq_begin[i], ls = R.l_seq[i];
+    if (nc < 0 || c0 < 0 || c0 > R.n_ops || nc > R.n_ops - c0 || ls < 0 || s0 < 0 || s0 > R.n_bases || ls > R.n_bases - s0) {
+        atomicOr(flags, F_LAYOUT);
+        nc = 0;
+    }
+    long long ref = start, rd = 0, found = 0;
+    unsigned e = 0;
+    for (long long k = 0; k < nc; k++) {
+        const unsigned c = R.cigar[c0 + k];
+        const unsigned op = c & 15u;
+        const long long len = c >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            const long long lo = lower_bound(R.positions, R.P, ref), hi = lower_bound(R.positions, R.P, ref + len);
+            if (hi > lo) {
+                found += hi - lo;
+                if (rd + (R.positions[hi - 1] - ref) >= ls) e |= F_INDEX;  // the largest read index of the block
+            }
+            ref += len;
+            rd += len;
+        } else if (op == 2 || op == 3) {
+            ref += len;
+        } else if (op == 1 || op == 4 || op == 5 || op == 6) {
+            rd += len;
+        } else {
+            e |= F_OP;
+        }
+    }
+    if (ref > INT_MAX) {
+        atomicOr(flags, F_LAYOUT);
+        ref = INT_MAX;
+    }
+    end[i] = (int)ref;
+    n_obs[i] = (ull)found;
+    err[i] = (unsigned char)e;
+    key[i] = (ull)((unsigned)R.cb[i] ^ 0x80000000u) << 32 | ((unsigned)R.ub[i] ^ 0x80000000u);
+    idx[i] = (unsigned)i;
+}
+
+__global__ __launch_bounds__(256) void k_cr_events(const int *__restrict__ start, const ull *__restrict__ is_event, const ull *__restrict__ rank,
+                                                   long long n, long long *__restrict__ threshold, unsigned *__restrict__ event_read)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !is_event[i]) return;
+    threshold[rank[i] - 1] = (long long)start[i] - SEGMENT;
+    event_read[rank[i] - 1] = (unsigned)i;
+}
+
+__global__ __launch_bounds__(256) void k_cr_heads(const ull *__restrict__ sorted, long long n, ull *__restrict__ head)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    head[j] = (j == 0 || sorted[j] != sorted[j - 1]) ? 1ull : 0ull;
+}
+
+// run number << 32 | biased reference_end: the prefix maximum of these is (this run, the run's reach so far)
+__global__ __launch_bounds__(256) void k_cr_reach_in(const ull *__restrict__ run, const unsigned *__restrict__ idx, const int *__restrict__ end,
+                                                     long long n, ull *__restrict__ out)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    out[j] = run[j] << 32 | ((unsigned)end[idx[j]] ^ 0x80000000u);
+}
+
+// Stage 2.  Read j of the sorted order is the last of its molecule when its (cb, ub) run ends with it, or when the first
+// event after it that flushes the molecule (threshold above the reach) comes before the run's next read.
+__global__ __launch_bounds__(256) void k_cr_bounds(const ull *__restrict__ key, const unsigned *__restrict__ idx, const ull *__restrict__ reach,
+                                                   const ull *__restrict__ event_rank, const long long *__restrict__ threshold,
+                                                   const unsigned *__restrict__ event_read, long long n_events, long long n,
+                                                   ull *__restrict__ head, unsigned char *__restrict__ last, unsigned *__restrict__ flush)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned r = idx[j];
+    const long long m = (long long)(int)((unsigned)reach[j] ^ 0x80000000u);
+    long long lo = (long long)event_rank[r], hi = n_events;  // events after read r: numbers event_rank[r] ..
+    while (lo < hi) {                                        // the first of them whose threshold is above m
+        const long long mid = (lo + hi) >> 1;
+        if (threshold[mid] > m)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    const bool run_goes_on = j + 1 < n && key[j + 1] == key[j];
+    const bool is_last = !run_goes_on || (lo < n_events && event_read[lo] < idx[j + 1]);
+    last[j] = is_last ? 1 : 0;
+    flush[j] = (unsigned)lo;  // n_events: the final flush
+    if (j == 0) head[0] = 1ull;
+    if (j + 1 < n) head[j + 1] = is_last ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_cr_groups(const ull *__restrict__ key, const unsigned *__restrict__ idx, const ull *__restrict__ head,
+                                                   const ull *__restrict__ group_at, const unsigned char *__restrict__ last,
+                                                   const unsigned *__restrict__ flush, const int *__restrict__ start, long long n,
+                                                   unsigned *__restrict__ group_of_read, unsigned *__restrict__ g_first, unsigned *__restrict__ g_head,
+                                                   unsigned *__restrict__ g_flush, ull *__restrict__ g_key, ull *__restrict__ span_head)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned g = (unsigned)(group_at[j] - 1), r = idx[j];
+    group_of_read[r] = g;
+    if (head[j]) {
+        g_first[g] = r;
+        g_head[g] = (unsigned)j;
+        g_key[g] = key[j];
+    }
+    if (last[j]) g_flush[g] = flush[j];
+    // reads of one molecule with one start are neighbours here (the input is sorted by start): spans of (molecule, start)
+    span_head[j] = (head[j] || start[r] != start[idx[j - 1]]) ? 1ull : 0ull;
+}
+
+// Stage 3
+__global__ __launch_bounds__(256) void k_cr_dup_keys(const unsigned *__restrict__ idx, const int *__restrict__ end, const int *__restrict__ score,
+                                                     long long n, ull *__restrict__ key, unsigned *__restrict__ at)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned r = idx[j];
+    key[j] = (ull)(unsigned)end[r] << 32 | (unsigned)score[r];
+    at[j] = (unsigned)j;
+}
+
+__global__ __launch_bounds__(256) void k_cr_span_of(const unsigned *__restrict__ at, const ull *__restrict__ span_at, long long n,
+                                                    unsigned *__restrict__ span)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    span[t] = (unsigned)(span_at[at[t]] - 1);
+}
+
+// after the two stable sorts: spans in order, inside a span (end, score) ascending, equal reads by index
+__global__ __launch_bounds__(256) void k_cr_dups(const unsigned *__restrict__ span, const unsigned *__restrict__ at, const unsigned *__restrict__ idx,
+                                                 const int *__restrict__ end, const int *__restrict__ score, long long n,
+                                                 unsigned char *__restrict__ dup)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const unsigned r = idx[at[t]];
+    bool d = false;
+    if (t > 0 && span[t] == span[t - 1]) {
+        const unsigned q = idx[at[t - 1]];
+        d = end[q] == end[r] && score[q] == score[r];
+    }
+    dup[r] = d ? 1 : 0;
+}
+
+// per read: the observations it will emit, its error bits if it counts; per sorted read: is it kept
+__global__ __launch_bounds__(256) void k_cr_kept(const unsigned char *__restrict__ dup, const unsigned char *__restrict__ err,
+                                                 const unsigned *__restrict__ idx, long long n, ull *__restrict__ n_obs, ull *__restrict__ kept,
+                                                 int *flags)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    if (dup[j])
+        n_obs[j] = 0ull;
+    else if (err[j])
+        atomicOr(flags, (int)err[j]);
+    kept[j] = dup[idx[j]] ? 0ull : 1ull;
+}
+
+__global__ __launch_bounds__(256) void k_cr_kept_list(const ull *__restrict__ kept, const ull *__restrict__ kept_at, const unsigned *__restrict__ idx,
+                                                      long long n, unsigned *__restrict__ list)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n || !kept[j]) return;
+    list[kept_at[j] - 1] = idx[j];
+}
+
+// float64 product of p_misaligned over the molecule's kept reads, in read order, rounded once
+__global__ __launch_bounds__(256) void k_cr_group_p(const unsigned *__restrict__ g_head, const ull *__restrict__ kept_at, const unsigned *__restrict__ list,
+                                                    long long n_kept, const unsigned *__restrict__ group_of_read, const double *__restrict__ p,
+                                                    long long G, float *__restrict__ g_p)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    long long k = (long long)kept_at[g_head[g]] - 1;  // a molecule's first read is never a duplicate
+    double product = 1.0;
+    for (; k < n_kept; k++) {
+        const unsigned r = list[k];
+        if (group_of_read[r] != (unsigned)g) break;
+        product = product * p[r];
+    }
+    g_p[g] = (float)product;
+}
+
+// Stage 4: key (molecule << position_bits | position rank), value (read << 11 | base << 8 | quality), in (read, position) order
+__global__ __launch_bounds__(256) void k_cr_emit(Reads R, const ull *__restrict__ n_obs, const ull *__restrict__ obs_at,
+                                                 const unsigned *__restrict__ group_of_read, int position_bits, ull *__restrict__ key,
+                                                 ull *__restrict__ value, int *flags)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n || n_obs[i] == 0) return;
+    ull at = obs_at[i] - n_obs[i];
+    const ull stop = obs_at[i];
+    const long long c0 = R.cigar_begin[i], nc = R.n_cigar[i], s0 = R.seq_begin[i], ls = R.l_seq[i];
+    const ull g = group_of_read[i];
+    long long ref = R.start[i], rd = 0;
+    for (long long k = 0; k < nc; k++) {
+        const unsigned c = R.cigar[c0 + k];
+        const unsigned op = c & 15u;
+        const long long len = c >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            const long long lo = lower_bound(R.positions, R.P, ref), hi = lower_bound(R.positions, R.P, ref + len);
+            for (long long q = lo; q < hi && at < stop; q++) {
+                const long long b = rd + (R.positions[q] - ref);
+                unsigned code = 0, quality = 0;
+                if (b >= 0 && b < ls) {  // (otherwise F_INDEX is set already)
+                    const unsigned char letter = R.seq[s0 + b];
+                    quality = R.qual[s0 + b];
+                    code = letter == 'A' ? 0 : letter == 'C' ? 1 : letter == 'G' ? 2 : letter == 'T' ? 3 : letter == 'N' ? 4 : 5;
+                    if (code == 5) {
+                        atomicOr(flags, F_LETTER);
+                        code = 0;
+                    }
+                }
+                key[at] = g << position_bits | (ull)q;
+                value[at] = (ull)i << 11 | code << 8 | quality;
+                at++;
+            }
+            ref += len;
+            rd += len;
+        } else if (op == 2 || op == 3) {
+            ref += len;
+        } else if (op == 1 || op == 4 || op == 5 || op == 6) {
+            rd += len;
+        }
+    }
+}
+
+// Stage 5: the first observation of every (molecule, position) folds the run
+__global__ __launch_bounds__(256) void k_cr_fold(const ull *__restrict__ key, const ull *__restrict__ value, long long n,
+                                                 const double *__restrict__ table, int position_bits, ull *__restrict__ emits,
+                                                 unsigned *__restrict__ c_group, unsigned *__restrict__ c_first, unsigned char *__restrict__ c_base,
+                                                 float *__restrict__ c_p, unsigned char *__restrict__ has_call)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const ull k = key[t];
+    if (t > 0 && key[t - 1] == k) {
+        emits[t] = 0ull;
+        return;
+    }
+    double product[5] = {1.0, 1.0, 1.0, 1.0, 1.0};
+    unsigned seen = 0;
+    for (long long u = t; u < n && key[u] == k; u++) {
+        const unsigned v = (unsigned)value[u] & 0x7FFu;
+        const unsigned code = v >> 8, quality = v & 0xFFu;
+        const double p_wrong = table[quality < QUALITY_CAP ? quality : QUALITY_CAP];
+#pragma unroll
+        for (unsigned b = 0; b < 5; b++)
+            if (b == code) product[b] = product[b] * p_wrong;
+        seen |= 1u << code;
+    }
+    int left = 0, base = 0;
+    if (__popc(seen) > 1) {
+        double best = 0.0;
+        bool any = false;
+#pragma unroll
+        for (int b = 0; b < 5; b++)
+            if ((seen >> b & 1u) && (!any || product[b] < best)) {
+                best = product[b];
+                any = true;
+            }
+        const double limit = best * 1000.0;
+#pragma unroll
+        for (int b = 0; b < 5; b++)
+            if ((seen >> b & 1u) && product[b] <= limit) {
+                left++;
+                base = b;
+            }
+    } else {
+        left = 1;
+        base = __ffs((int)seen) - 1;
+    }
+    emits[t] = left == 1 ? 1ull : 0ull;
+    if (left != 1) return;
+    double p = product[0];
+#pragma unroll
+    for (int b = 1; b < 5; b++)
+        if (b == base) p = product[b];
+    const unsigned g = (unsigned)(k >> position_bits);
+    c_group[t] = g;
+    c_first[t] = (unsigned)(value[t] >> 11);  // the run is in read order: its first observation is the first read's
+    c_base[t] = (unsigned char)base;
+    c_p[t] = (float)p;
+    has_call[g] = 1;
+}
+
+// Stage 6
+__global__ __launch_bounds__(256) void k_cr_group_keys(const unsigned *__restrict__ g_flush, const unsigned *__restrict__ g_first, long long G,
+                                                       ull *__restrict__ key, unsigned *__restrict__ value)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    key[g] = (ull)g_flush[g] << 32 | g_first[g];
+    value[g] = (unsigned)g;
+}
+
+__global__ __launch_bounds__(256) void k_cr_group_flags(const unsigned *__restrict__ order, const unsigned char *__restrict__ has_call, long long G,
+                                                        ull *__restrict__ flag)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= G) return;
+    flag[k] = has_call[order[k]] ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_cr_molecules(const unsigned *__restrict__ order, const ull *__restrict__ flag, const ull *__restrict__ at,
+                                                      long long G, const ull *__restrict__ g_key, const float *__restrict__ g_p,
+                                                      unsigned *__restrict__ molecule_of_group, unsigned char *__restrict__ records)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= G || !flag[k]) return;
+    const unsigned g = order[k];
+    const ull m = at[k] - 1;
+    molecule_of_group[g] = (unsigned)m;
+    const int cb = (int)((unsigned)(g_key[g] >> 32) ^ 0x80000000u), ub = (int)((unsigned)g_key[g] ^ 0x80000000u);
+    int *record = (int *)(records + m * MOLECULE_BYTES);  // 12-byte records: 4-byte aligned
+    record[0] = cb;
+    record[1] = ub;
+    record[2] = __float_as_int(g_p[g]);
+}
+
+__global__ __launch_bounds__(256) void k_cr_call_keys(const ull *__restrict__ emits, const ull *__restrict__ at, long long n,
+                                                      const unsigned *__restrict__ c_group, const unsigned *__restrict__ c_first,
+                                                      const unsigned *__restrict__ molecule_of_group, ull *__restrict__ key,
+                                                      unsigned *__restrict__ source)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n || !emits[t]) return;
+    const ull o = at[t] - 1;
+    key[o] = (ull)molecule_of_group[c_group[t]] << 32 | c_first[t];
+    source[o] = (unsigned)t;
+}
+
+__global__ __launch_bounds__(256) void k_cr_calls(const ull *__restrict__ key, const unsigned *__restrict__ source, long long n_calls,
+                                                  const ull *__restrict__ obs_key, int position_bits, const int *__restrict__ positions,
+                                                  const unsigned char *__restrict__ c_base, const float *__restrict__ c_p,
+                                                  unsigned char *__restrict__ records)
+{
+    const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= n_calls) return;
+    const unsigned t = source[o];
+    const int molecule = (int)(key[o] >> 32);
+    const int position = positions[obs_key[t] & ((1ull << position_bits) - 1)];
+    const float p = c_p[t];
+    unsigned char *record = records + o * SNP_CALL_BYTES;  // packed 13-byte records: bytes
+    __builtin_memcpy(record, &molecule, 4);
+    __builtin_memcpy(record + 4, &position, 4);
+    record[8] = c_base[t];
+    __builtin_memcpy(record + 9, &p, 4);
+}
+
+// hipEvents at the stage boundaries (dmx_get_count_reads_timings)
+struct StageClock {
+    hipEvent_t ev[dmx::COUNT_READS_STAGES + 1] = {};
+    int n = 0;
+    ~StageClock()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int tick(hipStream_t st)
+    {
+        HIP_TRY(hipEventCreate(&ev[n]));
+        HIP_TRY(hipEventRecord(ev[n], st));
+        n++;
+        return 0;
+    }
+};
+
+int flag_error(int flags)
+{
+    if (flags & F_POSITIONS) return fail(DMX_ERR_INVALID, "count_reads: positions must be strictly ascending");
+    if (flags & F_LAYOUT) return fail(DMX_ERR_INVALID, "count_reads: a read's cigar / seq range lies outside the arrays, or its reference_end is beyond 2^31");
+    if (flags & F_UNSORTED) return fail(DMX_ERR_INVALID, "count_reads: reference_start must be non-decreasing in read order");
+    if (flags & F_OP) return fail(DMX_ERR_INVALID, "count_reads: unknown CIGAR operation (codes 0 .. 8 are known)");
+    if (flags & F_INDEX) return fail(DMX_ERR_INVALID, "count_reads: a SNP position falls on a base beyond l_seq");
+    if (flags & F_LETTER) return fail(DMX_ERR_INVALID, "count_reads: a base other than A, C, G, T, N at a SNP position");
+    return 0;
+}
+
+int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions, long long P, const double *table, long long *n_molecules,
+                long long *n_calls)
+{
+    hipStream_t st = c->stream;
+    dmx::host::release_count_reads(c);
+    const long long n = h->n_reads;
+    Scratch sc(c);
+    StageClock clock;
+    DMX_TRY(clock.tick(st));
+
+    // ---- upload
+    Reads R;
+    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases, R.P = P;
+    int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *d_positions, *flags;
+    double *d_p, *d_table;
+    long long *d_cigar_begin, *d_seq_begin;
+    unsigned *d_cigar;
+    unsigned char *d_seq, *d_qual;
+    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cb, h->compressed_cb, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_ub, h->compressed_ub, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_score, h->alignment_score, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_p, h->p_misaligned, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
+    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
+    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
+    DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
+    DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
+    DMX_TRY(sc.get(&flags, 1));
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+    R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
+    R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual, R.positions = d_positions;
+    DMX_TRY(clock.tick(st));
+
+    // ---- 1 walk
+    int *end;
+    ull *n_obs, *is_event, *event_rank, *key;
+    unsigned char *err;
+    unsigned *idx;
+    DMX_TRY(sc.get(&end, (size_t)n));
+    DMX_TRY(sc.get(&n_obs, (size_t)n));
+    DMX_TRY(sc.get(&is_event, (size_t)n));
+    DMX_TRY(sc.get(&event_rank, (size_t)n));
+    DMX_TRY(sc.get(&key, (size_t)n));
+    DMX_TRY(sc.get(&err, (size_t)n));
+    DMX_TRY(sc.get(&idx, (size_t)n));
+    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
+    DMX_TRY(launched("k_cr_positions"));
+    hipLaunchKernelGGL(k_cr_walk, dim3(grid_for(n)), dim3(256), 0, st, R, end, n_obs, err, is_event, key, idx, flags);
+    DMX_TRY(launched("k_cr_walk"));
+    ull n_events = 0;
+    DMX_TRY(sum_scan(sc, is_event, event_rank, (size_t)n, &n_events, st));  // (the caller's arrays are free to change from here on)
+    long long *threshold;
+    unsigned *event_read;
+    DMX_TRY(sc.get(&threshold, (size_t)n_events));
+    DMX_TRY(sc.get(&event_read, (size_t)n_events));
+    hipLaunchKernelGGL(k_cr_events, dim3(grid_for(n)), dim3(256), 0, st, d_start, is_event, event_rank, n, threshold, event_read);
+    DMX_TRY(launched("k_cr_events"));
+    DMX_TRY(clock.tick(st));
+
+    // ---- 2 groups
+    ull *skey, *head, *run, *reach_in, *reach, *group_at, *span_head, *span_at;
+    unsigned *sidx, *flush;
+    unsigned char *last;
+    DMX_TRY(sc.get(&skey, (size_t)n));
+    DMX_TRY(sc.get(&sidx, (size_t)n));
+    DMX_TRY(sc.get(&head, (size_t)n));
+    DMX_TRY(sc.get(&run, (size_t)n));
+    DMX_TRY(sc.get(&reach_in, (size_t)n));
+    DMX_TRY(sc.get(&reach, (size_t)n));
+    DMX_TRY(sc.get(&group_at, (size_t)n));
+    DMX_TRY(sc.get(&span_head, (size_t)n));
+    DMX_TRY(sc.get(&span_at, (size_t)n));
+    DMX_TRY(sc.get(&flush, (size_t)n));
+    DMX_TRY(sc.get(&last, (size_t)n));
+    DMX_TRY(sort_pairs(sc, key, skey, idx, sidx, (size_t)n, 64u, st));
+    hipLaunchKernelGGL(k_cr_heads, dim3(grid_for(n)), dim3(256), 0, st, skey, n, head);
+    DMX_TRY(launched("k_cr_heads"));
+    ull n_runs = 0, top = 0, G = 0, n_spans = 0;
+    DMX_TRY(sum_scan(sc, head, run, (size_t)n, &n_runs, st));
+    hipLaunchKernelGGL(k_cr_reach_in, dim3(grid_for(n)), dim3(256), 0, st, run, sidx, end, n, reach_in);
+    DMX_TRY(launched("k_cr_reach_in"));
+    DMX_TRY(inclusive_scan_total(sc, reach_in, reach, (size_t)n, &top, rocprim::maximum<ull>(), st));
+    hipLaunchKernelGGL(k_cr_bounds, dim3(grid_for(n)), dim3(256), 0, st, skey, sidx, reach, event_rank, threshold, event_read,
+                       (long long)n_events, n, head, last, flush);
+    DMX_TRY(launched("k_cr_bounds"));
+    DMX_TRY(sum_scan(sc, head, group_at, (size_t)n, &G, st));
+    unsigned *group_of_read, *g_first, *g_head, *g_flush;
+    ull *g_key;
+    float *g_p;
+    DMX_TRY(sc.get(&group_of_read, (size_t)n));
+    DMX_TRY(sc.get(&g_first, (size_t)G));
+    DMX_TRY(sc.get(&g_head, (size_t)G));
+    DMX_TRY(sc.get(&g_flush, (size_t)G));
+    DMX_TRY(sc.get(&g_key, (size_t)G));
+    DMX_TRY(sc.get(&g_p, (size_t)G));
+    hipLaunchKernelGGL(k_cr_groups, dim3(grid_for(n)), dim3(256), 0, st, skey, sidx, head, group_at, last, flush, d_start, n, group_of_read,
+                       g_first, g_head, g_flush, g_key, span_head);
+    DMX_TRY(launched("k_cr_groups"));
+    DMX_TRY(clock.tick(st));
+
+    // ---- 3 duplicates, p_group_misaligned
+    DMX_TRY(sum_scan(sc, span_head, span_at, (size_t)n, &n_spans, st));
+    ull *dkey = reach_in, *dkey_sorted = reach;  // (their contents are no longer needed)
+    unsigned *at, *at_sorted, *span, *span_sorted, *at_final;
+    unsigned char *dup;
+    DMX_TRY(sc.get(&at, (size_t)n));
+    DMX_TRY(sc.get(&at_sorted, (size_t)n));
+    DMX_TRY(sc.get(&span, (size_t)n));
+    DMX_TRY(sc.get(&span_sorted, (size_t)n));
+    DMX_TRY(sc.get(&at_final, (size_t)n));
+    DMX_TRY(sc.get(&dup, (size_t)n));
+    hipLaunchKernelGGL(k_cr_dup_keys, dim3(grid_for(n)), dim3(256), 0, st, sidx, end, d_score, n, dkey, at);
+    DMX_TRY(launched("k_cr_dup_keys"));
+    DMX_TRY(sort_pairs(sc, dkey, dkey_sorted, at, at_sorted, (size_t)n, 64u, st));
+    hipLaunchKernelGGL(k_cr_span_of, dim3(grid_for(n)), dim3(256), 0, st, at_sorted, span_at, n, span);
+    DMX_TRY(launched("k_cr_span_of"));
+    DMX_TRY(sort_pairs(sc, span, span_sorted, at_sorted, at_final, (size_t)n, (unsigned)bits_for(n_spans), st));
+    hipLaunchKernelGGL(k_cr_dups, dim3(grid_for(n)), dim3(256), 0, st, span_sorted, at_final, sidx, end, d_score, n, dup);
+    DMX_TRY(launched("k_cr_dups"));
+    ull *kept = run, *kept_at = head, *obs_at = is_event, n_kept = 0, n_observations = 0;
+    hipLaunchKernelGGL(k_cr_kept, dim3(grid_for(n)), dim3(256), 0, st, dup, err, sidx, n, n_obs, kept, flags);
+    DMX_TRY(launched("k_cr_kept"));
+    DMX_TRY(sum_scan(sc, kept, kept_at, (size_t)n, &n_kept, st));
+    unsigned *kept_list;
+    DMX_TRY(sc.get(&kept_list, (size_t)n_kept));
+    hipLaunchKernelGGL(k_cr_kept_list, dim3(grid_for(n)), dim3(256), 0, st, kept, kept_at, sidx, n, kept_list);
+    DMX_TRY(launched("k_cr_kept_list"));
+    hipLaunchKernelGGL(k_cr_group_p, dim3(grid_for((long long)G)), dim3(256), 0, st, g_head, kept_at, kept_list, (long long)n_kept, group_of_read,
+                       d_p, (long long)G, g_p);
+    DMX_TRY(launched("k_cr_group_p"));
+    DMX_TRY(clock.tick(st));
+
+    // ---- 4 observations
+    DMX_TRY(sum_scan(sc, n_obs, obs_at, (size_t)n, &n_observations, st));
+    int h_flags = 0;
+    HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    DMX_TRY(flag_error(h_flags));
+    const int position_bits = bits_for((ull)P), group_bits = bits_for(G);
+    if (position_bits + group_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu molecules x %lld positions do not fit a 64-bit key", G, P);
+    if (n_observations >= (1ull << 32)) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu observations in one call (at most 2^32 - 1): split the chromosome", n_observations);
+    const long long n_o = (long long)n_observations;
+    ull *okey, *oval, *okey_sorted, *oval_sorted;
+    DMX_TRY(sc.get(&okey, (size_t)n_o));
+    DMX_TRY(sc.get(&oval, (size_t)n_o));
+    DMX_TRY(sc.get(&okey_sorted, (size_t)n_o));
+    DMX_TRY(sc.get(&oval_sorted, (size_t)n_o));
+    hipLaunchKernelGGL(k_cr_emit, dim3(grid_for(n)), dim3(256), 0, st, R, n_obs, obs_at, group_of_read, position_bits, okey, oval, flags);
+    DMX_TRY(launched("k_cr_emit"));
+    DMX_TRY(sort_pairs(sc, okey, okey_sorted, oval, oval_sorted, (size_t)n_o, (unsigned)(position_bits + group_bits), st));
+    DMX_TRY(clock.tick(st));
+
+    // ---- 5 fold
+    ull *emits = okey, *emit_at = oval, n_c = 0;  // (the unsorted observations are no longer needed)
+    unsigned *c_group, *c_first;
+    unsigned char *c_base, *has_call;
+    float *c_p;
+    DMX_TRY(sc.get(&c_group, (size_t)n_o));
+    DMX_TRY(sc.get(&c_first, (size_t)n_o));
+    DMX_TRY(sc.get(&c_base, (size_t)n_o));
+    DMX_TRY(sc.get(&c_p, (size_t)n_o));
+    DMX_TRY(sc.get(&has_call, (size_t)G));
+    HIP_TRY(hipMemsetAsync(has_call, 0, (size_t)(G ? G : 1), st));
+    if (n_o) hipLaunchKernelGGL(k_cr_fold, dim3(grid_for(n_o)), dim3(256), 0, st, okey_sorted, oval_sorted, n_o, d_table, position_bits, emits,
+                                c_group, c_first, c_base, c_p, has_call);
+    DMX_TRY(launched("k_cr_fold"));
+    DMX_TRY(sum_scan(sc, emits, emit_at, (size_t)n_o, &n_c, st));
+    HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    DMX_TRY(flag_error(h_flags));
+    DMX_TRY(clock.tick(st));
+
+    // ---- 6 order, records
+    ull *gkey, *gkey_sorted, *gflag, *gflag_at, n_m = 0;
+    unsigned *gval, *gorder, *molecule_of_group;
+    DMX_TRY(sc.get(&gkey, (size_t)G));
+    DMX_TRY(sc.get(&gkey_sorted, (size_t)G));
+    DMX_TRY(sc.get(&gflag, (size_t)G));
+    DMX_TRY(sc.get(&gflag_at, (size_t)G));
+    DMX_TRY(sc.get(&gval, (size_t)G));
+    DMX_TRY(sc.get(&gorder, (size_t)G));
+    DMX_TRY(sc.get(&molecule_of_group, (size_t)G));
+    hipLaunchKernelGGL(k_cr_group_keys, dim3(grid_for((long long)G)), dim3(256), 0, st, g_flush, g_first, (long long)G, gkey, gval);
+    DMX_TRY(launched("k_cr_group_keys"));
+    DMX_TRY(sort_pairs(sc, gkey, gkey_sorted, gval, gorder, (size_t)G, (unsigned)(32 + bits_for(n_events + 1)), st));
+    hipLaunchKernelGGL(k_cr_group_flags, dim3(grid_for((long long)G)), dim3(256), 0, st, gorder, has_call, (long long)G, gflag);
+    DMX_TRY(launched("k_cr_group_flags"));
+    DMX_TRY(sum_scan(sc, gflag, gflag_at, (size_t)G, &n_m, st));
+    DMX_TRY(dev_alloc(c, c->d_cr_molecules, (size_t)n_m * MOLECULE_BYTES));
+    DMX_TRY(dev_alloc(c, c->d_cr_calls, (size_t)n_c * SNP_CALL_BYTES));
+    hipLaunchKernelGGL(k_cr_molecules, dim3(grid_for((long long)G)), dim3(256), 0, st, gorder, gflag, gflag_at, (long long)G, g_key, g_p,
+                       molecule_of_group, c->d_cr_molecules.p);
+    DMX_TRY(launched("k_cr_molecules"));
+    if (n_c) {
+        ull *ckey, *ckey_sorted;
+        unsigned *csrc, *csrc_sorted;
+        DMX_TRY(sc.get(&ckey, (size_t)n_c));
+        DMX_TRY(sc.get(&ckey_sorted, (size_t)n_c));
+        DMX_TRY(sc.get(&csrc, (size_t)n_c));
+        DMX_TRY(sc.get(&csrc_sorted, (size_t)n_c));
+        hipLaunchKernelGGL(k_cr_call_keys, dim3(grid_for(n_o)), dim3(256), 0, st, emits, emit_at, n_o, c_group, c_first, molecule_of_group, ckey, csrc);
+        DMX_TRY(launched("k_cr_call_keys"));
+        DMX_TRY(sort_pairs(sc, ckey, ckey_sorted, csrc, csrc_sorted, (size_t)n_c, (unsigned)(32 + bits_for(n_m)), st));
+        hipLaunchKernelGGL(k_cr_calls, dim3(grid_for((long long)n_c)), dim3(256), 0, st, ckey_sorted, csrc_sorted, (long long)n_c, okey_sorted,
+                           position_bits, d_positions, c_base, c_p, c->d_cr_calls.p);
+        DMX_TRY(launched("k_cr_calls"));
+    }
+    DMX_TRY(clock.tick(st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < dmx::COUNT_READS_STAGES; s++) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, clock.ev[s], clock.ev[s + 1]));
+        c->cr_stage_ms[s] = ms;
+    }
+    c->cr_molecules = (long long)n_m;
+    c->cr_calls = (long long)n_c;
+    *n_molecules = (long long)n_m;
+    *n_calls = (long long)n_c;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmx_count_reads(dmx_ctx *c, const dmx_decoded_reads *reads, const int32_t *positions, int64_t n_positions, const double *qual_table41,
+                    int64_t *n_molecules, int64_t *n_calls)
+{
+    DMX_TRY(bind(c));
+    if (!reads || !n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "count_reads: null argument");
+    if (reads->n_reads < 0 || reads->n_reads > INT_MAX) return fail(DMX_ERR_INVALID, "count_reads: n_reads must be 0 .. 2^31 - 1");
+    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads: bad positions");
+    if (reads->n_cigar_ops < 0 || reads->n_bases < 0 || (reads->n_cigar_ops && !reads->cigar) || (reads->n_bases && (!reads->seq || !reads->qual)))
+        return fail(DMX_ERR_INVALID, "count_reads: bad cigar / seq / qual arrays");
+    if (reads->n_reads && (!reads->reference_start || !reads->compressed_cb || !reads->compressed_ub || !reads->p_misaligned ||
+                           !reads->alignment_score || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
+        return fail(DMX_ERR_INVALID, "count_reads: null per-read array");
+    *n_molecules = *n_calls = 0;
+    if (reads->n_reads == 0) {
+        dmx::host::release_count_reads(c);
+        c->cr_molecules = c->cr_calls = 0;
+        for (double &ms : c->cr_stage_ms) ms = 0.0;
+        return 0;
+    }
+    long long n_m = 0, n_c = 0;
+    const int rc = count_reads(c, reads, positions, n_positions, qual_table41, &n_m, &n_c);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        return rc;
+    }
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+int dmx_count_reads_fetch(dmx_ctx *c, void *molecules_out, void *snp_calls_out)
+{
+    DMX_TRY(bind(c));
+    if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads before dmx_count_reads_fetch");
+    if ((c->cr_molecules && !molecules_out) || (c->cr_calls && !snp_calls_out)) return fail(DMX_ERR_INVALID, "count_reads_fetch: null output");
+    if (c->cr_molecules)
+        HIP_TRY(hipMemcpyAsync(molecules_out, c->d_cr_molecules.p, (size_t)c->cr_molecules * MOLECULE_BYTES, hipMemcpyDeviceToHost, c->stream));
+    if (c->cr_calls)
+        HIP_TRY(hipMemcpyAsync(snp_calls_out, c->d_cr_calls.p, (size_t)c->cr_calls * SNP_CALL_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int dmx_get_count_reads_timings(dmx_ctx *c, double *stage_ms)
+{
+    DMX_TRY(bind(c));
+    if (!stage_ms) return fail(DMX_ERR_INVALID, "null stage_ms");
+    if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads before dmx_get_count_reads_timings");
+    for (int s = 0; s < dmx::COUNT_READS_STAGES; s++) stage_ms[s] = c->cr_stage_ms[s];
+    return 0;
+}
+
+}  // extern "C"

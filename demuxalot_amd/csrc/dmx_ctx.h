@@ -209,6 +209,11 @@ struct dmx_ctx {
     long long sd_P = -1;
     int sd_D = 0;
     bool sd_scored = false;
+    // read counting (count_reads.hip): the records of the last dmx_count_reads; cr_molecules < 0: none
+    DevBuf<unsigned char> d_cr_molecules;  // [cr_molecules] packed 12-byte molecule records
+    DevBuf<unsigned char> d_cr_calls;      // [cr_calls] packed 13-byte call records
+    long long cr_molecules = -1, cr_calls = 0;
+    double cr_stage_ms[dmx::COUNT_READS_STAGES] = {};
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at

@@ -9,6 +9,8 @@
 
 namespace dmx {
 
+constexpr int COUNT_READS_STAGES = 7;  // stages dmx_count_reads times (count_reads.hip; dmx_get_count_reads_timings fills that many)
+
 // records a message for dmx_last_error() and returns `code`
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 

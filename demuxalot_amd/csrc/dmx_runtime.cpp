@@ -579,6 +579,14 @@ void release_snp_detection(dmx_ctx *c)
     c->sd_scored = false;
 }
 
+void release_count_reads(dmx_ctx *c)
+{
+    dev_free(c, c->d_cr_molecules);
+    dev_free(c, c->d_cr_calls);
+    c->cr_molecules = -1;
+    c->cr_calls = 0;
+}
+
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)
 {
     if (!dst) return 0;
@@ -646,6 +654,7 @@ int dmx_destroy(dmx_ctx *c)
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     release_problem(c);
     release_snp_detection(c);
+    release_count_reads(c);
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too
@@ -674,6 +683,7 @@ int dmx_release_problem(dmx_ctx *c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     release_problem(c);
     release_snp_detection(c);
+    release_count_reads(c);
     dmx::release_staged_calls(c);
     return 0;
 }

@@ -399,6 +399,31 @@ class DeviceContext:
         check(self._lib.dmx_snp_select(self._h, int(n_best_per_donor), int(n_additional), ptr(selected), ctypes.byref(n)))
         return selected[:n.value].copy()
 
+    # ---- read counting (include/demux_hip.h: dmx_count_reads / _fetch; demuxalot_amd/snp_counter.py) ----
+    def count_reads(self, reads, positions, qual_table):
+        """(molecules, snp_calls) structured arrays (snp_counter.MOLECULE_DTYPE / SNP_CALL_DTYPE) counted on the device from a
+        DecodedReads at the strictly ascending int32 `positions`; qual_table float64[41].  The resident problem stays."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+        positions = as_c(positions, np.int32)
+        qual_table = as_c(qual_table, np.float64)
+        assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
+        arrays = reads.arrays()  # C-contiguous arrays of the ABI's dtypes; kept alive until the call returns
+        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
+                                       **{name: ptr(a) for name, a in arrays.items()})
+        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.dmx_count_reads(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), ptr(positions), len(positions),
+                                        ptr(qual_table), ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
+        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
+        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
+        return molecules, snp_calls
+
+    def count_reads_timings(self):
+        """{stage: milliseconds} of the last count_reads (include/demux_hip_debug.h: dmx_get_count_reads_timings)."""
+        ms = (ctypes.c_double * len(_lib.COUNT_READS_STAGES))()
+        check(self._lib.dmx_get_count_reads_timings(self._h, ms))
+        return dict(zip(_lib.COUNT_READS_STAGES, ms))
+
     def get_top_options(self, k):
         """The k (<= 4) best options per barcode, best first: (int32[B, k], float32[B, k])."""
         options = np.empty((self.B, int(k)), dtype=np.int32)

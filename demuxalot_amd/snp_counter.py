@@ -1,13 +1,17 @@
 """CompressedSNPCalls: the input wire format of the hot path (mirror of the container at
-demuxalot/snp_counter.py:77-139; the BAM scanner that fills it is out of scope).
+demuxalot/snp_counter.py:77-139), and the step that fills it: the compute half of the reference's count_snps
+(snp_counter.py:37-69, 142-276) on the GPU, from reads the caller has decoded (include/demux_hip.h "Read counting",
+csrc/count_reads.hip; the contract is in DESIGN.md "Read counting").  Reading and decompressing BAM files stays with the caller.
 
-Two growable structured arrays whose first n_* entries are valid:
+Two structured arrays whose first n_* entries are valid:
   molecules  (compressed_cb i32, compressed_ub i32, p_group_misaligned f32)
   snp_calls  (molecule_index i32, snp_position i32, base_index u8, p_base_wrong f32)
 Demultiplexer reads only `[:n]` slices, so objects produced by the reference's count_snps can
-be passed in unchanged (duck typing); this class only holds the arrays (from_arrays builds one from
-plain columns) -- filling, growing and joining containers is the BAM scanner's business."""
+be passed in unchanged (duck typing).  from_arrays builds a container from plain columns, concatenate joins the
+containers of the regions of one chromosome, count_snps_from_reads produces them from DecodedReads."""
 import numpy as np
+
+from .device import get_context, shared_context_lock
 
 MOLECULE_DTYPE = np.dtype([('compressed_cb', 'int32'), ('compressed_ub', 'int32'), ('p_group_misaligned', 'float32')])
 SNP_CALL_DTYPE = np.dtype([('molecule_index', 'int32'), ('snp_position', 'int32'), ('base_index', 'uint8'),
@@ -39,3 +43,150 @@ class CompressedSNPCalls:
         out.snp_calls['p_base_wrong'] = p_base_wrong
         out.n_molecules, out.n_snp_calls = len(out.molecules), len(out.snp_calls)
         return out
+
+    def minimize_memory_footprint(self):
+        """Drops the unused tail of both arrays (snp_counter.py:114-118)."""
+        self.snp_calls = self.snp_calls[:self.n_snp_calls].copy()
+        self.molecules = self.molecules[:self.n_molecules].copy()
+        assert np.all(self.molecules['p_group_misaligned'] != -1)
+        assert np.all(self.snp_calls['p_base_wrong'] != -1)
+
+    @staticmethod
+    def concatenate(snp_calls_list) -> 'CompressedSNPCalls':
+        """Joins containers of the same chromosome, in the list's order (snp_counter.py:120-139): the molecule indices of
+        every part are shifted by the molecules before it."""
+        molecules, snp_calls, n_molecules = [], [], 0
+        for part in snp_calls_list:
+            calls = part.snp_calls[:part.n_snp_calls].copy()
+            calls['molecule_index'] += n_molecules
+            snp_calls.append(calls)
+            molecules.append(part.molecules[:part.n_molecules])
+            n_molecules += part.n_molecules
+        out = CompressedSNPCalls(start_snps_size=1, start_molecule_size=1)
+        out.molecules = np.concatenate(molecules)
+        out.snp_calls = np.concatenate(snp_calls)
+        out.n_molecules, out.n_snp_calls = len(out.molecules), len(out.snp_calls)
+        return out
+
+
+QUALITY_CAP = 40  # base qualities count up to this (snp_counter.py:172)
+
+
+def quality_table():
+    """float64[41]: probability that a base of quality q is wrong, with the reference's expression (snp_counter.py:172)."""
+    return np.array([0.1 ** (0.1 * q) for q in range(QUALITY_CAP + 1)], dtype=np.float64)
+
+
+class DecodedReads:
+    """The reads of one chromosome that the reference's scanner would keep (parse_read(read) and
+    barcode_handler.get_barcode_index(read) both not None), in fetch order, as plain arrays that mirror a BAM record:
+
+      per read  reference_start i32, compressed_cb i32, compressed_ub i32, p_misaligned f64, alignment_score i32 (AS),
+                cigar_begin i64, n_cigar i32, seq_begin i64, l_seq i32
+      cigar     u32, BAM-encoded (length << 4 | op); read r owns cigar[cigar_begin[r] : cigar_begin[r] + n_cigar[r]]
+      seq       u8, ASCII letters; qual u8; read r owns [seq_begin[r] : seq_begin[r] + l_seq[r]] of both
+    """
+    PER_READ = (('reference_start', np.int32), ('compressed_cb', np.int32), ('compressed_ub', np.int32),
+                ('p_misaligned', np.float64), ('alignment_score', np.int32), ('cigar_begin', np.int64), ('n_cigar', np.int32),
+                ('seq_begin', np.int64), ('l_seq', np.int32))
+    FLAT = (('cigar', np.uint32), ('seq', np.uint8), ('qual', np.uint8))
+
+    def __init__(self, **arrays):
+        expected = [name for name, _ in self.PER_READ + self.FLAT]
+        if sorted(arrays) != sorted(expected):
+            raise TypeError(f'DecodedReads takes exactly the arrays {expected}')
+        for name, dtype in self.PER_READ + self.FLAT:
+            value = np.ascontiguousarray(arrays[name], dtype=dtype)
+            if value.ndim != 1:
+                raise ValueError(f'{name} must be one-dimensional')
+            setattr(self, name, value)
+        for name, _ in self.PER_READ:
+            if len(getattr(self, name)) != len(self.reference_start):
+                raise ValueError(f'{name} has {len(getattr(self, name))} entries for {len(self.reference_start)} reads')
+        if len(self.seq) != len(self.qual):
+            raise ValueError('seq and qual must have the same length')
+        if self.n_reads >= 2 ** 31:
+            raise ValueError('at most 2^31 - 1 reads per call')
+
+    @property
+    def n_reads(self):
+        return len(self.reference_start)
+
+    def arrays(self):
+        return {name: getattr(self, name) for name, _ in self.PER_READ + self.FLAT}
+
+    @staticmethod
+    def from_reads(reads, barcode_handler, parse_read) -> 'DecodedReads':
+        """From an iterable of pysam-like reads (reference_start, cigartuples, seq, query_qualities, get_tag, has_tag, mapq),
+        with the two filters of the reference's scanner (snp_counter.py:251-256).  Host Python: for tests and for callers who
+        read their BAM files with pysam."""
+        columns = {name: [] for name, _ in DecodedReads.PER_READ}
+        cigar, seq, qual = [], [], []
+        n_cigar_total = n_seq_total = 0
+        for read in reads:
+            parsed = parse_read(read)
+            if parsed is None:
+                continue
+            cb = barcode_handler.get_barcode_index(read)
+            if cb is None:
+                continue
+            p_misaligned, ub = parsed
+            ops = [(int(length) << 4) | int(op) for op, length in read.cigartuples]
+            letters = np.frombuffer(read.seq.encode('ascii'), dtype=np.uint8)
+            qualities = np.asarray(read.query_qualities, dtype=np.uint8)
+            if len(qualities) != len(letters):
+                raise ValueError('a read has a different number of bases and qualities')
+            for name, value in (('reference_start', read.reference_start), ('compressed_cb', cb), ('compressed_ub', ub),
+                                ('p_misaligned', p_misaligned), ('alignment_score', read.get_tag('AS')),
+                                ('cigar_begin', n_cigar_total), ('n_cigar', len(ops)), ('seq_begin', n_seq_total),
+                                ('l_seq', len(letters))):
+                columns[name].append(value)
+            cigar.append(np.asarray(ops, dtype=np.uint32))
+            seq.append(letters)
+            qual.append(qualities)
+            n_cigar_total += len(ops)
+            n_seq_total += len(letters)
+
+        def flat(parts, dtype):
+            return np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype)
+        return DecodedReads(cigar=flat(cigar, np.uint32), seq=flat(seq, np.uint8), qual=flat(qual, np.uint8), **columns)
+
+
+def _container(molecules, snp_calls):
+    out = CompressedSNPCalls(start_snps_size=1, start_molecule_size=1)
+    out.molecules, out.snp_calls = molecules, snp_calls
+    out.n_molecules, out.n_snp_calls = len(molecules), len(snp_calls)
+    return out
+
+
+def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=None):
+    """count_snps (snp_counter.py:279-327) with the BAM reading replaced by reads the caller has decoded: per chromosome of
+    chromosome2positions (in its order) one device call that groups the reads into molecules, walks the CIGARs to the
+    SNP positions, multiplies the base-error probabilities and resolves conflicting bases (DESIGN.md "Read counting").
+
+    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing)
+    :param chromosome2positions: dict chromosome -> strictly ascending zero-based SNP positions
+    :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
+    :return: dict chromosome -> CompressedSNPCalls, record for record what the reference's count_call_variants_for_chromosome
+        returns.  A chromosome without reads gives an empty container; reads of a chromosome without positions are skipped.
+    """
+    if not isinstance(chromosome2reads, dict) or not isinstance(chromosome2positions, dict):
+        raise TypeError('chromosome2reads and chromosome2positions must be dicts keyed by chromosome')
+    table = quality_table()
+
+    def run(ctx):
+        result = {}
+        for chromosome, positions in chromosome2positions.items():
+            reads = chromosome2reads.get(chromosome)
+            if reads is not None and not isinstance(reads, DecodedReads):
+                raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads')
+            if reads is None or reads.n_reads == 0:
+                result[chromosome] = _container(np.zeros(0, dtype=MOLECULE_DTYPE), np.zeros(0, dtype=SNP_CALL_DTYPE))
+                continue
+            result[chromosome] = _container(*ctx.count_reads(reads, positions, table))
+        return result
+
+    if on_context is not None:
+        return run(on_context)
+    with shared_context_lock:
+        return run(get_context())

@@ -223,3 +223,39 @@ def as_objects(problem: SyntheticProblem, n_chromosomes=3):
             base_index=base_index[snp_of_call[sel] % 4, problem.variant_id[sel] % 2],
             p_base_wrong=problem.p_base_wrong[sel])
     return calls, genotypes, handler
+
+
+def generate_reads(n_reads, n_positions, read_length=100, n_barcodes=10_000, reads_per_molecule=3, seed=0):
+    """Decoded reads for the read-counting path (snp_counter.count_snps_from_reads): (DecodedReads, positions int32).
+    One chromosome of 1000 bases per SNP position; reads of `read_length` aligned bases (one M operation, every 16th read with
+    a 10-base N-skip in the middle) at sorted uniform starts; molecules of `reads_per_molecule` reads on average that start within
+    200 bases of each other, a tenth of the reads exactly at their molecule's anchor (complete duplicates of each other); letters uniform over
+    ACGT, qualities uniform over 2 .. 41."""
+    from .snp_counter import DecodedReads
+    rng = np.random.default_rng(seed)
+    length = 1000 * n_positions
+    positions = np.sort(rng.choice(length, size=n_positions, replace=False)).astype(np.int32)
+    n_molecules = max(1, n_reads // reads_per_molecule)
+    molecule = rng.integers(0, n_molecules, n_reads)
+    anchor = rng.integers(0, length - read_length - 300, n_molecules)
+    start = anchor[molecule] + rng.integers(0, 200, n_reads)
+    duplicate = rng.random(n_reads) < 0.1
+    start[duplicate] = anchor[molecule[duplicate]]
+    order = np.argsort(start, kind='stable')
+    start, molecule = start[order].astype(np.int32), molecule[order]
+    skip = (np.arange(n_reads) % 16 == 0) & ~duplicate[order]
+    n_cigar = np.where(skip, 3, 1).astype(np.int32)
+    cigar_begin = (np.cumsum(n_cigar, dtype=np.int64) - n_cigar).astype(np.int64)
+    cigar = np.full(int(n_cigar.sum()), read_length << 4, dtype=np.uint32)
+    half = read_length // 2
+    cigar[cigar_begin[skip]] = half << 4
+    cigar[cigar_begin[skip] + 1] = 10 << 4 | 3
+    cigar[cigar_begin[skip] + 2] = (read_length - half) << 4
+    reads = DecodedReads(
+        reference_start=start, compressed_cb=(molecule % n_barcodes).astype(np.int32), compressed_ub=(molecule // n_barcodes).astype(np.int32),
+        p_misaligned=np.full(n_reads, 0.01), alignment_score=np.full(n_reads, read_length - 2, dtype=np.int32),
+        cigar_begin=cigar_begin, n_cigar=n_cigar, seq_begin=np.arange(n_reads, dtype=np.int64) * read_length,
+        l_seq=np.full(n_reads, read_length, dtype=np.int32), cigar=cigar,
+        seq=np.frombuffer(b'ACGT', dtype=np.uint8)[rng.integers(0, 4, n_reads * read_length, dtype=np.uint8)],
+        qual=rng.integers(2, 42, n_reads * read_length, dtype=np.uint8))
+    return reads, positions

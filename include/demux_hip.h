@@ -374,6 +374,49 @@ int dmx_snp_score(dmx_ctx *ctx, double regularization, int32_t *chrom, int32_t *
 int dmx_snp_select(dmx_ctx *ctx, int64_t n_best_per_donor, int64_t n_additional, int64_t *selected, int64_t *n_selected);
 
 /* ------------------------------------------------------------------------- *
+ * Read counting: the compute half of the reference's count_snps (demuxalot/snp_counter.py:37-69, 142-276) on reads the
+ * caller has decoded from its BAM file: the reads of ONE chromosome that the reference's scanner keeps (parse_read and
+ * get_barcode_index both answer), in fetch order, as plain arrays (INTEGRATION.md "Filling DecodedReads from htslib").
+ * Read r owns cigar[cigar_begin[r] .. + n_cigar[r]) (BAM encoding: length << 4 | op) and [seq_begin[r] .. + l_seq[r]) of
+ * seq (ASCII letters) and qual.
+ *   dmx_count_reads        positions int32[n_positions]: strictly ascending zero-based SNP positions; qual_table41[q] =
+ *                          probability that a base of quality q is wrong, q = 0 .. 40 (the caller computes 0.1 ** (0.1 q)).
+ *                          Groups the reads into molecules by (cb, ub) and the reference's 1000-base flush rule, skips
+ *                          duplicates (equal start, end and alignment score within a molecule), walks the CIGARs to the
+ *                          positions, multiplies the error probabilities per (molecule, position, base) in float64 in read
+ *                          order, keeps a position when one base is left after the 1000x rule, and orders molecules and
+ *                          calls as the reference emits them (DESIGN.md "Read counting" has the contract in full).
+ *                          DMX_ERR_INVALID: reference_start decreasing, a range outside cigar / seq, positions not ascending,
+ *                          and, in a read that counts: a CIGAR operation above 8, a SNP position on a base beyond l_seq, a
+ *                          letter other than ACGTN at a SNP position.  Nothing traps on the device; the context stays usable.
+ *   dmx_count_reads_fetch  the packed records of the last dmx_count_reads into caller-owned buffers: molecules
+ *                          (int32 cb, int32 ub, float32 p_group_misaligned: 12 bytes), snp_calls (int32 molecule_index,
+ *                          int32 snp_position, uint8 base_index, float32 p_base_wrong: 13 bytes).
+ * The records sit in buffers of their own: the resident problem, its results and every other entry point are untouched;
+ * dmx_release_problem and dmx_destroy free them.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+    int64_t n_reads;                 /* < 2^31 */
+    const int32_t *reference_start;  /* [n_reads] non-decreasing */
+    const int32_t *compressed_cb;    /* [n_reads] */
+    const int32_t *compressed_ub;    /* [n_reads] */
+    const double *p_misaligned;      /* [n_reads] */
+    const int32_t *alignment_score;  /* [n_reads] the AS tag */
+    const int64_t *cigar_begin;      /* [n_reads] */
+    const int32_t *n_cigar;          /* [n_reads] */
+    const int64_t *seq_begin;        /* [n_reads] */
+    const int32_t *l_seq;            /* [n_reads] */
+    int64_t n_cigar_ops;
+    const uint32_t *cigar;           /* [n_cigar_ops] */
+    int64_t n_bases;
+    const uint8_t *seq;              /* [n_bases] */
+    const uint8_t *qual;             /* [n_bases] */
+} dmx_decoded_reads;
+int dmx_count_reads(dmx_ctx *ctx, const dmx_decoded_reads *reads, const int32_t *positions, int64_t n_positions,
+                    const double *qual_table41, int64_t *n_molecules, int64_t *n_calls);
+int dmx_count_reads_fetch(dmx_ctx *ctx, void *molecules_out, void *snp_calls_out);
+
+/* ------------------------------------------------------------------------- *
  * Multi-GPU: one ctx per rank, barcodes sharded by the caller (every rank installs the calls of ITS barcodes, all
  * variants, the whole beta table).  E-step rows need nothing from other ranks.  The M-step (demux.py:113-118) sums over
  * the calls of a variant, i.e. over the barcodes of all ranks; it is sharded on VARIANTS (slices cut at SNP boundaries,

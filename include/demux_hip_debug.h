@@ -175,6 +175,11 @@ int dmx_test_expf(dmx_ctx *ctx, const float *in, float *out, int64_t n);
 int dmx_test_log2_hw(dmx_ctx *ctx, const float *in, float *out, int64_t n);
 int dmx_test_softmax(dmx_ctx *ctx, const float *in, float *out, int64_t rows, int64_t cols);
 
+/* Stage times of the last dmx_count_reads, milliseconds between hipEvents on the ctx stream (scripts/count_reads_timing.py):
+ * stage_ms[7] = upload, CIGAR walk + events, molecules, duplicates + p_group_misaligned, observations (emit + sort),
+ * per-position folds, order + records (csrc/count_reads.hip). */
+int dmx_get_count_reads_timings(dmx_ctx *ctx, double *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif
