@@ -69,8 +69,6 @@ SIGNATURES = {
     'dmx_get_prior_betas': (c_int, [_P, _P]),
     'dmx_get_learnt_betas': (c_int, [_P, _P]),
     'dmx_exchange_slices': (c_int, [c_int64, _P, c_int32, _P, POINTER(c_int64), POINTER(c_int32)]),
-    'dmx_runtime_info': (c_int, [c_char_p, c_int64]),
-    'dmx_get_exchange_mode': (c_int, [_P, POINTER(c_int32)]),
     'dmx_comm_unique_id': (c_int, [_P]),
     'dmx_comm_init': (c_int, [_P, c_int, c_int, _P, c_int]),
     'dmx_comm_init_host': (c_int, [_P, c_int, c_int, _P, _P, c_int]),
@@ -85,13 +83,15 @@ SIGNATURES = {
     'dmx_trim_device_caches': (c_int, [c_int, POINTER(c_int64)]),
     'dmx_set_exact_additions': (c_int, [_P, c_int]),
     'dmx_set_estep_mode': (c_int, [_P, c_int]),
-    'dmx_get_guard_stats': (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     'dmx_set_msteps_expected': (c_int, [_P, c_int64]),
     'dmx_snp_count': (c_int, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, c_int32, POINTER(c_int64)]),
     'dmx_snp_score': (c_int, [_P, c_double, _P, _P, _P, _P, _P, _P]),
     'dmx_snp_select': (c_int, [_P, c_int64, c_int64, _P, POINTER(c_int64)]),
     'dmx_count_reads': (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), POINTER(c_int64)]),
     'dmx_count_reads_fetch': (c_int, [_P, _P, _P]),
+    'dmx_coverage_count': (c_int, [_P, _P, c_int32, c_int32, c_int32, _P]),
+    'dmx_coverage_candidates': (c_int, [_P, c_double, c_double, c_double, c_double, c_int64, POINTER(c_int64)]),
+    'dmx_coverage_fetch_candidates': (c_int, [_P, _P, _P]),
 }
 # every symbol include/demux_hip_debug.h declares (tests, bench.py, scripts: switches, controller read-outs, self-tests)
 DEBUG_SIGNATURES = {
@@ -120,9 +120,16 @@ DEBUG_SIGNATURES = {
     'dmx_test_expf': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_log2_hw': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_softmax': (c_int, [_P, _P, _P, c_int64, c_int64]),
+    'dmx_runtime_info': (c_int, [c_char_p, c_int64]),
+    'dmx_get_exchange_mode': (c_int, [_P, POINTER(c_int32)]),
+    'dmx_get_guard_stats': (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     'dmx_get_count_reads_timings': (c_int, [_P, POINTER(c_double)]),
+    'dmx_set_coverage_form': (c_int, [_P, c_int]),
+    'dmx_get_coverage_timings': (c_int, [_P, POINTER(c_double)]),
 }
 
+COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings
+COVERAGE_ATOMIC, COVERAGE_TILED = 0, 1  # dmx_set_coverage_form
 COUNT_READS_STAGES = ('upload', 'walk', 'molecules', 'duplicates', 'observations', 'fold', 'order')  # dmx_get_count_reads_timings
 
 
@@ -179,7 +186,7 @@ def as_c(a, dtype):
 
 def runtime_info():
     """{'hip': [files], 'rccl_mapped': [files], 'rccl_loaded': file or ''}: the HIP / RCCL runtime files this process
-    has mapped (include/demux_hip.h: dmx_runtime_info).  A multi-rank worker must show exactly one 'hip'."""
+    has mapped (include/demux_hip_debug.h: dmx_runtime_info).  A multi-rank worker must show exactly one 'hip'."""
     buf = ctypes.create_string_buffer(8192)
     check(load().dmx_runtime_info(buf, len(buf)))
     info = {'hip': [], 'rccl_mapped': [], 'rccl_loaded': ''}

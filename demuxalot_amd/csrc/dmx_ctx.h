@@ -214,6 +214,14 @@ struct dmx_ctx {
     DevBuf<unsigned char> d_cr_calls;      // [cr_calls] packed 13-byte call records
     long long cr_molecules = -1, cr_calls = 0;
     double cr_stage_ms[dmx::COUNT_READS_STAGES] = {};
+    // coverage (coverage.hip): the counts of the last dmx_coverage_count and the candidates of the last dmx_coverage_candidates,
+    // read and written by the dmx_coverage_* entry points only; cov_W < 0: no window counted, cov_candidates < 0: none selected
+    DevBuf<int> d_cov_counts;       // [4, cov_W] rows A, C, G, T
+    DevBuf<int> d_cov_cand_pos;     // [cov_candidates] absolute positions, ascending
+    DevBuf<int> d_cov_cand_counts;  // [cov_candidates, 4]
+    long long cov_W = -1, cov_start = 0, cov_candidates = -1;
+    int coverage_form = DMX_COVERAGE_TILED;  // dmx_set_coverage_form
+    double cov_stage_ms[dmx::COVERAGE_STAGES] = {};
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at

@@ -587,6 +587,15 @@ void release_count_reads(dmx_ctx *c)
     c->cr_calls = 0;
 }
 
+void release_coverage(dmx_ctx *c)
+{
+    dev_free(c, c->d_cov_counts);
+    dev_free(c, c->d_cov_cand_pos);
+    dev_free(c, c->d_cov_cand_counts);
+    c->cov_W = c->cov_candidates = -1;
+    c->cov_start = 0;
+}
+
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)
 {
     if (!dst) return 0;
@@ -655,6 +664,7 @@ int dmx_destroy(dmx_ctx *c)
     release_problem(c);
     release_snp_detection(c);
     release_count_reads(c);
+    release_coverage(c);
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too
@@ -684,6 +694,7 @@ int dmx_release_problem(dmx_ctx *c)
     release_problem(c);
     release_snp_detection(c);
     release_count_reads(c);
+    release_coverage(c);
     dmx::release_staged_calls(c);
     return 0;
 }

@@ -424,6 +424,42 @@ class DeviceContext:
         check(self._lib.dmx_get_count_reads_timings(self._h, ms))
         return dict(zip(_lib.COUNT_READS_STAGES, ms))
 
+    # ---- coverage (include/demux_hip.h: dmx_coverage_count / _candidates / _fetch_candidates; demuxalot_amd/snp_detection.py) ----
+    def coverage_count(self, reads, start, stop, quality_threshold=15, fetch=True):
+        """int32[4, stop - start] (rows A, C, G, T) counted on the device from a DecodedReads, by the rules of pysam's
+        count_coverage; None unless fetched (the window stays on the device for coverage_candidates).  The resident problem stays."""
+        arrays = reads.arrays()  # kept alive until the call returns
+        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
+                                       **{name: ptr(a) for name, a in arrays.items()})
+        out = np.empty((4, max(0, int(stop) - int(start))), dtype=np.int32) if fetch else None
+        check(self._lib.dmx_coverage_count(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), int(start), int(stop),
+                                           int(quality_threshold), ptr(out)))
+        return out
+
+    def coverage_candidates(self, minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                            minimum_fraction_of_ref_and_alt, max_snp_candidates, fetch_counts=False):
+        """Candidate positions of the last coverage_count: int32 absolute positions, ascending (with fetch_counts: and their
+        int32[n, 4] A, C, G, T counts)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_coverage_candidates(self._h, float(minimum_coverage), float(minimum_alternative_fraction),
+                                                float(minimum_alternative_coverage), float(minimum_fraction_of_ref_and_alt),
+                                                int(max_snp_candidates), ctypes.byref(n)))
+        positions = np.empty(n.value, dtype=np.int32)
+        counts = np.empty((n.value, 4), dtype=np.int32) if fetch_counts else None
+        check(self._lib.dmx_coverage_fetch_candidates(self._h, ptr(positions), ptr(counts)))
+        return (positions, counts) if fetch_counts else positions
+
+    def coverage_timings(self):
+        """{stage: milliseconds} of the last coverage_count and coverage_candidates (include/demux_hip_debug.h:
+        dmx_get_coverage_timings)."""
+        ms = (ctypes.c_double * len(_lib.COVERAGE_STAGES))()
+        check(self._lib.dmx_get_coverage_timings(self._h, ms))
+        return dict(zip(_lib.COVERAGE_STAGES, ms))
+
+    def set_coverage_form(self, form):
+        """_lib.COVERAGE_ATOMIC or _lib.COVERAGE_TILED (include/demux_hip_debug.h: dmx_set_coverage_form); same integers."""
+        check(self._lib.dmx_set_coverage_form(self._h, int(form)))
+
     def get_top_options(self, k):
         """The k (<= 4) best options per barcode, best first: (int32[B, k], float32[B, k])."""
         options = np.empty((self.B, int(k)), dtype=np.int32)
@@ -497,7 +533,7 @@ class DeviceContext:
 
     def exchange_mode(self):
         """None (no communicator) | 'variant' (M-step sharded on variants, posteriors all-gathered) | 'reduce_scatter' |
-        'allreduce' (exchanges of the per-rank sums); include/demux_hip.h: dmx_get_exchange_mode."""
+        'allreduce' (exchanges of the per-rank sums); include/demux_hip_debug.h: dmx_get_exchange_mode."""
         mode = ctypes.c_int32(0)
         check(self._lib.dmx_get_exchange_mode(self._h, ctypes.byref(mode)))
         return {0: None, 1: 'variant', 2: 'reduce_scatter', 3: 'allreduce'}[mode.value]
@@ -510,7 +546,7 @@ class DeviceContext:
 
     def guard_stats(self):
         """(barcodes the last guarded E-step redid exactly, the same over all E-steps since reset_timings, barcode rows
-        those E-steps walked); include/demux_hip.h: dmx_get_guard_stats."""
+        those E-steps walked); include/demux_hip_debug.h: dmx_get_guard_stats."""
         last, total, rows = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         check(self._lib.dmx_get_guard_stats(self._h, ctypes.byref(last), ctypes.byref(total), ctypes.byref(rows)))
         return last.value, total.value, rows.value

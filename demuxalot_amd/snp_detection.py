@@ -1,9 +1,25 @@
-"""Detection of new SNPs from the calls at candidate positions: the compute half of the reference's
-detect_snps_positions (demuxalot/snp_detection.py:78-125, 128-242), with counting, scoring and selection on the GPU
-(include/demux_hip.h "SNP detection", csrc/snp_detect.hip).  Reading BAM files - the coverage filter of stage 1 and
-count_snps - stays with the caller: the calls come as the containers count_snps produces.
+"""Detection of new SNPs: the compute half of the reference's detect_snps_positions (demuxalot/snp_detection.py:32-125,
+128-242) on the GPU.  Stage 1 - the per-base coverage of every read, the ref / alt filter and the max_snp_candidates cut
+(include/demux_hip.h "Coverage", csrc/coverage.hip) - gives the candidate positions from decoded reads; counting, scoring and
+selection (include/demux_hip.h "SNP detection", csrc/snp_detect.hip) work on the calls at those positions.
+detect_snps_positions_from_reads runs the whole chain from DecodedReads; reading and decompressing BAM files stays with the
+caller.
 
-Contract (what differs from the reference is marked):
+Contract of the coverage and the candidates (what differs from the reference is marked; DESIGN.md "Coverage and candidates"):
+  * the coverage is pysam's count_coverage with a read callback: every read counts, aligned pairs as pysam forms them (H and
+    P move neither cursor), a base counts when its quality is >= quality_threshold (or the threshold is 0) and its letter is
+    exactly one of A C G T
+  * ref / alt are the largest / second largest count of a position; the four comparisons of snp_detection.py:46-50 in float64
+  * more candidates than max_snp_candidates: those with the largest alt, a tie at the cut going to the HIGHER position (the
+    reference's unstable argsort leaves it to chance)
+  * positions are ABSOLUTE, start + index (for a fragment with start > 0 the reference hands window-relative indices to
+    count_snps: a bug that is not repeated)
+  * negative minimum_coverage / minimum_alternative_coverage, max_snp_candidates < 1 and non-finite thresholds raise
+    ValueError (they would let the reference's tail pick positions that are no candidates)
+  * DecodedReads by contract hold the reads with a whitelisted barcode only, while the reference's stage 1 filters by
+    parse_read alone: pass the larger set as coverage_reads to repeat that
+
+Contract of scoring and selection (what differs from the reference is marked):
   * a call counts when p_base_wrong < float32(0.01), its barcode has a donor, and (not in the reference, which raises
     IndexError) base_index < 4; every (barcode, position, base) adds min(calls, max_contribution_to_base_count_from_barcode)
   * importances are the reference's float64 formulas in its operation order; ref = the base of the largest total, alt
@@ -20,6 +36,7 @@ import pandas as pd
 
 from .demux import Demultiplexer, DevicePosteriors
 from .device import get_context, shared_context_lock
+from .snp_counter import DecodedReads, count_snps_from_reads
 
 P_BASE_WRONG_BELOW = np.float32(0.01)  # calls['p_base_wrong'] < 0.01 compares in float32 (snp_detection.py:111)
 ASSIGNMENT_THRESHOLD = 0.8             # posterior above which a barcode counts for its donor (snp_detection.py:166)
@@ -129,6 +146,145 @@ def detect_snps_positions_from_calls(known_calls, candidate_calls, genotypes, ba
         sorted_donors, donor_of_barcode = _donor_of_barcode(posteriors.assignments(ASSIGNMENT_THRESHOLD), barcode_handler)
         selected = _select_on(posteriors._ctx, candidate_calls, sorted_donors, donor_of_barcode, regularization,
                               n_best_snps_per_donor, n_additional_best_snps, max_contribution_to_base_count_from_barcode)
+    finally:
+        posteriors.close()
+    return _finish(selected, genotypes, ignore_known_snps, result_beta_prior_filename)
+
+
+def _check_candidate_arguments(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                               minimum_fraction_of_ref_and_alt, max_snp_candidates, max_fragment_step, quality_threshold):
+    for name, value in (('minimum_coverage', minimum_coverage), ('minimum_alternative_fraction', minimum_alternative_fraction),
+                        ('minimum_alternative_coverage', minimum_alternative_coverage),
+                        ('minimum_fraction_of_ref_and_alt', minimum_fraction_of_ref_and_alt)):
+        if not np.isfinite(value):
+            raise ValueError(f'{name} must be finite, got {value!r}')
+    for name, value in (('minimum_coverage', minimum_coverage), ('minimum_alternative_coverage', minimum_alternative_coverage)):
+        if value < 0:
+            raise ValueError(f'{name} must be >= 0, got {value!r}')
+    if int(max_snp_candidates) != max_snp_candidates or max_snp_candidates < 1:
+        raise ValueError(f'max_snp_candidates must be a positive integer, got {max_snp_candidates!r}')
+    if int(max_fragment_step) != max_fragment_step or max_fragment_step < 1:
+        raise ValueError(f'max_fragment_step must be a positive integer, got {max_fragment_step!r}')
+    if int(quality_threshold) != quality_threshold or not 0 <= quality_threshold <= 255:
+        raise ValueError(f'quality_threshold must be an integer 0 .. 255, got {quality_threshold!r}')
+
+
+def reference_ends(reads):
+    """int64 reference_end of every read of a DecodedReads: start + the operations that advance the reference (0, 2, 3, 7, 8)."""
+    cigar = reads.cigar
+    first, last = reads.cigar_begin, reads.cigar_begin + reads.n_cigar
+    if reads.n_reads and (reads.n_cigar.min() < 0 or first.min() < 0 or last.max() > len(cigar)):
+        raise ValueError("a read's cigar range lies outside the cigar array")
+    advances = np.isin(cigar & 15, (0, 2, 3, 7, 8)) * (cigar >> 4).astype(np.int64)
+    consumed = np.concatenate([[0], np.cumsum(advances, dtype=np.int64)])
+    return reads.reference_start.astype(np.int64) + consumed[last] - consumed[first]
+
+
+def coverage_from_reads(reads, start, stop, *, quality_threshold=15, on_context=None):
+    """The counterpart of pysam's AlignmentFile.count_coverage(chromosome, start, stop, quality_threshold, read_callback) on
+    the reads of one chromosome: int32[4, stop - start], rows A, C, G, T (the contract is in the module docstring).
+
+    :param reads: DecodedReads of the chromosome (reference_start non-decreasing)
+    :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
+    """
+    if not isinstance(reads, DecodedReads):
+        raise TypeError('reads must be a DecodedReads')
+    if not 0 <= start <= stop:
+        raise ValueError(f'the window must satisfy 0 <= start <= stop, got [{start}, {stop})')
+    if on_context is not None:
+        return on_context.coverage_count(reads, start, stop, quality_threshold)
+    with shared_context_lock:
+        return get_context().coverage_count(reads, start, stop, quality_threshold)
+
+
+def find_candidate_positions(chromosome2reads, *, minimum_coverage, minimum_alternative_fraction=0.01,
+                             minimum_alternative_coverage=100, max_snp_candidates=10000, minimum_fraction_of_ref_and_alt=0.98,
+                             max_fragment_step=10_000_000, chromosome2length=None, quality_threshold=15, on_context=None):
+    """Stage 1 of detect_snps_for_chromosome (snp_detection.py:32-57) for every fragment of every chromosome: coverage, the
+    ref / alt filter, the max_snp_candidates cut, on the device.  The fragments are the reference's (:194-195):
+    [k * max_fragment_step, min((k + 1) * max_fragment_step, length)); the cut applies per fragment.
+
+    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing)
+    :param chromosome2length: dict chromosome -> reference length; default (and for chromosomes it does not list): the largest
+        reference_end of the chromosome's reads
+    :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
+    :return: dict chromosome -> ascending int32 ABSOLUTE positions, in the order of chromosome2reads; a chromosome without
+        reads gives an empty array
+    """
+    if not isinstance(chromosome2reads, dict):
+        raise TypeError('chromosome2reads must be a dict chromosome -> DecodedReads')
+    _check_candidate_arguments(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                               minimum_fraction_of_ref_and_alt, max_snp_candidates, max_fragment_step, quality_threshold)
+    lengths = {}
+    for chromosome, reads in chromosome2reads.items():
+        if not isinstance(reads, DecodedReads):
+            raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads')
+        if chromosome2length is not None and chromosome in chromosome2length:
+            lengths[chromosome] = int(chromosome2length[chromosome])
+        else:
+            lengths[chromosome] = int(max(0, reference_ends(reads).max())) if reads.n_reads else 0
+        if lengths[chromosome] >= 2 ** 31:
+            raise ValueError(f'chromosome {chromosome!r}: length {lengths[chromosome]} is beyond 2^31 - 1')
+
+    def run(ctx):
+        result = {}
+        for chromosome, reads in chromosome2reads.items():
+            found = [np.zeros(0, dtype=np.int32)]
+            if reads.n_reads:
+                for start in range(0, lengths[chromosome], int(max_fragment_step)):
+                    ctx.coverage_count(reads, start, min(start + int(max_fragment_step), lengths[chromosome]), quality_threshold,
+                                       fetch=False)
+                    found.append(ctx.coverage_candidates(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                                                         minimum_fraction_of_ref_and_alt, int(max_snp_candidates)))
+            result[chromosome] = np.concatenate(found)
+        return result
+
+    if on_context is not None:
+        return run(on_context)
+    with shared_context_lock:
+        return run(get_context())
+
+
+def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handler, *, minimum_coverage,
+                                     minimum_alternative_fraction=0.01, minimum_alternative_coverage=100, max_snp_candidates=10000,
+                                     minimum_fraction_of_ref_and_alt=0.98, max_fragment_step=10_000_000, chromosome2length=None,
+                                     quality_threshold=15, regularization=3., n_best_snps_per_donor=100,
+                                     n_additional_best_snps=1000, max_contribution_to_base_count_from_barcode=3,
+                                     ignore_known_snps=True, result_beta_prior_filename=None, coverage_reads=None):
+    """detect_snps_positions (snp_detection.py:128-215) from decoded reads:
+      1. count_snps_from_reads at the genotypes' positions,
+      2. predict_posteriors without doublets, its posteriors left on the GPU, and their assignments(0.8),
+      3. find_candidate_positions,
+      4. count_snps_from_reads at the candidates,
+      5. scoring and selection as in detect_snps_positions_from_calls.
+    Steps 2 to 5 run on the posteriors' device context.  Chromosomes are taken in the order of chromosome2reads; a
+    chromosome without candidates is left out (the reference's `return []`).
+
+    :param coverage_reads: dict chromosome -> DecodedReads for step 3 when they differ from chromosome2reads.  The reference's
+        stage 1 counts every read parse_read accepts, while DecodedReads by contract also drop the reads without a whitelisted
+        barcode (INTEGRATION.md "Reads for the coverage pass"); the default counts the coverage over chromosome2reads.
+    :return: as select_snps_from_calls
+    """
+    _check_arguments({}, regularization, n_best_snps_per_donor, n_additional_best_snps, max_contribution_to_base_count_from_barcode)
+    _check_candidate_arguments(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                               minimum_fraction_of_ref_and_alt, max_snp_candidates, max_fragment_step, quality_threshold)
+    if coverage_reads is None:
+        coverage_reads = chromosome2reads
+    known_calls = count_snps_from_reads(chromosome2reads, genotypes.get_chromosome2positions())
+    posteriors = Demultiplexer.predict_posteriors(known_calls, genotypes, barcode_handler, doublet_prior=0.0, on_device=True)
+    try:
+        ctx = posteriors._ctx
+        sorted_donors, donor_of_barcode = _donor_of_barcode(posteriors.assignments(ASSIGNMENT_THRESHOLD), barcode_handler)
+        candidates = find_candidate_positions(
+            {chromosome: coverage_reads[chromosome] for chromosome in chromosome2reads if chromosome in coverage_reads},
+            minimum_coverage=minimum_coverage, minimum_alternative_fraction=minimum_alternative_fraction,
+            minimum_alternative_coverage=minimum_alternative_coverage, max_snp_candidates=max_snp_candidates,
+            minimum_fraction_of_ref_and_alt=minimum_fraction_of_ref_and_alt, max_fragment_step=max_fragment_step,
+            chromosome2length=chromosome2length, quality_threshold=quality_threshold, on_context=ctx)
+        candidates = {chromosome: positions for chromosome, positions in candidates.items() if len(positions)}
+        candidate_calls = count_snps_from_reads(chromosome2reads, candidates, on_context=ctx)
+        selected = _select_on(ctx, candidate_calls, sorted_donors, donor_of_barcode, regularization, n_best_snps_per_donor,
+                              n_additional_best_snps, max_contribution_to_base_count_from_barcode)
     finally:
         posteriors.close()
     return _finish(selected, genotypes, ignore_known_snps, result_beta_prior_filename)

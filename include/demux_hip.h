@@ -202,10 +202,6 @@ int dmx_set_msteps_expected(dmx_ctx *ctx, int64_t n);
 #define DMX_ESTEP_FAST 1
 #define DMX_ESTEP_GUARDED 2
 int dmx_set_estep_mode(dmx_ctx *ctx, int mode);
-/* Barcodes the guarded E-steps computed with the exact kernel (the queued ones, or all of them in an E-step that ran direct:
- * below): in the last E-step, and in all E-steps / out of how many barcode rows since the context was created or
- * dmx_reset_timings (instrumentation; any pointer may be NULL). */
-int dmx_get_guard_stats(dmx_ctx *ctx, int64_t *redone_last, int64_t *redone_total, int64_t *rows_total);
 /* The reference's learn_genotypes returns the learnt genotypes and the LAST iteration's posteriors - no logits (demux.py:55-66).  A
  * caller that will not read the logits of the last E-step of its dmx_em / dmx_run_iterations calls says so with needed = 0: that E-step
  * is then one "whose logits nobody reads" like the ones before it and may take the coarse pass - its posteriors proven within the
@@ -417,6 +413,44 @@ int dmx_count_reads(dmx_ctx *ctx, const dmx_decoded_reads *reads, const int32_t 
 int dmx_count_reads_fetch(dmx_ctx *ctx, void *molecules_out, void *snp_calls_out);
 
 /* ------------------------------------------------------------------------- *
+ * Coverage: stage 1 of the reference's detect_snps_for_chromosome (demuxalot/snp_detection.py:32-57) on decoded reads: the
+ * per-base coverage of a window of one chromosome, the ref / alt filter and the max_snp_candidates cut (DESIGN.md "Coverage
+ * and candidates" has the contract in full).
+ *   dmx_coverage_count             reads as for dmx_count_reads; compressed_cb, compressed_ub, p_misaligned and alignment_score
+ *                                  are not read (they may be null).  Window 0 <= start <= stop; quality_threshold 0 .. 255.
+ *                                  coverage_out (nullable) int32[4 * (stop - start)], rows A, C, G, T.  The rules are those of
+ *                                  pysam's count_coverage with a read callback: every read counts (no molecules, no duplicate
+ *                                  removal); the CIGAR walk is pysam's aligned pairs - operations 0, 7, 8 advance both cursors
+ *                                  and yield pairs (q, r), 1 and 4 advance the read cursor, 2 and 3 the reference cursor, 5 and 6
+ *                                  NEITHER (dmx_count_reads repeats the reference's own walker, which moves the read cursor on
+ *                                  H and P); a pair counts when start <= r < stop, quality_threshold == 0 or qual[q] >=
+ *                                  quality_threshold, and seq[q] is exactly one of A C G T (N, lower case and anything else are
+ *                                  not counted).  DMX_ERR_INVALID, whatever the window: reference_start decreasing, a range
+ *                                  outside cigar / seq, a CIGAR operation above 8, an aligned base beyond l_seq, a
+ *                                  reference_end beyond 2^31 - 1.  Nothing traps on the device; the context stays usable.
+ *   dmx_coverage_candidates        on the last counted window (:44-57): total = the column sum, ref / alt = the largest / second
+ *                                  largest of the four counts as values; a position is a candidate when (ref + alt) >
+ *                                  minimum_coverage, (ref + alt) > minimum_fraction_of_ref_and_alt * total, alt >
+ *                                  minimum_alternative_coverage and alt > ref * minimum_alternative_fraction (float64: the two
+ *                                  products rounded once, the comparisons exact).  If more than max_snp_candidates qualify, those
+ *                                  with the largest alt are kept, a tie at the cut going to the HIGHER position (the tail of a
+ *                                  stable ascending argsort; the reference's argsort leaves it to chance).  DMX_ERR_INVALID: a
+ *                                  threshold that is not finite, minimum_coverage or minimum_alternative_coverage below 0,
+ *                                  max_snp_candidates below 1 (they would let the reference's tail pick non-candidates).
+ *   dmx_coverage_fetch_candidates  positions_out int32[n_candidates]: ABSOLUTE positions (start + index; the reference hands
+ *                                  window-relative indices on), ascending; counts_out (nullable) int32[n_candidates * 4]: their
+ *                                  A, C, G, T counts.
+ * The window and the candidates sit in buffers of their own: the resident problem, the SNP-detection state, the records of
+ * dmx_count_reads and every other entry point are untouched; dmx_release_problem and dmx_destroy free them.
+ * ------------------------------------------------------------------------- */
+int dmx_coverage_count(dmx_ctx *ctx, const dmx_decoded_reads *reads, int32_t start, int32_t stop, int32_t quality_threshold,
+                       int32_t *coverage_out);
+int dmx_coverage_candidates(dmx_ctx *ctx, double minimum_coverage, double minimum_alternative_fraction,
+                            double minimum_alternative_coverage, double minimum_fraction_of_ref_and_alt,
+                            int64_t max_snp_candidates, int64_t *n_candidates);
+int dmx_coverage_fetch_candidates(dmx_ctx *ctx, int32_t *positions_out, int32_t *counts_out);
+
+/* ------------------------------------------------------------------------- *
  * Multi-GPU: one ctx per rank, barcodes sharded by the caller (every rank installs the calls of ITS barcodes, all
  * variants, the whole beta table).  E-step rows need nothing from other ranks.  The M-step (demux.py:113-118) sums over
  * the calls of a variant, i.e. over the barcodes of all ranks; it is sharded on VARIANTS (slices cut at SNP boundaries,
@@ -452,22 +486,6 @@ int dmx_count_reads_fetch(dmx_ctx *ctx, void *molecules_out, void *snp_calls_out
  * communicator attached (or dmx_comm_init* with a problem resident), dmx_probs_from_betas, dmx_mstep (all ranks pass
  * addition_out or none does), dmx_em, dmx_run_iterations, dmx_get_addition.
  * ------------------------------------------------------------------------- */
-/* The exchange the resident problem runs (see above): no communicator, or with one attached the M-step sharded on
- * variants / the reduce-scatter of the sums / the all-reduce of the sums (with one rank nothing travels either way). */
-#define DMX_EXCHANGE_NONE 0
-#define DMX_EXCHANGE_VARIANT 1
-#define DMX_EXCHANGE_REDUCE_SCATTER 2
-#define DMX_EXCHANGE_ALLREDUCE 3
-int dmx_get_exchange_mode(dmx_ctx *ctx, int32_t *mode);
-
-/* Which HIP / RCCL runtime files this process has mapped, one "key=path" per line: hip=... (one line per distinct
- * libamdhip64 - exactly one in a healthy process), rccl_mapped=..., rccl_loaded=<the file dmx_comm_* bound, if any>.
- * RCCL is always taken from the directory of the HIP runtime libdemux_hip.so itself resolved, and dmx_comm_unique_id /
- * dmx_comm_init refuse a process that has two HIP runtimes mapped (e.g. one that imported torch): streams and
- * buffers of one runtime must not be handed to collectives of another.  Environment: DEMUXALOT_AMD_RCCL=<file>,
- * DEMUXALOT_AMD_ALLOW_FOREIGN_RCCL=1. */
-int dmx_runtime_info(char *out, int64_t capacity);
-
 /* Host only: the variant slices dmx_comm_init would cut for nranks ranks: cuts int64[nranks + 1] (first variant of
  * every slice, each at the first variant of a SNP), *slice_rows = rows of the longest slice (nullable),
  * *contiguous = 1 when every SNP's variants are contiguous in the numbering (nullable). */

@@ -175,10 +175,46 @@ int dmx_test_expf(dmx_ctx *ctx, const float *in, float *out, int64_t n);
 int dmx_test_log2_hw(dmx_ctx *ctx, const float *in, float *out, int64_t n);
 int dmx_test_softmax(dmx_ctx *ctx, const float *in, float *out, int64_t rows, int64_t cols);
 
+/* ------------------------------------------------------------------------- *
+ * Read-outs that describe what the library did or loaded, for tests, bench.py and diagnostics; no front-end needs them to
+ * run the path (they sat in demux_hip.h until the coverage entry points took their places there: the public header stays
+ * at 64 entry points at most).
+ * ------------------------------------------------------------------------- */
+/* Barcodes the guarded E-steps computed with the exact kernel (the queued ones, or all of them in an E-step that ran direct): in the last E-step, and in all E-steps / out of how many barcode rows since the context was created or
+ * dmx_reset_timings (instrumentation; any pointer may be NULL). */
+int dmx_get_guard_stats(dmx_ctx *ctx, int64_t *redone_last, int64_t *redone_total, int64_t *rows_total);
+
+/* The exchange the resident problem runs (demux_hip.h "Multi-GPU"): no communicator, or with one attached the M-step sharded on
+ * variants / the reduce-scatter of the sums / the all-reduce of the sums (with one rank nothing travels either way). */
+#define DMX_EXCHANGE_NONE 0
+#define DMX_EXCHANGE_VARIANT 1
+#define DMX_EXCHANGE_REDUCE_SCATTER 2
+#define DMX_EXCHANGE_ALLREDUCE 3
+int dmx_get_exchange_mode(dmx_ctx *ctx, int32_t *mode);
+
+/* Which HIP / RCCL runtime files this process has mapped, one "key=path" per line: hip=... (one line per distinct
+ * libamdhip64 - exactly one in a healthy process), rccl_mapped=..., rccl_loaded=<the file dmx_comm_* bound, if any>.
+ * RCCL is always taken from the directory of the HIP runtime libdemux_hip.so itself resolved, and dmx_comm_unique_id /
+ * dmx_comm_init refuse a process that has two HIP runtimes mapped (e.g. one that imported torch): streams and
+ * buffers of one runtime must not be handed to collectives of another.  Environment: DEMUXALOT_AMD_RCCL=<file>,
+ * DEMUXALOT_AMD_ALLOW_FOREIGN_RCCL=1. */
+int dmx_runtime_info(char *out, int64_t capacity);
+
 /* Stage times of the last dmx_count_reads, milliseconds between hipEvents on the ctx stream (scripts/count_reads_timing.py):
  * stage_ms[7] = upload, CIGAR walk + events, molecules, duplicates + p_group_misaligned, observations (emit + sort),
  * per-position folds, order + records (csrc/count_reads.hip). */
 int dmx_get_count_reads_timings(dmx_ctx *ctx, double *stage_ms);
+
+/* The accumulation form of dmx_coverage_count (csrc/coverage.hip): no-return global atomics into the dense window, or position
+ * tiles in LDS that are stored once (the default: DESIGN.md "Coverage and candidates" has the measurements).  Both give the
+ * same integers; the switch exists for scripts/coverage_timing.py and for the tests that compare the two. */
+#define DMX_COVERAGE_ATOMIC 0
+#define DMX_COVERAGE_TILED 1
+int dmx_set_coverage_form(dmx_ctx *ctx, int form);
+/* Stage times of the last dmx_coverage_count and dmx_coverage_candidates, milliseconds between hipEvents on the ctx stream
+ * (scripts/coverage_timing.py): stage_ms[6] = upload (with clearing the window), CIGAR walk + prefix maximum, window / tile bounds,
+ * accumulate; filter + compaction, top-n + emit (0 until dmx_coverage_candidates has run on the window). */
+int dmx_get_coverage_timings(dmx_ctx *ctx, double *stage_ms);
 
 #ifdef __cplusplus
 }
