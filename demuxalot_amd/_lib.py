@@ -124,6 +124,11 @@ DEBUG_SIGNATURES = {
     'dmx_get_exchange_mode': (c_int, [_P, POINTER(c_int32)]),
     'dmx_get_guard_stats': (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     'dmx_get_count_reads_timings': (c_int, [_P, POINTER(c_double)]),
+    'dmx_count_reads_begin': (c_int, [_P, _P, c_int64, _P]),
+    'dmx_count_reads_push': (c_int, [_P, _P, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    'dmx_count_reads_end': (c_int, [_P]),
+    'dmx_get_count_reads_carry': (c_int, [_P, POINTER(c_int64)]),
+    'dmx_get_count_reads_peak_bytes': (c_int, [_P, POINTER(c_int64)]),
     'dmx_set_coverage_form': (c_int, [_P, c_int]),
     'dmx_get_coverage_timings': (c_int, [_P, POINTER(c_double)]),
 }

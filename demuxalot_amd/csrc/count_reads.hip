@@ -21,6 +21,11 @@
 // The per-molecule and per-(molecule, position) products are sequential on purpose: their order fixes the float64 bits.
 // Nothing traps: malformed input sets a flag word the host reads.  The state (the records of the last call) lives in
 // dmx_ctx::d_cr_*, which nothing else touches; dmx_release_problem and dmx_destroy free it.
+//
+// Streaming (dmx_count_reads_begin / _push / _end, include/demux_hip_debug.h; DESIGN.md "Read counting", "Streaming"): a push runs the same six stages on
+// carry + chunk.  The carry, the reads of the molecules no event has flushed yet, stays on the device between pushes
+// (dmx_ctx::d_crs_*).  Carried reads are never events; molecules whose flushing event is "none" are left out of stages 3 to 6
+// of a push that is not final, and their reads are compacted into the next carry.
 #include <climits>
 #include <cstring>
 
@@ -78,16 +83,21 @@ __global__ __launch_bounds__(256) void k_cr_positions(const int *__restrict__ po
 
 // Stage 1.  A read whose arrays do not lie inside cigar / seq is flagged and treated as empty: nothing is read out of bounds.
 __global__ __launch_bounds__(256) void k_cr_walk(Reads R, int *__restrict__ end, ull *__restrict__ n_obs, unsigned char *__restrict__ err,
-                                                 ull *__restrict__ is_event, ull *__restrict__ key, unsigned *__restrict__ idx, int *flags)
+                                                 ull *__restrict__ is_event, ull *__restrict__ key, unsigned *__restrict__ idx, int *flags,
+                                                 long long n_carry, int has_previous, long long previous_start)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R.n) return;
     const long long start = R.start[i];
-    bool event = true;
-    if (i > 0) {
-        const long long before = R.start[i - 1];
+    // a stream's carried reads (the first n_carry) are never events; the first read behind them is compared with the last read
+    // of the previous chunk, which need not be among them
+    bool event = false;
+    if (i == n_carry && !has_previous) {
+        event = true;  // the first read of a chromosome
+    } else if (i > 0 || i == n_carry) {
+        const long long before = i == n_carry ? previous_start : R.start[i - 1];
         if (start < before) atomicOr(flags, F_UNSORTED);
-        event = segment_of(start) != segment_of(before);
+        event = i >= n_carry && segment_of(start) != segment_of(before);
     }
     is_event[i] = event ? 1ull : 0ull;
     long long c0 = R.cigar_begin[i], nc = R.n_cigar[i];
@@ -237,13 +247,14 @@ __global__ __launch_bounds__(256) void k_cr_dups(const unsigned *__restrict__ sp
 }
 
 // per read: the observations it will emit, its error bits if it counts; per sorted read: is it kept
+// (a read of an open molecule of a stream neither observes nor errs in this push: it is judged when its molecule is emitted)
 __global__ __launch_bounds__(256) void k_cr_kept(const unsigned char *__restrict__ dup, const unsigned char *__restrict__ err,
-                                                 const unsigned *__restrict__ idx, long long n, ull *__restrict__ n_obs, ull *__restrict__ kept,
-                                                 int *flags)
+                                                 const unsigned char *__restrict__ open, const unsigned *__restrict__ idx, long long n,
+                                                 ull *__restrict__ n_obs, ull *__restrict__ kept, int *flags)
 {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    if (dup[j])
+    if (dup[j] || open[j])
         n_obs[j] = 0ull;
     else if (err[j])
         atomicOr(flags, (int)err[j]);
@@ -427,12 +438,12 @@ __global__ __launch_bounds__(256) void k_cr_call_keys(const ull *__restrict__ em
 __global__ __launch_bounds__(256) void k_cr_calls(const ull *__restrict__ key, const unsigned *__restrict__ source, long long n_calls,
                                                   const ull *__restrict__ obs_key, int position_bits, const int *__restrict__ positions,
                                                   const unsigned char *__restrict__ c_base, const float *__restrict__ c_p,
-                                                  unsigned char *__restrict__ records)
+                                                  long long molecule_base, unsigned char *__restrict__ records)
 {
     const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= n_calls) return;
     const unsigned t = source[o];
-    const int molecule = (int)(key[o] >> 32);
+    const int molecule = (int)(molecule_base + (long long)(key[o] >> 32));  // (a stream counts its molecules on across pushes)
     const int position = positions[obs_key[t] & ((1ull << position_bits) - 1)];
     const float p = c_p[t];
     unsigned char *record = records + o * SNP_CALL_BYTES;  // packed 13-byte records: bytes
@@ -440,6 +451,115 @@ __global__ __launch_bounds__(256) void k_cr_calls(const ull *__restrict__ key, c
     __builtin_memcpy(record + 4, &position, 4);
     record[8] = c_base[t];
     __builtin_memcpy(record + 9, &p, 4);
+}
+
+// ---- streaming: the combined input of a push, the open molecules, the next carry
+
+// The chunk's reads lie behind the carry's in the combined arrays: their cigar_begin / seq_begin move by the carry's lengths.
+// A begin outside the chunk's own arrays is flagged and pinned to the chunk's end (the walk then sees an empty or flagged read).
+__global__ __launch_bounds__(256) void k_cr_rebase(long long *__restrict__ cigar_begin, long long *__restrict__ seq_begin, long long n_carry,
+                                                   long long n, long long carry_ops, long long carry_bases, long long chunk_ops,
+                                                   long long chunk_bases, int *flags)
+{
+    const long long i = n_carry + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long c0 = cigar_begin[i], s0 = seq_begin[i];
+    if (c0 < 0 || c0 > chunk_ops || s0 < 0 || s0 > chunk_bases) {
+        atomicOr(flags, F_LAYOUT);
+        c0 = chunk_ops;
+        s0 = chunk_bases;
+    }
+    cigar_begin[i] = c0 + carry_ops;
+    seq_begin[i] = s0 + carry_bases;
+}
+
+// per read: does its molecule stay open (no event of this push flushes it)
+__global__ __launch_bounds__(256) void k_cr_open(const unsigned *__restrict__ group_of_read, const unsigned *__restrict__ g_flush,
+                                                 long long n_events, long long n, unsigned char *__restrict__ open)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    open[i] = (long long)g_flush[group_of_read[i]] == n_events ? 1 : 0;
+}
+
+// what every read adds to the next carry (run once the walk's layout flag was read: the lengths are valid)
+__global__ __launch_bounds__(256) void k_cr_carry_sizes(const unsigned char *__restrict__ open, const int *__restrict__ n_cigar,
+                                                        const int *__restrict__ l_seq, long long n, ull *__restrict__ reads,
+                                                        ull *__restrict__ ops, ull *__restrict__ bases)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool o = open[i] != 0;
+    reads[i] = o ? 1ull : 0ull;
+    ops[i] = o ? (ull)n_cigar[i] : 0ull;
+    bases[i] = o ? (ull)l_seq[i] : 0ull;
+}
+
+struct CarryColumns {
+    int *start, *cb, *ub, *score, *n_cigar, *l_seq;
+    double *p_misaligned;
+    long long *cigar_begin, *seq_begin;
+};
+
+// the nine per-read columns of the open reads, in read order; cigar_begin / seq_begin count from the carry's own start
+__global__ __launch_bounds__(256) void k_cr_carry_reads(Reads R, const unsigned char *__restrict__ open, const ull *__restrict__ read_at,
+                                                        const ull *__restrict__ ops_at, const ull *__restrict__ bases_at, CarryColumns out,
+                                                        long long *__restrict__ old_cigar_begin, long long *__restrict__ old_seq_begin)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n || !open[i]) return;
+    const long long k = (long long)read_at[i] - 1;
+    out.start[k] = R.start[i];
+    out.cb[k] = R.cb[i];
+    out.ub[k] = R.ub[i];
+    out.score[k] = R.score[i];
+    out.n_cigar[k] = R.n_cigar[i];
+    out.l_seq[k] = R.l_seq[i];
+    out.p_misaligned[k] = R.p_misaligned[i];
+    out.cigar_begin[k] = (long long)ops_at[i] - R.n_cigar[i];
+    out.seq_begin[k] = (long long)bases_at[i] - R.l_seq[i];
+    old_cigar_begin[k] = R.cigar_begin[i];
+    old_seq_begin[k] = R.seq_begin[i];
+}
+
+// the carried read that owns element e of the carry's cigar / seq: the last one whose begin is <= e (reads without elements
+// share their begin with the read behind them, which is then the one found)
+__device__ __forceinline__ long long owner_of(const long long *__restrict__ begin, long long n, long long e)
+{
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (begin[mid] <= e)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo - 1;
+}
+
+// One lane per element, not one per read: a molecule held open by a long N-skip rides through many pushes, and a read's
+// bases are copied by as many lanes as it has bases.
+__global__ __launch_bounds__(256) void k_cr_carry_ops(const long long *__restrict__ begin, const long long *__restrict__ old_begin,
+                                                      long long n_reads, long long n_ops, const unsigned *__restrict__ cigar,
+                                                      unsigned *__restrict__ out)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ops) return;
+    const long long k = owner_of(begin, n_reads, e);
+    out[e] = cigar[old_begin[k] + (e - begin[k])];
+}
+
+__global__ __launch_bounds__(256) void k_cr_carry_bases(const long long *__restrict__ begin, const long long *__restrict__ old_begin,
+                                                        long long n_reads, long long n_bases, const unsigned char *__restrict__ seq,
+                                                        const unsigned char *__restrict__ qual, unsigned char *__restrict__ seq_out,
+                                                        unsigned char *__restrict__ qual_out)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_bases) return;
+    const long long k = owner_of(begin, n_reads, e);
+    const long long from = old_begin[k] + (e - begin[k]);
+    seq_out[e] = seq[from];
+    qual_out[e] = qual[from];
 }
 
 // hipEvents at the stage boundaries (dmx_get_count_reads_timings)
@@ -471,43 +591,26 @@ int flag_error(int flags)
     return 0;
 }
 
-int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions, long long P, const double *table, long long *n_molecules,
-                long long *n_calls)
+// what a pass over carry + chunk knows of its stream (the one-shot call: the defaults)
+struct Pass {
+    long long n_carry = 0, previous_start = 0, molecule_base = 0;
+    bool has_previous = false;  // a read came before the chunk's first: previous_start is the last one's start
+    bool keep_open = false;     // not the final push: molecules no event flushes stay behind as the next carry
+    size_t resident_bytes = 0;  // the stream's positions and table (the peak meter counts the input whole)
+};
+
+size_t carry_bytes(const dmx_ctx *c)
+{
+    return dev_bytes(c->d_crs_start) * 6 + dev_bytes(c->d_crs_p) + dev_bytes(c->d_crs_cigar_begin) * 2 + dev_bytes(c->d_crs_cigar) +
+           dev_bytes(c->d_crs_seq) * 2;
+}
+
+// The six stages on the reads R (device arrays; the first pass.n_carry are a stream's carry), then the next carry.
+int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *flags, const double *d_table, const Pass &pass,
+               long long *n_molecules, long long *n_calls)
 {
     hipStream_t st = c->stream;
-    dmx::host::release_count_reads(c);
-    const long long n = h->n_reads;
-    Scratch sc(c);
-    StageClock clock;
-    DMX_TRY(clock.tick(st));
-
-    // ---- upload
-    Reads R;
-    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases, R.P = P;
-    int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *d_positions, *flags;
-    double *d_p, *d_table;
-    long long *d_cigar_begin, *d_seq_begin;
-    unsigned *d_cigar;
-    unsigned char *d_seq, *d_qual;
-    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cb, h->compressed_cb, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_ub, h->compressed_ub, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_score, h->alignment_score, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_p, h->p_misaligned, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
-    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
-    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
-    DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
-    DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
-    DMX_TRY(sc.get(&flags, 1));
-    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-    R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
-    R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual, R.positions = d_positions;
-    DMX_TRY(clock.tick(st));
+    const long long n = R.n;
 
     // ---- 1 walk
     int *end;
@@ -521,9 +624,8 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     DMX_TRY(sc.get(&key, (size_t)n));
     DMX_TRY(sc.get(&err, (size_t)n));
     DMX_TRY(sc.get(&idx, (size_t)n));
-    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
-    DMX_TRY(launched("k_cr_positions"));
-    hipLaunchKernelGGL(k_cr_walk, dim3(grid_for(n)), dim3(256), 0, st, R, end, n_obs, err, is_event, key, idx, flags);
+    hipLaunchKernelGGL(k_cr_walk, dim3(grid_for(n)), dim3(256), 0, st, R, end, n_obs, err, is_event, key, idx, flags, pass.n_carry,
+                       pass.has_previous ? 1 : 0, pass.previous_start);
     DMX_TRY(launched("k_cr_walk"));
     ull n_events = 0;
     DMX_TRY(sum_scan(sc, is_event, event_rank, (size_t)n, &n_events, st));  // (the caller's arrays are free to change from here on)
@@ -531,7 +633,7 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     unsigned *event_read;
     DMX_TRY(sc.get(&threshold, (size_t)n_events));
     DMX_TRY(sc.get(&event_read, (size_t)n_events));
-    hipLaunchKernelGGL(k_cr_events, dim3(grid_for(n)), dim3(256), 0, st, d_start, is_event, event_rank, n, threshold, event_read);
+    hipLaunchKernelGGL(k_cr_events, dim3(grid_for(n)), dim3(256), 0, st, R.start, is_event, event_rank, n, threshold, event_read);
     DMX_TRY(launched("k_cr_events"));
     DMX_TRY(clock.tick(st));
 
@@ -571,9 +673,18 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     DMX_TRY(sc.get(&g_flush, (size_t)G));
     DMX_TRY(sc.get(&g_key, (size_t)G));
     DMX_TRY(sc.get(&g_p, (size_t)G));
-    hipLaunchKernelGGL(k_cr_groups, dim3(grid_for(n)), dim3(256), 0, st, skey, sidx, head, group_at, last, flush, d_start, n, group_of_read,
+    hipLaunchKernelGGL(k_cr_groups, dim3(grid_for(n)), dim3(256), 0, st, skey, sidx, head, group_at, last, flush, R.start, n, group_of_read,
                        g_first, g_head, g_flush, g_key, span_head);
     DMX_TRY(launched("k_cr_groups"));
+    // a stream's open molecules: no event of this push flushes them (a final push and the one-shot call flush everything)
+    unsigned char *open;
+    DMX_TRY(sc.get(&open, (size_t)n));
+    if (pass.keep_open) {
+        hipLaunchKernelGGL(k_cr_open, dim3(grid_for(n)), dim3(256), 0, st, group_of_read, g_flush, (long long)n_events, n, open);
+        DMX_TRY(launched("k_cr_open"));
+    } else {
+        HIP_TRY(hipMemsetAsync(open, 0, (size_t)n, st));
+    }
     DMX_TRY(clock.tick(st));
 
     // ---- 3 duplicates, p_group_misaligned
@@ -587,16 +698,16 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     DMX_TRY(sc.get(&span_sorted, (size_t)n));
     DMX_TRY(sc.get(&at_final, (size_t)n));
     DMX_TRY(sc.get(&dup, (size_t)n));
-    hipLaunchKernelGGL(k_cr_dup_keys, dim3(grid_for(n)), dim3(256), 0, st, sidx, end, d_score, n, dkey, at);
+    hipLaunchKernelGGL(k_cr_dup_keys, dim3(grid_for(n)), dim3(256), 0, st, sidx, end, R.score, n, dkey, at);
     DMX_TRY(launched("k_cr_dup_keys"));
     DMX_TRY(sort_pairs(sc, dkey, dkey_sorted, at, at_sorted, (size_t)n, 64u, st));
     hipLaunchKernelGGL(k_cr_span_of, dim3(grid_for(n)), dim3(256), 0, st, at_sorted, span_at, n, span);
     DMX_TRY(launched("k_cr_span_of"));
     DMX_TRY(sort_pairs(sc, span, span_sorted, at_sorted, at_final, (size_t)n, (unsigned)bits_for(n_spans), st));
-    hipLaunchKernelGGL(k_cr_dups, dim3(grid_for(n)), dim3(256), 0, st, span_sorted, at_final, sidx, end, d_score, n, dup);
+    hipLaunchKernelGGL(k_cr_dups, dim3(grid_for(n)), dim3(256), 0, st, span_sorted, at_final, sidx, end, R.score, n, dup);
     DMX_TRY(launched("k_cr_dups"));
     ull *kept = run, *kept_at = head, *obs_at = is_event, n_kept = 0, n_observations = 0;
-    hipLaunchKernelGGL(k_cr_kept, dim3(grid_for(n)), dim3(256), 0, st, dup, err, sidx, n, n_obs, kept, flags);
+    hipLaunchKernelGGL(k_cr_kept, dim3(grid_for(n)), dim3(256), 0, st, dup, err, open, sidx, n, n_obs, kept, flags);
     DMX_TRY(launched("k_cr_kept"));
     DMX_TRY(sum_scan(sc, kept, kept_at, (size_t)n, &n_kept, st));
     unsigned *kept_list;
@@ -604,7 +715,7 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     hipLaunchKernelGGL(k_cr_kept_list, dim3(grid_for(n)), dim3(256), 0, st, kept, kept_at, sidx, n, kept_list);
     DMX_TRY(launched("k_cr_kept_list"));
     hipLaunchKernelGGL(k_cr_group_p, dim3(grid_for((long long)G)), dim3(256), 0, st, g_head, kept_at, kept_list, (long long)n_kept, group_of_read,
-                       d_p, (long long)G, g_p);
+                       R.p_misaligned, (long long)G, g_p);
     DMX_TRY(launched("k_cr_group_p"));
     DMX_TRY(clock.tick(st));
 
@@ -614,8 +725,8 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     DMX_TRY(flag_error(h_flags));
-    const int position_bits = bits_for((ull)P), group_bits = bits_for(G);
-    if (position_bits + group_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu molecules x %lld positions do not fit a 64-bit key", G, P);
+    const int position_bits = bits_for((ull)R.P), group_bits = bits_for(G);
+    if (position_bits + group_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu molecules x %lld positions do not fit a 64-bit key", G, R.P);
     if (n_observations >= (1ull << 32)) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu observations in one call (at most 2^32 - 1): split the chromosome", n_observations);
     const long long n_o = (long long)n_observations;
     ull *okey, *oval, *okey_sorted, *oval_sorted;
@@ -664,6 +775,8 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     hipLaunchKernelGGL(k_cr_group_flags, dim3(grid_for((long long)G)), dim3(256), 0, st, gorder, has_call, (long long)G, gflag);
     DMX_TRY(launched("k_cr_group_flags"));
     DMX_TRY(sum_scan(sc, gflag, gflag_at, (size_t)G, &n_m, st));
+    if (pass.molecule_base + (long long)n_m > INT_MAX)
+        return fail(DMX_ERR_UNSUPPORTED, "count_reads: more than 2^31 - 1 molecules in one stream");
     DMX_TRY(dev_alloc(c, c->d_cr_molecules, (size_t)n_m * MOLECULE_BYTES));
     DMX_TRY(dev_alloc(c, c->d_cr_calls, (size_t)n_c * SNP_CALL_BYTES));
     hipLaunchKernelGGL(k_cr_molecules, dim3(grid_for((long long)G)), dim3(256), 0, st, gorder, gflag, gflag_at, (long long)G, g_key, g_p,
@@ -680,8 +793,52 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
         DMX_TRY(launched("k_cr_call_keys"));
         DMX_TRY(sort_pairs(sc, ckey, ckey_sorted, csrc, csrc_sorted, (size_t)n_c, (unsigned)(32 + bits_for(n_m)), st));
         hipLaunchKernelGGL(k_cr_calls, dim3(grid_for((long long)n_c)), dim3(256), 0, st, ckey_sorted, csrc_sorted, (long long)n_c, okey_sorted,
-                           position_bits, d_positions, c_base, c_p, c->d_cr_calls.p);
+                           position_bits, R.positions, c_base, c_p, pass.molecule_base, c->d_cr_calls.p);
         DMX_TRY(launched("k_cr_calls"));
+    }
+    // ---- the next carry: the open molecules' reads in read order, their cigar / seq / qual segments behind one another
+    if (pass.keep_open) {
+        ull *f_reads = span_head, *f_ops = span_at, *f_bases = group_at, *read_at = reach_in, *ops_at = reach, *bases_at = skey;  // (all free)
+        ull n_open = 0, open_ops = 0, open_bases = 0;
+        hipLaunchKernelGGL(k_cr_carry_sizes, dim3(grid_for(n)), dim3(256), 0, st, open, R.n_cigar, R.l_seq, n, f_reads, f_ops, f_bases);
+        DMX_TRY(launched("k_cr_carry_sizes"));
+        DMX_TRY(sum_scan(sc, f_reads, read_at, (size_t)n, &n_open, st));
+        if (n_open) {
+            DMX_TRY(sum_scan(sc, f_ops, ops_at, (size_t)n, &open_ops, st));
+            DMX_TRY(sum_scan(sc, f_bases, bases_at, (size_t)n, &open_bases, st));
+            DMX_TRY(dev_alloc(c, c->d_crs_start, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_cb, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_ub, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_score, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_n_cigar, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_l_seq, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_p, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_cigar_begin, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_seq_begin, (size_t)n_open));
+            DMX_TRY(dev_alloc(c, c->d_crs_cigar, (size_t)open_ops));
+            DMX_TRY(dev_alloc(c, c->d_crs_seq, (size_t)open_bases));
+            DMX_TRY(dev_alloc(c, c->d_crs_qual, (size_t)open_bases));
+            long long *old_cigar_begin, *old_seq_begin;
+            DMX_TRY(sc.get(&old_cigar_begin, (size_t)n_open));
+            DMX_TRY(sc.get(&old_seq_begin, (size_t)n_open));
+            CarryColumns out;
+            out.start = c->d_crs_start.p, out.cb = c->d_crs_cb.p, out.ub = c->d_crs_ub.p, out.score = c->d_crs_score.p;
+            out.n_cigar = c->d_crs_n_cigar.p, out.l_seq = c->d_crs_l_seq.p, out.p_misaligned = c->d_crs_p.p;
+            out.cigar_begin = c->d_crs_cigar_begin.p, out.seq_begin = c->d_crs_seq_begin.p;
+            hipLaunchKernelGGL(k_cr_carry_reads, dim3(grid_for(n)), dim3(256), 0, st, R, open, read_at, ops_at, bases_at, out, old_cigar_begin,
+                               old_seq_begin);
+            DMX_TRY(launched("k_cr_carry_reads"));
+            if (open_ops) hipLaunchKernelGGL(k_cr_carry_ops, dim3(grid_for((long long)open_ops)), dim3(256), 0, st, c->d_crs_cigar_begin.p,
+                                             old_cigar_begin, (long long)n_open, (long long)open_ops, R.cigar, c->d_crs_cigar.p);
+            DMX_TRY(launched("k_cr_carry_ops"));
+            if (open_bases) hipLaunchKernelGGL(k_cr_carry_bases, dim3(grid_for((long long)open_bases)), dim3(256), 0, st, c->d_crs_seq_begin.p,
+                                               old_seq_begin, (long long)n_open, (long long)open_bases, R.seq, R.qual, c->d_crs_seq.p,
+                                               c->d_crs_qual.p);
+            DMX_TRY(launched("k_cr_carry_bases"));
+        }
+        c->crs_carry = (long long)n_open;
+        c->crs_ops = (long long)open_ops;
+        c->crs_bases = (long long)open_bases;
     }
     DMX_TRY(clock.tick(st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -692,8 +849,163 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     }
     c->cr_molecules = (long long)n_m;
     c->cr_calls = (long long)n_c;
+    c->cr_peak_bytes = (int64_t)(sc.held + pass.resident_bytes + (c->crs_carry ? carry_bytes(c) : 0));
     *n_molecules = (long long)n_m;
     *n_calls = (long long)n_c;
+    return 0;
+}
+
+int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions, long long P, const double *table, long long *n_molecules,
+                long long *n_calls)
+{
+    hipStream_t st = c->stream;
+    dmx::host::release_count_reads(c);
+    const long long n = h->n_reads;
+    Scratch sc(c);
+    StageClock clock;
+    DMX_TRY(clock.tick(st));
+
+    // ---- upload
+    Reads R;
+    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases, R.P = P;
+    int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *d_positions, *flags;
+    double *d_p, *d_table;
+    long long *d_cigar_begin, *d_seq_begin;
+    unsigned *d_cigar;
+    unsigned char *d_seq, *d_qual;
+    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cb, h->compressed_cb, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_ub, h->compressed_ub, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_score, h->alignment_score, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_p, h->p_misaligned, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
+    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
+    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
+    DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
+    DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
+    DMX_TRY(sc.get(&flags, 1));
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+    R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
+    R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual, R.positions = d_positions;
+    DMX_TRY(clock.tick(st));
+    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
+    DMX_TRY(launched("k_cr_positions"));
+    return count_pass(c, sc, clock, R, flags, d_table, Pass(), n_molecules, n_calls);
+}
+
+// ---- streaming
+
+enum { STREAM_NONE = 0, STREAM_OPEN = 1, STREAM_FINISHED = 2, STREAM_DEAD = 3 };  // dmx_ctx::crs_state
+
+// one column of carry + chunk: the carry device to device, the chunk uploaded behind it
+template <typename T>
+int combine(Scratch &sc, T **out, const DevBuf<T> &carry, size_t n_carry, const T *host, size_t n_chunk, hipStream_t st)
+{
+    DMX_TRY(sc.get(out, n_carry + n_chunk));
+    if (n_carry) HIP_TRY(hipMemcpyAsync(*out, carry.p, n_carry * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if (n_chunk) HIP_TRY(hipMemcpyAsync(*out + n_carry, host, n_chunk * sizeof(T), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+int stream_push(dmx_ctx *c, const dmx_decoded_reads *h, bool final, long long *n_molecules, long long *n_calls)
+{
+    hipStream_t st = c->stream;
+    dmx::host::release_count_reads(c);
+    const size_t n_chunk = h ? (size_t)h->n_reads : 0, chunk_ops = h ? (size_t)h->n_cigar_ops : 0, chunk_bases = h ? (size_t)h->n_bases : 0;
+    const size_t n_carry = (size_t)c->crs_carry, carry_ops = (size_t)c->crs_ops, carry_bases = (size_t)c->crs_bases;
+    if (n_carry + n_chunk > (size_t)INT_MAX)
+        return fail(DMX_ERR_UNSUPPORTED, "count_reads_push: %zu carried reads + %zu reads of the chunk (at most 2^31 - 1 in one push)", n_carry, n_chunk);
+    if (n_chunk && c->crs_has_previous && h->reference_start[0] < c->crs_previous_start)
+        return fail(DMX_ERR_INVALID, "count_reads_push: the chunk starts at %d, below the previous chunk's last reference_start %lld",
+                    (int)h->reference_start[0], c->crs_previous_start);
+    Pass pass;
+    pass.n_carry = (long long)n_carry, pass.previous_start = c->crs_previous_start, pass.has_previous = c->crs_has_previous;
+    pass.molecule_base = c->crs_molecules, pass.keep_open = !final;
+    pass.resident_bytes = dev_bytes(c->d_crs_positions) + dev_bytes(c->d_crs_table);
+    long long n_m = 0, n_c = 0;
+    if (n_carry + n_chunk == 0) {  // nothing to count: no records (a first or a final push without reads)
+        c->cr_molecules = c->cr_calls = 0;
+        for (double &ms : c->cr_stage_ms) ms = 0.0;
+        c->cr_peak_bytes = (int64_t)pass.resident_bytes;
+    } else {
+        Scratch sc(c);
+        StageClock clock;
+        DMX_TRY(clock.tick(st));
+        Reads R;
+        R.n = (long long)(n_carry + n_chunk), R.n_ops = (long long)(carry_ops + chunk_ops), R.n_bases = (long long)(carry_bases + chunk_bases);
+        R.P = c->crs_P;
+        int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *flags;
+        double *d_p;
+        long long *d_cigar_begin, *d_seq_begin;
+        unsigned *d_cigar;
+        unsigned char *d_seq, *d_qual;
+        DMX_TRY(combine(sc, &d_start, c->d_crs_start, n_carry, h ? h->reference_start : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_cb, c->d_crs_cb, n_carry, h ? h->compressed_cb : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_ub, c->d_crs_ub, n_carry, h ? h->compressed_ub : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_score, c->d_crs_score, n_carry, h ? h->alignment_score : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_n_cigar, c->d_crs_n_cigar, n_carry, h ? h->n_cigar : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_l_seq, c->d_crs_l_seq, n_carry, h ? h->l_seq : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_p, c->d_crs_p, n_carry, h ? h->p_misaligned : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_cigar_begin, c->d_crs_cigar_begin, n_carry, h ? (const long long *)h->cigar_begin : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_seq_begin, c->d_crs_seq_begin, n_carry, h ? (const long long *)h->seq_begin : nullptr, n_chunk, st));
+        DMX_TRY(combine(sc, &d_cigar, c->d_crs_cigar, carry_ops, h ? h->cigar : nullptr, chunk_ops, st));
+        DMX_TRY(combine(sc, &d_seq, c->d_crs_seq, carry_bases, h ? h->seq : nullptr, chunk_bases, st));
+        DMX_TRY(combine(sc, &d_qual, c->d_crs_qual, carry_bases, h ? h->qual : nullptr, chunk_bases, st));
+        dmx::host::release_count_reads_carry(c);  // (stream order: the copies above read the blocks before anything re-uses them)
+        DMX_TRY(sc.get(&flags, 1));
+        HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+        if (n_chunk) hipLaunchKernelGGL(k_cr_rebase, dim3(grid_for((long long)n_chunk)), dim3(256), 0, st, d_cigar_begin, d_seq_begin, (long long)n_carry,
+                                        R.n, (long long)carry_ops, (long long)carry_bases, (long long)chunk_ops, (long long)chunk_bases, flags);
+        DMX_TRY(launched("k_cr_rebase"));
+        R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
+        R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual;
+        R.positions = c->d_crs_positions.p;
+        DMX_TRY(clock.tick(st));
+        DMX_TRY(count_pass(c, sc, clock, R, flags, c->d_crs_table.p, pass, &n_m, &n_c));
+    }
+    if (n_chunk) {
+        c->crs_previous_start = h->reference_start[n_chunk - 1];
+        c->crs_has_previous = true;
+    }
+    c->crs_molecules += n_m;
+    c->cr_carried = c->crs_carry;
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+int stream_begin(dmx_ctx *c, const int32_t *positions, long long P, const double *table)
+{
+    hipStream_t st = c->stream;
+    Scratch sc(c);
+    int *flags, h_flags = 0;
+    DMX_TRY(dev_alloc(c, c->d_crs_positions, (size_t)P));
+    DMX_TRY(dev_alloc(c, c->d_crs_table, (size_t)QUALITY_CAP + 1));
+    if (P) HIP_TRY(hipMemcpyAsync(c->d_crs_positions.p, positions, (size_t)P * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_crs_table.p, table, ((size_t)QUALITY_CAP + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    DMX_TRY(sc.get(&flags, 1));
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, c->d_crs_positions.p, P, flags);
+    DMX_TRY(launched("k_cr_positions"));
+    HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    DMX_TRY(flag_error(h_flags));
+    c->crs_P = P;
+    return 0;
+}
+
+int check_reads(const dmx_decoded_reads *reads, const char *who)
+{
+    if (reads->n_reads < 0 || reads->n_reads > INT_MAX) return fail(DMX_ERR_INVALID, "%s: n_reads must be 0 .. 2^31 - 1", who);
+    if (reads->n_cigar_ops < 0 || reads->n_bases < 0 || (reads->n_cigar_ops && !reads->cigar) || (reads->n_bases && (!reads->seq || !reads->qual)))
+        return fail(DMX_ERR_INVALID, "%s: bad cigar / seq / qual arrays", who);
+    if (reads->n_reads && (!reads->reference_start || !reads->compressed_cb || !reads->compressed_ub || !reads->p_misaligned ||
+                           !reads->alignment_score || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
+        return fail(DMX_ERR_INVALID, "%s: null per-read array", who);
     return 0;
 }
 
@@ -706,17 +1018,14 @@ int dmx_count_reads(dmx_ctx *c, const dmx_decoded_reads *reads, const int32_t *p
 {
     DMX_TRY(bind(c));
     if (!reads || !n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "count_reads: null argument");
-    if (reads->n_reads < 0 || reads->n_reads > INT_MAX) return fail(DMX_ERR_INVALID, "count_reads: n_reads must be 0 .. 2^31 - 1");
+    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
     if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads: bad positions");
-    if (reads->n_cigar_ops < 0 || reads->n_bases < 0 || (reads->n_cigar_ops && !reads->cigar) || (reads->n_bases && (!reads->seq || !reads->qual)))
-        return fail(DMX_ERR_INVALID, "count_reads: bad cigar / seq / qual arrays");
-    if (reads->n_reads && (!reads->reference_start || !reads->compressed_cb || !reads->compressed_ub || !reads->p_misaligned ||
-                           !reads->alignment_score || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
-        return fail(DMX_ERR_INVALID, "count_reads: null per-read array");
+    DMX_TRY(check_reads(reads, "count_reads"));
     *n_molecules = *n_calls = 0;
     if (reads->n_reads == 0) {
         dmx::host::release_count_reads(c);
         c->cr_molecules = c->cr_calls = 0;
+        c->cr_peak_bytes = 0;
         for (double &ms : c->cr_stage_ms) ms = 0.0;
         return 0;
     }
@@ -732,10 +1041,59 @@ int dmx_count_reads(dmx_ctx *c, const dmx_decoded_reads *reads, const int32_t *p
     return 0;
 }
 
+int dmx_count_reads_begin(dmx_ctx *c, const int32_t *positions, int64_t n_positions, const double *qual_table41)
+{
+    DMX_TRY(bind(c));
+    if (!qual_table41) return fail(DMX_ERR_INVALID, "count_reads_begin: null argument");
+    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
+    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads_begin: bad positions");
+    dmx::host::release_count_reads(c);
+    const int rc = stream_begin(c, positions, n_positions, qual_table41);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads_stream(c);
+        return rc;
+    }
+    c->crs_state = STREAM_OPEN;
+    return 0;
+}
+
+int dmx_count_reads_push(dmx_ctx *c, const dmx_decoded_reads *chunk, int final, int64_t *n_molecules, int64_t *n_calls)
+{
+    DMX_TRY(bind(c));
+    if (!n_molecules || !n_calls) return fail(DMX_ERR_INVALID, "count_reads_push: null argument");
+    *n_molecules = *n_calls = 0;
+    if (c->crs_state == STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_begin before dmx_count_reads_push");
+    if (c->crs_state == STREAM_FINISHED) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_push after the final push");
+    if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
+    int rc = chunk ? check_reads(chunk, "count_reads_push") : 0;
+    long long n_m = 0, n_c = 0;
+    if (!rc) rc = stream_push(c, chunk, final != 0, &n_m, &n_c);
+    if (rc) {  // the stream is dead: its carry goes, the records of its earlier pushes stand for nothing
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        dmx::host::release_count_reads_carry(c);
+        c->crs_state = STREAM_DEAD;
+        return rc;
+    }
+    if (final) c->crs_state = STREAM_FINISHED;
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+int dmx_count_reads_end(dmx_ctx *c)
+{
+    DMX_TRY(bind(c));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dmx::host::release_count_reads_stream(c);  // (the records of the last push stay for dmx_count_reads_fetch)
+    return 0;
+}
+
 int dmx_count_reads_fetch(dmx_ctx *c, void *molecules_out, void *snp_calls_out)
 {
     DMX_TRY(bind(c));
-    if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads before dmx_count_reads_fetch");
+    if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads or dmx_count_reads_push before dmx_count_reads_fetch");
     if ((c->cr_molecules && !molecules_out) || (c->cr_calls && !snp_calls_out)) return fail(DMX_ERR_INVALID, "count_reads_fetch: null output");
     if (c->cr_molecules)
         HIP_TRY(hipMemcpyAsync(molecules_out, c->d_cr_molecules.p, (size_t)c->cr_molecules * MOLECULE_BYTES, hipMemcpyDeviceToHost, c->stream));
@@ -751,6 +1109,23 @@ int dmx_get_count_reads_timings(dmx_ctx *c, double *stage_ms)
     if (!stage_ms) return fail(DMX_ERR_INVALID, "null stage_ms");
     if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads before dmx_get_count_reads_timings");
     for (int s = 0; s < dmx::COUNT_READS_STAGES; s++) stage_ms[s] = c->cr_stage_ms[s];
+    return 0;
+}
+
+int dmx_get_count_reads_carry(dmx_ctx *c, int64_t *n_reads)
+{
+    DMX_TRY(bind(c));
+    if (!n_reads) return fail(DMX_ERR_INVALID, "null n_reads");
+    *n_reads = c->crs_state == STREAM_NONE ? 0 : c->cr_carried;
+    return 0;
+}
+
+int dmx_get_count_reads_peak_bytes(dmx_ctx *c, int64_t *bytes)
+{
+    DMX_TRY(bind(c));
+    if (!bytes) return fail(DMX_ERR_INVALID, "null bytes");
+    if (c->cr_molecules < 0) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads or dmx_count_reads_push before dmx_get_count_reads_peak_bytes");
+    *bytes = c->cr_peak_bytes;
     return 0;
 }
 

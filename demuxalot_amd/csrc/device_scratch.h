@@ -17,6 +17,7 @@ typedef unsigned long long ull;
 struct Scratch {
     dmx_ctx *ctx;
     std::vector<void *> ptrs;
+    size_t held = 0;  // bytes asked for so far; nothing goes back before the call leaves, so this is also the peak
     explicit Scratch(dmx_ctx *c) : ctx(c) {}
     Scratch(const Scratch &) = delete;
     Scratch &operator=(const Scratch &) = delete;
@@ -34,6 +35,7 @@ struct Scratch {
         const int rc = ctx_malloc(ctx, &p, (count ? count : 1) * sizeof(T));
         if (rc) return rc;
         ptrs.push_back(p);
+        held += (count ? count : 1) * sizeof(T);
         *out = (T *)p;
         return 0;
     }

@@ -214,6 +214,22 @@ struct dmx_ctx {
     DevBuf<unsigned char> d_cr_calls;      // [cr_calls] packed 13-byte call records
     long long cr_molecules = -1, cr_calls = 0;
     double cr_stage_ms[dmx::COUNT_READS_STAGES] = {};
+    int64_t cr_peak_bytes = 0;  // scratch + input the last call or push held at its end, when it holds the most (dmx_get_count_reads_peak_bytes)
+    long long cr_carried = 0;   // reads the last push left as the carry (dmx_get_count_reads_carry)
+    // streamed read counting (dmx_count_reads_begin / _push / _end; one stream per context): the stream's positions and quality
+    // table, and the carry: the reads of the molecules no event has flushed yet, in read order, laid out as a dmx_decoded_reads
+    DevBuf<int> d_crs_positions;  // [crs_P]
+    DevBuf<double> d_crs_table;   // [41]
+    DevBuf<int> d_crs_start, d_crs_cb, d_crs_ub, d_crs_score, d_crs_n_cigar, d_crs_l_seq;  // [crs_carry]
+    DevBuf<double> d_crs_p;                                                               // [crs_carry]
+    DevBuf<long long> d_crs_cigar_begin, d_crs_seq_begin;                                 // [crs_carry]
+    DevBuf<unsigned> d_crs_cigar;                                                         // [crs_ops]
+    DevBuf<unsigned char> d_crs_seq, d_crs_qual;                                          // [crs_bases]
+    int crs_state = 0;  // 0: no stream, 1: open, 2: the final push is done, 3: a push failed (count_reads.hip: STREAM_*)
+    long long crs_P = 0, crs_carry = 0, crs_ops = 0, crs_bases = 0;
+    long long crs_molecules = 0;       // molecules the stream has emitted: the molecule_index of the next push counts on from here
+    long long crs_previous_start = 0;  // reference_start of the last read of the last non-empty chunk ...
+    bool crs_has_previous = false;     // ... if there was one
     // coverage (coverage.hip): the counts of the last dmx_coverage_count and the candidates of the last dmx_coverage_candidates,
     // read and written by the dmx_coverage_* entry points only; cov_W < 0: no window counted, cov_candidates < 0: none selected
     DevBuf<int> d_cov_counts;       // [4, cov_W] rows A, C, G, T

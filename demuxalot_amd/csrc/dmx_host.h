@@ -22,7 +22,9 @@ void release_incremental(dmx_ctx *c);
 void release_coarse_stream(dmx_ctx *c);
 void release_problem(dmx_ctx *c);
 void release_snp_detection(dmx_ctx *c);  // the buffers of the dmx_snp_* entry points (snp_detect.hip)
-void release_count_reads(dmx_ctx *c);    // the records of dmx_count_reads (count_reads.hip)
+void release_count_reads(dmx_ctx *c);    // the records of dmx_count_reads / dmx_count_reads_push (count_reads.hip)
+void release_count_reads_carry(dmx_ctx *c);   // the carry of a read-counting stream
+void release_count_reads_stream(dmx_ctx *c);  // the whole stream: carry, positions, table, state
 void release_coverage(dmx_ctx *c);       // the window and the candidates of dmx_coverage_* (coverage.hip)
 int build_row_segments(dmx_ctx *c);
 int ensure_options(dmx_ctx *c, int with_doublets, const float *penalties);

@@ -587,6 +587,33 @@ void release_count_reads(dmx_ctx *c)
     c->cr_calls = 0;
 }
 
+void release_count_reads_carry(dmx_ctx *c)
+{
+    dev_free(c, c->d_crs_start);
+    dev_free(c, c->d_crs_cb);
+    dev_free(c, c->d_crs_ub);
+    dev_free(c, c->d_crs_score);
+    dev_free(c, c->d_crs_n_cigar);
+    dev_free(c, c->d_crs_l_seq);
+    dev_free(c, c->d_crs_p);
+    dev_free(c, c->d_crs_cigar_begin);
+    dev_free(c, c->d_crs_seq_begin);
+    dev_free(c, c->d_crs_cigar);
+    dev_free(c, c->d_crs_seq);
+    dev_free(c, c->d_crs_qual);
+    c->crs_carry = c->crs_ops = c->crs_bases = 0;
+}
+
+void release_count_reads_stream(dmx_ctx *c)
+{
+    release_count_reads_carry(c);
+    dev_free(c, c->d_crs_positions);
+    dev_free(c, c->d_crs_table);
+    c->crs_state = 0;
+    c->crs_P = c->crs_molecules = c->crs_previous_start = c->cr_carried = 0;
+    c->crs_has_previous = false;
+}
+
 void release_coverage(dmx_ctx *c)
 {
     dev_free(c, c->d_cov_counts);
@@ -664,6 +691,7 @@ int dmx_destroy(dmx_ctx *c)
     release_problem(c);
     release_snp_detection(c);
     release_count_reads(c);
+    release_count_reads_stream(c);
     release_coverage(c);
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
@@ -694,6 +722,7 @@ int dmx_release_problem(dmx_ctx *c)
     release_problem(c);
     release_snp_detection(c);
     release_count_reads(c);
+    release_count_reads_stream(c);
     release_coverage(c);
     dmx::release_staged_calls(c);
     return 0;

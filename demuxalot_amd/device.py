@@ -419,10 +419,48 @@ class DeviceContext:
         return molecules, snp_calls
 
     def count_reads_timings(self):
-        """{stage: milliseconds} of the last count_reads (include/demux_hip_debug.h: dmx_get_count_reads_timings)."""
+        """{stage: milliseconds} of the last count_reads or count_reads_push (include/demux_hip_debug.h: dmx_get_count_reads_timings)."""
         ms = (ctypes.c_double * len(_lib.COUNT_READS_STAGES))()
         check(self._lib.dmx_get_count_reads_timings(self._h, ms))
         return dict(zip(_lib.COUNT_READS_STAGES, ms))
+
+    # streamed (dmx_count_reads_begin / _push / _end; snp_counter.ReadCounter is the front)
+    def count_reads_begin(self, positions, qual_table):
+        positions = as_c(positions, np.int32)
+        qual_table = as_c(qual_table, np.float64)
+        assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
+        check(self._lib.dmx_count_reads_begin(self._h, ptr(positions), len(positions), ptr(qual_table)))
+
+    def count_reads_push(self, reads, final=False):
+        """(molecules, snp_calls) this push emitted, molecule_index counting on across the stream; reads: a DecodedReads or None."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+        desc = None
+        if reads is not None:
+            arrays = reads.arrays()  # kept alive until the call returns
+            desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
+                                           **{name: ptr(a) for name, a in arrays.items()})
+        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.dmx_count_reads_push(self._h, None if desc is None else ctypes.cast(ctypes.byref(desc), ctypes.c_void_p),
+                                             1 if final else 0, ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
+        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
+        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
+        return molecules, snp_calls
+
+    def count_reads_end(self):
+        check(self._lib.dmx_count_reads_end(self._h))
+
+    def count_reads_carry(self):
+        """Reads the last push of the open stream left on the device (include/demux_hip_debug.h: dmx_get_count_reads_carry)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_get_count_reads_carry(self._h, ctypes.byref(n)))
+        return n.value
+
+    def count_reads_peak_bytes(self):
+        """Device bytes the last count_reads or count_reads_push held (include/demux_hip_debug.h: dmx_get_count_reads_peak_bytes)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_get_count_reads_peak_bytes(self._h, ctypes.byref(n)))
+        return n.value
 
     # ---- coverage (include/demux_hip.h: dmx_coverage_count / _candidates / _fetch_candidates; demuxalot_amd/snp_detection.py) ----
     def coverage_count(self, reads, start, stop, quality_threshold=15, fetch=True):

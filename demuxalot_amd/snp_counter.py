@@ -115,6 +115,23 @@ class DecodedReads:
     def arrays(self):
         return {name: getattr(self, name) for name, _ in self.PER_READ + self.FLAT}
 
+    def slice(self, lo, hi) -> 'DecodedReads':
+        """The reads [lo, hi) (as a Python slice clips them) with cigar_begin and seq_begin re-based to arrays of their own: a
+        chunk of a stream (ReadCounter).  On the host; the reads' cigar and seq ranges must be non-decreasing in read order, as
+        from_reads and a BAM decoder lay them out."""
+        lo, hi, _ = slice(lo, hi).indices(self.n_reads)
+        hi = max(lo, hi)
+        columns = {name: getattr(self, name)[lo:hi] for name, _ in self.PER_READ}
+        if hi == lo:
+            return DecodedReads(cigar=self.cigar[:0], seq=self.seq[:0], qual=self.qual[:0], **columns)
+        c0, s0 = int(self.cigar_begin[lo]), int(self.seq_begin[lo])
+        c1, s1 = int(self.cigar_begin[hi - 1]) + int(self.n_cigar[hi - 1]), int(self.seq_begin[hi - 1]) + int(self.l_seq[hi - 1])
+        if np.any(np.diff(columns['cigar_begin']) < 0) or np.any(np.diff(columns['seq_begin']) < 0):
+            raise ValueError('slice needs cigar_begin and seq_begin non-decreasing in read order')
+        columns['cigar_begin'] = columns['cigar_begin'] - c0
+        columns['seq_begin'] = columns['seq_begin'] - s0
+        return DecodedReads(cigar=self.cigar[c0:c1], seq=self.seq[s0:s1], qual=self.qual[s0:s1], **columns)
+
     @staticmethod
     def from_reads(reads, barcode_handler, parse_read) -> 'DecodedReads':
         """From an iterable of pysam-like reads (reference_start, cigartuples, seq, query_qualities, get_tag, has_tag, mapq),
@@ -159,7 +176,127 @@ def _container(molecules, snp_calls):
     return out
 
 
-def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=None):
+def _empty_container():
+    return _container(np.zeros(0, dtype=MOLECULE_DTYPE), np.zeros(0, dtype=SNP_CALL_DTYPE))
+
+
+class ReadCounter:
+    """The reads of ONE chromosome counted in chunks, in device memory bounded by the chunk and the molecules still open
+    (include/demux_hip_debug.h "Streamed read counting"; DESIGN.md "Read counting", "Streaming").  A context manager:
+
+        with ReadCounter(positions) as counter:
+            for chunk in chunks:                      # DecodedReads, in read order
+                molecules, snp_calls = counter.push(chunk)
+            molecules, snp_calls = counter.finish()
+
+    push returns the records of the molecules that chunk's reads flushed, finish the rest; concatenated they are the records of
+    count_snps_from_reads on all the reads (molecule_index counts on across the pushes).  Without on_context the shared context
+    is used and its lock is held from __enter__ to __exit__.  One stream per context."""
+
+    def __init__(self, positions, on_context=None):
+        self._positions = np.ascontiguousarray(positions, dtype=np.int32)
+        self._on_context = on_context
+        self._ctx = None
+        self._finished = False
+
+    def __enter__(self):
+        if self._ctx is not None:
+            raise RuntimeError('this ReadCounter is open already')
+        locked = self._on_context is None
+        if locked:
+            shared_context_lock.acquire()
+        try:
+            ctx = get_context() if locked else self._on_context
+            ctx.count_reads_begin(self._positions, quality_table())
+        except BaseException:
+            if locked:
+                shared_context_lock.release()
+            raise
+        self._ctx, self._finished = ctx, False
+        return self
+
+    def __exit__(self, *_exc):
+        ctx, self._ctx = self._ctx, None
+        try:
+            ctx.count_reads_end()
+        finally:
+            if self._on_context is None:
+                shared_context_lock.release()
+
+    def _push(self, reads, final):
+        if self._ctx is None:
+            raise RuntimeError('ReadCounter is a context manager: push inside its with block')
+        if self._finished:
+            raise RuntimeError('this ReadCounter has finished')
+        if reads is not None and not isinstance(reads, DecodedReads):
+            raise TypeError('a chunk must be a DecodedReads')
+        out = self._ctx.count_reads_push(reads, final=final)
+        self._finished = final
+        return out
+
+    def push(self, reads):
+        """(molecules, snp_calls) of the molecules the reads of this chunk flushed."""
+        return self._push(reads, False)
+
+    def finish(self, reads=None):
+        """(molecules, snp_calls) of a last chunk (optional) and of every molecule still open."""
+        return self._push(reads, True)
+
+    @property
+    def carried_reads(self):
+        """Reads the last push left on the device: those of the molecules still open."""
+        return 0 if self._ctx is None else self._ctx.count_reads_carry()
+
+
+def _count_chunks(ctx, chunks, positions):
+    """One chromosome's container from an iterable of chunks, one chunk alive at a time."""
+    molecules, snp_calls = [], []
+    with ReadCounter(positions, on_context=ctx) as counter:
+        iterator = iter(chunks)
+        while True:
+            chunk = next(iterator, None)
+            part = counter.finish() if chunk is None else counter.push(chunk)
+            molecules.append(part[0])
+            snp_calls.append(part[1])
+            if chunk is None:
+                break
+            del chunk
+    return _container(np.concatenate(molecules), np.concatenate(snp_calls))
+
+
+def _on(on_context, run):
+    if on_context is not None:
+        return run(on_context)
+    with shared_context_lock:
+        return run(get_context())
+
+
+def count_snps_from_read_chunks(chromosome2chunks, chromosome2positions, *, on_context=None):
+    """count_snps_from_reads for reads that arrive in batches: chromosome2chunks maps a chromosome to an iterable of
+    DecodedReads (a generator is fine), the chunks of that chromosome in read order.  Every iterable is consumed lazily, one
+    chunk alive at a time, so neither the host nor the device ever holds a whole chromosome (ReadCounter).
+
+    :return: what count_snps_from_reads returns on the concatenated chunks.  A chromosome without chunks gives an empty
+        container; the chunks of a chromosome without positions are consumed and skipped.
+    """
+    if not isinstance(chromosome2chunks, dict) or not isinstance(chromosome2positions, dict):
+        raise TypeError('chromosome2chunks and chromosome2positions must be dicts keyed by chromosome')
+
+    def run(ctx):
+        result = {}
+        for chromosome, positions in chromosome2positions.items():
+            chunks = chromosome2chunks.get(chromosome)
+            result[chromosome] = _empty_container() if chunks is None else _count_chunks(ctx, chunks, positions)
+        for chromosome, chunks in chromosome2chunks.items():
+            if chromosome not in chromosome2positions:
+                for _chunk in chunks:
+                    pass
+        return result
+
+    return _on(on_context, run)
+
+
+def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=None, max_reads_per_call=None):
     """count_snps (snp_counter.py:279-327) with the BAM reading replaced by reads the caller has decoded: per chromosome of
     chromosome2positions (in its order) one device call that groups the reads into molecules, walks the CIGARs to the
     SNP positions, multiplies the base-error probabilities and resolves conflicting bases (DESIGN.md "Read counting").
@@ -167,11 +304,15 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
     :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing)
     :param chromosome2positions: dict chromosome -> strictly ascending zero-based SNP positions
     :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
+    :param max_reads_per_call: None: one device call per chromosome.  A number: every chromosome is cut into slices of at most
+        that many reads and streamed (ReadCounter), which bounds the device memory by the slice; the result is the same.
     :return: dict chromosome -> CompressedSNPCalls, record for record what the reference's count_call_variants_for_chromosome
         returns.  A chromosome without reads gives an empty container; reads of a chromosome without positions are skipped.
     """
     if not isinstance(chromosome2reads, dict) or not isinstance(chromosome2positions, dict):
         raise TypeError('chromosome2reads and chromosome2positions must be dicts keyed by chromosome')
+    if max_reads_per_call is not None and int(max_reads_per_call) < 1:
+        raise ValueError('max_reads_per_call must be at least 1')
     table = quality_table()
 
     def run(ctx):
@@ -181,12 +322,12 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
             if reads is not None and not isinstance(reads, DecodedReads):
                 raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads')
             if reads is None or reads.n_reads == 0:
-                result[chromosome] = _container(np.zeros(0, dtype=MOLECULE_DTYPE), np.zeros(0, dtype=SNP_CALL_DTYPE))
-                continue
-            result[chromosome] = _container(*ctx.count_reads(reads, positions, table))
+                result[chromosome] = _empty_container()
+            elif max_reads_per_call is None:
+                result[chromosome] = _container(*ctx.count_reads(reads, positions, table))
+            else:
+                step = int(max_reads_per_call)
+                result[chromosome] = _count_chunks(ctx, (reads.slice(lo, lo + step) for lo in range(0, reads.n_reads, step)), positions)
         return result
 
-    if on_context is not None:
-        return run(on_context)
-    with shared_context_lock:
-        return run(get_context())
+    return _on(on_context, run)

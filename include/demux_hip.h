@@ -390,6 +390,12 @@ int dmx_snp_select(dmx_ctx *ctx, int64_t n_best_per_donor, int64_t n_additional,
  *                          int32 snp_position, uint8 base_index, float32 p_base_wrong: 13 bytes).
  * The records sit in buffers of their own: the resident problem, its results and every other entry point are untouched;
  * dmx_release_problem and dmx_destroy free them.
+ *
+ * Streaming: dmx_count_reads_begin / dmx_count_reads_push / dmx_count_reads_end count the reads of one chromosome pushed in
+ * chunks, in device memory bounded by the chunk and the molecules still open; their records, push after push, are those of
+ * one dmx_count_reads.  This header is kept to 64 entry points (tests/test_host_cpu.py), so they are declared in
+ * demux_hip_debug.h, "Streamed read counting", with their contract.  While a stream is open on a context, dmx_count_reads
+ * answers DMX_ERR_INVALID.
  * ------------------------------------------------------------------------- */
 typedef struct {
     int64_t n_reads;                 /* < 2^31 */

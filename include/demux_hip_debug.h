@@ -200,10 +200,41 @@ int dmx_get_exchange_mode(dmx_ctx *ctx, int32_t *mode);
  * DEMUXALOT_AMD_ALLOW_FOREIGN_RCCL=1. */
 int dmx_runtime_info(char *out, int64_t capacity);
 
+/* Streamed read counting (product API, not a debug switch: it is declared here because demux_hip.h is kept to 64 entry points).
+ * The reads of one chromosome pushed in chunks, in read order, in device memory bounded by the chunk and the
+ * molecules still open (DESIGN.md "Read counting", "Streaming").  One stream per context.
+ *   dmx_count_reads_begin  opens the stream: positions and qual_table41 as for dmx_count_reads, uploaded and checked once.
+ *   dmx_count_reads_push   counts carry + chunk, where the carry is the reads of the molecules no event has flushed so far.
+ *                          A push that is not final emits the molecules an event of this chunk flushes and keeps the reads of
+ *                          the others (duplicates included) on the device; the final push (final != 0) emits everything.
+ *                          chunk may be NULL or empty.  cigar_begin / seq_begin count from the chunk's own cigar / seq.
+ *                          *n_molecules, *n_calls: the records THIS push emitted; dmx_count_reads_fetch returns them, with
+ *                          molecule_index counting on across the pushes of the stream.  The pushes' records, concatenated, are
+ *                          the records of one dmx_count_reads on all the reads.  The number of reads of a stream is not limited.
+ *                          DMX_ERR_INVALID: no stream, a push after the final push or after a failed one, a chunk whose first
+ *                          reference_start lies below the previous chunk's last, and whatever dmx_count_reads refuses (errors
+ *                          in reads that count are decided when their molecule is emitted).  DMX_ERR_UNSUPPORTED: carry +
+ *                          chunk above 2^31 - 1 reads, more than 2^31 - 1 molecules in the stream.  After a failed push the
+ *                          stream is dead: the records of its earlier pushes stand for nothing, dmx_count_reads_end is left.
+ *   dmx_count_reads_end    closes the stream and drops the carry (the records of the last push stay fetchable).
+ *                          dmx_release_problem and dmx_destroy close it too.
+ * While a stream is open, dmx_count_reads and a second dmx_count_reads_begin answer DMX_ERR_INVALID. */
+int dmx_count_reads_begin(dmx_ctx *ctx, const int32_t *positions, int64_t n_positions, const double *qual_table41);
+int dmx_count_reads_push(dmx_ctx *ctx, const dmx_decoded_reads *chunk, int final, int64_t *n_molecules, int64_t *n_calls);
+int dmx_count_reads_end(dmx_ctx *ctx);
+
 /* Stage times of the last dmx_count_reads, milliseconds between hipEvents on the ctx stream (scripts/count_reads_timing.py):
  * stage_ms[7] = upload, CIGAR walk + events, molecules, duplicates + p_group_misaligned, observations (emit + sort),
  * per-position folds, order + records (csrc/count_reads.hip). */
 int dmx_get_count_reads_timings(dmx_ctx *ctx, double *stage_ms);
+/* The same for the last dmx_count_reads_push: upload holds the carry's device-to-device copy as well, order + records the
+ * compaction of the next carry.
+ * dmx_get_count_reads_carry: reads the last push of the open stream left on the device as the carry (0 without a stream).
+ * dmx_get_count_reads_peak_bytes: bytes the last dmx_count_reads or dmx_count_reads_push held at its end, when it holds the
+ * most: the temporaries and the input on the device (for a push: carry + chunk, the stream's positions and table, the next
+ * carry), as asked of the context's allocator. */
+int dmx_get_count_reads_carry(dmx_ctx *ctx, int64_t *n_reads);
+int dmx_get_count_reads_peak_bytes(dmx_ctx *ctx, int64_t *bytes);
 
 /* The accumulation form of dmx_coverage_count (csrc/coverage.hip): no-return global atomics into the dense window, or position
  * tiles in LDS that are stored once (the default: DESIGN.md "Coverage and candidates" has the measurements).  Both give the
