@@ -131,10 +131,18 @@ DEBUG_SIGNATURES = {
     'dmx_get_count_reads_peak_bytes': (c_int, [_P, POINTER(c_int64)]),
     'dmx_set_coverage_form': (c_int, [_P, c_int]),
     'dmx_get_coverage_timings': (c_int, [_P, POINTER(c_double)]),
+    'dmx_reads_upload': (c_int, [_P, _P, POINTER(c_int64)]),
+    'dmx_reads_release': (c_int, [_P, c_int64]),
+    'dmx_reads_info': (c_int, [_P, c_int64, POINTER(c_int64)]),
+    'dmx_count_reads_resident': (c_int, [_P, c_int64, _P, c_int64, _P, POINTER(c_int64), POINTER(c_int64)]),
+    'dmx_coverage_count_resident': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P]),
+    'dmx_count_reads_push_resident': (c_int, [_P, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    'dmx_get_reads_upload_bytes': (c_int, [_P, POINTER(c_int64)]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings
 COVERAGE_ATOMIC, COVERAGE_TILED = 0, 1  # dmx_set_coverage_form
+READS_INFO = ('n_reads', 'n_cigar_ops', 'n_bases', 'nbytes', 'reference_length')  # dmx_reads_info
 COUNT_READS_STAGES = ('upload', 'walk', 'molecules', 'duplicates', 'observations', 'fold', 'order')  # dmx_get_count_reads_timings
 
 

@@ -885,6 +885,7 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
     DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
     DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
+    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(n, h->n_cigar_ops, h->n_bases, true);
     DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
     DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
     DMX_TRY(sc.get(&flags, 1));
@@ -897,31 +898,212 @@ int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions
     return count_pass(c, sc, clock, R, flags, d_table, Pass(), n_molecules, n_calls);
 }
 
+// the device-side view of a resident set's reads [first, first + n): the per-read columns move, cigar / seq / qual stay whole
+// (cigar_begin / seq_begin count from the set's own arrays)
+Reads reads_of(const ResidentReads &set, long long first, long long n)
+{
+    Reads R;
+    R.n = n, R.n_ops = set.n_ops, R.n_bases = set.n_bases, R.P = 0;
+    R.start = set.start.p + first, R.cb = set.cb.p + first, R.ub = set.ub.p + first, R.score = set.score.p + first;
+    R.n_cigar = set.n_cigar.p + first, R.l_seq = set.l_seq.p + first, R.p_misaligned = set.p.p + first;
+    R.cigar_begin = set.cigar_begin.p + first, R.seq_begin = set.seq_begin.p + first;
+    R.cigar = set.cigar.p, R.seq = set.seq.p, R.qual = set.qual.p;
+    R.positions = nullptr;
+    return R;
+}
+
+// dmx_count_reads on a resident set: the six stages read the set's buffers in place
+int count_reads_resident(dmx_ctx *c, const ResidentReads &set, const int32_t *positions, long long P, const double *table,
+                         long long *n_molecules, long long *n_calls)
+{
+    hipStream_t st = c->stream;
+    dmx::host::release_count_reads(c);
+    Scratch sc(c);
+    StageClock clock;
+    DMX_TRY(clock.tick(st));
+    Reads R = reads_of(set, 0, set.n);
+    R.P = P;
+    int *d_positions, *flags;
+    double *d_table;
+    DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
+    DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
+    DMX_TRY(sc.get(&flags, 1));
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+    R.positions = d_positions;
+    DMX_TRY(clock.tick(st));
+    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
+    DMX_TRY(launched("k_cr_positions"));
+    return count_pass(c, sc, clock, R, flags, d_table, Pass(), n_molecules, n_calls);
+}
+
 // ---- streaming
 
 enum { STREAM_NONE = 0, STREAM_OPEN = 1, STREAM_FINISHED = 2, STREAM_DEAD = 3 };  // dmx_ctx::crs_state
 
-// one column of carry + chunk: the carry device to device, the chunk uploaded behind it
+// the per-read, per-operation and per-base columns of carry + chunk
+struct Combined {
+    int *start, *cb, *ub, *score, *n_cigar, *l_seq;
+    double *p;
+    long long *cigar_begin, *seq_begin;
+    unsigned *cigar;
+    unsigned char *seq, *qual;
+};
+
+// one column of carry + chunk: room for both, the carry copied device to device
 template <typename T>
-int combine(Scratch &sc, T **out, const DevBuf<T> &carry, size_t n_carry, const T *host, size_t n_chunk, hipStream_t st)
+int combine(Scratch &sc, T **out, const DevBuf<T> &carry, size_t n_carry, size_t n_chunk, hipStream_t st)
 {
     DMX_TRY(sc.get(out, n_carry + n_chunk));
     if (n_carry) HIP_TRY(hipMemcpyAsync(*out, carry.p, n_carry * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (n_chunk) HIP_TRY(hipMemcpyAsync(*out + n_carry, host, n_chunk * sizeof(T), hipMemcpyHostToDevice, st));
     return 0;
 }
 
-int stream_push(dmx_ctx *c, const dmx_decoded_reads *h, bool final, long long *n_molecules, long long *n_calls)
+template <typename T>
+int behind(T *out, size_t n_carry, const T *host, size_t n_chunk, hipStream_t st)
+{
+    if (n_chunk) HIP_TRY(hipMemcpyAsync(out + n_carry, host, n_chunk * sizeof(T), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// A chunk of host arrays: its sizes are the caller's, its columns are uploaded behind the carry's; cigar_begin / seq_begin
+// count from the chunk's own arrays (k_cr_rebase moves them).
+struct HostChunk {
+    struct Measured {
+        size_t ops = 0, bases = 0;
+    };
+    const dmx_decoded_reads *h;
+    size_t n() const { return h ? (size_t)h->n_reads : 0; }
+    int ends(dmx_ctx *, int *first, int *last) const
+    {
+        *first = h->reference_start[0];
+        *last = h->reference_start[h->n_reads - 1];
+        return 0;
+    }
+    int measure(dmx_ctx *, Scratch &, int *, Measured *m) const
+    {
+        m->ops = h ? (size_t)h->n_cigar_ops : 0;
+        m->bases = h ? (size_t)h->n_bases : 0;
+        return 0;
+    }
+    int place(dmx_ctx *c, Scratch &, const Measured &, const Combined &d, size_t n_carry, size_t carry_ops, size_t carry_bases) const
+    {
+        hipStream_t st = c->stream;
+        const size_t m = n();
+        if (!h) return 0;
+        DMX_TRY(behind(d.start, n_carry, h->reference_start, m, st));
+        DMX_TRY(behind(d.cb, n_carry, h->compressed_cb, m, st));
+        DMX_TRY(behind(d.ub, n_carry, h->compressed_ub, m, st));
+        DMX_TRY(behind(d.score, n_carry, h->alignment_score, m, st));
+        DMX_TRY(behind(d.n_cigar, n_carry, h->n_cigar, m, st));
+        DMX_TRY(behind(d.l_seq, n_carry, h->l_seq, m, st));
+        DMX_TRY(behind(d.p, n_carry, h->p_misaligned, m, st));
+        DMX_TRY(behind(d.cigar_begin, n_carry, (const long long *)h->cigar_begin, m, st));
+        DMX_TRY(behind(d.seq_begin, n_carry, (const long long *)h->seq_begin, m, st));
+        DMX_TRY(behind(d.cigar, carry_ops, h->cigar, (size_t)h->n_cigar_ops, st));
+        DMX_TRY(behind(d.seq, carry_bases, h->seq, (size_t)h->n_bases, st));
+        DMX_TRY(behind(d.qual, carry_bases, h->qual, (size_t)h->n_bases, st));
+        c->reads_upload_bytes += dmx::host::decoded_reads_bytes(h->n_reads, h->n_cigar_ops, h->n_bases, true);
+        return 0;
+    }
+};
+
+// per read of a range of a resident set: do its cigar / seq ranges lie inside the set's arrays (what the gather relies on)
+__global__ __launch_bounds__(256) void k_rr_check_range(Reads R, int *flags)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n) return;
+    const long long c0 = R.cigar_begin[i], nc = R.n_cigar[i], s0 = R.seq_begin[i], ls = R.l_seq[i];
+    if (nc < 0 || c0 < 0 || c0 > R.n_ops || nc > R.n_ops - c0 || ls < 0 || s0 < 0 || s0 > R.n_bases || ls > R.n_bases - s0) atomicOr(flags, F_LAYOUT);
+}
+
+// A range of a resident set.  cigar_begin and seq_begin of a set are arbitrary offsets, so the range is no contiguous range
+// of operations or bases: it is gathered behind the carry the way the carry itself is placed (every read "open"): the three
+// sizes are scanned, one lane per read gathers the columns, one lane per operation and per base finds its read by binary search.
+struct ResidentChunk {
+    struct Measured {  // the sizes of the range and the scans behind them, which place() gathers by
+        size_t ops = 0, bases = 0;
+        ull *ops_at = nullptr, *bases_at = nullptr, *read_at = nullptr;
+        unsigned char *open = nullptr;
+    };
+    const ResidentReads *set;
+    long long first, count;
+    size_t n() const { return (size_t)count; }
+    int ends(dmx_ctx *c, int *lo, int *hi) const
+    {
+        HIP_TRY(hipMemcpyAsync(lo, set->start.p + first, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hi, set->start.p + first + count - 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    int measure(dmx_ctx *c, Scratch &sc, int *flags, Measured *m) const
+    {
+        hipStream_t st = c->stream;
+        if (!count) return 0;
+        const Reads R = reads_of(*set, first, count);
+        hipLaunchKernelGGL(k_rr_check_range, dim3(grid_for(count)), dim3(256), 0, st, R, flags);
+        DMX_TRY(launched("k_rr_check_range"));
+        int h_flags = 0;
+        HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        DMX_TRY(flag_error(h_flags));  // (the lengths are valid from here on)
+        ull *f_reads, *f_ops, *f_bases, n_reads = 0, n_ops = 0, n_bases = 0;
+        DMX_TRY(sc.get(&m->open, (size_t)count));
+        DMX_TRY(sc.get(&f_reads, (size_t)count));
+        DMX_TRY(sc.get(&f_ops, (size_t)count));
+        DMX_TRY(sc.get(&f_bases, (size_t)count));
+        DMX_TRY(sc.get(&m->read_at, (size_t)count));
+        DMX_TRY(sc.get(&m->ops_at, (size_t)count));
+        DMX_TRY(sc.get(&m->bases_at, (size_t)count));
+        HIP_TRY(hipMemsetAsync(m->open, 1, (size_t)count, st));
+        hipLaunchKernelGGL(k_cr_carry_sizes, dim3(grid_for(count)), dim3(256), 0, st, m->open, R.n_cigar, R.l_seq, count, f_reads, f_ops, f_bases);
+        DMX_TRY(launched("k_cr_carry_sizes"));
+        DMX_TRY(sum_scan(sc, f_reads, m->read_at, (size_t)count, &n_reads, st));
+        DMX_TRY(sum_scan(sc, f_ops, m->ops_at, (size_t)count, &n_ops, st));
+        DMX_TRY(sum_scan(sc, f_bases, m->bases_at, (size_t)count, &n_bases, st));
+        m->ops = (size_t)n_ops;
+        m->bases = (size_t)n_bases;
+        return 0;
+    }
+    int place(dmx_ctx *c, Scratch &sc, const Measured &m, const Combined &d, size_t n_carry, size_t carry_ops, size_t carry_bases) const
+    {
+        hipStream_t st = c->stream;
+        if (!count) return 0;
+        const Reads R = reads_of(*set, first, count);
+        long long *old_cigar_begin, *old_seq_begin;
+        DMX_TRY(sc.get(&old_cigar_begin, (size_t)count));
+        DMX_TRY(sc.get(&old_seq_begin, (size_t)count));
+        CarryColumns out;
+        out.start = d.start + n_carry, out.cb = d.cb + n_carry, out.ub = d.ub + n_carry, out.score = d.score + n_carry;
+        out.n_cigar = d.n_cigar + n_carry, out.l_seq = d.l_seq + n_carry, out.p_misaligned = d.p + n_carry;
+        out.cigar_begin = d.cigar_begin + n_carry, out.seq_begin = d.seq_begin + n_carry;  // from the chunk's own start: k_cr_rebase moves them
+        hipLaunchKernelGGL(k_cr_carry_reads, dim3(grid_for(count)), dim3(256), 0, st, R, m.open, m.read_at, m.ops_at, m.bases_at, out,
+                           old_cigar_begin, old_seq_begin);
+        DMX_TRY(launched("k_cr_carry_reads"));
+        const size_t chunk_ops = m.ops, chunk_bases = m.bases;
+        if (chunk_ops) hipLaunchKernelGGL(k_cr_carry_ops, dim3(grid_for((long long)chunk_ops)), dim3(256), 0, st, out.cigar_begin, old_cigar_begin,
+                                          count, (long long)chunk_ops, R.cigar, d.cigar + carry_ops);
+        DMX_TRY(launched("k_cr_carry_ops"));
+        if (chunk_bases) hipLaunchKernelGGL(k_cr_carry_bases, dim3(grid_for((long long)chunk_bases)), dim3(256), 0, st, out.seq_begin, old_seq_begin,
+                                            count, (long long)chunk_bases, R.seq, R.qual, d.seq + carry_bases, d.qual + carry_bases);
+        DMX_TRY(launched("k_cr_carry_bases"));
+        return 0;
+    }
+};
+
+template <typename Chunk>
+int stream_push(dmx_ctx *c, const Chunk &chunk, bool final, long long *n_molecules, long long *n_calls)
 {
     hipStream_t st = c->stream;
     dmx::host::release_count_reads(c);
-    const size_t n_chunk = h ? (size_t)h->n_reads : 0, chunk_ops = h ? (size_t)h->n_cigar_ops : 0, chunk_bases = h ? (size_t)h->n_bases : 0;
+    const size_t n_chunk = chunk.n();
     const size_t n_carry = (size_t)c->crs_carry, carry_ops = (size_t)c->crs_ops, carry_bases = (size_t)c->crs_bases;
     if (n_carry + n_chunk > (size_t)INT_MAX)
         return fail(DMX_ERR_UNSUPPORTED, "count_reads_push: %zu carried reads + %zu reads of the chunk (at most 2^31 - 1 in one push)", n_carry, n_chunk);
-    if (n_chunk && c->crs_has_previous && h->reference_start[0] < c->crs_previous_start)
+    int first_start = 0, last_start = 0;
+    if (n_chunk) DMX_TRY(chunk.ends(c, &first_start, &last_start));
+    if (n_chunk && c->crs_has_previous && first_start < c->crs_previous_start)
         return fail(DMX_ERR_INVALID, "count_reads_push: the chunk starts at %d, below the previous chunk's last reference_start %lld",
-                    (int)h->reference_start[0], c->crs_previous_start);
+                    first_start, c->crs_previous_start);
     Pass pass;
     pass.n_carry = (long long)n_carry, pass.previous_start = c->crs_previous_start, pass.has_previous = c->crs_has_previous;
     pass.molecule_base = c->crs_molecules, pass.keep_open = !final;
@@ -935,40 +1117,41 @@ int stream_push(dmx_ctx *c, const dmx_decoded_reads *h, bool final, long long *n
         Scratch sc(c);
         StageClock clock;
         DMX_TRY(clock.tick(st));
+        int *flags;
+        DMX_TRY(sc.get(&flags, 1));
+        HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
+        typename Chunk::Measured measured;
+        DMX_TRY(chunk.measure(c, sc, flags, &measured));
+        const size_t chunk_ops = measured.ops, chunk_bases = measured.bases;
         Reads R;
         R.n = (long long)(n_carry + n_chunk), R.n_ops = (long long)(carry_ops + chunk_ops), R.n_bases = (long long)(carry_bases + chunk_bases);
         R.P = c->crs_P;
-        int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *flags;
-        double *d_p;
-        long long *d_cigar_begin, *d_seq_begin;
-        unsigned *d_cigar;
-        unsigned char *d_seq, *d_qual;
-        DMX_TRY(combine(sc, &d_start, c->d_crs_start, n_carry, h ? h->reference_start : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_cb, c->d_crs_cb, n_carry, h ? h->compressed_cb : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_ub, c->d_crs_ub, n_carry, h ? h->compressed_ub : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_score, c->d_crs_score, n_carry, h ? h->alignment_score : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_n_cigar, c->d_crs_n_cigar, n_carry, h ? h->n_cigar : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_l_seq, c->d_crs_l_seq, n_carry, h ? h->l_seq : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_p, c->d_crs_p, n_carry, h ? h->p_misaligned : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_cigar_begin, c->d_crs_cigar_begin, n_carry, h ? (const long long *)h->cigar_begin : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_seq_begin, c->d_crs_seq_begin, n_carry, h ? (const long long *)h->seq_begin : nullptr, n_chunk, st));
-        DMX_TRY(combine(sc, &d_cigar, c->d_crs_cigar, carry_ops, h ? h->cigar : nullptr, chunk_ops, st));
-        DMX_TRY(combine(sc, &d_seq, c->d_crs_seq, carry_bases, h ? h->seq : nullptr, chunk_bases, st));
-        DMX_TRY(combine(sc, &d_qual, c->d_crs_qual, carry_bases, h ? h->qual : nullptr, chunk_bases, st));
+        Combined d;
+        DMX_TRY(combine(sc, &d.start, c->d_crs_start, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.cb, c->d_crs_cb, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.ub, c->d_crs_ub, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.score, c->d_crs_score, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.n_cigar, c->d_crs_n_cigar, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.l_seq, c->d_crs_l_seq, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.p, c->d_crs_p, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.cigar_begin, c->d_crs_cigar_begin, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.seq_begin, c->d_crs_seq_begin, n_carry, n_chunk, st));
+        DMX_TRY(combine(sc, &d.cigar, c->d_crs_cigar, carry_ops, chunk_ops, st));
+        DMX_TRY(combine(sc, &d.seq, c->d_crs_seq, carry_bases, chunk_bases, st));
+        DMX_TRY(combine(sc, &d.qual, c->d_crs_qual, carry_bases, chunk_bases, st));
+        DMX_TRY(chunk.place(c, sc, measured, d, n_carry, carry_ops, carry_bases));
         dmx::host::release_count_reads_carry(c);  // (stream order: the copies above read the blocks before anything re-uses them)
-        DMX_TRY(sc.get(&flags, 1));
-        HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-        if (n_chunk) hipLaunchKernelGGL(k_cr_rebase, dim3(grid_for((long long)n_chunk)), dim3(256), 0, st, d_cigar_begin, d_seq_begin, (long long)n_carry,
+        if (n_chunk) hipLaunchKernelGGL(k_cr_rebase, dim3(grid_for((long long)n_chunk)), dim3(256), 0, st, d.cigar_begin, d.seq_begin, (long long)n_carry,
                                         R.n, (long long)carry_ops, (long long)carry_bases, (long long)chunk_ops, (long long)chunk_bases, flags);
         DMX_TRY(launched("k_cr_rebase"));
-        R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
-        R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual;
+        R.start = d.start, R.cb = d.cb, R.ub = d.ub, R.score = d.score, R.n_cigar = d.n_cigar, R.l_seq = d.l_seq, R.p_misaligned = d.p;
+        R.cigar_begin = d.cigar_begin, R.seq_begin = d.seq_begin, R.cigar = d.cigar, R.seq = d.seq, R.qual = d.qual;
         R.positions = c->d_crs_positions.p;
         DMX_TRY(clock.tick(st));
         DMX_TRY(count_pass(c, sc, clock, R, flags, c->d_crs_table.p, pass, &n_m, &n_c));
     }
     if (n_chunk) {
-        c->crs_previous_start = h->reference_start[n_chunk - 1];
+        c->crs_previous_start = last_start;
         c->crs_has_previous = true;
     }
     c->crs_molecules += n_m;
@@ -1041,6 +1224,36 @@ int dmx_count_reads(dmx_ctx *c, const dmx_decoded_reads *reads, const int32_t *p
     return 0;
 }
 
+int dmx_count_reads_resident(dmx_ctx *c, int64_t handle, const int32_t *positions, int64_t n_positions, const double *qual_table41,
+                             int64_t *n_molecules, int64_t *n_calls)
+{
+    DMX_TRY(bind(c));
+    if (!n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "count_reads_resident: null argument");
+    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
+    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads_resident: bad positions");
+    ResidentReads *set = nullptr;
+    DMX_TRY(dmx::host::find_resident_reads(c, handle, "count_reads_resident", &set));
+    if (!set->countable) return fail(DMX_ERR_INVALID, "count_reads_resident: the set was uploaded without compressed_cb / compressed_ub / p_misaligned / alignment_score: it serves coverage only");
+    *n_molecules = *n_calls = 0;
+    if (set->n == 0) {
+        dmx::host::release_count_reads(c);
+        c->cr_molecules = c->cr_calls = 0;
+        c->cr_peak_bytes = 0;
+        for (double &ms : c->cr_stage_ms) ms = 0.0;
+        return 0;
+    }
+    long long n_m = 0, n_c = 0;
+    const int rc = count_reads_resident(c, *set, positions, n_positions, qual_table41, &n_m, &n_c);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        return rc;
+    }
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
 int dmx_count_reads_begin(dmx_ctx *c, const int32_t *positions, int64_t n_positions, const double *qual_table41)
 {
     DMX_TRY(bind(c));
@@ -1068,8 +1281,39 @@ int dmx_count_reads_push(dmx_ctx *c, const dmx_decoded_reads *chunk, int final, 
     if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
     int rc = chunk ? check_reads(chunk, "count_reads_push") : 0;
     long long n_m = 0, n_c = 0;
-    if (!rc) rc = stream_push(c, chunk, final != 0, &n_m, &n_c);
+    if (!rc) rc = stream_push(c, HostChunk{chunk}, final != 0, &n_m, &n_c);
     if (rc) {  // the stream is dead: its carry goes, the records of its earlier pushes stand for nothing
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        dmx::host::release_count_reads_carry(c);
+        c->crs_state = STREAM_DEAD;
+        return rc;
+    }
+    if (final) c->crs_state = STREAM_FINISHED;
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+int dmx_count_reads_push_resident(dmx_ctx *c, int64_t handle, int64_t first_read, int64_t last_read, int final, int64_t *n_molecules,
+                                  int64_t *n_calls)
+{
+    DMX_TRY(bind(c));
+    if (!n_molecules || !n_calls) return fail(DMX_ERR_INVALID, "count_reads_push_resident: null argument");
+    *n_molecules = *n_calls = 0;
+    if (c->crs_state == STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_begin before dmx_count_reads_push_resident");
+    if (c->crs_state == STREAM_FINISHED) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_push_resident after the final push");
+    if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
+    // the arguments are looked at before the stream is: a bad handle or range leaves it open
+    ResidentReads *set = nullptr;
+    DMX_TRY(dmx::host::find_resident_reads(c, handle, "count_reads_push_resident", &set));
+    if (!set->countable) return fail(DMX_ERR_INVALID, "count_reads_push_resident: the set was uploaded without compressed_cb / compressed_ub / p_misaligned / alignment_score: it serves coverage only");
+    if (first_read < 0 || last_read < first_read || last_read > set->n)
+        return fail(DMX_ERR_INVALID, "count_reads_push_resident: the range [%lld, %lld) must satisfy 0 <= first_read <= last_read <= %lld reads",
+                    (long long)first_read, (long long)last_read, set->n);
+    long long n_m = 0, n_c = 0;
+    const int rc = stream_push(c, ResidentChunk{set, first_read, last_read - first_read}, final != 0, &n_m, &n_c);
+    if (rc) {  // the stream is dead, as after a failed dmx_count_reads_push
         (void)hipStreamSynchronize(c->stream);
         dmx::host::release_count_reads(c);
         dmx::host::release_count_reads_carry(c);

@@ -315,33 +315,16 @@ int flag_error(int flags)
     return 0;
 }
 
-int coverage_count(dmx_ctx *c, const dmx_decoded_reads *h, long long w_lo, long long w_hi, unsigned quality_threshold)
+// Stages 1 to 3 on the reads R (device arrays the caller placed: uploaded into sc, or a resident set's own), after the
+// "upload" stage, which also clears the window.
+int coverage_window(dmx_ctx *c, Scratch &sc, Clock &clock, const Reads &R, long long w_lo, long long w_hi, unsigned quality_threshold)
 {
     hipStream_t st = c->stream;
-    const long long n = h->n_reads, W = w_hi - w_lo;
-    Scratch sc(c);
-    Clock clock;
-    DMX_TRY(clock.tick(st));
-
-    // ---- upload (compressed_cb, compressed_ub, p_misaligned and alignment_score are not read)
-    Reads R;
-    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases;
-    int *d_start, *d_n_cigar, *d_l_seq, *flags;
-    long long *d_cigar_begin, *d_seq_begin;
-    unsigned *d_cigar;
-    unsigned char *d_seq, *d_qual;
-    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
-    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
-    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
+    const long long n = R.n, W = w_hi - w_lo;
+    const int *d_start = R.start;
+    int *flags;
     DMX_TRY(sc.get(&flags, 1));
     HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-    R.start = d_start, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin;
-    R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual;
     DMX_TRY(dev_alloc(c, c->d_cov_counts, (size_t)(4 * W)));
     HIP_TRY(hipMemsetAsync(c->d_cov_counts.p, 0, dev_bytes(c->d_cov_counts), st));
     DMX_TRY(clock.tick(st));
@@ -400,6 +383,68 @@ int coverage_count(dmx_ctx *c, const dmx_decoded_reads *h, long long w_lo, long 
     HIP_TRY(hipStreamSynchronize(st));
     for (double &ms : c->cov_stage_ms) ms = 0.0;
     DMX_TRY(clock.read(c->cov_stage_ms, 0));
+    return 0;
+}
+
+int coverage_count(dmx_ctx *c, const dmx_decoded_reads *h, long long w_lo, long long w_hi, unsigned quality_threshold)
+{
+    hipStream_t st = c->stream;
+    const long long n = h->n_reads;
+    Scratch sc(c);
+    Clock clock;
+    DMX_TRY(clock.tick(st));
+
+    // ---- upload (compressed_cb, compressed_ub, p_misaligned and alignment_score are not read)
+    Reads R;
+    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases;
+    int *d_start, *d_n_cigar, *d_l_seq;
+    long long *d_cigar_begin, *d_seq_begin;
+    unsigned *d_cigar;
+    unsigned char *d_seq, *d_qual;
+    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
+    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
+    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
+    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
+    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(n, h->n_cigar_ops, h->n_bases, false);
+    R.start = d_start, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin;
+    R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual;
+    return coverage_window(c, sc, clock, R, w_lo, w_hi, quality_threshold);
+}
+
+// dmx_coverage_count on a resident set: the stages read the set's buffers in place
+int coverage_count_resident(dmx_ctx *c, const ResidentReads &set, long long w_lo, long long w_hi, unsigned quality_threshold)
+{
+    Scratch sc(c);
+    Clock clock;
+    DMX_TRY(clock.tick(c->stream));
+    Reads R;
+    R.n = set.n, R.n_ops = set.n_ops, R.n_bases = set.n_bases;
+    R.start = set.start.p, R.n_cigar = set.n_cigar.p, R.l_seq = set.l_seq.p, R.cigar_begin = set.cigar_begin.p, R.seq_begin = set.seq_begin.p;
+    R.cigar = set.cigar.p, R.seq = set.seq.p, R.qual = set.qual.p;
+    return coverage_window(c, sc, clock, R, w_lo, w_hi, quality_threshold);
+}
+
+// what both entry points do around the pass: the previous window goes, a failed pass leaves none
+template <typename Pass>
+int count_window(dmx_ctx *c, int32_t start, int32_t stop, int32_t *coverage_out, Pass pass)
+{
+    dmx::host::release_coverage(c);
+    const int rc = pass();
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_coverage(c);
+        return rc;
+    }
+    c->cov_W = (long long)stop - start;
+    c->cov_start = start;
+    if (coverage_out && c->cov_W) {
+        HIP_TRY(hipMemcpyAsync(coverage_out, c->d_cov_counts.p, (size_t)c->cov_W * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return 0;
 }
 
@@ -470,20 +515,17 @@ int dmx_coverage_count(dmx_ctx *c, const dmx_decoded_reads *reads, int32_t start
         return fail(DMX_ERR_INVALID, "coverage: bad cigar / seq / qual arrays");
     if (reads->n_reads && (!reads->reference_start || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
         return fail(DMX_ERR_INVALID, "coverage: null per-read array");
-    dmx::host::release_coverage(c);
-    const int rc = coverage_count(c, reads, start, stop, (unsigned)quality_threshold);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        dmx::host::release_coverage(c);
-        return rc;
-    }
-    c->cov_W = (long long)stop - start;
-    c->cov_start = start;
-    if (coverage_out && c->cov_W) {
-        HIP_TRY(hipMemcpyAsync(coverage_out, c->d_cov_counts.p, (size_t)c->cov_W * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return count_window(c, start, stop, coverage_out, [&] { return coverage_count(c, reads, start, stop, (unsigned)quality_threshold); });
+}
+
+int dmx_coverage_count_resident(dmx_ctx *c, int64_t handle, int32_t start, int32_t stop, int32_t quality_threshold, int32_t *coverage_out)
+{
+    DMX_TRY(bind(c));
+    if (start < 0 || stop < start) return fail(DMX_ERR_INVALID, "coverage: the window must satisfy 0 <= start <= stop");
+    if (quality_threshold < 0 || quality_threshold > 255) return fail(DMX_ERR_INVALID, "coverage: quality_threshold must be 0 .. 255");
+    ResidentReads *set = nullptr;
+    DMX_TRY(dmx::host::find_resident_reads(c, handle, "coverage_count_resident", &set));
+    return count_window(c, start, stop, coverage_out, [&] { return coverage_count_resident(c, *set, start, stop, (unsigned)quality_threshold); });
 }
 
 int dmx_coverage_candidates(dmx_ctx *c, double minimum_coverage, double minimum_alternative_fraction, double minimum_alternative_coverage,

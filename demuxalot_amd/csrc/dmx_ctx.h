@@ -56,6 +56,20 @@ struct DevBuf {
     size_t n = 0;
 };
 
+// A resident read set (include/demux_hip_debug.h "Resident reads"; csrc/resident_reads.hip): the arrays of one dmx_decoded_reads
+// in buffers of the context, laid out as the caller's.  Read-only to every pass.
+struct ResidentReads {
+    long long n = 0, n_ops = 0, n_bases = 0;
+    long long reference_length = 0;  // the largest reference_end (0 without reads)
+    bool countable = false;          // cb, ub, p and score are held (else the set serves coverage only)
+    int64_t bytes = 0;               // device bytes held
+    DevBuf<int> start, cb, ub, score, n_cigar, l_seq;
+    DevBuf<double> p;
+    DevBuf<long long> cigar_begin, seq_begin;
+    DevBuf<unsigned> cigar;
+    DevBuf<unsigned char> seq, qual;
+};
+
 struct dmx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -238,6 +252,9 @@ struct dmx_ctx {
     long long cov_W = -1, cov_start = 0, cov_candidates = -1;
     int coverage_form = DMX_COVERAGE_TILED;  // dmx_set_coverage_form
     double cov_stage_ms[dmx::COVERAGE_STAGES] = {};
+    // resident read sets (resident_reads.hip): the caller's, by handle; they outlive dmx_release_problem, dmx_destroy frees them
+    std::map<int64_t, ResidentReads> resident_reads;
+    int64_t reads_upload_bytes = 0;  // decoded-read arrays copied host to device so far (dmx_get_reads_upload_bytes)
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at

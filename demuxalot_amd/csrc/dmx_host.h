@@ -26,6 +26,11 @@ void release_count_reads(dmx_ctx *c);    // the records of dmx_count_reads / dmx
 void release_count_reads_carry(dmx_ctx *c);   // the carry of a read-counting stream
 void release_count_reads_stream(dmx_ctx *c);  // the whole stream: carry, positions, table, state
 void release_coverage(dmx_ctx *c);       // the window and the candidates of dmx_coverage_* (coverage.hip)
+void release_resident_reads(dmx_ctx *c, ResidentReads &set);  // the buffers of one resident read set (resident_reads.hip)
+// the set behind a handle of dmx_reads_upload on this context; a stale or foreign handle: DMX_ERR_INVALID
+int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentReads **set);
+// bytes of the decoded-read arrays a call copies to the device: the eight a coverage pass reads, or all twelve
+int64_t decoded_reads_bytes(long long n_reads, long long n_ops, long long n_bases, bool with_counting_columns);
 int build_row_segments(dmx_ctx *c);
 int ensure_options(dmx_ctx *c, int with_doublets, const float *penalties);
 int upload_prior_logits(dmx_ctx *c, const void *prior, int dtype);

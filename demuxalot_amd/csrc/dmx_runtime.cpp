@@ -623,6 +623,38 @@ void release_coverage(dmx_ctx *c)
     c->cov_start = 0;
 }
 
+void release_resident_reads(dmx_ctx *c, ResidentReads &set)
+{
+    dev_free(c, set.start);
+    dev_free(c, set.cb);
+    dev_free(c, set.ub);
+    dev_free(c, set.score);
+    dev_free(c, set.n_cigar);
+    dev_free(c, set.l_seq);
+    dev_free(c, set.p);
+    dev_free(c, set.cigar_begin);
+    dev_free(c, set.seq_begin);
+    dev_free(c, set.cigar);
+    dev_free(c, set.seq);
+    dev_free(c, set.qual);
+    set = ResidentReads();
+}
+
+int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentReads **set)
+{
+    const auto it = c->resident_reads.find(handle);
+    if (it == c->resident_reads.end())
+        return fail(DMX_ERR_INVALID, "%s: %lld is no resident read set of this context (released, or another context's)", who, (long long)handle);
+    *set = &it->second;
+    return 0;
+}
+
+int64_t decoded_reads_bytes(long long n_reads, long long n_ops, long long n_bases, bool with_counting_columns)
+{
+    const long long per_read = 3 * 4 + 2 * 8 + (with_counting_columns ? 3 * 4 + 8 : 0);
+    return (int64_t)(n_reads * per_read + n_ops * 4 + n_bases * 2);
+}
+
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)
 {
     if (!dst) return 0;
@@ -693,6 +725,8 @@ int dmx_destroy(dmx_ctx *c)
     release_count_reads(c);
     release_count_reads_stream(c);
     release_coverage(c);
+    for (auto &entry : c->resident_reads) release_resident_reads(c, entry.second);
+    c->resident_reads.clear();
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too

@@ -462,6 +462,66 @@ class DeviceContext:
         check(self._lib.dmx_get_count_reads_peak_bytes(self._h, ctypes.byref(n)))
         return n.value
 
+    # ---- resident reads (include/demux_hip_debug.h "Resident reads"; snp_counter.ResidentReads is the front) ----
+    def reads_upload(self, reads, coverage_only=False):
+        """Handle of the DecodedReads' arrays uploaded once to this context; coverage_only leaves out the four columns only
+        counting reads (compressed_cb, compressed_ub, p_misaligned, alignment_score)."""
+        arrays = reads.arrays()  # kept alive until the call returns
+        pointers = {name: ptr(a) for name, a in arrays.items()}
+        if coverage_only:
+            for name in ('compressed_cb', 'compressed_ub', 'p_misaligned', 'alignment_score'):
+                pointers[name] = None
+        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']), **pointers)
+        handle = ctypes.c_int64(0)
+        check(self._lib.dmx_reads_upload(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), ctypes.byref(handle)))
+        return handle.value
+
+    def reads_release(self, handle):
+        check(self._lib.dmx_reads_release(self._h, int(handle)))
+
+    def reads_info(self, handle):
+        """{n_reads, n_cigar_ops, n_bases, nbytes, reference_length} of a resident set (dmx_reads_info)."""
+        info = (ctypes.c_int64 * len(_lib.READS_INFO))()
+        check(self._lib.dmx_reads_info(self._h, int(handle), info))
+        return dict(zip(_lib.READS_INFO, (int(v) for v in info)))
+
+    def reads_upload_bytes(self):
+        """Bytes of decoded-read arrays this context has copied host to device so far (dmx_get_reads_upload_bytes)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_get_reads_upload_bytes(self._h, ctypes.byref(n)))
+        return n.value
+
+    def count_reads_resident(self, handle, positions, qual_table):
+        """count_reads on a resident set."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+        positions = as_c(positions, np.int32)
+        qual_table = as_c(qual_table, np.float64)
+        assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
+        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.dmx_count_reads_resident(self._h, int(handle), ptr(positions), len(positions), ptr(qual_table),
+                                                 ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
+        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
+        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
+        return molecules, snp_calls
+
+    def count_reads_push_resident(self, handle, first_read, last_read, final=False):
+        """count_reads_push with the reads [first_read, last_read) of a resident set as the chunk."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.dmx_count_reads_push_resident(self._h, int(handle), int(first_read), int(last_read), 1 if final else 0,
+                                                      ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
+        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
+        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
+        return molecules, snp_calls
+
+    def coverage_count_resident(self, handle, start, stop, quality_threshold=15, fetch=True):
+        """coverage_count on a resident set."""
+        out = np.empty((4, max(0, int(stop) - int(start))), dtype=np.int32) if fetch else None
+        check(self._lib.dmx_coverage_count_resident(self._h, int(handle), int(start), int(stop), int(quality_threshold), ptr(out)))
+        return out
+
     # ---- coverage (include/demux_hip.h: dmx_coverage_count / _candidates / _fetch_candidates; demuxalot_amd/snp_detection.py) ----
     def coverage_count(self, reads, start, stop, quality_threshold=15, fetch=True):
         """int32[4, stop - start] (rows A, C, G, T) counted on the device from a DecodedReads, by the rules of pysam's

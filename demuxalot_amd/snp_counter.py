@@ -169,6 +169,94 @@ class DecodedReads:
         return DecodedReads(cigar=flat(cigar, np.uint32), seq=flat(seq, np.uint8), qual=flat(qual, np.uint8), **columns)
 
 
+class ResidentReads:
+    """The arrays of one chromosome's DecodedReads uploaded ONCE to a device context and accepted wherever a DecodedReads is:
+    counting, coverage, candidate search and detection then move no read to the device (include/demux_hip_debug.h
+    "Resident reads"; DESIGN.md "Resident reads").  A context manager:
+
+        with ResidentReads(decoded) as resident:
+            calls = count_snps_from_reads({'chr1': resident}, {'chr1': positions})
+            candidates = find_candidate_positions({'chr1': resident}, minimum_coverage=200)
+
+    Without on_context the set lives on the shared context, and every call that takes it runs there under the shared lock;
+    with one, on that context (the caller holds it) - a call that names another context raises ValueError.  The set keeps
+    no reference to the host arrays.  coverage_only leaves compressed_cb, compressed_ub, p_misaligned and alignment_score
+    on the host: such a set serves coverage_from_reads and find_candidate_positions, counting on it fails."""
+
+    def __init__(self, reads, on_context=None, *, coverage_only=False):
+        self._ctx = self._handle = None
+        if not isinstance(reads, DecodedReads):
+            raise TypeError('reads must be a DecodedReads')
+        self._shared = on_context is None
+        self._coverage_only = bool(coverage_only)
+
+        def upload(ctx):
+            handle = ctx.reads_upload(reads, coverage_only=self._coverage_only)
+            return ctx, handle, ctx.reads_info(handle)
+
+        if self._shared:
+            with shared_context_lock:
+                self._ctx, self._handle, self._info = upload(get_context())
+        else:
+            self._ctx, self._handle, self._info = upload(on_context)
+
+    def _check(self, on_context=None):
+        if self._handle is None:
+            raise ValueError('this ResidentReads is closed')
+        if on_context is not None and on_context is not self._ctx:
+            raise ValueError('this ResidentReads lives on another context than the one the call runs on')
+
+    @property
+    def closed(self):
+        """True once close() has run (or the with block was left); every other use then raises ValueError."""
+        return self._handle is None
+
+    @property
+    def coverage_only(self):
+        """True for a set uploaded without the four counting columns."""
+        return self._coverage_only
+
+    @property
+    def n_reads(self):
+        self._check()
+        return self._info['n_reads']
+
+    @property
+    def nbytes(self):
+        """Device bytes the set holds."""
+        self._check()
+        return self._info['nbytes']
+
+    @property
+    def reference_length(self):
+        """The largest reference_end of the reads (0 without reads), found on the device when the set was uploaded."""
+        self._check()
+        return max(0, self._info['reference_length'])
+
+    def close(self):
+        ctx, handle, self._handle = self._ctx, self._handle, None
+        if handle is None or getattr(ctx, '_h', None) is None:  # (a destroyed context has freed its sets)
+            return
+        if self._shared:
+            with shared_context_lock:
+                ctx.reads_release(handle)
+        else:
+            ctx.reads_release(handle)
+
+    def __enter__(self):
+        self._check()
+        return self
+
+    def __exit__(self, *_exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def _container(molecules, snp_calls):
     out = CompressedSNPCalls(start_snps_size=1, start_molecule_size=1)
     out.molecules, out.snp_calls = molecules, snp_calls
@@ -228,14 +316,24 @@ class ReadCounter:
             raise RuntimeError('ReadCounter is a context manager: push inside its with block')
         if self._finished:
             raise RuntimeError('this ReadCounter has finished')
-        if reads is not None and not isinstance(reads, DecodedReads):
-            raise TypeError('a chunk must be a DecodedReads')
-        out = self._ctx.count_reads_push(reads, final=final)
+        if isinstance(reads, ResidentReads):
+            reads = (reads, 0, reads.n_reads)
+        if isinstance(reads, tuple):
+            if len(reads) != 3 or not isinstance(reads[0], ResidentReads):
+                raise TypeError('a device range is (ResidentReads, first_read, last_read)')
+            resident, lo, hi = reads
+            resident._check(self._ctx)
+            out = self._ctx.count_reads_push_resident(resident._handle, lo, hi, final=final)
+        elif reads is not None and not isinstance(reads, DecodedReads):
+            raise TypeError('a chunk must be a DecodedReads, a ResidentReads or a (ResidentReads, first_read, last_read) range')
+        else:
+            out = self._ctx.count_reads_push(reads, final=final)
         self._finished = final
         return out
 
     def push(self, reads):
-        """(molecules, snp_calls) of the molecules the reads of this chunk flushed."""
+        """(molecules, snp_calls) of the molecules the reads of this chunk flushed.  reads: a DecodedReads, or reads that are
+        on the counter's context already: a ResidentReads (all of it) or a (ResidentReads, first_read, last_read) range."""
         return self._push(reads, False)
 
     def finish(self, reads=None):
@@ -264,11 +362,23 @@ def _count_chunks(ctx, chunks, positions):
     return _container(np.concatenate(molecules), np.concatenate(snp_calls))
 
 
-def _on(on_context, run):
+def _on(on_context, run, reads=()):
+    """run(ctx) on the context the call belongs to: on_context (the caller holds it), else the context of the ResidentReads
+    among `reads` (the shared one under its lock), else the shared context under its lock."""
+    sets = [r for r in reads if isinstance(r, ResidentReads)]
+    for resident in sets:
+        resident._check(on_context)
+        if resident._ctx is not sets[0]._ctx:
+            raise ValueError('the ResidentReads of one call must live on one context')
     if on_context is not None:
         return run(on_context)
+    if sets and not sets[0]._shared:
+        return run(sets[0]._ctx)
     with shared_context_lock:
-        return run(get_context())
+        ctx = get_context()
+        if sets and sets[0]._ctx is not ctx:
+            raise ValueError('the shared context these ResidentReads were uploaded to is no longer the shared context')
+        return run(ctx)
 
 
 def count_snps_from_read_chunks(chromosome2chunks, chromosome2positions, *, on_context=None):
@@ -301,11 +411,13 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
     chromosome2positions (in its order) one device call that groups the reads into molecules, walks the CIGARs to the
     SNP positions, multiplies the base-error probabilities and resolves conflicting bases (DESIGN.md "Read counting").
 
-    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing)
+    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing) or ResidentReads (the reads are
+        on the device already: nothing is uploaded, and the call runs on their context)
     :param chromosome2positions: dict chromosome -> strictly ascending zero-based SNP positions
     :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
     :param max_reads_per_call: None: one device call per chromosome.  A number: every chromosome is cut into slices of at most
-        that many reads and streamed (ReadCounter), which bounds the device memory by the slice; the result is the same.
+        that many reads and streamed (ReadCounter), which bounds the device memory by the slice; the result is the same.  The
+        slices of a ResidentReads are ranges on the device, cut where the host slices are.
     :return: dict chromosome -> CompressedSNPCalls, record for record what the reference's count_call_variants_for_chromosome
         returns.  A chromosome without reads gives an empty container; reads of a chromosome without positions are skipped.
     """
@@ -319,15 +431,21 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
         result = {}
         for chromosome, positions in chromosome2positions.items():
             reads = chromosome2reads.get(chromosome)
-            if reads is not None and not isinstance(reads, DecodedReads):
-                raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads')
+            if reads is not None and not isinstance(reads, (DecodedReads, ResidentReads)):
+                raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads or a ResidentReads')
+            resident = isinstance(reads, ResidentReads)
             if reads is None or reads.n_reads == 0:
                 result[chromosome] = _empty_container()
             elif max_reads_per_call is None:
-                result[chromosome] = _container(*ctx.count_reads(reads, positions, table))
+                counted = ctx.count_reads_resident(reads._handle, positions, table) if resident else ctx.count_reads(reads, positions, table)
+                result[chromosome] = _container(*counted)
             else:
-                step = int(max_reads_per_call)
-                result[chromosome] = _count_chunks(ctx, (reads.slice(lo, lo + step) for lo in range(0, reads.n_reads, step)), positions)
+                step, n = int(max_reads_per_call), reads.n_reads
+                if resident:
+                    chunks = ((reads, lo, min(lo + step, n)) for lo in range(0, n, step))
+                else:
+                    chunks = (reads.slice(lo, lo + step) for lo in range(0, n, step))
+                result[chromosome] = _count_chunks(ctx, chunks, positions)
         return result
 
-    return _on(on_context, run)
+    return _on(on_context, run, [chromosome2reads.get(chromosome) for chromosome in chromosome2positions])

@@ -36,7 +36,7 @@ import pandas as pd
 
 from .demux import Demultiplexer, DevicePosteriors
 from .device import get_context, shared_context_lock
-from .snp_counter import DecodedReads, count_snps_from_reads
+from .snp_counter import DecodedReads, ResidentReads, _on, count_snps_from_reads
 
 P_BASE_WRONG_BELOW = np.float32(0.01)  # calls['p_base_wrong'] < 0.01 compares in float32 (snp_detection.py:111)
 ASSIGNMENT_THRESHOLD = 0.8             # posterior above which a barcode counts for its donor (snp_detection.py:166)
@@ -169,12 +169,18 @@ def _check_candidate_arguments(minimum_coverage, minimum_alternative_fraction, m
         raise ValueError(f'quality_threshold must be an integer 0 .. 255, got {quality_threshold!r}')
 
 
+def _check_cigar_ranges(reads):
+    first, last = reads.cigar_begin, reads.cigar_begin + reads.n_cigar
+    if reads.n_reads and (reads.n_cigar.min() < 0 or first.min() < 0 or last.max() > len(reads.cigar)):
+        raise ValueError("a read's cigar range lies outside the cigar array")
+
+
 def reference_ends(reads):
-    """int64 reference_end of every read of a DecodedReads: start + the operations that advance the reference (0, 2, 3, 7, 8)."""
+    """int64 reference_end of every read of a DecodedReads: start + the operations that advance the reference (0, 2, 3, 7, 8).
+    On the host; a ResidentReads knows the largest of them from the device (reference_length)."""
+    _check_cigar_ranges(reads)
     cigar = reads.cigar
     first, last = reads.cigar_begin, reads.cigar_begin + reads.n_cigar
-    if reads.n_reads and (reads.n_cigar.min() < 0 or first.min() < 0 or last.max() > len(cigar)):
-        raise ValueError("a read's cigar range lies outside the cigar array")
     advances = np.isin(cigar & 15, (0, 2, 3, 7, 8)) * (cigar >> 4).astype(np.int64)
     consumed = np.concatenate([[0], np.cumsum(advances, dtype=np.int64)])
     return reads.reference_start.astype(np.int64) + consumed[last] - consumed[first]
@@ -184,17 +190,17 @@ def coverage_from_reads(reads, start, stop, *, quality_threshold=15, on_context=
     """The counterpart of pysam's AlignmentFile.count_coverage(chromosome, start, stop, quality_threshold, read_callback) on
     the reads of one chromosome: int32[4, stop - start], rows A, C, G, T (the contract is in the module docstring).
 
-    :param reads: DecodedReads of the chromosome (reference_start non-decreasing)
+    :param reads: DecodedReads of the chromosome (reference_start non-decreasing), or a ResidentReads (nothing is uploaded; the
+        call runs on its context)
     :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
     """
-    if not isinstance(reads, DecodedReads):
-        raise TypeError('reads must be a DecodedReads')
+    if not isinstance(reads, (DecodedReads, ResidentReads)):
+        raise TypeError('reads must be a DecodedReads or a ResidentReads')
     if not 0 <= start <= stop:
         raise ValueError(f'the window must satisfy 0 <= start <= stop, got [{start}, {stop})')
-    if on_context is not None:
-        return on_context.coverage_count(reads, start, stop, quality_threshold)
-    with shared_context_lock:
-        return get_context().coverage_count(reads, start, stop, quality_threshold)
+    if isinstance(reads, ResidentReads):
+        return _on(on_context, lambda ctx: ctx.coverage_count_resident(reads._handle, start, stop, quality_threshold), [reads])
+    return _on(on_context, lambda ctx: ctx.coverage_count(reads, start, stop, quality_threshold))
 
 
 def find_candidate_positions(chromosome2reads, *, minimum_coverage, minimum_alternative_fraction=0.01,
@@ -204,10 +210,16 @@ def find_candidate_positions(chromosome2reads, *, minimum_coverage, minimum_alte
     ref / alt filter, the max_snp_candidates cut, on the device.  The fragments are the reference's (:194-195):
     [k * max_fragment_step, min((k + 1) * max_fragment_step, length)); the cut applies per fragment.
 
-    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing)
+    :param chromosome2reads: dict chromosome -> DecodedReads (reference_start non-decreasing) or ResidentReads.  A DecodedReads
+        is uploaded once for all its fragments, as a temporary coverage-only set that is released before the next chromosome
+        (the device holds one chromosome and one window at a time); a ResidentReads is counted where it lies.
     :param chromosome2length: dict chromosome -> reference length; default (and for chromosomes it does not list): the largest
-        reference_end of the chromosome's reads
-    :param on_context: a DeviceContext to run on (the caller holds it); default: the shared context, under its lock
+        reference_end of the chromosome's reads, found on the device (ResidentReads.reference_length).  For a DecodedReads that
+        end is known only once the chromosome is uploaded, so a default length beyond 2^31 - 1 raises its ValueError when the
+        run reaches that chromosome, after the ones before it were counted; given lengths, the lengths of ResidentReads and
+        cigar ranges outside the array are refused before anything is counted.
+    :param on_context: a DeviceContext to run on (the caller holds it); default: the context of the ResidentReads if there are
+        any, else the shared context, under its lock
     :return: dict chromosome -> ascending int32 ABSOLUTE positions, in the order of chromosome2reads; a chromosome without
         reads gives an empty array
     """
@@ -215,34 +227,60 @@ def find_candidate_positions(chromosome2reads, *, minimum_coverage, minimum_alte
         raise TypeError('chromosome2reads must be a dict chromosome -> DecodedReads')
     _check_candidate_arguments(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
                                minimum_fraction_of_ref_and_alt, max_snp_candidates, max_fragment_step, quality_threshold)
-    lengths = {}
+
+    def checked(chromosome, length):
+        if length >= 2 ** 31:
+            raise ValueError(f'chromosome {chromosome!r}: length {length} is beyond 2^31 - 1')
+        return length
+
+    lengths = {}  # what is known before anything is counted; the others: the temporary set's reference_length
     for chromosome, reads in chromosome2reads.items():
-        if not isinstance(reads, DecodedReads):
-            raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads')
+        if not isinstance(reads, (DecodedReads, ResidentReads)):
+            raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads or a ResidentReads')
         if chromosome2length is not None and chromosome in chromosome2length:
-            lengths[chromosome] = int(chromosome2length[chromosome])
+            lengths[chromosome] = checked(chromosome, int(chromosome2length[chromosome]))
+        elif isinstance(reads, ResidentReads):
+            lengths[chromosome] = checked(chromosome, reads.reference_length)
+        elif reads.n_reads == 0:
+            lengths[chromosome] = 0
         else:
-            lengths[chromosome] = int(max(0, reference_ends(reads).max())) if reads.n_reads else 0
-        if lengths[chromosome] >= 2 ** 31:
-            raise ValueError(f'chromosome {chromosome!r}: length {lengths[chromosome]} is beyond 2^31 - 1')
+            _check_cigar_ranges(reads)
+
+    def fragments(ctx, count, length):
+        found = [np.zeros(0, dtype=np.int32)]
+        for start in range(0, length, int(max_fragment_step)):
+            count(start, min(start + int(max_fragment_step), length))
+            found.append(ctx.coverage_candidates(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
+                                                 minimum_fraction_of_ref_and_alt, int(max_snp_candidates)))
+        return np.concatenate(found)
 
     def run(ctx):
         result = {}
         for chromosome, reads in chromosome2reads.items():
-            found = [np.zeros(0, dtype=np.int32)]
-            if reads.n_reads:
-                for start in range(0, lengths[chromosome], int(max_fragment_step)):
-                    ctx.coverage_count(reads, start, min(start + int(max_fragment_step), lengths[chromosome]), quality_threshold,
-                                       fetch=False)
-                    found.append(ctx.coverage_candidates(minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
-                                                         minimum_fraction_of_ref_and_alt, int(max_snp_candidates)))
-            result[chromosome] = np.concatenate(found)
+            if reads.n_reads == 0:
+                result[chromosome] = np.zeros(0, dtype=np.int32)
+            elif isinstance(reads, ResidentReads):
+                result[chromosome] = fragments(ctx, lambda start, stop, handle=reads._handle: ctx.coverage_count_resident(
+                    handle, start, stop, quality_threshold, fetch=False), lengths[chromosome])
+            elif not hasattr(ctx, 'reads_upload'):
+                # duck-typed compatibility path: `on_context` may be any object with coverage_count / coverage_candidates (the
+                # tests' host restatement is one).  One that keeps no reads is handed the arrays per fragment, and the length
+                # comes from the host walk; a DeviceContext never takes this branch.
+                length = lengths[chromosome] if chromosome in lengths else checked(chromosome, int(max(0, reference_ends(reads).max())))
+                result[chromosome] = fragments(ctx, lambda start, stop, reads=reads: ctx.coverage_count(
+                    reads, start, stop, quality_threshold, fetch=False), length)
+            else:
+                handle = ctx.reads_upload(reads, coverage_only=True)
+                try:
+                    length = lengths[chromosome] if chromosome in lengths else checked(
+                        chromosome, max(0, ctx.reads_info(handle)['reference_length']))
+                    result[chromosome] = fragments(ctx, lambda start, stop, handle=handle: ctx.coverage_count_resident(
+                        handle, start, stop, quality_threshold, fetch=False), length)
+                finally:
+                    ctx.reads_release(handle)
         return result
 
-    if on_context is not None:
-        return run(on_context)
-    with shared_context_lock:
-        return run(get_context())
+    return _on(on_context, run, list(chromosome2reads.values()))
 
 
 def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handler, *, minimum_coverage,
@@ -259,6 +297,8 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
       5. scoring and selection as in detect_snps_positions_from_calls.
     Steps 2 to 5 run on the posteriors' device context.  Chromosomes are taken in the order of chromosome2reads; a
     chromosome without candidates is left out (the reference's `return []`).
+    chromosome2reads and coverage_reads may hold ResidentReads: the three read passes (steps 1, 3 and 4) then run on the sets'
+    context and upload nothing, steps 2 and 5 on the posteriors' context; the candidate calls cross as host containers.
 
     :param coverage_reads: dict chromosome -> DecodedReads for step 3 when they differ from chromosome2reads.  The reference's
         stage 1 counts every read parse_read accepts, while DecodedReads by contract also drop the reads without a whitelisted
@@ -270,6 +310,8 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
                                minimum_fraction_of_ref_and_alt, max_snp_candidates, max_fragment_step, quality_threshold)
     if coverage_reads is None:
         coverage_reads = chromosome2reads
+    # reads that are resident decide where the read passes run; host arrays go to the posteriors' context, as ever
+    resident = any(isinstance(reads, ResidentReads) for reads in list(chromosome2reads.values()) + list(coverage_reads.values()))
     known_calls = count_snps_from_reads(chromosome2reads, genotypes.get_chromosome2positions())
     posteriors = Demultiplexer.predict_posteriors(known_calls, genotypes, barcode_handler, doublet_prior=0.0, on_device=True)
     try:
@@ -280,9 +322,9 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
             minimum_coverage=minimum_coverage, minimum_alternative_fraction=minimum_alternative_fraction,
             minimum_alternative_coverage=minimum_alternative_coverage, max_snp_candidates=max_snp_candidates,
             minimum_fraction_of_ref_and_alt=minimum_fraction_of_ref_and_alt, max_fragment_step=max_fragment_step,
-            chromosome2length=chromosome2length, quality_threshold=quality_threshold, on_context=ctx)
+            chromosome2length=chromosome2length, quality_threshold=quality_threshold, on_context=None if resident else ctx)
         candidates = {chromosome: positions for chromosome, positions in candidates.items() if len(positions)}
-        candidate_calls = count_snps_from_reads(chromosome2reads, candidates, on_context=ctx)
+        candidate_calls = count_snps_from_reads(chromosome2reads, candidates, on_context=None if resident else ctx)
         selected = _select_on(ctx, candidate_calls, sorted_donors, donor_of_barcode, regularization, n_best_snps_per_donor,
                               n_additional_best_snps, max_contribution_to_base_count_from_barcode)
     finally:

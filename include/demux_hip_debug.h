@@ -232,7 +232,9 @@ int dmx_get_count_reads_timings(dmx_ctx *ctx, double *stage_ms);
  * dmx_get_count_reads_carry: reads the last push of the open stream left on the device as the carry (0 without a stream).
  * dmx_get_count_reads_peak_bytes: bytes the last dmx_count_reads or dmx_count_reads_push held at its end, when it holds the
  * most: the temporaries and the input on the device (for a push: carry + chunk, the stream's positions and table, the next
- * carry), as asked of the context's allocator. */
+ * carry), as asked of the context's allocator.  For the resident calls ("Resident reads" below): the call's own temporaries
+ * and the input it gathered (positions and table; for a push: carry + the gathered range, the next carry) - NOT the set, whose
+ * bytes dmx_reads_info reports. */
 int dmx_get_count_reads_carry(dmx_ctx *ctx, int64_t *n_reads);
 int dmx_get_count_reads_peak_bytes(dmx_ctx *ctx, int64_t *bytes);
 
@@ -246,6 +248,49 @@ int dmx_set_coverage_form(dmx_ctx *ctx, int form);
  * (scripts/coverage_timing.py): stage_ms[6] = upload (with clearing the window), CIGAR walk + prefix maximum, window / tile bounds,
  * accumulate; filter + compaction, top-n + emit (0 until dmx_coverage_candidates has run on the window). */
 int dmx_get_coverage_timings(dmx_ctx *ctx, double *stage_ms);
+
+/* ------------------------------------------------------------------------- *
+ * Resident reads (product API; declared here because demux_hip.h is kept to 64 entry points).
+ * The arrays of one dmx_decoded_reads uploaded ONCE into buffers the context owns, named by a handle, and taken by the
+ * read-side passes in place of host arrays: counting, coverage and the pushes of a stream then move no read to the device
+ * (DESIGN.md "Resident reads").  Several sets may be resident at once (one per chromosome).  A set is read-only to every pass.
+ *   dmx_reads_upload    copies the arrays and returns the handle.  It refuses only what the host-array calls refuse before they
+ *                       upload (n_reads outside 0 .. 2^31 - 1, negative sizes, null cigar / seq / qual or per-read arrays):
+ *                       whether a READ is invalid stays the decision of the pass that consumes it - counting judges the reads
+ *                       that count, coverage every read -, with the status the host-array call gives on the same reads.
+ *                       compressed_cb, compressed_ub, p_misaligned and alignment_score may be null, as for dmx_coverage_count
+ *                       (all four are kept, or none): such a set serves coverage only, counting on it answers
+ *                       DMX_ERR_INVALID.  Handles are unique in the process and never reused: a released handle and a handle
+ *                       of another context answer DMX_ERR_INVALID everywhere.  The caller's arrays are free when it returns.
+ *   dmx_reads_release   frees one set.  dmx_destroy frees what is left; dmx_release_problem does NOT: the sets are the caller's,
+ *                       not part of the problem.
+ *   dmx_reads_info      info[5] = n_reads, n_cigar_ops, n_bases, device bytes held, the largest reference_end: reference_start
+ *                       plus the lengths of the operations 0, 2, 3, 7, 8 (M D N = X; the rule both CIGAR walkers share), found
+ *                       on the device at upload; a read whose CIGAR range lies outside the array ends where it starts; 0 for
+ *                       no reads.
+ *   dmx_count_reads_resident      dmx_count_reads on the set.
+ *   dmx_coverage_count_resident   dmx_coverage_count on the set.
+ *   dmx_count_reads_push_resident dmx_count_reads_push with the reads [first_read, last_read) of the set as the chunk (cigar_begin
+ *                       and seq_begin of a set are arbitrary offsets: the range is gathered behind the carry on the device).
+ *                       A bad handle or range (first_read < 0, last_read < first_read, last_read > n_reads) is refused before the
+ *                       stream is looked at and leaves it open; every other failure ends the stream as a failed
+ *                       dmx_count_reads_push does.
+ *   dmx_get_reads_upload_bytes    cumulative bytes of decoded-read arrays this context copied host to device: by
+ *                       dmx_reads_upload, dmx_count_reads, dmx_count_reads_push (twelve arrays) and dmx_coverage_count (the
+ *                       eight it reads).  Positions and tables are not reads.  The resident calls add nothing.
+ * Records, coverage arrays, candidates, status codes and error flags of a resident call are those of the host-array call on
+ * the same reads, float fields bit for bit; fetch, candidates, timings, carry and the stream's begin / end are the existing
+ * entry points. */
+int dmx_reads_upload(dmx_ctx *ctx, const dmx_decoded_reads *reads, int64_t *handle);
+int dmx_reads_release(dmx_ctx *ctx, int64_t handle);
+int dmx_reads_info(dmx_ctx *ctx, int64_t handle, int64_t *info);
+int dmx_count_reads_resident(dmx_ctx *ctx, int64_t handle, const int32_t *positions, int64_t n_positions, const double *qual_table41,
+                             int64_t *n_molecules, int64_t *n_calls);
+int dmx_coverage_count_resident(dmx_ctx *ctx, int64_t handle, int32_t start, int32_t stop, int32_t quality_threshold,
+                                int32_t *coverage_out);
+int dmx_count_reads_push_resident(dmx_ctx *ctx, int64_t handle, int64_t first_read, int64_t last_read, int final, int64_t *n_molecules,
+                                  int64_t *n_calls);
+int dmx_get_reads_upload_bytes(dmx_ctx *ctx, int64_t *bytes);
 
 #ifdef __cplusplus
 }
