@@ -24,7 +24,7 @@
 //
 // Streaming (dmx_count_reads_begin / _push / _end, include/demux_hip_debug.h; DESIGN.md "Read counting", "Streaming"): a push runs the same six stages on
 // carry + chunk.  The carry, the reads of the molecules no event has flushed yet, stays on the device between pushes
-// (dmx_ctx::d_crs_*).  Carried reads are never events; molecules whose flushing event is "none" are left out of stages 3 to 6
+// (dmx_ctx::crs_carry, a ReadColumns).  Carried reads are never events; molecules whose flushing event is "none" are left out of stages 3 to 6
 // of a push that is not final, and their reads are compacted into the next carry.
 #include <climits>
 #include <cstring>
@@ -34,26 +34,19 @@
 
 #include "device_scratch.h"
 #include "dmx_host.h"
+#include "read_columns.h"
 
 namespace {
 
 using dmx::host::bind;
 using namespace dmx::scratch;
+using namespace dmx::reads;
 
 constexpr int MOLECULE_BYTES = 12, SNP_CALL_BYTES = 13, SEGMENT = 1000, QUALITY_CAP = 40;
 // flag word
 constexpr int F_UNSORTED = 1, F_LAYOUT = 2, F_OP = 4, F_INDEX = 8, F_LETTER = 16, F_POSITIONS = 32;
 
-// the reads and positions on the device
-struct Reads {
-    long long n, n_ops, n_bases, P;
-    const int *start, *cb, *ub, *score, *n_cigar, *l_seq;
-    const double *p_misaligned;
-    const long long *cigar_begin, *seq_begin;
-    const unsigned *cigar;
-    const unsigned char *seq, *qual;
-    const int *positions;
-};
+typedef StageClock<dmx::COUNT_READS_STAGES> Clock;
 
 __device__ __forceinline__ long long segment_of(long long start)  // Python's start // 1000
 {
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(256) void k_cr_positions(const int *__restrict__ po
 }
 
 // Stage 1.  A read whose arrays do not lie inside cigar / seq is flagged and treated as empty: nothing is read out of bounds.
-__global__ __launch_bounds__(256) void k_cr_walk(Reads R, int *__restrict__ end, ull *__restrict__ n_obs, unsigned char *__restrict__ err,
+__global__ __launch_bounds__(256) void k_cr_walk(ReadsView R, const int *__restrict__ positions, long long P, int *__restrict__ end, ull *__restrict__ n_obs, unsigned char *__restrict__ err,
                                                  ull *__restrict__ is_event, ull *__restrict__ key, unsigned *__restrict__ idx, int *flags,
                                                  long long n_carry, int has_previous, long long previous_start)
 {
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256) void k_cr_walk(Reads R, int *__restrict__ end,
     is_event[i] = event ? 1ull : 0ull;
     long long c0 = R.cigar_begin[i], nc = R.n_cigar[i];
     const long long s0 = R.seq_begin[i], ls = R.l_seq[i];
-    if (nc < 0 || c0 < 0 || c0 > R.n_ops || nc > R.n_ops - c0 || ls < 0 || s0 < 0 || s0 > R.n_bases || ls > R.n_bases - s0) {
+    if (outside(c0, nc, R.n_ops) || outside(s0, ls, R.n_bases)) {
         atomicOr(flags, F_LAYOUT);
         nc = 0;
     }
@@ -113,10 +106,10 @@ __global__ __launch_bounds__(256) void k_cr_walk(Reads R, int *__restrict__ end,
         const unsigned op = c & 15u;
         const long long len = c >> 4;
         if (op == 0 || op == 7 || op == 8) {
-            const long long lo = lower_bound(R.positions, R.P, ref), hi = lower_bound(R.positions, R.P, ref + len);
+            const long long lo = lower_bound(positions, P, ref), hi = lower_bound(positions, P, ref + len);
             if (hi > lo) {
                 found += hi - lo;
-                if (rd + (R.positions[hi - 1] - ref) >= ls) e |= F_INDEX;  // the largest read index of the block
+                if (rd + (positions[hi - 1] - ref) >= ls) e |= F_INDEX;  // the largest read index of the block
             }
             ref += len;
             rd += len;
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(256) void k_cr_group_p(const unsigned *__restrict__
 }
 
 // Stage 4: key (molecule << position_bits | position rank), value (read << 11 | base << 8 | quality), in (read, position) order
-__global__ __launch_bounds__(256) void k_cr_emit(Reads R, const ull *__restrict__ n_obs, const ull *__restrict__ obs_at,
+__global__ __launch_bounds__(256) void k_cr_emit(ReadsView R, const int *__restrict__ positions, long long P, const ull *__restrict__ n_obs, const ull *__restrict__ obs_at,
                                                  const unsigned *__restrict__ group_of_read, int position_bits, ull *__restrict__ key,
                                                  ull *__restrict__ value, int *flags)
 {
@@ -303,9 +296,9 @@ __global__ __launch_bounds__(256) void k_cr_emit(Reads R, const ull *__restrict_
         const unsigned op = c & 15u;
         const long long len = c >> 4;
         if (op == 0 || op == 7 || op == 8) {
-            const long long lo = lower_bound(R.positions, R.P, ref), hi = lower_bound(R.positions, R.P, ref + len);
+            const long long lo = lower_bound(positions, P, ref), hi = lower_bound(positions, P, ref + len);
             for (long long q = lo; q < hi && at < stop; q++) {
-                const long long b = rd + (R.positions[q] - ref);
+                const long long b = rd + (positions[q] - ref);
                 unsigned code = 0, quality = 0;
                 if (b >= 0 && b < ls) {  // (otherwise F_INDEX is set already)
                     const unsigned char letter = R.seq[s0 + b];
@@ -495,15 +488,9 @@ __global__ __launch_bounds__(256) void k_cr_carry_sizes(const unsigned char *__r
     bases[i] = o ? (ull)l_seq[i] : 0ull;
 }
 
-struct CarryColumns {
-    int *start, *cb, *ub, *score, *n_cigar, *l_seq;
-    double *p_misaligned;
-    long long *cigar_begin, *seq_begin;
-};
-
 // the nine per-read columns of the open reads, in read order; cigar_begin / seq_begin count from the carry's own start
-__global__ __launch_bounds__(256) void k_cr_carry_reads(Reads R, const unsigned char *__restrict__ open, const ull *__restrict__ read_at,
-                                                        const ull *__restrict__ ops_at, const ull *__restrict__ bases_at, CarryColumns out,
+__global__ __launch_bounds__(256) void k_cr_carry_reads(ReadsView R, const unsigned char *__restrict__ open, const ull *__restrict__ read_at,
+                                                        const ull *__restrict__ ops_at, const ull *__restrict__ bases_at, ReadsOut out,
                                                         long long *__restrict__ old_cigar_begin, long long *__restrict__ old_seq_begin)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -562,24 +549,6 @@ __global__ __launch_bounds__(256) void k_cr_carry_bases(const long long *__restr
     qual_out[e] = qual[from];
 }
 
-// hipEvents at the stage boundaries (dmx_get_count_reads_timings)
-struct StageClock {
-    hipEvent_t ev[dmx::COUNT_READS_STAGES + 1] = {};
-    int n = 0;
-    ~StageClock()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int tick(hipStream_t st)
-    {
-        HIP_TRY(hipEventCreate(&ev[n]));
-        HIP_TRY(hipEventRecord(ev[n], st));
-        n++;
-        return 0;
-    }
-};
-
 int flag_error(int flags)
 {
     if (flags & F_POSITIONS) return fail(DMX_ERR_INVALID, "count_reads: positions must be strictly ascending");
@@ -599,15 +568,54 @@ struct Pass {
     size_t resident_bytes = 0;  // the stream's positions and table (the peak meter counts the input whole)
 };
 
-size_t carry_bytes(const dmx_ctx *c)
+// ---- the gather: the reads flagged in open[] out of a view, in read order, into columns whose cigar / seq / qual segments
+// lie behind one another.  The next carry of a push is one (the open molecules' reads), a range of a resident set another
+// (every read flagged).  The plan finds the sizes, for the destination to be allocated by; the run copies.
+struct Gather {
+    const unsigned char *open = nullptr;
+    ull *read_at = nullptr, *ops_at = nullptr, *bases_at = nullptr;  // inclusive scans over the reads of what the flagged ones hold
+    ReadCounts total;
+};
+
+// work: six arrays of R.n elements the caller has free (the three scans stay in them until the run).  R's lengths are valid.
+int gather_plan(Scratch &sc, const ReadsView &R, const unsigned char *open, ull *const work[6], Gather *g, hipStream_t st)
 {
-    return dev_bytes(c->d_crs_start) * 6 + dev_bytes(c->d_crs_p) + dev_bytes(c->d_crs_cigar_begin) * 2 + dev_bytes(c->d_crs_cigar) +
-           dev_bytes(c->d_crs_seq) * 2;
+    ull n_reads = 0, n_ops = 0, n_bases = 0;
+    g->open = open, g->read_at = work[3], g->ops_at = work[4], g->bases_at = work[5];
+    hipLaunchKernelGGL(k_cr_carry_sizes, dim3(grid_for(R.n)), dim3(256), 0, st, open, R.n_cigar, R.l_seq, R.n, work[0], work[1], work[2]);
+    DMX_TRY(launched("k_cr_carry_sizes"));
+    DMX_TRY(sum_scan(sc, work[0], g->read_at, (size_t)R.n, &n_reads, st));
+    if (n_reads) {
+        DMX_TRY(sum_scan(sc, work[1], g->ops_at, (size_t)R.n, &n_ops, st));
+        DMX_TRY(sum_scan(sc, work[2], g->bases_at, (size_t)R.n, &n_bases, st));
+    }
+    g->total.n = (long long)n_reads, g->total.n_ops = (long long)n_ops, g->total.n_bases = (long long)n_bases;
+    return 0;
 }
 
-// The six stages on the reads R (device arrays; the first pass.n_carry are a stream's carry), then the next carry.
-int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *flags, const double *d_table, const Pass &pass,
-               long long *n_molecules, long long *n_calls)
+// out: room for g.total; its cigar_begin / seq_begin count from out's own cigar / seq
+int gather_run(Scratch &sc, const ReadsView &R, const Gather &g, const ReadsOut &out, hipStream_t st)
+{
+    if (!g.total.n) return 0;
+    long long *old_cigar_begin, *old_seq_begin;
+    DMX_TRY(sc.get(&old_cigar_begin, g.total.of(PER_READ)));
+    DMX_TRY(sc.get(&old_seq_begin, g.total.of(PER_READ)));
+    hipLaunchKernelGGL(k_cr_carry_reads, dim3(grid_for(R.n)), dim3(256), 0, st, R, g.open, g.read_at, g.ops_at, g.bases_at, out, old_cigar_begin,
+                       old_seq_begin);
+    DMX_TRY(launched("k_cr_carry_reads"));
+    if (g.total.n_ops) hipLaunchKernelGGL(k_cr_carry_ops, dim3(grid_for(g.total.n_ops)), dim3(256), 0, st, out.cigar_begin, old_cigar_begin,
+                                          g.total.n, g.total.n_ops, R.cigar, out.cigar);
+    DMX_TRY(launched("k_cr_carry_ops"));
+    if (g.total.n_bases) hipLaunchKernelGGL(k_cr_carry_bases, dim3(grid_for(g.total.n_bases)), dim3(256), 0, st, out.seq_begin, old_seq_begin,
+                                            g.total.n, g.total.n_bases, R.seq, R.qual, out.seq, out.qual);
+    DMX_TRY(launched("k_cr_carry_bases"));
+    return 0;
+}
+
+// The six stages on the reads R (device arrays; the first pass.n_carry are a stream's carry) and the P positions, then the
+// next carry.
+int count_pass(dmx_ctx *c, Scratch &sc, Clock &clock, const ReadsView &R, const int *d_positions, long long P, int *flags, const double *d_table,
+               const Pass &pass, long long *n_molecules, long long *n_calls)
 {
     hipStream_t st = c->stream;
     const long long n = R.n;
@@ -624,7 +632,8 @@ int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *
     DMX_TRY(sc.get(&key, (size_t)n));
     DMX_TRY(sc.get(&err, (size_t)n));
     DMX_TRY(sc.get(&idx, (size_t)n));
-    hipLaunchKernelGGL(k_cr_walk, dim3(grid_for(n)), dim3(256), 0, st, R, end, n_obs, err, is_event, key, idx, flags, pass.n_carry,
+    hipLaunchKernelGGL(k_cr_walk, dim3(grid_for(n)), dim3(256), 0, st, R, d_positions, P, end, n_obs, err, is_event, key, idx, flags,
+                       pass.n_carry,
                        pass.has_previous ? 1 : 0, pass.previous_start);
     DMX_TRY(launched("k_cr_walk"));
     ull n_events = 0;
@@ -725,8 +734,8 @@ int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *
     HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     DMX_TRY(flag_error(h_flags));
-    const int position_bits = bits_for((ull)R.P), group_bits = bits_for(G);
-    if (position_bits + group_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu molecules x %lld positions do not fit a 64-bit key", G, R.P);
+    const int position_bits = bits_for((ull)P), group_bits = bits_for(G);
+    if (position_bits + group_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu molecules x %lld positions do not fit a 64-bit key", G, P);
     if (n_observations >= (1ull << 32)) return fail(DMX_ERR_UNSUPPORTED, "count_reads: %llu observations in one call (at most 2^32 - 1): split the chromosome", n_observations);
     const long long n_o = (long long)n_observations;
     ull *okey, *oval, *okey_sorted, *oval_sorted;
@@ -734,7 +743,8 @@ int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *
     DMX_TRY(sc.get(&oval, (size_t)n_o));
     DMX_TRY(sc.get(&okey_sorted, (size_t)n_o));
     DMX_TRY(sc.get(&oval_sorted, (size_t)n_o));
-    hipLaunchKernelGGL(k_cr_emit, dim3(grid_for(n)), dim3(256), 0, st, R, n_obs, obs_at, group_of_read, position_bits, okey, oval, flags);
+    hipLaunchKernelGGL(k_cr_emit, dim3(grid_for(n)), dim3(256), 0, st, R, d_positions, P, n_obs, obs_at, group_of_read, position_bits, okey,
+                       oval, flags);
     DMX_TRY(launched("k_cr_emit"));
     DMX_TRY(sort_pairs(sc, okey, okey_sorted, oval, oval_sorted, (size_t)n_o, (unsigned)(position_bits + group_bits), st));
     DMX_TRY(clock.tick(st));
@@ -793,184 +803,59 @@ int count_pass(dmx_ctx *c, Scratch &sc, StageClock &clock, const Reads &R, int *
         DMX_TRY(launched("k_cr_call_keys"));
         DMX_TRY(sort_pairs(sc, ckey, ckey_sorted, csrc, csrc_sorted, (size_t)n_c, (unsigned)(32 + bits_for(n_m)), st));
         hipLaunchKernelGGL(k_cr_calls, dim3(grid_for((long long)n_c)), dim3(256), 0, st, ckey_sorted, csrc_sorted, (long long)n_c, okey_sorted,
-                           position_bits, R.positions, c_base, c_p, pass.molecule_base, c->d_cr_calls.p);
+                           position_bits, d_positions, c_base, c_p, pass.molecule_base, c->d_cr_calls.p);
         DMX_TRY(launched("k_cr_calls"));
     }
     // ---- the next carry: the open molecules' reads in read order, their cigar / seq / qual segments behind one another
     if (pass.keep_open) {
-        ull *f_reads = span_head, *f_ops = span_at, *f_bases = group_at, *read_at = reach_in, *ops_at = reach, *bases_at = skey;  // (all free)
-        ull n_open = 0, open_ops = 0, open_bases = 0;
-        hipLaunchKernelGGL(k_cr_carry_sizes, dim3(grid_for(n)), dim3(256), 0, st, open, R.n_cigar, R.l_seq, n, f_reads, f_ops, f_bases);
-        DMX_TRY(launched("k_cr_carry_sizes"));
-        DMX_TRY(sum_scan(sc, f_reads, read_at, (size_t)n, &n_open, st));
-        if (n_open) {
-            DMX_TRY(sum_scan(sc, f_ops, ops_at, (size_t)n, &open_ops, st));
-            DMX_TRY(sum_scan(sc, f_bases, bases_at, (size_t)n, &open_bases, st));
-            DMX_TRY(dev_alloc(c, c->d_crs_start, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_cb, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_ub, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_score, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_n_cigar, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_l_seq, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_p, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_cigar_begin, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_seq_begin, (size_t)n_open));
-            DMX_TRY(dev_alloc(c, c->d_crs_cigar, (size_t)open_ops));
-            DMX_TRY(dev_alloc(c, c->d_crs_seq, (size_t)open_bases));
-            DMX_TRY(dev_alloc(c, c->d_crs_qual, (size_t)open_bases));
-            long long *old_cigar_begin, *old_seq_begin;
-            DMX_TRY(sc.get(&old_cigar_begin, (size_t)n_open));
-            DMX_TRY(sc.get(&old_seq_begin, (size_t)n_open));
-            CarryColumns out;
-            out.start = c->d_crs_start.p, out.cb = c->d_crs_cb.p, out.ub = c->d_crs_ub.p, out.score = c->d_crs_score.p;
-            out.n_cigar = c->d_crs_n_cigar.p, out.l_seq = c->d_crs_l_seq.p, out.p_misaligned = c->d_crs_p.p;
-            out.cigar_begin = c->d_crs_cigar_begin.p, out.seq_begin = c->d_crs_seq_begin.p;
-            hipLaunchKernelGGL(k_cr_carry_reads, dim3(grid_for(n)), dim3(256), 0, st, R, open, read_at, ops_at, bases_at, out, old_cigar_begin,
-                               old_seq_begin);
-            DMX_TRY(launched("k_cr_carry_reads"));
-            if (open_ops) hipLaunchKernelGGL(k_cr_carry_ops, dim3(grid_for((long long)open_ops)), dim3(256), 0, st, c->d_crs_cigar_begin.p,
-                                             old_cigar_begin, (long long)n_open, (long long)open_ops, R.cigar, c->d_crs_cigar.p);
-            DMX_TRY(launched("k_cr_carry_ops"));
-            if (open_bases) hipLaunchKernelGGL(k_cr_carry_bases, dim3(grid_for((long long)open_bases)), dim3(256), 0, st, c->d_crs_seq_begin.p,
-                                               old_seq_begin, (long long)n_open, (long long)open_bases, R.seq, R.qual, c->d_crs_seq.p,
-                                               c->d_crs_qual.p);
-            DMX_TRY(launched("k_cr_carry_bases"));
-        }
-        c->crs_carry = (long long)n_open;
-        c->crs_ops = (long long)open_ops;
-        c->crs_bases = (long long)open_bases;
+        ull *const free_now[6] = {span_head, span_at, group_at, reach_in, reach, skey};
+        Gather open_reads;
+        DMX_TRY(gather_plan(sc, R, open, free_now, &open_reads, st));
+        if (open_reads.total.n) DMX_TRY(alloc_read_columns(c, c->crs_carry, open_reads.total, true));
+        DMX_TRY(gather_run(sc, R, open_reads, out_of(c->crs_carry), st));
     }
     DMX_TRY(clock.tick(st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (int s = 0; s < dmx::COUNT_READS_STAGES; s++) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, clock.ev[s], clock.ev[s + 1]));
-        c->cr_stage_ms[s] = ms;
-    }
+    DMX_TRY(clock.read(c->cr_stage_ms, 0));
     c->cr_molecules = (long long)n_m;
     c->cr_calls = (long long)n_c;
-    c->cr_peak_bytes = (int64_t)(sc.held + pass.resident_bytes + (c->crs_carry ? carry_bytes(c) : 0));
+    c->cr_peak_bytes = (int64_t)(sc.held + pass.resident_bytes + read_columns_bytes(c->crs_carry));
     *n_molecules = (long long)n_m;
     *n_calls = (long long)n_c;
     return 0;
 }
 
-int count_reads(dmx_ctx *c, const dmx_decoded_reads *h, const int32_t *positions, long long P, const double *table, long long *n_molecules,
-                long long *n_calls)
-{
-    hipStream_t st = c->stream;
-    dmx::host::release_count_reads(c);
-    const long long n = h->n_reads;
-    Scratch sc(c);
-    StageClock clock;
-    DMX_TRY(clock.tick(st));
-
-    // ---- upload
-    Reads R;
-    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases, R.P = P;
-    int *d_start, *d_cb, *d_ub, *d_score, *d_n_cigar, *d_l_seq, *d_positions, *flags;
-    double *d_p, *d_table;
-    long long *d_cigar_begin, *d_seq_begin;
-    unsigned *d_cigar;
-    unsigned char *d_seq, *d_qual;
-    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cb, h->compressed_cb, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_ub, h->compressed_ub, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_score, h->alignment_score, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_p, h->p_misaligned, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
-    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
-    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
-    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(n, h->n_cigar_ops, h->n_bases, true);
-    DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
-    DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
-    DMX_TRY(sc.get(&flags, 1));
-    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-    R.start = d_start, R.cb = d_cb, R.ub = d_ub, R.score = d_score, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.p_misaligned = d_p;
-    R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin, R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual, R.positions = d_positions;
-    DMX_TRY(clock.tick(st));
-    if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
-    DMX_TRY(launched("k_cr_positions"));
-    return count_pass(c, sc, clock, R, flags, d_table, Pass(), n_molecules, n_calls);
-}
-
-// the device-side view of a resident set's reads [first, first + n): the per-read columns move, cigar / seq / qual stay whole
-// (cigar_begin / seq_begin count from the set's own arrays)
-Reads reads_of(const ResidentReads &set, long long first, long long n)
-{
-    Reads R;
-    R.n = n, R.n_ops = set.n_ops, R.n_bases = set.n_bases, R.P = 0;
-    R.start = set.start.p + first, R.cb = set.cb.p + first, R.ub = set.ub.p + first, R.score = set.score.p + first;
-    R.n_cigar = set.n_cigar.p + first, R.l_seq = set.l_seq.p + first, R.p_misaligned = set.p.p + first;
-    R.cigar_begin = set.cigar_begin.p + first, R.seq_begin = set.seq_begin.p + first;
-    R.cigar = set.cigar.p, R.seq = set.seq.p, R.qual = set.qual.p;
-    R.positions = nullptr;
-    return R;
-}
-
-// dmx_count_reads on a resident set: the six stages read the set's buffers in place
-int count_reads_resident(dmx_ctx *c, const ResidentReads &set, const int32_t *positions, long long P, const double *table,
-                         long long *n_molecules, long long *n_calls)
+// dmx_count_reads and dmx_count_reads_resident: place() gives the reads, uploaded into the call's temporaries or a resident
+// set's own buffers, which the six stages then read in place
+template <typename Place>
+int count_reads(dmx_ctx *c, Place place, const int32_t *positions, long long P, const double *table, long long *n_molecules, long long *n_calls)
 {
     hipStream_t st = c->stream;
     dmx::host::release_count_reads(c);
     Scratch sc(c);
-    StageClock clock;
+    Clock clock;
     DMX_TRY(clock.tick(st));
-    Reads R = reads_of(set, 0, set.n);
-    R.P = P;
+    ReadsView R;
+    DMX_TRY(place(sc, &R));
     int *d_positions, *flags;
     double *d_table;
     DMX_TRY(upload(sc, &d_positions, positions, (size_t)P, st));
     DMX_TRY(upload(sc, &d_table, table, (size_t)QUALITY_CAP + 1, st));
     DMX_TRY(sc.get(&flags, 1));
     HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-    R.positions = d_positions;
     DMX_TRY(clock.tick(st));
     if (P) hipLaunchKernelGGL(k_cr_positions, dim3(grid_for(P)), dim3(256), 0, st, d_positions, P, flags);
     DMX_TRY(launched("k_cr_positions"));
-    return count_pass(c, sc, clock, R, flags, d_table, Pass(), n_molecules, n_calls);
+    return count_pass(c, sc, clock, R, d_positions, P, flags, d_table, Pass(), n_molecules, n_calls);
 }
 
 // ---- streaming
 
 enum { STREAM_NONE = 0, STREAM_OPEN = 1, STREAM_FINISHED = 2, STREAM_DEAD = 3 };  // dmx_ctx::crs_state
 
-// the per-read, per-operation and per-base columns of carry + chunk
-struct Combined {
-    int *start, *cb, *ub, *score, *n_cigar, *l_seq;
-    double *p;
-    long long *cigar_begin, *seq_begin;
-    unsigned *cigar;
-    unsigned char *seq, *qual;
-};
-
-// one column of carry + chunk: room for both, the carry copied device to device
-template <typename T>
-int combine(Scratch &sc, T **out, const DevBuf<T> &carry, size_t n_carry, size_t n_chunk, hipStream_t st)
-{
-    DMX_TRY(sc.get(out, n_carry + n_chunk));
-    if (n_carry) HIP_TRY(hipMemcpyAsync(*out, carry.p, n_carry * sizeof(T), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-template <typename T>
-int behind(T *out, size_t n_carry, const T *host, size_t n_chunk, hipStream_t st)
-{
-    if (n_chunk) HIP_TRY(hipMemcpyAsync(out + n_carry, host, n_chunk * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
 // A chunk of host arrays: its sizes are the caller's, its columns are uploaded behind the carry's; cigar_begin / seq_begin
 // count from the chunk's own arrays (k_cr_rebase moves them).
 struct HostChunk {
-    struct Measured {
-        size_t ops = 0, bases = 0;
-    };
     const dmx_decoded_reads *h;
     size_t n() const { return h ? (size_t)h->n_reads : 0; }
     int ends(dmx_ctx *, int *first, int *last) const
@@ -979,114 +864,64 @@ struct HostChunk {
         *last = h->reference_start[h->n_reads - 1];
         return 0;
     }
-    int measure(dmx_ctx *, Scratch &, int *, Measured *m) const
+    int measure(dmx_ctx *, Scratch &, int *, Gather *g) const
     {
-        m->ops = h ? (size_t)h->n_cigar_ops : 0;
-        m->bases = h ? (size_t)h->n_bases : 0;
+        if (h) g->total = host_reads(h);
         return 0;
     }
-    int place(dmx_ctx *c, Scratch &, const Measured &, const Combined &d, size_t n_carry, size_t carry_ops, size_t carry_bases) const
+    int place(dmx_ctx *c, Scratch &, const Gather &, const ReadsOut &out) const
     {
-        hipStream_t st = c->stream;
-        const size_t m = n();
         if (!h) return 0;
-        DMX_TRY(behind(d.start, n_carry, h->reference_start, m, st));
-        DMX_TRY(behind(d.cb, n_carry, h->compressed_cb, m, st));
-        DMX_TRY(behind(d.ub, n_carry, h->compressed_ub, m, st));
-        DMX_TRY(behind(d.score, n_carry, h->alignment_score, m, st));
-        DMX_TRY(behind(d.n_cigar, n_carry, h->n_cigar, m, st));
-        DMX_TRY(behind(d.l_seq, n_carry, h->l_seq, m, st));
-        DMX_TRY(behind(d.p, n_carry, h->p_misaligned, m, st));
-        DMX_TRY(behind(d.cigar_begin, n_carry, (const long long *)h->cigar_begin, m, st));
-        DMX_TRY(behind(d.seq_begin, n_carry, (const long long *)h->seq_begin, m, st));
-        DMX_TRY(behind(d.cigar, carry_ops, h->cigar, (size_t)h->n_cigar_ops, st));
-        DMX_TRY(behind(d.seq, carry_bases, h->seq, (size_t)h->n_bases, st));
-        DMX_TRY(behind(d.qual, carry_bases, h->qual, (size_t)h->n_bases, st));
+        DMX_TRY(copy_in(out, host_reads(h), true, c->stream));
         c->reads_upload_bytes += dmx::host::decoded_reads_bytes(h->n_reads, h->n_cigar_ops, h->n_bases, true);
         return 0;
     }
 };
 
 // per read of a range of a resident set: do its cigar / seq ranges lie inside the set's arrays (what the gather relies on)
-__global__ __launch_bounds__(256) void k_rr_check_range(Reads R, int *flags)
+__global__ __launch_bounds__(256) void k_rr_check_range(ReadsView R, int *flags)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R.n) return;
     const long long c0 = R.cigar_begin[i], nc = R.n_cigar[i], s0 = R.seq_begin[i], ls = R.l_seq[i];
-    if (nc < 0 || c0 < 0 || c0 > R.n_ops || nc > R.n_ops - c0 || ls < 0 || s0 < 0 || s0 > R.n_bases || ls > R.n_bases - s0) atomicOr(flags, F_LAYOUT);
+    if (outside(c0, nc, R.n_ops) || outside(s0, ls, R.n_bases)) atomicOr(flags, F_LAYOUT);
 }
 
-// A range of a resident set.  cigar_begin and seq_begin of a set are arbitrary offsets, so the range is no contiguous range
-// of operations or bases: it is gathered behind the carry the way the carry itself is placed (every read "open"): the three
-// sizes are scanned, one lane per read gathers the columns, one lane per operation and per base finds its read by binary search.
+// A range of a countable resident set.  cigar_begin and seq_begin of a set are arbitrary offsets, so the range is no contiguous
+// range of operations or bases: it is gathered behind the carry the way the carry itself is placed, every read flagged.
 struct ResidentChunk {
-    struct Measured {  // the sizes of the range and the scans behind them, which place() gathers by
-        size_t ops = 0, bases = 0;
-        ull *ops_at = nullptr, *bases_at = nullptr, *read_at = nullptr;
-        unsigned char *open = nullptr;
-    };
     const ResidentReads *set;
     long long first, count;
     size_t n() const { return (size_t)count; }
+    ReadsView reads() const { return view_of(set->columns, first, count, true); }
     int ends(dmx_ctx *c, int *lo, int *hi) const
     {
-        HIP_TRY(hipMemcpyAsync(lo, set->start.p + first, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(hi, set->start.p + first + count - 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        const int *start = set->columns.start.p + first;
+        HIP_TRY(hipMemcpyAsync(lo, start, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hi, start + count - 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return 0;
     }
-    int measure(dmx_ctx *c, Scratch &sc, int *flags, Measured *m) const
+    int measure(dmx_ctx *c, Scratch &sc, int *flags, Gather *g) const
     {
         hipStream_t st = c->stream;
         if (!count) return 0;
-        const Reads R = reads_of(*set, first, count);
-        hipLaunchKernelGGL(k_rr_check_range, dim3(grid_for(count)), dim3(256), 0, st, R, flags);
+        hipLaunchKernelGGL(k_rr_check_range, dim3(grid_for(count)), dim3(256), 0, st, reads(), flags);
         DMX_TRY(launched("k_rr_check_range"));
         int h_flags = 0;
         HIP_TRY(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         DMX_TRY(flag_error(h_flags));  // (the lengths are valid from here on)
-        ull *f_reads, *f_ops, *f_bases, n_reads = 0, n_ops = 0, n_bases = 0;
-        DMX_TRY(sc.get(&m->open, (size_t)count));
-        DMX_TRY(sc.get(&f_reads, (size_t)count));
-        DMX_TRY(sc.get(&f_ops, (size_t)count));
-        DMX_TRY(sc.get(&f_bases, (size_t)count));
-        DMX_TRY(sc.get(&m->read_at, (size_t)count));
-        DMX_TRY(sc.get(&m->ops_at, (size_t)count));
-        DMX_TRY(sc.get(&m->bases_at, (size_t)count));
-        HIP_TRY(hipMemsetAsync(m->open, 1, (size_t)count, st));
-        hipLaunchKernelGGL(k_cr_carry_sizes, dim3(grid_for(count)), dim3(256), 0, st, m->open, R.n_cigar, R.l_seq, count, f_reads, f_ops, f_bases);
-        DMX_TRY(launched("k_cr_carry_sizes"));
-        DMX_TRY(sum_scan(sc, f_reads, m->read_at, (size_t)count, &n_reads, st));
-        DMX_TRY(sum_scan(sc, f_ops, m->ops_at, (size_t)count, &n_ops, st));
-        DMX_TRY(sum_scan(sc, f_bases, m->bases_at, (size_t)count, &n_bases, st));
-        m->ops = (size_t)n_ops;
-        m->bases = (size_t)n_bases;
-        return 0;
+        unsigned char *every;
+        ull *work[6];
+        DMX_TRY(sc.get(&every, (size_t)count));
+        for (ull *&w : work) DMX_TRY(sc.get(&w, (size_t)count));
+        HIP_TRY(hipMemsetAsync(every, 1, (size_t)count, st));
+        return gather_plan(sc, reads(), every, work, g, st);
     }
-    int place(dmx_ctx *c, Scratch &sc, const Measured &m, const Combined &d, size_t n_carry, size_t carry_ops, size_t carry_bases) const
+    int place(dmx_ctx *c, Scratch &sc, const Gather &g, const ReadsOut &out) const
     {
-        hipStream_t st = c->stream;
-        if (!count) return 0;
-        const Reads R = reads_of(*set, first, count);
-        long long *old_cigar_begin, *old_seq_begin;
-        DMX_TRY(sc.get(&old_cigar_begin, (size_t)count));
-        DMX_TRY(sc.get(&old_seq_begin, (size_t)count));
-        CarryColumns out;
-        out.start = d.start + n_carry, out.cb = d.cb + n_carry, out.ub = d.ub + n_carry, out.score = d.score + n_carry;
-        out.n_cigar = d.n_cigar + n_carry, out.l_seq = d.l_seq + n_carry, out.p_misaligned = d.p + n_carry;
-        out.cigar_begin = d.cigar_begin + n_carry, out.seq_begin = d.seq_begin + n_carry;  // from the chunk's own start: k_cr_rebase moves them
-        hipLaunchKernelGGL(k_cr_carry_reads, dim3(grid_for(count)), dim3(256), 0, st, R, m.open, m.read_at, m.ops_at, m.bases_at, out,
-                           old_cigar_begin, old_seq_begin);
-        DMX_TRY(launched("k_cr_carry_reads"));
-        const size_t chunk_ops = m.ops, chunk_bases = m.bases;
-        if (chunk_ops) hipLaunchKernelGGL(k_cr_carry_ops, dim3(grid_for((long long)chunk_ops)), dim3(256), 0, st, out.cigar_begin, old_cigar_begin,
-                                          count, (long long)chunk_ops, R.cigar, d.cigar + carry_ops);
-        DMX_TRY(launched("k_cr_carry_ops"));
-        if (chunk_bases) hipLaunchKernelGGL(k_cr_carry_bases, dim3(grid_for((long long)chunk_bases)), dim3(256), 0, st, out.seq_begin, old_seq_begin,
-                                            count, (long long)chunk_bases, R.seq, R.qual, d.seq + carry_bases, d.qual + carry_bases);
-        DMX_TRY(launched("k_cr_carry_bases"));
-        return 0;
+        return count ? gather_run(sc, reads(), g, out, c->stream) : 0;  // (begins from the chunk's own start: k_cr_rebase moves them)
     }
 };
 
@@ -1096,66 +931,59 @@ int stream_push(dmx_ctx *c, const Chunk &chunk, bool final, long long *n_molecul
     hipStream_t st = c->stream;
     dmx::host::release_count_reads(c);
     const size_t n_chunk = chunk.n();
-    const size_t n_carry = (size_t)c->crs_carry, carry_ops = (size_t)c->crs_ops, carry_bases = (size_t)c->crs_bases;
-    if (n_carry + n_chunk > (size_t)INT_MAX)
-        return fail(DMX_ERR_UNSUPPORTED, "count_reads_push: %zu carried reads + %zu reads of the chunk (at most 2^31 - 1 in one push)", n_carry, n_chunk);
+    const ReadCounts carry = c->crs_carry;
+    if (carry.of(PER_READ) + n_chunk > (size_t)INT_MAX)
+        return fail(DMX_ERR_UNSUPPORTED, "count_reads_push: %zu carried reads + %zu reads of the chunk (at most 2^31 - 1 in one push)",
+                    carry.of(PER_READ), n_chunk);
     int first_start = 0, last_start = 0;
     if (n_chunk) DMX_TRY(chunk.ends(c, &first_start, &last_start));
     if (n_chunk && c->crs_has_previous && first_start < c->crs_previous_start)
         return fail(DMX_ERR_INVALID, "count_reads_push: the chunk starts at %d, below the previous chunk's last reference_start %lld",
                     first_start, c->crs_previous_start);
     Pass pass;
-    pass.n_carry = (long long)n_carry, pass.previous_start = c->crs_previous_start, pass.has_previous = c->crs_has_previous;
+    pass.n_carry = carry.n, pass.previous_start = c->crs_previous_start, pass.has_previous = c->crs_has_previous;
     pass.molecule_base = c->crs_molecules, pass.keep_open = !final;
     pass.resident_bytes = dev_bytes(c->d_crs_positions) + dev_bytes(c->d_crs_table);
     long long n_m = 0, n_c = 0;
-    if (n_carry + n_chunk == 0) {  // nothing to count: no records (a first or a final push without reads)
+    if (carry.of(PER_READ) + n_chunk == 0) {  // nothing to count: no records (a first or a final push without reads)
         c->cr_molecules = c->cr_calls = 0;
         for (double &ms : c->cr_stage_ms) ms = 0.0;
         c->cr_peak_bytes = (int64_t)pass.resident_bytes;
     } else {
         Scratch sc(c);
-        StageClock clock;
+        Clock clock;
         DMX_TRY(clock.tick(st));
         int *flags;
         DMX_TRY(sc.get(&flags, 1));
         HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int), st));
-        typename Chunk::Measured measured;
+        Gather measured;
         DMX_TRY(chunk.measure(c, sc, flags, &measured));
-        const size_t chunk_ops = measured.ops, chunk_bases = measured.bases;
-        Reads R;
-        R.n = (long long)(n_carry + n_chunk), R.n_ops = (long long)(carry_ops + chunk_ops), R.n_bases = (long long)(carry_bases + chunk_bases);
-        R.P = c->crs_P;
-        Combined d;
-        DMX_TRY(combine(sc, &d.start, c->d_crs_start, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.cb, c->d_crs_cb, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.ub, c->d_crs_ub, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.score, c->d_crs_score, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.n_cigar, c->d_crs_n_cigar, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.l_seq, c->d_crs_l_seq, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.p, c->d_crs_p, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.cigar_begin, c->d_crs_cigar_begin, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.seq_begin, c->d_crs_seq_begin, n_carry, n_chunk, st));
-        DMX_TRY(combine(sc, &d.cigar, c->d_crs_cigar, carry_ops, chunk_ops, st));
-        DMX_TRY(combine(sc, &d.seq, c->d_crs_seq, carry_bases, chunk_bases, st));
-        DMX_TRY(combine(sc, &d.qual, c->d_crs_qual, carry_bases, chunk_bases, st));
-        DMX_TRY(chunk.place(c, sc, measured, d, n_carry, carry_ops, carry_bases));
+        const ReadCounts in = measured.total;
+        ReadCounts all;
+        all.n = carry.n + in.n, all.n_ops = carry.n_ops + in.n_ops, all.n_bases = carry.n_bases + in.n_bases;
+        // the columns of carry + chunk: room for both, the carry copied device to device, the chunk placed behind it
+        ReadsOut d;
+        DMX_TRY(each_read_column(
+            [&](ReadExtent e, bool, auto &to, const auto &held) {
+                DMX_TRY(sc.get(&to, all.of(e)));
+                if (carry.of(e)) HIP_TRY(hipMemcpyAsync(to, held.p, carry.of(e) * sizeof(*to), hipMemcpyDeviceToDevice, st));
+                return 0;
+            },
+            d, c->crs_carry));
+        DMX_TRY(chunk.place(c, sc, measured, offset(d, carry)));
         dmx::host::release_count_reads_carry(c);  // (stream order: the copies above read the blocks before anything re-uses them)
-        if (n_chunk) hipLaunchKernelGGL(k_cr_rebase, dim3(grid_for((long long)n_chunk)), dim3(256), 0, st, d.cigar_begin, d.seq_begin, (long long)n_carry,
-                                        R.n, (long long)carry_ops, (long long)carry_bases, (long long)chunk_ops, (long long)chunk_bases, flags);
+        if (n_chunk) hipLaunchKernelGGL(k_cr_rebase, dim3(grid_for(in.n)), dim3(256), 0, st, d.cigar_begin, d.seq_begin, carry.n, all.n, carry.n_ops,
+                                        carry.n_bases, in.n_ops, in.n_bases, flags);
         DMX_TRY(launched("k_cr_rebase"));
-        R.start = d.start, R.cb = d.cb, R.ub = d.ub, R.score = d.score, R.n_cigar = d.n_cigar, R.l_seq = d.l_seq, R.p_misaligned = d.p;
-        R.cigar_begin = d.cigar_begin, R.seq_begin = d.seq_begin, R.cigar = d.cigar, R.seq = d.seq, R.qual = d.qual;
-        R.positions = c->d_crs_positions.p;
         DMX_TRY(clock.tick(st));
-        DMX_TRY(count_pass(c, sc, clock, R, flags, c->d_crs_table.p, pass, &n_m, &n_c));
+        DMX_TRY(count_pass(c, sc, clock, view_of(d, all), c->d_crs_positions.p, c->crs_P, flags, c->d_crs_table.p, pass, &n_m, &n_c));
     }
     if (n_chunk) {
         c->crs_previous_start = last_start;
         c->crs_has_previous = true;
     }
     c->crs_molecules += n_m;
-    c->cr_carried = c->crs_carry;
+    c->cr_carried = c->crs_carry.n;
     *n_molecules = n_m;
     *n_calls = n_c;
     return 0;
@@ -1181,14 +1009,73 @@ int stream_begin(dmx_ctx *c, const int32_t *positions, long long P, const double
     return 0;
 }
 
-int check_reads(const dmx_decoded_reads *reads, const char *who)
+bool bad_positions(const int32_t *positions, int64_t n_positions) { return n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions); }
+
+// What both one-shot entry points do around the pass.  input() looks at the reads the call names and says how many they are;
+// pass() counts them.  Without reads there are no records; a failed pass leaves none.
+template <typename Input, typename CountPass>
+int count_once(dmx_ctx *c, const char *who, bool null_input, const int32_t *positions, int64_t n_positions, const double *qual_table41,
+               int64_t *n_molecules, int64_t *n_calls, Input input, CountPass pass)
 {
-    if (reads->n_reads < 0 || reads->n_reads > INT_MAX) return fail(DMX_ERR_INVALID, "%s: n_reads must be 0 .. 2^31 - 1", who);
-    if (reads->n_cigar_ops < 0 || reads->n_bases < 0 || (reads->n_cigar_ops && !reads->cigar) || (reads->n_bases && (!reads->seq || !reads->qual)))
-        return fail(DMX_ERR_INVALID, "%s: bad cigar / seq / qual arrays", who);
-    if (reads->n_reads && (!reads->reference_start || !reads->compressed_cb || !reads->compressed_ub || !reads->p_misaligned ||
-                           !reads->alignment_score || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
-        return fail(DMX_ERR_INVALID, "%s: null per-read array", who);
+    DMX_TRY(bind(c));
+    if (null_input || !n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "%s: null argument", who);
+    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
+    if (bad_positions(positions, n_positions)) return fail(DMX_ERR_INVALID, "%s: bad positions", who);
+    long long n_reads = 0;
+    DMX_TRY(input(&n_reads));
+    *n_molecules = *n_calls = 0;
+    if (n_reads == 0) {
+        dmx::host::release_count_reads(c);
+        c->cr_molecules = c->cr_calls = 0;
+        c->cr_peak_bytes = 0;
+        for (double &ms : c->cr_stage_ms) ms = 0.0;
+        return 0;
+    }
+    long long n_m = 0, n_c = 0;
+    const int rc = pass(&n_m, &n_c);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        return rc;
+    }
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+// What both push entry points do around the push.  input() looks at arguments that, when they are bad, leave the stream
+// open; whatever push() refuses kills it: its carry goes, the records of its earlier pushes stand for nothing.
+template <typename Input, typename Push>
+int push_once(dmx_ctx *c, const char *who, int final, int64_t *n_molecules, int64_t *n_calls, Input input, Push push)
+{
+    DMX_TRY(bind(c));
+    if (!n_molecules || !n_calls) return fail(DMX_ERR_INVALID, "%s: null argument", who);
+    *n_molecules = *n_calls = 0;
+    if (c->crs_state == STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_begin before dmx_%s", who);
+    if (c->crs_state == STREAM_FINISHED) return fail(DMX_ERR_INVALID, "call order: dmx_%s after the final push", who);
+    if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
+    DMX_TRY(input());
+    long long n_m = 0, n_c = 0;
+    const int rc = push(&n_m, &n_c);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        dmx::host::release_count_reads(c);
+        dmx::host::release_count_reads_carry(c);
+        c->crs_state = STREAM_DEAD;
+        return rc;
+    }
+    if (final) c->crs_state = STREAM_FINISHED;
+    *n_molecules = n_m;
+    *n_calls = n_c;
+    return 0;
+}
+
+// the countable set behind a handle
+int find_countable(dmx_ctx *c, int64_t handle, const char *who, ResidentReads **set)
+{
+    DMX_TRY(dmx::host::find_resident_reads(c, handle, who, set));
+    if (!(*set)->countable)
+        return fail(DMX_ERR_INVALID, "%s: the set was uploaded without compressed_cb / compressed_ub / p_misaligned / alignment_score: it serves coverage only", who);
     return 0;
 }
 
@@ -1199,59 +1086,37 @@ extern "C" {
 int dmx_count_reads(dmx_ctx *c, const dmx_decoded_reads *reads, const int32_t *positions, int64_t n_positions, const double *qual_table41,
                     int64_t *n_molecules, int64_t *n_calls)
 {
-    DMX_TRY(bind(c));
-    if (!reads || !n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "count_reads: null argument");
-    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
-    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads: bad positions");
-    DMX_TRY(check_reads(reads, "count_reads"));
-    *n_molecules = *n_calls = 0;
-    if (reads->n_reads == 0) {
-        dmx::host::release_count_reads(c);
-        c->cr_molecules = c->cr_calls = 0;
-        c->cr_peak_bytes = 0;
-        for (double &ms : c->cr_stage_ms) ms = 0.0;
-        return 0;
-    }
-    long long n_m = 0, n_c = 0;
-    const int rc = count_reads(c, reads, positions, n_positions, qual_table41, &n_m, &n_c);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        dmx::host::release_count_reads(c);
-        return rc;
-    }
-    *n_molecules = n_m;
-    *n_calls = n_c;
-    return 0;
+    return count_once(
+        c, "count_reads", !reads, positions, n_positions, qual_table41, n_molecules, n_calls,
+        [&](long long *n_reads) {
+            *n_reads = reads->n_reads;
+            return check_reads(reads, "count_reads", false);
+        },
+        [&](long long *n_m, long long *n_c) {
+            const auto upload_them = [&](Scratch &sc, ReadsView *R) {
+                DMX_TRY(upload_reads(sc, host_reads(reads), true, R, c->stream));
+                c->reads_upload_bytes += dmx::host::decoded_reads_bytes(reads->n_reads, reads->n_cigar_ops, reads->n_bases, true);
+                return 0;
+            };
+            return count_reads(c, upload_them, positions, n_positions, qual_table41, n_m, n_c);
+        });
 }
 
 int dmx_count_reads_resident(dmx_ctx *c, int64_t handle, const int32_t *positions, int64_t n_positions, const double *qual_table41,
                              int64_t *n_molecules, int64_t *n_calls)
 {
-    DMX_TRY(bind(c));
-    if (!n_molecules || !n_calls || !qual_table41) return fail(DMX_ERR_INVALID, "count_reads_resident: null argument");
-    if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
-    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads_resident: bad positions");
     ResidentReads *set = nullptr;
-    DMX_TRY(dmx::host::find_resident_reads(c, handle, "count_reads_resident", &set));
-    if (!set->countable) return fail(DMX_ERR_INVALID, "count_reads_resident: the set was uploaded without compressed_cb / compressed_ub / p_misaligned / alignment_score: it serves coverage only");
-    *n_molecules = *n_calls = 0;
-    if (set->n == 0) {
-        dmx::host::release_count_reads(c);
-        c->cr_molecules = c->cr_calls = 0;
-        c->cr_peak_bytes = 0;
-        for (double &ms : c->cr_stage_ms) ms = 0.0;
-        return 0;
-    }
-    long long n_m = 0, n_c = 0;
-    const int rc = count_reads_resident(c, *set, positions, n_positions, qual_table41, &n_m, &n_c);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        dmx::host::release_count_reads(c);
-        return rc;
-    }
-    *n_molecules = n_m;
-    *n_calls = n_c;
-    return 0;
+    return count_once(
+        c, "count_reads_resident", false, positions, n_positions, qual_table41, n_molecules, n_calls,
+        [&](long long *n_reads) {
+            DMX_TRY(find_countable(c, handle, "count_reads_resident", &set));
+            *n_reads = set->columns.n;
+            return 0;
+        },
+        [&](long long *n_m, long long *n_c) {
+            const auto in_place = [&](Scratch &, ReadsView *R) { return *R = view_of(set->columns, 0, set->columns.n, true), 0; };
+            return count_reads(c, in_place, positions, n_positions, qual_table41, n_m, n_c);
+        });
 }
 
 int dmx_count_reads_begin(dmx_ctx *c, const int32_t *positions, int64_t n_positions, const double *qual_table41)
@@ -1259,7 +1124,7 @@ int dmx_count_reads_begin(dmx_ctx *c, const int32_t *positions, int64_t n_positi
     DMX_TRY(bind(c));
     if (!qual_table41) return fail(DMX_ERR_INVALID, "count_reads_begin: null argument");
     if (c->crs_state != STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: a read-counting stream is open on this context (dmx_count_reads_end first)");
-    if (n_positions < 0 || n_positions > INT_MAX || (n_positions && !positions)) return fail(DMX_ERR_INVALID, "count_reads_begin: bad positions");
+    if (bad_positions(positions, n_positions)) return fail(DMX_ERR_INVALID, "count_reads_begin: bad positions");
     dmx::host::release_count_reads(c);
     const int rc = stream_begin(c, positions, n_positions, qual_table41);
     if (rc) {
@@ -1273,57 +1138,28 @@ int dmx_count_reads_begin(dmx_ctx *c, const int32_t *positions, int64_t n_positi
 
 int dmx_count_reads_push(dmx_ctx *c, const dmx_decoded_reads *chunk, int final, int64_t *n_molecules, int64_t *n_calls)
 {
-    DMX_TRY(bind(c));
-    if (!n_molecules || !n_calls) return fail(DMX_ERR_INVALID, "count_reads_push: null argument");
-    *n_molecules = *n_calls = 0;
-    if (c->crs_state == STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_begin before dmx_count_reads_push");
-    if (c->crs_state == STREAM_FINISHED) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_push after the final push");
-    if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
-    int rc = chunk ? check_reads(chunk, "count_reads_push") : 0;
-    long long n_m = 0, n_c = 0;
-    if (!rc) rc = stream_push(c, HostChunk{chunk}, final != 0, &n_m, &n_c);
-    if (rc) {  // the stream is dead: its carry goes, the records of its earlier pushes stand for nothing
-        (void)hipStreamSynchronize(c->stream);
-        dmx::host::release_count_reads(c);
-        dmx::host::release_count_reads_carry(c);
-        c->crs_state = STREAM_DEAD;
-        return rc;
-    }
-    if (final) c->crs_state = STREAM_FINISHED;
-    *n_molecules = n_m;
-    *n_calls = n_c;
-    return 0;
+    return push_once(
+        c, "count_reads_push", final, n_molecules, n_calls, [] { return 0; },
+        [&](long long *n_m, long long *n_c) {
+            if (chunk) DMX_TRY(check_reads(chunk, "count_reads_push", false));
+            return stream_push(c, HostChunk{chunk}, final != 0, n_m, n_c);
+        });
 }
 
 int dmx_count_reads_push_resident(dmx_ctx *c, int64_t handle, int64_t first_read, int64_t last_read, int final, int64_t *n_molecules,
                                   int64_t *n_calls)
 {
-    DMX_TRY(bind(c));
-    if (!n_molecules || !n_calls) return fail(DMX_ERR_INVALID, "count_reads_push_resident: null argument");
-    *n_molecules = *n_calls = 0;
-    if (c->crs_state == STREAM_NONE) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_begin before dmx_count_reads_push_resident");
-    if (c->crs_state == STREAM_FINISHED) return fail(DMX_ERR_INVALID, "call order: dmx_count_reads_push_resident after the final push");
-    if (c->crs_state == STREAM_DEAD) return fail(DMX_ERR_INVALID, "call order: a push of this stream failed (dmx_count_reads_end is what is left to do)");
-    // the arguments are looked at before the stream is: a bad handle or range leaves it open
     ResidentReads *set = nullptr;
-    DMX_TRY(dmx::host::find_resident_reads(c, handle, "count_reads_push_resident", &set));
-    if (!set->countable) return fail(DMX_ERR_INVALID, "count_reads_push_resident: the set was uploaded without compressed_cb / compressed_ub / p_misaligned / alignment_score: it serves coverage only");
-    if (first_read < 0 || last_read < first_read || last_read > set->n)
-        return fail(DMX_ERR_INVALID, "count_reads_push_resident: the range [%lld, %lld) must satisfy 0 <= first_read <= last_read <= %lld reads",
-                    (long long)first_read, (long long)last_read, set->n);
-    long long n_m = 0, n_c = 0;
-    const int rc = stream_push(c, ResidentChunk{set, first_read, last_read - first_read}, final != 0, &n_m, &n_c);
-    if (rc) {  // the stream is dead, as after a failed dmx_count_reads_push
-        (void)hipStreamSynchronize(c->stream);
-        dmx::host::release_count_reads(c);
-        dmx::host::release_count_reads_carry(c);
-        c->crs_state = STREAM_DEAD;
-        return rc;
-    }
-    if (final) c->crs_state = STREAM_FINISHED;
-    *n_molecules = n_m;
-    *n_calls = n_c;
-    return 0;
+    return push_once(
+        c, "count_reads_push_resident", final, n_molecules, n_calls,
+        [&] {  // the arguments are looked at before the stream is: a bad handle or range leaves it open
+            DMX_TRY(find_countable(c, handle, "count_reads_push_resident", &set));
+            if (first_read < 0 || last_read < first_read || last_read > set->columns.n)
+                return fail(DMX_ERR_INVALID, "count_reads_push_resident: the range [%lld, %lld) must satisfy 0 <= first_read <= last_read <= %lld reads",
+                            (long long)first_read, (long long)last_read, set->columns.n);
+            return 0;
+        },
+        [&](long long *n_m, long long *n_c) { return stream_push(c, ResidentChunk{set, first_read, last_read - first_read}, final != 0, n_m, n_c); });
 }
 
 int dmx_count_reads_end(dmx_ctx *c)

@@ -28,11 +28,13 @@
 
 #include "device_scratch.h"
 #include "dmx_host.h"
+#include "read_columns.h"
 
 namespace {
 
 using dmx::host::bind;
 using namespace dmx::scratch;
+using namespace dmx::reads;
 
 constexpr int WAVE = 64, BLOCK = 256, WAVES = BLOCK / WAVE;
 constexpr int READS_PER_WAVE = 4;  // atomic form: consecutive reads one wavefront takes
@@ -41,19 +43,13 @@ constexpr int CHUNK = 1024;        // tiled form: reads one workgroup takes of a
 // flag word
 constexpr int F_UNSORTED = 1, F_LAYOUT = 2, F_OP = 4, F_INDEX = 8;
 
-struct Reads {
-    long long n, n_ops, n_bases;
-    const int *start, *n_cigar, *l_seq;
-    const long long *cigar_begin, *seq_begin;
-    const unsigned *cigar;
-    const unsigned char *seq, *qual;
-};
+typedef StageClock<dmx::COVERAGE_STAGES> Clock;
 
 __device__ __forceinline__ ull biased(int v) { return (ull)((unsigned)v ^ 0x80000000u); }
 
 // Stage 1.  Everything the later stages rely on is checked here, for every read of the input whatever the window: they run
 // only when no flag was raised, and then no index they form lies outside cigar / seq.
-__global__ __launch_bounds__(256) void k_cov_walk(Reads R, int *__restrict__ end, ull *__restrict__ reach_in, int *flags)
+__global__ __launch_bounds__(256) void k_cov_walk(ReadsView R, int *__restrict__ end, ull *__restrict__ reach_in, int *flags)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R.n) return;
@@ -61,7 +57,7 @@ __global__ __launch_bounds__(256) void k_cov_walk(Reads R, int *__restrict__ end
     if (i > 0 && start < R.start[i - 1]) atomicOr(flags, F_UNSORTED);
     long long c0 = R.cigar_begin[i], nc = R.n_cigar[i];
     const long long s0 = R.seq_begin[i], ls = R.l_seq[i];
-    if (nc < 0 || c0 < 0 || c0 > R.n_ops || nc > R.n_ops - c0 || ls < 0 || s0 < 0 || s0 > R.n_bases || ls > R.n_bases - s0) {
+    if (outside(c0, nc, R.n_ops) || outside(s0, ls, R.n_bases)) {
         atomicOr(flags, F_LAYOUT);
         nc = 0;
     }
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(256) void k_cov_tiles(const ull *__restrict__ reach
 
 // Stage 3: the aligned bases of read i inside [lo, hi), one lane per base of an operation; dst[code * stride + (r - lo)] += 1.
 // All lanes of the wavefront hold the same i.  LDS or global counters: the same atomic add, never returning.
-__device__ __forceinline__ void add_read(const Reads &R, long long i, int lane, long long lo, long long hi, int *dst, long long stride,
+__device__ __forceinline__ void add_read(const ReadsView &R, long long i, int lane, long long lo, long long hi, int *dst, long long stride,
                                          unsigned quality_threshold)
 {
     const long long c0 = R.cigar_begin[i], nc = R.n_cigar[i], s0 = R.seq_begin[i];
@@ -169,7 +165,7 @@ __device__ __forceinline__ void add_read(const Reads &R, long long i, int lane, 
 // the reads of [first, last) that end beyond lo, 64 at a time: one lane looks at one read's end, the wavefront then takes
 // the reads that passed one after the other (a read far before the tile is inside the prefix-maximum bound when an earlier
 // read with a long N skip reaches over it)
-__device__ __forceinline__ void add_reads(const Reads &R, const int *__restrict__ end, long long first, long long last, long long step, int lane,
+__device__ __forceinline__ void add_reads(const ReadsView &R, const int *__restrict__ end, long long first, long long last, long long step, int lane,
                                           long long lo, long long hi, int *dst, long long stride, unsigned quality_threshold)
 {
     for (long long base = first; base < last; base += step) {
@@ -183,7 +179,7 @@ __device__ __forceinline__ void add_reads(const Reads &R, const int *__restrict_
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_cov_atomic(Reads R, const int *__restrict__ end, long long first, long long last, long long w_lo,
+__global__ __launch_bounds__(BLOCK) void k_cov_atomic(ReadsView R, const int *__restrict__ end, long long first, long long last, long long w_lo,
                                                       long long w_hi, int *__restrict__ counts, unsigned quality_threshold)
 {
     const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(BLOCK) void k_cov_atomic(Reads R, const int *__rest
 }
 
 // workgroup g takes chunk (g - groups before its tile) of the tile whose inclusive group count is the first above g
-__global__ __launch_bounds__(BLOCK) void k_cov_tiled(Reads R, const int *__restrict__ end, const long long *__restrict__ first,
+__global__ __launch_bounds__(BLOCK) void k_cov_tiled(ReadsView R, const int *__restrict__ end, const long long *__restrict__ first,
                                                      const long long *__restrict__ last, const ull *__restrict__ groups_at, long long n_tiles,
                                                      long long w_lo, long long w_hi, int *__restrict__ counts, unsigned quality_threshold)
 {
@@ -279,33 +275,6 @@ __global__ __launch_bounds__(256) void k_cov_emit(const unsigned *__restrict__ i
     for (int b = 0; b < 4; b++) cand_counts[j * 4 + b] = counts[b * W + p];
 }
 
-struct Clock {
-    hipEvent_t ev[dmx::COVERAGE_STAGES + 1] = {};
-    int n = 0;
-    ~Clock()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int tick(hipStream_t st)
-    {
-        HIP_TRY(hipEventCreate(&ev[n]));
-        HIP_TRY(hipEventRecord(ev[n], st));
-        n++;
-        return 0;
-    }
-    // the spans between the ticks so far into ms[first ..]
-    int read(double *ms, int first)
-    {
-        for (int s = 0; s + 1 < n; s++) {
-            float span = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&span, ev[s], ev[s + 1]));
-            ms[first + s] = span;
-        }
-        return 0;
-    }
-};
-
 int flag_error(int flags)
 {
     if (flags & F_LAYOUT) return fail(DMX_ERR_INVALID, "coverage: a read's cigar / seq range lies outside the arrays, or its reference_end is beyond 2^31");
@@ -317,7 +286,7 @@ int flag_error(int flags)
 
 // Stages 1 to 3 on the reads R (device arrays the caller placed: uploaded into sc, or a resident set's own), after the
 // "upload" stage, which also clears the window.
-int coverage_window(dmx_ctx *c, Scratch &sc, Clock &clock, const Reads &R, long long w_lo, long long w_hi, unsigned quality_threshold)
+int coverage_window(dmx_ctx *c, Scratch &sc, Clock &clock, const ReadsView &R, long long w_lo, long long w_hi, unsigned quality_threshold)
 {
     hipStream_t st = c->stream;
     const long long n = R.n, W = w_hi - w_lo;
@@ -389,29 +358,14 @@ int coverage_window(dmx_ctx *c, Scratch &sc, Clock &clock, const Reads &R, long 
 int coverage_count(dmx_ctx *c, const dmx_decoded_reads *h, long long w_lo, long long w_hi, unsigned quality_threshold)
 {
     hipStream_t st = c->stream;
-    const long long n = h->n_reads;
     Scratch sc(c);
     Clock clock;
     DMX_TRY(clock.tick(st));
 
-    // ---- upload (compressed_cb, compressed_ub, p_misaligned and alignment_score are not read)
-    Reads R;
-    R.n = n, R.n_ops = h->n_cigar_ops, R.n_bases = h->n_bases;
-    int *d_start, *d_n_cigar, *d_l_seq;
-    long long *d_cigar_begin, *d_seq_begin;
-    unsigned *d_cigar;
-    unsigned char *d_seq, *d_qual;
-    DMX_TRY(upload(sc, &d_start, h->reference_start, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_n_cigar, h->n_cigar, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_l_seq, h->l_seq, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar_begin, (const long long *)h->cigar_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_seq_begin, (const long long *)h->seq_begin, (size_t)n, st));
-    DMX_TRY(upload(sc, &d_cigar, h->cigar, (size_t)h->n_cigar_ops, st));
-    DMX_TRY(upload(sc, &d_seq, h->seq, (size_t)h->n_bases, st));
-    DMX_TRY(upload(sc, &d_qual, h->qual, (size_t)h->n_bases, st));
-    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(n, h->n_cigar_ops, h->n_bases, false);
-    R.start = d_start, R.n_cigar = d_n_cigar, R.l_seq = d_l_seq, R.cigar_begin = d_cigar_begin, R.seq_begin = d_seq_begin;
-    R.cigar = d_cigar, R.seq = d_seq, R.qual = d_qual;
+    // ---- upload (the counting-only columns are not read)
+    ReadsView R;
+    DMX_TRY(upload_reads(sc, host_reads(h), false, &R, st));
+    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(h->n_reads, h->n_cigar_ops, h->n_bases, false);
     return coverage_window(c, sc, clock, R, w_lo, w_hi, quality_threshold);
 }
 
@@ -421,11 +375,7 @@ int coverage_count_resident(dmx_ctx *c, const ResidentReads &set, long long w_lo
     Scratch sc(c);
     Clock clock;
     DMX_TRY(clock.tick(c->stream));
-    Reads R;
-    R.n = set.n, R.n_ops = set.n_ops, R.n_bases = set.n_bases;
-    R.start = set.start.p, R.n_cigar = set.n_cigar.p, R.l_seq = set.l_seq.p, R.cigar_begin = set.cigar_begin.p, R.seq_begin = set.seq_begin.p;
-    R.cigar = set.cigar.p, R.seq = set.seq.p, R.qual = set.qual.p;
-    return coverage_window(c, sc, clock, R, w_lo, w_hi, quality_threshold);
+    return coverage_window(c, sc, clock, view_of(set.columns, 0, set.columns.n, false), w_lo, w_hi, quality_threshold);
 }
 
 // what both entry points do around the pass: the previous window goes, a failed pass leaves none

@@ -1,5 +1,6 @@
 // device_scratch.h -- what the multi-stage device passes (count_reads.hip, coverage.hip) share on the host side: temporaries
-// from the context's block cache that go back when the call leaves, uploads, rocPRIM scans and sorts on the ctx stream.
+// from the context's block cache that go back when the call leaves, uploads, rocPRIM scans and sorts on the ctx stream, the
+// stage clock.
 #pragma once
 #include <cstring>
 #include <vector>
@@ -92,6 +93,35 @@ int sort_pairs(Scratch &sc, const K *keys_in, K *keys_out, const V *vals_in, V *
     HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
     return 0;
 }
+
+// hipEvents at the boundaries of a pass's N stages (dmx_get_count_reads_timings, dmx_get_coverage_timings)
+template <int N>
+struct StageClock {
+    hipEvent_t ev[N + 1] = {};
+    int n = 0;
+    ~StageClock()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int tick(hipStream_t st)
+    {
+        HIP_TRY(hipEventCreate(&ev[n]));
+        HIP_TRY(hipEventRecord(ev[n], st));
+        n++;
+        return 0;
+    }
+    // the spans between the ticks so far into ms[first ..]
+    int read(double *ms, int first)
+    {
+        for (int s = 0; s + 1 < n; s++) {
+            float span = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&span, ev[s], ev[s + 1]));
+            ms[first + s] = span;
+        }
+        return 0;
+    }
+};
 
 inline int launched(const char *what)
 {

@@ -56,18 +56,51 @@ struct DevBuf {
     size_t n = 0;
 };
 
-// A resident read set (include/demux_hip_debug.h "Resident reads"; csrc/resident_reads.hip): the arrays of one dmx_decoded_reads
-// in buffers of the context, laid out as the caller's.  Read-only to every pass.
-struct ResidentReads {
+// The twelve arrays of a dmx_decoded_reads (include/demux_hip.h) on the device.  Every struct that holds them names them alike
+// (ReadColumns here; the pointer structs of read_columns.h), and each_read_column below is the one place that lists them.
+enum ReadExtent { PER_READ, PER_OP, PER_BASE };
+
+struct ReadCounts {
     long long n = 0, n_ops = 0, n_bases = 0;
-    long long reference_length = 0;  // the largest reference_end (0 without reads)
-    bool countable = false;          // cb, ub, p and score are held (else the set serves coverage only)
-    int64_t bytes = 0;               // device bytes held
+    size_t of(ReadExtent e) const { return (size_t)(e == PER_READ ? n : e == PER_OP ? n_ops : n_bases); }
+};
+
+// f(extent, counting_only, column ...) for every column, with that column of every struct given; the first status that is
+// not 0 ends the round and is returned.  counting_only: read by the counting passes alone (a coverage pass leaves them null).
+template <typename F, typename... Structs>
+int each_read_column(F &&f, Structs &...s)
+{
+    DMX_TRY(f(PER_READ, false, s.start...));
+    DMX_TRY(f(PER_READ, true, s.cb...));
+    DMX_TRY(f(PER_READ, true, s.ub...));
+    DMX_TRY(f(PER_READ, true, s.p_misaligned...));
+    DMX_TRY(f(PER_READ, true, s.score...));
+    DMX_TRY(f(PER_READ, false, s.cigar_begin...));
+    DMX_TRY(f(PER_READ, false, s.n_cigar...));
+    DMX_TRY(f(PER_READ, false, s.seq_begin...));
+    DMX_TRY(f(PER_READ, false, s.l_seq...));
+    DMX_TRY(f(PER_OP, false, s.cigar...));
+    DMX_TRY(f(PER_BASE, false, s.seq...));
+    DMX_TRY(f(PER_BASE, false, s.qual...));
+    return 0;
+}
+
+// The columns in buffers of the context, laid out as the caller's dmx_decoded_reads: a resident read set, a stream's carry.
+struct ReadColumns : ReadCounts {
     DevBuf<int> start, cb, ub, score, n_cigar, l_seq;
-    DevBuf<double> p;
+    DevBuf<double> p_misaligned;
     DevBuf<long long> cigar_begin, seq_begin;
     DevBuf<unsigned> cigar;
     DevBuf<unsigned char> seq, qual;
+};
+
+// A resident read set (include/demux_hip_debug.h "Resident reads"; csrc/resident_reads.hip): the arrays of one dmx_decoded_reads
+// in buffers of the context.  Read-only to every pass.
+struct ResidentReads {
+    ReadColumns columns;
+    long long reference_length = 0;  // the largest reference_end (0 without reads)
+    bool countable = false;          // the counting-only columns are held (else the set serves coverage only)
+    int64_t bytes = 0;               // device bytes held
 };
 
 struct dmx_ctx {
@@ -231,16 +264,12 @@ struct dmx_ctx {
     int64_t cr_peak_bytes = 0;  // scratch + input the last call or push held at its end, when it holds the most (dmx_get_count_reads_peak_bytes)
     long long cr_carried = 0;   // reads the last push left as the carry (dmx_get_count_reads_carry)
     // streamed read counting (dmx_count_reads_begin / _push / _end; one stream per context): the stream's positions and quality
-    // table, and the carry: the reads of the molecules no event has flushed yet, in read order, laid out as a dmx_decoded_reads
+    // table, and the carry: the reads of the molecules no event has flushed yet, in read order, a ReadColumns of their own
     DevBuf<int> d_crs_positions;  // [crs_P]
     DevBuf<double> d_crs_table;   // [41]
-    DevBuf<int> d_crs_start, d_crs_cb, d_crs_ub, d_crs_score, d_crs_n_cigar, d_crs_l_seq;  // [crs_carry]
-    DevBuf<double> d_crs_p;                                                               // [crs_carry]
-    DevBuf<long long> d_crs_cigar_begin, d_crs_seq_begin;                                 // [crs_carry]
-    DevBuf<unsigned> d_crs_cigar;                                                         // [crs_ops]
-    DevBuf<unsigned char> d_crs_seq, d_crs_qual;                                          // [crs_bases]
+    ReadColumns crs_carry;        // crs_carry.n reads, their operations and bases behind one another; allocated while n > 0
     int crs_state = 0;  // 0: no stream, 1: open, 2: the final push is done, 3: a push failed (count_reads.hip: STREAM_*)
-    long long crs_P = 0, crs_carry = 0, crs_ops = 0, crs_bases = 0;
+    long long crs_P = 0;
     long long crs_molecules = 0;       // molecules the stream has emitted: the molecule_index of the next push counts on from here
     long long crs_previous_start = 0;  // reference_start of the last read of the last non-empty chunk ...
     bool crs_has_previous = false;     // ... if there was one
@@ -391,6 +420,27 @@ inline int dev_grow(dmx_ctx *c, DevBuf<T> &b, size_t n)
     if (n <= b.n) return 0;
     dev_free(c, b);
     return dev_alloc(c, b, n);
+}
+
+// A ReadColumns as a whole: buffers for `counts` elements (the counting-only columns only where asked for; a failure leaves
+// what was allocated to free_read_columns), all of them back, the bytes of those that are held.
+inline int alloc_read_columns(dmx_ctx *c, ReadColumns &cols, const ReadCounts &counts, bool with_counting)
+{
+    static_cast<ReadCounts &>(cols) = counts;
+    return each_read_column([&](ReadExtent e, bool counting, auto &b) { return counting && !with_counting ? 0 : dev_alloc(c, b, counts.of(e)); }, cols);
+}
+
+inline void free_read_columns(dmx_ctx *c, ReadColumns &cols)
+{
+    (void)each_read_column([&](ReadExtent, bool, auto &b) { return dev_free(c, b), 0; }, cols);
+    cols = ReadColumns();
+}
+
+inline size_t read_columns_bytes(const ReadColumns &cols)
+{
+    size_t bytes = 0;
+    (void)each_read_column([&](ReadExtent, bool, const auto &b) { return bytes += b.p ? dev_bytes(b) : 0, 0; }, cols);
+    return bytes;
 }
 
 // hipMalloc / hipFree outside the block cache (the exchange's buffers, the prior logits), counted in c->bytes as well

@@ -587,22 +587,7 @@ void release_count_reads(dmx_ctx *c)
     c->cr_calls = 0;
 }
 
-void release_count_reads_carry(dmx_ctx *c)
-{
-    dev_free(c, c->d_crs_start);
-    dev_free(c, c->d_crs_cb);
-    dev_free(c, c->d_crs_ub);
-    dev_free(c, c->d_crs_score);
-    dev_free(c, c->d_crs_n_cigar);
-    dev_free(c, c->d_crs_l_seq);
-    dev_free(c, c->d_crs_p);
-    dev_free(c, c->d_crs_cigar_begin);
-    dev_free(c, c->d_crs_seq_begin);
-    dev_free(c, c->d_crs_cigar);
-    dev_free(c, c->d_crs_seq);
-    dev_free(c, c->d_crs_qual);
-    c->crs_carry = c->crs_ops = c->crs_bases = 0;
-}
+void release_count_reads_carry(dmx_ctx *c) { free_read_columns(c, c->crs_carry); }
 
 void release_count_reads_stream(dmx_ctx *c)
 {
@@ -625,18 +610,7 @@ void release_coverage(dmx_ctx *c)
 
 void release_resident_reads(dmx_ctx *c, ResidentReads &set)
 {
-    dev_free(c, set.start);
-    dev_free(c, set.cb);
-    dev_free(c, set.ub);
-    dev_free(c, set.score);
-    dev_free(c, set.n_cigar);
-    dev_free(c, set.l_seq);
-    dev_free(c, set.p);
-    dev_free(c, set.cigar_begin);
-    dev_free(c, set.seq_begin);
-    dev_free(c, set.cigar);
-    dev_free(c, set.seq);
-    dev_free(c, set.qual);
+    free_read_columns(c, set.columns);
     set = ResidentReads();
 }
 
@@ -651,8 +625,16 @@ int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentRea
 
 int64_t decoded_reads_bytes(long long n_reads, long long n_ops, long long n_bases, bool with_counting_columns)
 {
-    const long long per_read = 3 * 4 + 2 * 8 + (with_counting_columns ? 3 * 4 + 8 : 0);
-    return (int64_t)(n_reads * per_read + n_ops * 4 + n_bases * 2);
+    ReadColumns shape;  // (for the columns' extents and element types)
+    shape.n = n_reads, shape.n_ops = n_ops, shape.n_bases = n_bases;
+    int64_t bytes = 0;
+    (void)each_read_column(
+        [&](ReadExtent e, bool counting, const auto &b) {
+            if (with_counting_columns || !counting) bytes += (int64_t)(shape.of(e) * sizeof(*b.p));
+            return 0;
+        },
+        shape);
+    return bytes;
 }
 
 int copy_out(dmx_ctx *c, float *dst, const float *src, size_t count)

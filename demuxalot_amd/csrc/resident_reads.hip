@@ -5,7 +5,7 @@
 //            share), behind a bounds check of the read's CIGAR range; a reduction gives the largest end (dmx_reads_info)
 //
 // The passes that read a set live with their kernels: dmx_count_reads_resident and dmx_count_reads_push_resident in
-// count_reads.hip, dmx_coverage_count_resident in coverage.hip.  They point their device-side Reads at these buffers: no copy.
+// count_reads.hip, dmx_coverage_count_resident in coverage.hip.  They take a ReadsView of these buffers (read_columns.h): no copy.
 // Whether a read is valid stays their decision; the upload refuses only what the host-array calls refuse before they upload.
 #include <atomic>
 #include <climits>
@@ -16,11 +16,13 @@
 
 #include "device_scratch.h"
 #include "dmx_host.h"
+#include "read_columns.h"
 
 namespace {
 
 using dmx::host::bind;
 using namespace dmx::scratch;
+using namespace dmx::reads;
 
 // handles are unique in the process: one context's handle is never valid on another
 std::atomic<int64_t> g_next_handle{1};
@@ -34,7 +36,7 @@ __global__ __launch_bounds__(256) void k_rr_ends(const int *__restrict__ start, 
     if (i >= n) return;
     const long long c0 = cigar_begin[i];
     long long nc = n_cigar[i];
-    if (nc < 0 || c0 < 0 || c0 > n_ops || nc > n_ops - c0) nc = 0;
+    if (outside(c0, nc, n_ops)) nc = 0;
     long long ref = start[i];
     for (long long k = 0; k < nc; k++) {
         const unsigned c = cigar[c0 + k];
@@ -44,35 +46,16 @@ __global__ __launch_bounds__(256) void k_rr_ends(const int *__restrict__ start, 
     end[i] = ref;
 }
 
-template <typename T>
-int keep(dmx_ctx *c, DevBuf<T> &b, const T *host, size_t count, int64_t *bytes)
-{
-    DMX_TRY(dev_alloc(c, b, count));
-    *bytes += (int64_t)dev_bytes(b);
-    if (count) HIP_TRY(hipMemcpyAsync(b.p, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
-
 int reads_upload(dmx_ctx *c, const dmx_decoded_reads *h, ResidentReads &set)
 {
     hipStream_t st = c->stream;
     const size_t n = (size_t)h->n_reads;
-    set.n = h->n_reads, set.n_ops = h->n_cigar_ops, set.n_bases = h->n_bases;
+    const HostReads host = host_reads(h);
     set.countable = n == 0 || (h->compressed_cb && h->compressed_ub && h->p_misaligned && h->alignment_score);
-    DMX_TRY(keep(c, set.start, h->reference_start, n, &set.bytes));
-    DMX_TRY(keep(c, set.n_cigar, h->n_cigar, n, &set.bytes));
-    DMX_TRY(keep(c, set.l_seq, h->l_seq, n, &set.bytes));
-    DMX_TRY(keep(c, set.cigar_begin, (const long long *)h->cigar_begin, n, &set.bytes));
-    DMX_TRY(keep(c, set.seq_begin, (const long long *)h->seq_begin, n, &set.bytes));
-    DMX_TRY(keep(c, set.cigar, h->cigar, (size_t)h->n_cigar_ops, &set.bytes));
-    DMX_TRY(keep(c, set.seq, h->seq, (size_t)h->n_bases, &set.bytes));
-    DMX_TRY(keep(c, set.qual, h->qual, (size_t)h->n_bases, &set.bytes));
-    if (set.countable) {
-        DMX_TRY(keep(c, set.cb, h->compressed_cb, n, &set.bytes));
-        DMX_TRY(keep(c, set.ub, h->compressed_ub, n, &set.bytes));
-        DMX_TRY(keep(c, set.score, h->alignment_score, n, &set.bytes));
-        DMX_TRY(keep(c, set.p, h->p_misaligned, n, &set.bytes));
-    }
+    const int rc = alloc_read_columns(c, set.columns, host, set.countable);
+    set.bytes = (int64_t)read_columns_bytes(set.columns);
+    DMX_TRY(rc);
+    DMX_TRY(copy_in(out_of(set.columns), host, set.countable, st));
     // ---- ingest: the largest reference_end
     long long top = 0;
     if (n) {
@@ -80,8 +63,8 @@ int reads_upload(dmx_ctx *c, const dmx_decoded_reads *h, ResidentReads &set)
         long long *end, *d_top;
         DMX_TRY(sc.get(&end, n));
         DMX_TRY(sc.get(&d_top, 1));
-        hipLaunchKernelGGL(k_rr_ends, dim3(grid_for((long long)n)), dim3(256), 0, st, set.start.p, set.cigar_begin.p, set.n_cigar.p, set.cigar.p,
-                           (long long)n, set.n_ops, end);
+        hipLaunchKernelGGL(k_rr_ends, dim3(grid_for((long long)n)), dim3(256), 0, st, set.columns.start.p, set.columns.cigar_begin.p, set.columns.n_cigar.p,
+                           set.columns.cigar.p, (long long)n, set.columns.n_ops, end);
         DMX_TRY(launched("k_rr_ends"));
         size_t bytes = 0;
         HIP_TRY(rocprim::reduce(nullptr, bytes, end, d_top, (long long)LLONG_MIN, n, rocprim::maximum<long long>(), st));
@@ -92,7 +75,7 @@ int reads_upload(dmx_ctx *c, const dmx_decoded_reads *h, ResidentReads &set)
     }
     HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are free to change from here on)
     set.reference_length = top;
-    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(set.n, set.n_ops, set.n_bases, set.countable && n);
+    c->reads_upload_bytes += dmx::host::decoded_reads_bytes(h->n_reads, h->n_cigar_ops, h->n_bases, set.countable && n);
     return 0;
 }
 
@@ -105,11 +88,7 @@ int dmx_reads_upload(dmx_ctx *c, const dmx_decoded_reads *reads, int64_t *handle
     DMX_TRY(bind(c));
     if (!reads || !handle) return fail(DMX_ERR_INVALID, "reads_upload: null argument");
     *handle = 0;
-    if (reads->n_reads < 0 || reads->n_reads > INT_MAX) return fail(DMX_ERR_INVALID, "reads_upload: n_reads must be 0 .. 2^31 - 1");
-    if (reads->n_cigar_ops < 0 || reads->n_bases < 0 || (reads->n_cigar_ops && !reads->cigar) || (reads->n_bases && (!reads->seq || !reads->qual)))
-        return fail(DMX_ERR_INVALID, "reads_upload: bad cigar / seq / qual arrays");
-    if (reads->n_reads && (!reads->reference_start || !reads->cigar_begin || !reads->n_cigar || !reads->seq_begin || !reads->l_seq))
-        return fail(DMX_ERR_INVALID, "reads_upload: null per-read array");
+    DMX_TRY(check_reads(reads, "reads_upload", true));
     ResidentReads set;
     const int rc = reads_upload(c, reads, set);
     if (rc) {
@@ -140,9 +119,9 @@ int dmx_reads_info(dmx_ctx *c, int64_t handle, int64_t *info)
     if (!info) return fail(DMX_ERR_INVALID, "reads_info: null info");
     ResidentReads *set = nullptr;
     DMX_TRY(dmx::host::find_resident_reads(c, handle, "reads_info", &set));
-    info[0] = set->n;
-    info[1] = set->n_ops;
-    info[2] = set->n_bases;
+    info[0] = set->columns.n;
+    info[1] = set->columns.n_ops;
+    info[2] = set->columns.n_bases;
     info[3] = set->bytes;
     info[4] = set->reference_length;
     return 0;
