@@ -19,9 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "dmx_ctx.h"
+#include "device_scratch.h"
 
 namespace dmx {
+using namespace scratch;
 namespace {
 
 // range check without atomics in the good case: a wave only touches memory when it saw a bad index
@@ -264,64 +265,12 @@ __global__ __launch_bounds__(256) void k_bin_ptr(const unsigned *__restrict__ ce
     bin_ptr[i] = i < n_bins ? (long long)cell_start[(size_t)i * cells_per_bin] : total_groups;
 }
 
-inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
-
-inline unsigned bits_for(unsigned long long max_value)
-{
-    unsigned b = 1;
-    while (b < 64 && (max_value >> b) != 0) b++;
-    return b;
-}
-
-// scratch owner: frees everything on scope exit
-// Temporaries of one repack, taken from and returned to the context's block cache (dmx_ctx.h: ctx_malloc).  They go
-// back while the kernels that use them may still be queued: the context's next user of such a block runs behind them
-// on the same stream.
-struct Scratch {
-    dmx_ctx *ctx;
-    std::vector<void *> ptrs;
-    explicit Scratch(dmx_ctx *c) : ctx(c) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch()
-    {
-        for (void *p : ptrs) ctx_free(ctx, p);
-    }
-    template <typename T>
-    int get(T **out, size_t count)
-    {
-        void *p = nullptr;
-        const int rc = ctx_malloc(ctx, &p, (count ? count : 1) * sizeof(T));
-        if (rc) return rc;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return 0;
-    }
-};
-
-int sort_pairs(Scratch &sc, const unsigned *keys_in, unsigned *keys_out, const unsigned *vals_in, unsigned *vals_out,
-               size_t n, unsigned end_bit, hipStream_t st)
-{
-    if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    return 0;
-}
-
 // out[0..n] = exclusive prefix sums of in[0..n) (out has n+1 entries; the last is the total)
 int scan_with_total(Scratch &sc, const long long *in, long long *out, size_t n, hipStream_t st)
 {
     HIP_TRY(hipMemsetAsync(out, 0, sizeof(long long), st));
     if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, in, out + 1, n, rocprim::plus<long long>(), st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::inclusive_scan(tmp, bytes, in, out + 1, n, rocprim::plus<long long>(), st));
-    return 0;
+    return inclusive_scan(sc, in, out + 1, n, rocprim::plus<long long>(), st);
 }
 
 }  // namespace
@@ -369,8 +318,8 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
     DMX_TRY(sc.get(&keys_v, (size_t)N));
     DMX_TRY(sc.get(&perm_v, (size_t)N));
     if (N) hipLaunchKernelGGL(k_iota, dim3(grid_for(N)), dim3(256), 0, st, iota, N);
-    DMX_TRY(sort_pairs(sc, (const unsigned *)d_cb, keys_b, iota, perm_b, (size_t)N, bits_for(B ? B - 1 : 0), st));
-    DMX_TRY(sort_pairs(sc, (const unsigned *)d_variant, keys_v, iota, perm_v, (size_t)N, bits_for(V ? V - 1 : 0), st));
+    DMX_TRY(sort_pairs(sc, (const unsigned *)d_cb, keys_b, iota, perm_b, (size_t)N, bits_of(B ? B - 1 : 0), st));
+    DMX_TRY(sort_pairs(sc, (const unsigned *)d_variant, keys_v, iota, perm_v, (size_t)N, bits_of(V ? V - 1 : 0), st));
     long long *row_start = nullptr, *col_ptr = nullptr, *row_pairs = nullptr, *col_items = nullptr;
     DMX_TRY(sc.get(&row_start, (size_t)B + 1));
     DMX_TRY(sc.get(&col_ptr, (size_t)V + 1));
@@ -488,13 +437,7 @@ static int repack_core(dmx_ctx *c, Scratch &sc, const int *d_variant, const int 
         const dim3 row_grid((unsigned)((B + 3) / 4));
         hipLaunchKernelGGL(k_tile_groups<0>, row_grid, dim3(256), 0, st, c->d_call_pairs.p, c->d_pair_ptr.p, row_slot, B, (unsigned)G * 4u,
                            tile_rows, n_tiles, R, cnt, (const unsigned *)nullptr, (const unsigned *)nullptr, (CallPair *)nullptr);
-        {
-            size_t bytes = 0;
-            HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, cnt, cell_start, 0u, cells, rocprim::plus<unsigned>(), st));
-            char *tmp;
-            DMX_TRY(sc.get(&tmp, bytes));
-            HIP_TRY(rocprim::exclusive_scan(tmp, bytes, cnt, cell_start, 0u, cells, rocprim::plus<unsigned>(), st));
-        }
+        DMX_TRY(exclusive_scan(sc, cnt, cell_start, 0u, cells, rocprim::plus<unsigned>(), st));
         hipLaunchKernelGGL(k_row_tile_starts, dim3(grid_for(n_bins * R)), dim3(256), 0, st, cnt, n_bins, n_tiles, R, row_tile_start);
         hipLaunchKernelGGL(k_bin_ptr, dim3(grid_for(n_bins + 1)), dim3(256), 0, st, cell_start, n_bins, (size_t)n_tiles * R, total_groups,
                            c->d_bin_ptr.p);
@@ -623,7 +566,7 @@ int install_mstep_records(dmx_ctx *c, const uint4 *d_rec, long long n, long long
     DMX_TRY(sc.get(&row_keep, (size_t)m));
     if (n) hipLaunchKernelGGL(k_compact_slice, dim3(grid_for(n)), dim3(256), 0, st, d_rec, n, (unsigned)v_lo, (unsigned)v_hi, pos, variant, row_keep);
     if (m) hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, st, iota, m);
-    DMX_TRY(sort_pairs(sc, variant, keys_v, iota, perm, (size_t)m, bits_for(V ? V - 1 : 0), st));
+    DMX_TRY(sort_pairs(sc, variant, keys_v, iota, perm, (size_t)m, bits_of(V ? V - 1 : 0), st));
     // the old records and items go, the slice's come
     release_mstep_tiles(c);
     dev_free(c, c->d_csc);
@@ -740,18 +683,6 @@ __global__ __launch_bounds__(256) void k_tile_ptr(const unsigned *__restrict__ s
     }
     ptr[k] = lo;
 }
-
-int sort_pairs64(Scratch &sc, const unsigned *keys_in, unsigned *keys_out, const unsigned long long *vals_in,
-                 unsigned long long *vals_out, size_t n, unsigned end_bit, hipStream_t st)
-{
-    if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    return 0;
-}
 }  // namespace
 
 void release_mstep_tiles(dmx_ctx *c)
@@ -800,7 +731,7 @@ bool cut_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi, TileCut &t)
         c->n_simd = 4 * cus;
     }
     t.tv = std::max(1, std::min<int>(dmx::MTILE_MAX_VARIANTS, dmx::MTILE_LDS_BYTES / (G * 8)));
-    t.row_bits = bits_for(rows ? (unsigned long long)rows - 1 : 0);
+    t.row_bits = bits_of(rows ? (unsigned long long)rows - 1 : 0);
     t.tile_of.assign((size_t)V, 0u);
     t.vin_of.assign((size_t)V, 0u);
     // at most a 1024th of the calls per tile (four tiles per CU and more: most tiles end at their 128 variants first; a tile costs
@@ -822,7 +753,7 @@ bool cut_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi, TileCut &t)
             }
             v = w;
         }
-        const unsigned tile_bits = bits_for(t.tile_first.empty() ? 0 : (unsigned long long)t.tile_first.size() - 1);
+        const unsigned tile_bits = bits_of(t.tile_first.empty() ? 0 : (unsigned long long)t.tile_first.size() - 1);
         if (tile_bits + t.row_bits <= 32) break;
         if (cap >= m || attempt > 40) return false;  // even the widest tiles are too many for a 32-bit key: item form
         cap *= 2;
@@ -835,7 +766,7 @@ bool cut_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi, TileCut &t)
         long long longest = 1;
         for (long long v = t.tile_first[(size_t)i]; v < t.tile_first[(size_t)i + 1]; v++)
             longest = std::max(longest, first_call[(size_t)v + 1] - first_call[(size_t)v]);
-        t.tile_shift[(size_t)i] = std::min(50, 62 - (int)bits_for((unsigned long long)longest));
+        t.tile_shift[(size_t)i] = std::min(50, 62 - (int)bits_of((unsigned long long)longest));
     }
     return true;
 }
@@ -894,7 +825,7 @@ int build_slice_row_index(dmx_ctx *c)
     hipLaunchKernelGGL(k_slice_rows, dim3((unsigned)((c->n_items + 3) / 4)), dim3(256), 0, st, c->d_csc.p, c->d_item_start.p, c->d_item_len.p,
                        c->d_item_variant.p, c->n_items, keys, vals);
     DMX_TRY(dev_alloc(c, c->d_slice_rec, (size_t)m));
-    DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, (unsigned long long *)c->d_slice_rec.p, (size_t)m, bits_for((unsigned long long)(rows - 1)), st));
+    DMX_TRY(sort_pairs(sc, keys, keys_out, vals, (unsigned long long *)c->d_slice_rec.p, (size_t)m, bits_of((unsigned long long)(rows - 1)), st));
     DMX_TRY(dev_alloc(c, c->d_slice_ptr, (size_t)rows + 1));
     hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(rows + 1)), dim3(256), 0, st, keys_out, m, rows, c->d_slice_ptr.p);
     HIP_TRY(hipGetLastError());
@@ -958,7 +889,7 @@ int build_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi)
         DMX_TRY(dev_alloc(c, c->d_mt_stream, n));
         hipLaunchKernelGGL(k_mtile_from_rows, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, st, c->d_call_pairs.p, c->d_pair_ptr.p, c->B,
                            (unsigned)G * 4u, d_tile_of, (unsigned)n_mt, keys, vals);
-        DMX_TRY(sort_pairs64(sc, keys, keys_out, vals, (unsigned long long *)c->d_mt_stream.p, n, bits_for((unsigned long long)n_mt), st));
+        DMX_TRY(sort_pairs(sc, keys, keys_out, vals, (unsigned long long *)c->d_mt_stream.p, n, bits_of((unsigned long long)n_mt), st));
         DMX_TRY(dev_alloc(c, c->d_mt_ptr, (size_t)n_mt + 1));
         hipLaunchKernelGGL(k_tile_ptr, dim3(grid_for(n_mt + 1)), dim3(256), 0, st, keys_out, (long long)n, n_mt, c->d_mt_ptr.p);
         DMX_TRY(dev_alloc(c, c->d_mt_first, (size_t)n_mt + 1));
@@ -985,7 +916,7 @@ int build_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi)
     hipLaunchKernelGGL(k_mtile_keys, dim3((unsigned)c->n_items), dim3(256), 0, st, c->d_csc.p, c->d_item_start.p, c->d_item_len.p, c->d_item_variant.p,
                        d_tile_of, d_vin_of, row_bits, keys, rec);
     hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, st, iota, m);
-    const unsigned tile_bits = bits_for(n_mt > 1 ? (unsigned long long)n_mt - 1 : 0);
+    const unsigned tile_bits = bits_of(n_mt > 1 ? (unsigned long long)n_mt - 1 : 0);
     DMX_TRY(sort_pairs(sc, keys, keys_out, iota, perm, (size_t)m, std::max(1u, tile_bits + row_bits), st));
     DMX_TRY(dev_alloc(c, c->d_mt_stream, (size_t)m));
     hipLaunchKernelGGL(k_permute_records, dim3(grid_for(m)), dim3(256), 0, st, perm, rec, m, c->d_mt_stream.p);
@@ -1137,14 +1068,6 @@ __global__ __launch_bounds__(256) void k_products(const unsigned long long *keys
     u_count[u] = t - s;
 }
 
-template <typename T>
-int upload(Scratch &sc, T **dst, const T *src, size_t n, hipStream_t st)
-{
-    DMX_TRY(sc.get(dst, n));
-    if (n) HIP_TRY(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
-    return 0;
-}
-
 }  // namespace
 
 // The calls are already on the device (flat arrays owned by `sc`).
@@ -1161,7 +1084,7 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     DMX_TRY(upload(sc, &d_vchrom, var_chrom, (size_t)V, st));
     DMX_TRY(upload(sc, &d_vpos, var_pos, (size_t)V, st));
     DMX_TRY(upload(sc, &d_vbase, var_base, (size_t)V, st));
-    const unsigned table_bits = std::max(6u, bits_for((unsigned long long)(2 * V)));
+    const unsigned table_bits = std::max(6u, bits_of((unsigned long long)(2 * V)));
     const size_t table_slots = (size_t)1 << table_bits;
     unsigned long long *tkeys;
     unsigned *trows;
@@ -1185,13 +1108,7 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     if (n_calls)
         hipLaunchKernelGGL(k_match, dim3(grid_for(n_calls)), dim3(256), 0, st, d_cchrom, d_cpos, d_cbase, d_ccb, n_calls,
                            tkeys, trows, table_bits, call_variant, flag, bad);
-    {
-        size_t bytes = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, flag, pos_excl, 0u, (size_t)n_calls + 1, rocprim::plus<unsigned>(), st));
-        char *tmp;
-        DMX_TRY(sc.get(&tmp, bytes));
-        HIP_TRY(rocprim::exclusive_scan(tmp, bytes, flag, pos_excl, 0u, (size_t)n_calls + 1, rocprim::plus<unsigned>(), st));
-    }
+    DMX_TRY(exclusive_scan(sc, flag, pos_excl, 0u, (size_t)n_calls + 1, rocprim::plus<unsigned>(), st));
     unsigned h_matched = 0;
     int h_bad = 0;
     HIP_TRY(hipMemcpyAsync(&h_matched, pos_excl + n_calls, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1213,12 +1130,10 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     // aggregate_on_snps wants the matched molecule calls themselves, grouped by (barcode, SNP)
     if (c->keep_molecule_calls) DMX_TRY(build_snp_groups(c, keys, idx, d_cp, m));
     if (m) {
-        size_t bytes = 0;
-        const unsigned end_bit = 32 + bits_for(V ? V - 1 : 0);
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_sorted, idx, perm, (size_t)m, 0u, end_bit, st));
-        char *tmp;
-        DMX_TRY(sc.get(&tmp, bytes));
-        HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_sorted, idx, perm, (size_t)m, 0u, end_bit, st));
+        const unsigned end_bit = 32 + bits_of(V ? V - 1 : 0);
+        DMX_TRY(with_temp_storage(sc, "radix_sort_pairs", [&](void *t, size_t &b) {
+            return rocprim::radix_sort_pairs(t, b, keys, keys_sorted, idx, perm, (size_t)m, 0u, end_bit, st);
+        }));
     }
     // matched molecule calls per variant, from the sorted keys
     if (V) hipLaunchKernelGGL(k_variant_counts, dim3(grid_for(V)), dim3(256), 0, st, m ? keys_sorted : keys, m, V, d_mol);
@@ -1230,11 +1145,7 @@ static int pack_core(dmx_ctx *c, Scratch &sc, long long V, const int *var_chrom,
     long long n_u = 0;
     if (m) {
         hipLaunchKernelGGL(k_heads, dim3(grid_for(m)), dim3(256), 0, st, keys_sorted, m, head);
-        size_t bytes = 0;
-        HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, head, seg_incl, (size_t)m, rocprim::plus<unsigned>(), st));
-        char *tmp;
-        DMX_TRY(sc.get(&tmp, bytes));
-        HIP_TRY(rocprim::inclusive_scan(tmp, bytes, head, seg_incl, (size_t)m, rocprim::plus<unsigned>(), st));
+        DMX_TRY(inclusive_scan(sc, head, seg_incl, (size_t)m, rocprim::plus<unsigned>(), st));
         unsigned last = 0;
         HIP_TRY(hipMemcpyAsync(&last, seg_incl + (m - 1), sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

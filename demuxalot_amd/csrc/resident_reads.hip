@@ -66,11 +66,7 @@ int reads_upload(dmx_ctx *c, const dmx_decoded_reads *h, ResidentReads &set)
         hipLaunchKernelGGL(k_rr_ends, dim3(grid_for((long long)n)), dim3(256), 0, st, set.columns.start.p, set.columns.cigar_begin.p, set.columns.n_cigar.p,
                            set.columns.cigar.p, (long long)n, set.columns.n_ops, end);
         DMX_TRY(launched("k_rr_ends"));
-        size_t bytes = 0;
-        HIP_TRY(rocprim::reduce(nullptr, bytes, end, d_top, (long long)LLONG_MIN, n, rocprim::maximum<long long>(), st));
-        char *tmp = nullptr;
-        DMX_TRY(sc.get(&tmp, bytes));
-        HIP_TRY(rocprim::reduce(tmp, bytes, end, d_top, (long long)LLONG_MIN, n, rocprim::maximum<long long>(), st));
+        DMX_TRY(reduce(sc, end, d_top, (long long)LLONG_MIN, n, rocprim::maximum<long long>(), st));
         HIP_TRY(hipMemcpyAsync(&top, d_top, sizeof(long long), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are free to change from here on)

@@ -7,9 +7,11 @@
 //   the few best options of each barcode (singlet vs doublet calls)
 #include <hip/hip_runtime.h>
 
-#include "dmx_ctx.h"
+#include "device_scratch.h"
 
 namespace {
+
+using namespace dmx::scratch;
 
 constexpr int TOP_MAX = 4;
 
@@ -122,15 +124,6 @@ int check_ready(dmx_ctx *c, const char *who)
     return 0;
 }
 
-template <typename T>
-int scratch_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) return fail(DMX_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -138,37 +131,22 @@ extern "C" {
 int dmx_get_assignments_above(dmx_ctx *c, float threshold, int32_t *best, float *best_p, int64_t *n_assigned)
 {
     DMX_TRY(check_ready(c, "dmx_get_assignments_above"));
-    unsigned long long *d_n = nullptr;
-    DMX_TRY(scratch_alloc(&d_n, 1));
-    int rc = 0;
-    do {
-        if (hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream) != hipSuccess) {
-            rc = fail(DMX_ERR_HIP, "memset failed");
-            break;
-        }
-        if (c->B > 0) {
-            hipLaunchKernelGGL(k_top_options<1>, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, c->stream, c->d_post.p, c->B, c->K,
-                               threshold, c->d_best.p, c->d_bestp.p, d_n);
-            if (hipGetLastError() != hipSuccess) {
-                rc = fail(DMX_ERR_HIP, "assignment kernel launch failed");
-                break;
-            }
-        }
-        unsigned long long n = 0;
-        hipError_t e = hipSuccess;
-        if (best && c->B) e = hipMemcpyAsync(best, c->d_best.p, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && best_p && c->B) e = hipMemcpyAsync(best_p, c->d_bestp.p, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            rc = fail(DMX_ERR_HIP, "assignments: %s", hipGetErrorString(e));
-            break;
-        }
-        if (n_assigned) *n_assigned = (int64_t)n;
-    } while (false);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_n);
-    return rc;
+    Scratch sc(c);
+    unsigned long long *d_n;
+    DMX_TRY(sc.get(&d_n, 1));
+    HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream));
+    if (c->B > 0) {
+        hipLaunchKernelGGL(k_top_options<1>, dim3((unsigned)((c->B + 3) / 4)), dim3(256), 0, c->stream, c->d_post.p, c->B, c->K,
+                           threshold, c->d_best.p, c->d_bestp.p, d_n);
+        DMX_TRY(launched("k_top_options"));
+    }
+    unsigned long long n = 0;
+    if (best && c->B) HIP_TRY(hipMemcpyAsync(best, c->d_best.p, sizeof(int) * c->B, hipMemcpyDeviceToHost, c->stream));
+    if (best_p && c->B) HIP_TRY(hipMemcpyAsync(best_p, c->d_bestp.p, sizeof(float) * c->B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_assigned) *n_assigned = (int64_t)n;
+    return 0;
 }
 
 int dmx_get_top_options(dmx_ctx *c, int32_t k, int32_t *options, float *probs)
@@ -178,13 +156,11 @@ int dmx_get_top_options(dmx_ctx *c, int32_t k, int32_t *options, float *probs)
     if (c->B == 0) return 0;
     if (!options || !probs) return fail(DMX_ERR_INVALID, "null outputs");
     const size_t n = (size_t)c->B * k;
-    int *d_i = nullptr;
-    float *d_p = nullptr;
-    DMX_TRY(scratch_alloc(&d_i, n));
-    if (scratch_alloc(&d_p, n) != 0) {
-        (void)hipFree(d_i);
-        return DMX_ERR_HIP;
-    }
+    Scratch sc(c);
+    int *d_i;
+    float *d_p;
+    DMX_TRY(sc.get(&d_i, n));
+    DMX_TRY(sc.get(&d_p, n));
     const dim3 grid((unsigned)((c->B + 3) / 4)), block(256);
     const float none = -__builtin_inff();
     switch (k) {
@@ -193,14 +169,10 @@ int dmx_get_top_options(dmx_ctx *c, int32_t k, int32_t *options, float *probs)
     case 3: hipLaunchKernelGGL(k_top_options<3>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
     default: hipLaunchKernelGGL(k_top_options<4>, grid, block, 0, c->stream, c->d_post.p, c->B, c->K, none, d_i, d_p, nullptr); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(options, d_i, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(probs, d_p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_i);
-    (void)hipFree(d_p);
-    if (e != hipSuccess) return fail(DMX_ERR_HIP, "top options: %s", hipGetErrorString(e));
+    DMX_TRY(launched("k_top_options"));
+    HIP_TRY(hipMemcpyAsync(options, d_i, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(probs, d_p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -209,22 +181,16 @@ int dmx_get_option_sums(dmx_ctx *c, double *sums)
     DMX_TRY(check_ready(c, "dmx_get_option_sums"));
     if (!sums) return fail(DMX_ERR_INVALID, "null output");
     const int K = c->K;
-    double *d_part = nullptr, *d_sums = nullptr;
-    DMX_TRY(scratch_alloc(&d_part, (size_t)SUM_SLABS * K));
-    if (scratch_alloc(&d_sums, (size_t)K) != 0) {
-        (void)hipFree(d_part);
-        return DMX_ERR_HIP;
-    }
+    Scratch sc(c);
+    double *d_part, *d_sums;
+    DMX_TRY(sc.get(&d_part, (size_t)SUM_SLABS * K));
+    DMX_TRY(sc.get(&d_sums, (size_t)K));
     const unsigned kb = (unsigned)((K + 255) / 256);
     hipLaunchKernelGGL(k_option_partial, dim3(kb, SUM_SLABS), dim3(256), 0, c->stream, c->d_post.p, c->B, K, d_part);
     hipLaunchKernelGGL(k_option_final, dim3(kb), dim3(256), 0, c->stream, d_part, K, d_sums);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(sums, d_sums, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_part);
-    (void)hipFree(d_sums);
-    if (e != hipSuccess) return fail(DMX_ERR_HIP, "option sums: %s", hipGetErrorString(e));
+    DMX_TRY(launched("k_option_partial / k_option_final"));
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -27,16 +27,15 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "dmx_ctx.h"
+#include "device_scratch.h"
 #include "np_math.h"
 
 namespace {
 
 using dmx::fail;
+using namespace dmx::scratch;
 
 constexpr int SNP_MAX_OPTIONS = 256 * 33;  // doublets of 128 genotypes: 8256 options, about 100 KB of LDS per barcode
-
-inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 // ---- layout -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pair_keys(const unsigned long long *__restrict__ vb_keys, const int *__restrict__ v2snp,
@@ -545,50 +544,33 @@ int build_snp_groups(dmx_ctx *c, const unsigned long long *vb_keys, const unsign
     DMX_TRY(dev_alloc(c, c->d_mc_variant, (size_t)m));
     DMX_TRY(dev_alloc(c, c->d_mc_e, (size_t)m));
     DMX_TRY(dev_alloc(c, c->d_mc_start, (size_t)c->B + 1));
-    int *d_v2snp = nullptr;
-    unsigned long long *keys = nullptr, *keys_sorted = nullptr;
-    unsigned *idx = nullptr, *perm = nullptr, *longest = nullptr;
-    char *tmp = nullptr;
-    int rc = 0;
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc == 0 && hipMalloc(p, bytes ? bytes : 1) != hipSuccess) rc = fail(DMX_ERR_HIP, "hipMalloc of %zu bytes failed", bytes);
-    };
-    alloc((void **)&d_v2snp, sizeof(int) * (size_t)c->V);
-    alloc((void **)&keys, sizeof(unsigned long long) * (size_t)m);
-    alloc((void **)&keys_sorted, sizeof(unsigned long long) * (size_t)m);
-    alloc((void **)&idx, sizeof(unsigned) * (size_t)m);
-    alloc((void **)&perm, sizeof(unsigned) * (size_t)m);
-    alloc((void **)&longest, sizeof(unsigned));
-    do {
-        if (rc) break;
-        hipError_t e = hipSuccess;
-        if (c->V) e = hipMemcpyAsync(d_v2snp, c->h_v2snp.data(), sizeof(int) * (size_t)c->V, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(longest, 0, sizeof(unsigned), st);
-        if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "snp groups: %s", hipGetErrorString(e)); break; }
-        if (m) {
-            hipLaunchKernelGGL(k_pair_keys, dim3(grid_for(m)), dim3(256), 0, st, vb_keys, d_v2snp, m, keys, idx);
-            size_t bytes = 0;
-            e = rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_sorted, idx, perm, (size_t)m, 0u, 64u, st);
-            if (e == hipSuccess) alloc((void **)&tmp, bytes);
-            if (rc) break;
-            if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, bytes, keys, keys_sorted, idx, perm, (size_t)m, 0u, 64u, st);
-            if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "snp groups sort: %s", hipGetErrorString(e)); break; }
-            hipLaunchKernelGGL(k_pair_fill, dim3(grid_for(m)), dim3(256), 0, st, keys_sorted, perm, vb_keys, src_idx, src_p, m,
-                               c->d_mc_variant.p, c->d_mc_e.p);
-            hipLaunchKernelGGL(k_max_run, dim3(grid_for(m)), dim3(256), 0, st, c->d_mc_variant.p, m, longest);
-        }
-        hipLaunchKernelGGL(k_barcode_starts, dim3(grid_for(c->B + 1)), dim3(256), 0, st, keys_sorted, m, c->B, c->d_mc_start.p);
-        unsigned h_longest = 0;
-        e = hipMemcpyAsync(&h_longest, longest, sizeof(unsigned), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "snp groups: %s", hipGetErrorString(e)); break; }
-        c->mc_max_count = h_longest;
-    } while (false);
-    (void)hipStreamSynchronize(st);
-    for (void *p : {(void *)d_v2snp, (void *)keys, (void *)keys_sorted, (void *)idx, (void *)perm, (void *)longest, (void *)tmp})
-        if (p) (void)hipFree(p);
-    return rc;
+    Scratch sc(c);
+    int *d_v2snp;
+    unsigned long long *keys, *keys_sorted;
+    unsigned *idx, *perm, *longest;
+    DMX_TRY(upload(sc, &d_v2snp, c->h_v2snp.data(), (size_t)c->V, st));
+    DMX_TRY(sc.get(&keys, (size_t)m));
+    DMX_TRY(sc.get(&keys_sorted, (size_t)m));
+    DMX_TRY(sc.get(&idx, (size_t)m));
+    DMX_TRY(sc.get(&perm, (size_t)m));
+    DMX_TRY(sc.get(&longest, 1));
+    HIP_TRY(hipMemsetAsync(longest, 0, sizeof(unsigned), st));
+    if (m) {
+        hipLaunchKernelGGL(k_pair_keys, dim3(grid_for(m)), dim3(256), 0, st, vb_keys, d_v2snp, m, keys, idx);
+        DMX_TRY(with_temp_storage(sc, "radix_sort_pairs", [&](void *t, size_t &b) {
+            return rocprim::radix_sort_pairs(t, b, keys, keys_sorted, idx, perm, (size_t)m, 0u, 64u, st);
+        }));
+        hipLaunchKernelGGL(k_pair_fill, dim3(grid_for(m)), dim3(256), 0, st, keys_sorted, perm, vb_keys, src_idx, src_p, m,
+                           c->d_mc_variant.p, c->d_mc_e.p);
+        hipLaunchKernelGGL(k_max_run, dim3(grid_for(m)), dim3(256), 0, st, c->d_mc_variant.p, m, longest);
+    }
+    hipLaunchKernelGGL(k_barcode_starts, dim3(grid_for(c->B + 1)), dim3(256), 0, st, keys_sorted, m, c->B, c->d_mc_start.p);
+    unsigned h_longest = 0;
+    HIP_TRY(hipMemcpyAsync(&h_longest, longest, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    c->mc_max_count = h_longest;
+    return 0;
 }
 
 }  // namespace dmx
@@ -614,22 +596,12 @@ int dmx_set_molecule_calls(dmx_ctx *c, int64_t n, const int32_t *variant_id, con
             return fail(DMX_ERR_INVALID, "molecule call %lld outside the problem", (long long)j);
         keys[(size_t)j] = ((unsigned long long)(unsigned)variant_id[j] << 32) | (unsigned)compressed_cb[j];
     }
-    unsigned long long *d_keys = nullptr;
-    float *d_p = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_keys, sizeof(unsigned long long) * (size_t)(n ? n : 1)));
-    if (hipMalloc((void **)&d_p, sizeof(float) * (size_t)(n ? n : 1)) != hipSuccess) {
-        (void)hipFree(d_keys);
-        return fail(DMX_ERR_HIP, "hipMalloc failed");
-    }
-    int rc = 0;
-    if (n && (hipMemcpyAsync(d_keys, keys.data(), sizeof(unsigned long long) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-              hipMemcpyAsync(d_p, p_base_wrong, sizeof(float) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess))
-        rc = fail(DMX_ERR_HIP, "upload of the molecule calls failed");
-    if (rc == 0) rc = dmx::build_snp_groups(c, d_keys, nullptr, d_p, n);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_keys);
-    (void)hipFree(d_p);
-    return rc;
+    Scratch sc(c);
+    unsigned long long *d_keys;
+    float *d_p;
+    DMX_TRY(upload(sc, &d_keys, keys.data(), (size_t)n, c->stream));
+    DMX_TRY(upload(sc, &d_p, p_base_wrong, (size_t)n, c->stream));
+    return dmx::build_snp_groups(c, d_keys, nullptr, d_p, n);
 }
 
 int dmx_get_max_pair_count(dmx_ctx *c, int64_t *max_count)
@@ -662,70 +634,59 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
         for (int g1 = 0; g1 < G; g1++)
             for (int g2 = g1 + 1; g2 < G; g2++) pairs[k++] = (unsigned)g1 | ((unsigned)g2 << 16);
     }
-    unsigned *d_pairs = nullptr;
-    double *d_pow = nullptr;
-    void *d_prior = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_pairs, sizeof(unsigned) * K));
+    Scratch sc(c);
+    unsigned *d_pairs;
+    double *d_pow;
+    char *d_prior = nullptr;
+    const size_t prior_bytes = prior_logits ? bk * (prior_dtype == DMX_F64 ? 8 : 4) : 0;
+    DMX_TRY(upload(sc, &d_pairs, pairs.data(), (size_t)K, c->stream));
+    DMX_TRY(upload(sc, &d_pow, count_pow, (size_t)n_count_pow, c->stream));
+    if (prior_bytes) DMX_TRY(upload(sc, &d_prior, (const char *)prior_logits, prior_bytes, c->stream));
+    SnpArgs a;
+    a.bc_start = c->d_mc_start.p;
+    a.variant = c->d_mc_variant.p;
+    a.e = c->d_mc_e.p;
+    a.prob = c->d_prob.p;
+    a.prow = c->d_prow.p;
+    a.opt_pairs = d_pairs;
+    a.count_pow = d_pow;
+    a.prior = d_prior;
+    a.prior_dtype = prior_dtype;
+    a.logits = c->d_logits64.p;
+    a.post = c->d_post64.p;
+    a.log_bad = std::log(0.01 / (double)K);
+    a.sum_plan = nullptr;
+    a.sum_plan_values = 0;
+    if (K > 1024) {
+        DMX_TRY(dmx::ensure_sum_plan(c, K));
+        a.sum_plan = c->d_sum_plan.p;
+        a.sum_plan_values = c->sum_plan_values;
+    }
+    a.B = c->B;
+    a.G = G;
+    a.K = (int)K;
+    const bool pairs_on = with_doublets != 0;
     int rc = 0;
-    do {
-        if (hipMalloc((void **)&d_pow, sizeof(double) * n_count_pow) != hipSuccess) { rc = fail(DMX_ERR_HIP, "hipMalloc failed"); break; }
-        const size_t prior_bytes = prior_logits ? bk * (prior_dtype == DMX_F64 ? 8 : 4) : 0;
-        if (prior_bytes && hipMalloc(&d_prior, prior_bytes) != hipSuccess) { rc = fail(DMX_ERR_HIP, "hipMalloc failed"); break; }
-        hipError_t e = hipMemcpyAsync(d_pairs, pairs.data(), sizeof(unsigned) * K, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_pow, count_pow, sizeof(double) * n_count_pow, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && prior_bytes) e = hipMemcpyAsync(d_prior, prior_logits, prior_bytes, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "dmx_estep_snp uploads: %s", hipGetErrorString(e)); break; }
-        SnpArgs a;
-        a.bc_start = c->d_mc_start.p;
-        a.variant = c->d_mc_variant.p;
-        a.e = c->d_mc_e.p;
-        a.prob = c->d_prob.p;
-        a.prow = c->d_prow.p;
-        a.opt_pairs = d_pairs;
-        a.count_pow = d_pow;
-        a.prior = d_prior;
-        a.prior_dtype = prior_dtype;
-        a.logits = c->d_logits64.p;
-        a.post = c->d_post64.p;
-        a.log_bad = std::log(0.01 / (double)K);
-        a.sum_plan = nullptr;
-        a.sum_plan_values = 0;
-        if (K > 1024) {
-            rc = dmx::ensure_sum_plan(c, K);
-            if (rc) break;
-            a.sum_plan = c->d_sum_plan.p;
-            a.sum_plan_values = c->sum_plan_values;
-        }
-        a.B = c->B;
-        a.G = G;
-        a.K = (int)K;
-        const bool pairs_on = with_doublets != 0;
-        if (K <= 64) rc = launch_snp<1>(c, a, pairs_on);
-        else if (K <= 128) rc = launch_snp<2>(c, a, pairs_on);
-        else if (K <= 256) rc = launch_snp<4>(c, a, pairs_on);
-        else if (K <= 512) rc = launch_snp<8>(c, a, pairs_on);
-        else if (K <= 1024) rc = launch_snp<16>(c, a, pairs_on);
-        else if (K <= 256 * 6) rc = launch_snp_block<6>(c, a);  // K > 1024 is always the doublet table
-        else if (K <= 256 * 9) rc = launch_snp_block<9>(c, a);
-        else if (K <= 256 * 12) rc = launch_snp_block<12>(c, a);
-        else if (K <= 256 * 17) rc = launch_snp_block<17>(c, a);
-        else if (K <= 256 * 24) rc = launch_snp_block<24>(c, a);
-        else rc = launch_snp_block<33>(c, a);
-        if (rc) break;
-        if (logits_out && bk) e = hipMemcpyAsync(logits_out, c->d_logits64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && probs_out && bk) e = hipMemcpyAsync(probs_out, c->d_post64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(DMX_ERR_HIP, "dmx_estep_snp: %s", hipGetErrorString(e)); break; }
-        // the float32 logits / posteriors of dmx_estep (and the M-step's bitmaps) were laid out for the previous K
-        if ((int)K != c->K) c->have_post = false;
-        c->K = (int)K;
-        c->have_post64 = true;
-    } while (false);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_pairs);
-    if (d_pow) (void)hipFree(d_pow);
-    if (d_prior) (void)hipFree(d_prior);
-    return rc;
+    if (K <= 64) rc = launch_snp<1>(c, a, pairs_on);
+    else if (K <= 128) rc = launch_snp<2>(c, a, pairs_on);
+    else if (K <= 256) rc = launch_snp<4>(c, a, pairs_on);
+    else if (K <= 512) rc = launch_snp<8>(c, a, pairs_on);
+    else if (K <= 1024) rc = launch_snp<16>(c, a, pairs_on);
+    else if (K <= 256 * 6) rc = launch_snp_block<6>(c, a);  // K > 1024 is always the doublet table
+    else if (K <= 256 * 9) rc = launch_snp_block<9>(c, a);
+    else if (K <= 256 * 12) rc = launch_snp_block<12>(c, a);
+    else if (K <= 256 * 17) rc = launch_snp_block<17>(c, a);
+    else if (K <= 256 * 24) rc = launch_snp_block<24>(c, a);
+    else rc = launch_snp_block<33>(c, a);
+    DMX_TRY(rc);
+    if (logits_out && bk) HIP_TRY(hipMemcpyAsync(logits_out, c->d_logits64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream));
+    if (probs_out && bk) HIP_TRY(hipMemcpyAsync(probs_out, c->d_post64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the float32 logits / posteriors of dmx_estep (and the M-step's bitmaps) were laid out for the previous K
+    if ((int)K != c->K) c->have_post = false;
+    c->K = (int)K;
+    c->have_post64 = true;
+    return 0;
 }
 
 static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out, double *sums_out)

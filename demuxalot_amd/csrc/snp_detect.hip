@@ -17,94 +17,15 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "dmx_host.h"
+#include "device_scratch.h"
 
 namespace {
 
 using dmx::host::bind;
+using namespace dmx::scratch;
 
 constexpr int SNP_CALL_BYTES = 13, MOLECULE_BYTES = 12;
 constexpr int COUNT_CHUNK = 16;  // sorted keys per lane of the count accumulation
-
-struct Scratch {
-    dmx_ctx *ctx;
-    std::vector<void *> ptrs;
-    explicit Scratch(dmx_ctx *c) : ctx(c) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch()
-    {
-        for (void *p : ptrs) ctx_free(ctx, p);
-    }
-    template <typename T>
-    int get(T **out, size_t count)
-    {
-        void *p = nullptr;
-        const int rc = ctx_malloc(ctx, &p, (count ? count : 1) * sizeof(T));
-        if (rc) return rc;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return 0;
-    }
-};
-
-inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
-
-inline int bits_for(unsigned long long n)  // bits that hold the values 0 .. n-1
-{
-    int b = 0;
-    while (b < 64 && (n - 1) >> b) b++;
-    return n <= 1 ? 0 : b;
-}
-
-template <typename T>
-int upload(Scratch &sc, T **out, const T *host, size_t count, hipStream_t st)
-{
-    DMX_TRY(sc.get(out, count));
-    if (count) HIP_TRY(hipMemcpyAsync(*out, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-}
-
-// out[i] = in[0] + .. + in[i]; the last entry (the total) is returned through *total (synchronises)
-int inclusive_scan_total(Scratch &sc, const unsigned long long *in, unsigned long long *out, size_t n, unsigned long long *total,
-                         hipStream_t st)
-{
-    *total = 0;
-    if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::plus<unsigned long long>(), st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::inclusive_scan(tmp, bytes, in, out, n, rocprim::plus<unsigned long long>(), st));
-    HIP_TRY(hipMemcpyAsync(total, out + n - 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int sort_keys(Scratch &sc, const unsigned long long *in, unsigned long long *out, size_t n, unsigned end_bit, hipStream_t st)
-{
-    if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, in, out, n, 0u, end_bit, st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::radix_sort_keys(tmp, bytes, in, out, n, 0u, end_bit, st));
-    return 0;
-}
-
-// stable (LSD radix sort): equal keys keep their input order
-template <typename K>
-int sort_pairs(Scratch &sc, const K *keys_in, K *keys_out, const unsigned *vals_in, unsigned *vals_out, size_t n, unsigned end_bit,
-               hipStream_t st)
-{
-    if (n == 0) return 0;
-    size_t bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    char *tmp = nullptr;
-    DMX_TRY(sc.get(&tmp, bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, st));
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // count
@@ -378,13 +299,6 @@ __global__ __launch_bounds__(256) void k_sd_gather(const unsigned char *__restri
     selected[at[p] - 1] = p;
 }
 
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(DMX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
 int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const int32_t *donor_of_barcode, long long B, int D,
               float threshold, long long cap, long long *n_positions)
 {
@@ -429,7 +343,7 @@ int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const in
     // kept calls, compacted in input order
     unsigned long long *at_keep, m = 0;
     DMX_TRY(sc.get(&at_keep, (size_t)n));
-    DMX_TRY(inclusive_scan_total(sc, keep, at_keep, (size_t)n, &m, st));
+    DMX_TRY(sum_scan(sc, keep, at_keep, (size_t)n, &m, st));
     unsigned long long *kept_key, *sorted;
     unsigned *kept_base_cb;
     DMX_TRY(sc.get(&kept_key, (size_t)m));
@@ -445,7 +359,7 @@ int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const in
     DMX_TRY(sc.get(&at_head, (size_t)m));
     if (m) hipLaunchKernelGGL(k_sd_heads, dim3(grid_for(m)), dim3(256), 0, st, sorted, (long long)m, head);
     DMX_TRY(launched("k_sd_heads"));
-    DMX_TRY(inclusive_scan_total(sc, head, at_head, (size_t)m, &P, st));
+    DMX_TRY(sum_scan(sc, head, at_head, (size_t)m, &P, st));
     const int donor_bits = bits_for((unsigned long long)D), barcode_bits = bits_for((unsigned long long)B);
     const int key_bits = bits_for(P) + 2 + donor_bits + barcode_bits;
     if (key_bits > 64) return fail(DMX_ERR_UNSUPPORTED, "%llu positions x %d donors x %lld barcodes do not fit a 64-bit key", P, D, B);
@@ -592,7 +506,7 @@ int dmx_snp_select(dmx_ctx *c, int64_t n_best_per_donor, int64_t n_additional, i
     hipLaunchKernelGGL(k_sd_new_flags, dim3(grid_for(P)), dim3(256), 0, st, order, P, member, is_new);
     DMX_TRY(launched("k_sd_new_flags"));
     unsigned long long n_new = 0;
-    DMX_TRY(inclusive_scan_total(sc, is_new, cum, (size_t)P, &n_new, st));
+    DMX_TRY(sum_scan(sc, is_new, cum, (size_t)P, &n_new, st));
     HIP_TRY(hipMemcpyAsync(cut, &P, sizeof(long long), hipMemcpyHostToDevice, st));
     if ((unsigned long long)n_additional < n_new) {
         hipLaunchKernelGGL(k_sd_cut, dim3(grid_for(P)), dim3(256), 0, st, is_new, cum, P, (long long)n_additional, cut);
@@ -604,7 +518,7 @@ int dmx_snp_select(dmx_ctx *c, int64_t n_best_per_donor, int64_t n_additional, i
     hipLaunchKernelGGL(k_sd_flags, dim3(grid_for(P)), dim3(256), 0, st, member, P, flag);
     DMX_TRY(launched("k_sd_flags"));
     unsigned long long n_sel = 0;
-    DMX_TRY(inclusive_scan_total(sc, flag, at, (size_t)P, &n_sel, st));
+    DMX_TRY(sum_scan(sc, flag, at, (size_t)P, &n_sel, st));
     hipLaunchKernelGGL(k_sd_gather, dim3(grid_for(P)), dim3(256), 0, st, member, at, P, d_selected);
     DMX_TRY(launched("k_sd_gather"));
     if (selected && n_sel) HIP_TRY(hipMemcpyAsync(selected, d_selected, (size_t)n_sel * sizeof(int64_t), hipMemcpyDeviceToHost, st));

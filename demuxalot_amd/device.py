@@ -88,25 +88,35 @@ class DeviceContext:
                                         ptr(variant_id), ptr(compressed_cb), ptr(p_base_wrong), ptr(v2snp)))
         self.B, self.V, self.G, self.N = int(n_barcodes), int(n_variants), int(n_genotypes), len(variant_id)
 
+    @staticmethod
+    def _variant_arrays(var_chrom, var_pos, var_base, v2snp):
+        """The variants of a pack as the ABI's arrays: (var_chrom, var_pos, var_base, v2snp)."""
+        var_chrom, var_pos, var_base = as_c(var_chrom, np.int32), as_c(var_pos, np.int32), as_c(var_base, np.uint8)
+        v2snp = as_c(v2snp, np.int32)
+        assert len(v2snp) == len(var_pos)
+        return var_chrom, var_pos, var_base, v2snp
+
+    def _pack(self, entry, n_barcodes, n_genotypes, variants, *calls):
+        """One of the dmx_pack_*_and_set_problem entry points on `variants` (_variant_arrays) and its own description of the
+        calls; the packed problem becomes the resident one.  Returns (n_matched, n_unique, molecules per variant)."""
+        n_variants = len(variants[1])
+        mol_per_variant = np.zeros(n_variants, dtype=np.int64)
+        n_matched, n_unique = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(entry(self._h, n_barcodes, n_variants, n_genotypes, *(ptr(a) for a in variants), *calls,
+                    ctypes.byref(n_matched), ctypes.byref(n_unique), ptr(mol_per_variant)))
+        self.B, self.V, self.G, self.N = int(n_barcodes), int(n_variants), int(n_genotypes), n_unique.value
+        return n_matched.value, n_unique.value, mol_per_variant
+
     def pack_and_set_problem(self, n_barcodes, n_genotypes, var_chrom, var_pos, var_base, v2snp,
                              call_chrom, call_pos, call_base, call_cb, call_p):
         """Device pack (variant matching + de-duplication, demux.py:276-300, 332-365) installed directly as
         the resident problem. Returns (n_matched, n_unique, molecules per variant)."""
         self._resident_key = None  # (demux.py: _pack_on_device keeps the packed problem of the shared context across calls)
-        var_chrom, var_pos, var_base = as_c(var_chrom, np.int32), as_c(var_pos, np.int32), as_c(var_base, np.uint8)
-        v2snp = as_c(v2snp, np.int32)
+        variants = self._variant_arrays(var_chrom, var_pos, var_base, v2snp)
         call_chrom, call_pos = as_c(call_chrom, np.int32), as_c(call_pos, np.int32)
         call_base, call_cb, call_p = as_c(call_base, np.uint8), as_c(call_cb, np.int32), as_c(call_p, np.float32)
-        n_variants, n_calls = len(var_pos), len(call_pos)
-        assert len(v2snp) == n_variants
-        mol_per_variant = np.zeros(n_variants, dtype=np.int64)
-        n_matched, n_unique = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_pack_and_set_problem(
-            self._h, n_barcodes, n_variants, n_genotypes, ptr(var_chrom), ptr(var_pos), ptr(var_base), ptr(v2snp),
-            n_calls, ptr(call_chrom), ptr(call_pos), ptr(call_base), ptr(call_cb), ptr(call_p),
-            ctypes.byref(n_matched), ctypes.byref(n_unique), ptr(mol_per_variant)))
-        self.B, self.V, self.G, self.N = int(n_barcodes), int(n_variants), int(n_genotypes), n_unique.value
-        return n_matched.value, n_unique.value, mol_per_variant
+        return self._pack(self._lib.dmx_pack_and_set_problem, n_barcodes, n_genotypes, variants, len(call_pos),
+                          ptr(call_chrom), ptr(call_pos), ptr(call_base), ptr(call_cb), ptr(call_p))
 
     def _container_list(self, containers):
         from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
@@ -128,19 +138,10 @@ class DeviceContext:
         `containers` = [(chromosome index, snp_calls[:n] (SNP_CALL_DTYPE), molecules[:m] (MOLECULE_DTYPE))].
         The field extraction and the molecule -> barcode lookup happen on the GPU."""
         self._resident_key = None  # (demux.py: _pack_on_device keeps the packed problem of the shared context across calls)
-        var_chrom, var_pos, var_base = as_c(var_chrom, np.int32), as_c(var_pos, np.int32), as_c(var_base, np.uint8)
-        v2snp = as_c(v2snp, np.int32)
-        n_variants = len(var_pos)
-        assert len(v2snp) == n_variants
+        variants = self._variant_arrays(var_chrom, var_pos, var_base, v2snp)
         parts, _keep_alive = self._container_list(containers)
-        mol_per_variant = np.zeros(n_variants, dtype=np.int64)
-        n_matched, n_unique = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_pack_containers_and_set_problem(
-            self._h, n_barcodes, n_variants, n_genotypes, ptr(var_chrom), ptr(var_pos), ptr(var_base), ptr(v2snp),
-            ctypes.cast(parts, ctypes.c_void_p), len(containers), ctypes.byref(n_matched), ctypes.byref(n_unique),
-            ptr(mol_per_variant)))
-        self.B, self.V, self.G, self.N = int(n_barcodes), int(n_variants), int(n_genotypes), n_unique.value
-        return n_matched.value, n_unique.value, mol_per_variant
+        return self._pack(self._lib.dmx_pack_containers_and_set_problem, n_barcodes, n_genotypes, variants,
+                          ctypes.cast(parts, ctypes.c_void_p), len(containers))
 
     def stage_containers(self, containers):
         """First half of pack_containers_and_set_problem: upload + field extraction of the containers' records, which
@@ -154,18 +155,9 @@ class DeviceContext:
         """Second half: variant matching, de-duplication and layouts on the staged calls.  chrom_of_container[k] = the
         chromosome index (numbering of var_chrom) of the k-th staged container, -1 when no variant lies on it."""
         self._resident_key = None  # (demux.py: _pack_on_device keeps the packed problem of the shared context across calls)
-        var_chrom, var_pos, var_base = as_c(var_chrom, np.int32), as_c(var_pos, np.int32), as_c(var_base, np.uint8)
-        v2snp = as_c(v2snp, np.int32)
+        variants = self._variant_arrays(var_chrom, var_pos, var_base, v2snp)
         table = as_c(chrom_of_container, np.int32)
-        n_variants = len(var_pos)
-        assert len(v2snp) == n_variants
-        mol_per_variant = np.zeros(n_variants, dtype=np.int64)
-        n_matched, n_unique = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_pack_staged_and_set_problem(
-            self._h, n_barcodes, n_variants, n_genotypes, ptr(var_chrom), ptr(var_pos), ptr(var_base), ptr(v2snp),
-            ptr(table), len(table), ctypes.byref(n_matched), ctypes.byref(n_unique), ptr(mol_per_variant)))
-        self.B, self.V, self.G, self.N = int(n_barcodes), int(n_variants), int(n_genotypes), n_unique.value
-        return n_matched.value, n_unique.value, mol_per_variant
+        return self._pack(self._lib.dmx_pack_staged_and_set_problem, n_barcodes, n_genotypes, variants, ptr(table), len(table))
 
     def get_packed_calls(self):
         """Unique (variant, barcode) calls left on the device by pack_and_set_problem, variant-major."""
@@ -400,23 +392,41 @@ class DeviceContext:
         return selected[:n.value].copy()
 
     # ---- read counting (include/demux_hip.h: dmx_count_reads / _fetch; demuxalot_amd/snp_counter.py) ----
-    def count_reads(self, reads, positions, qual_table):
-        """(molecules, snp_calls) structured arrays (snp_counter.MOLECULE_DTYPE / SNP_CALL_DTYPE) counted on the device from a
-        DecodedReads at the strictly ascending int32 `positions`; qual_table float64[41].  The resident problem stays."""
-        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+    @staticmethod
+    def _reads_descriptor(reads, coverage_only=False):
+        """(pointer to the dmx_decoded_reads of a DecodedReads, what must stay alive until the call returns); coverage_only
+        leaves out the four columns only counting reads (compressed_cb, compressed_ub, p_misaligned, alignment_score)."""
+        arrays = reads.arrays()  # C-contiguous arrays of the ABI's dtypes
+        pointers = {name: ptr(a) for name, a in arrays.items()}
+        if coverage_only:
+            for name in ('compressed_cb', 'compressed_ub', 'p_misaligned', 'alignment_score'):
+                pointers[name] = None
+        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']), **pointers)
+        return ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), (desc, arrays)
+
+    @staticmethod
+    def _count_inputs(positions, qual_table):
         positions = as_c(positions, np.int32)
         qual_table = as_c(qual_table, np.float64)
         assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
-        arrays = reads.arrays()  # C-contiguous arrays of the ABI's dtypes; kept alive until the call returns
-        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
-                                       **{name: ptr(a) for name, a in arrays.items()})
+        return positions, qual_table
+
+    def _counted(self, entry, *args):
+        """(molecules, snp_calls) of a counting entry point: the call reports how many there are, dmx_count_reads_fetch copies them."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
         n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_count_reads(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), ptr(positions), len(positions),
-                                        ptr(qual_table), ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        check(entry(self._h, *args, ctypes.byref(n_molecules), ctypes.byref(n_calls)))
         molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
         snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
         check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
         return molecules, snp_calls
+
+    def count_reads(self, reads, positions, qual_table):
+        """(molecules, snp_calls) structured arrays (snp_counter.MOLECULE_DTYPE / SNP_CALL_DTYPE) counted on the device from a
+        DecodedReads at the strictly ascending int32 `positions`; qual_table float64[41].  The resident problem stays."""
+        positions, qual_table = self._count_inputs(positions, qual_table)
+        desc, _keep_alive = self._reads_descriptor(reads)
+        return self._counted(self._lib.dmx_count_reads, desc, ptr(positions), len(positions), ptr(qual_table))
 
     def count_reads_timings(self):
         """{stage: milliseconds} of the last count_reads or count_reads_push (include/demux_hip_debug.h: dmx_get_count_reads_timings)."""
@@ -426,26 +436,13 @@ class DeviceContext:
 
     # streamed (dmx_count_reads_begin / _push / _end; snp_counter.ReadCounter is the front)
     def count_reads_begin(self, positions, qual_table):
-        positions = as_c(positions, np.int32)
-        qual_table = as_c(qual_table, np.float64)
-        assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
+        positions, qual_table = self._count_inputs(positions, qual_table)
         check(self._lib.dmx_count_reads_begin(self._h, ptr(positions), len(positions), ptr(qual_table)))
 
     def count_reads_push(self, reads, final=False):
         """(molecules, snp_calls) this push emitted, molecule_index counting on across the stream; reads: a DecodedReads or None."""
-        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
-        desc = None
-        if reads is not None:
-            arrays = reads.arrays()  # kept alive until the call returns
-            desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
-                                           **{name: ptr(a) for name, a in arrays.items()})
-        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_count_reads_push(self._h, None if desc is None else ctypes.cast(ctypes.byref(desc), ctypes.c_void_p),
-                                             1 if final else 0, ctypes.byref(n_molecules), ctypes.byref(n_calls)))
-        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
-        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
-        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
-        return molecules, snp_calls
+        desc, _keep_alive = (None, None) if reads is None else self._reads_descriptor(reads)
+        return self._counted(self._lib.dmx_count_reads_push, desc, 1 if final else 0)
 
     def count_reads_end(self):
         check(self._lib.dmx_count_reads_end(self._h))
@@ -466,14 +463,9 @@ class DeviceContext:
     def reads_upload(self, reads, coverage_only=False):
         """Handle of the DecodedReads' arrays uploaded once to this context; coverage_only leaves out the four columns only
         counting reads (compressed_cb, compressed_ub, p_misaligned, alignment_score)."""
-        arrays = reads.arrays()  # kept alive until the call returns
-        pointers = {name: ptr(a) for name, a in arrays.items()}
-        if coverage_only:
-            for name in ('compressed_cb', 'compressed_ub', 'p_misaligned', 'alignment_score'):
-                pointers[name] = None
-        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']), **pointers)
+        desc, _keep_alive = self._reads_descriptor(reads, coverage_only)
         handle = ctypes.c_int64(0)
-        check(self._lib.dmx_reads_upload(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), ctypes.byref(handle)))
+        check(self._lib.dmx_reads_upload(self._h, desc, ctypes.byref(handle)))
         return handle.value
 
     def reads_release(self, handle):
@@ -493,28 +485,12 @@ class DeviceContext:
 
     def count_reads_resident(self, handle, positions, qual_table):
         """count_reads on a resident set."""
-        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
-        positions = as_c(positions, np.int32)
-        qual_table = as_c(qual_table, np.float64)
-        assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
-        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_count_reads_resident(self._h, int(handle), ptr(positions), len(positions), ptr(qual_table),
-                                                 ctypes.byref(n_molecules), ctypes.byref(n_calls)))
-        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
-        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
-        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
-        return molecules, snp_calls
+        positions, qual_table = self._count_inputs(positions, qual_table)
+        return self._counted(self._lib.dmx_count_reads_resident, int(handle), ptr(positions), len(positions), ptr(qual_table))
 
     def count_reads_push_resident(self, handle, first_read, last_read, final=False):
         """count_reads_push with the reads [first_read, last_read) of a resident set as the chunk."""
-        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
-        n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._lib.dmx_count_reads_push_resident(self._h, int(handle), int(first_read), int(last_read), 1 if final else 0,
-                                                      ctypes.byref(n_molecules), ctypes.byref(n_calls)))
-        molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
-        snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
-        check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
-        return molecules, snp_calls
+        return self._counted(self._lib.dmx_count_reads_push_resident, int(handle), int(first_read), int(last_read), 1 if final else 0)
 
     def coverage_count_resident(self, handle, start, stop, quality_threshold=15, fetch=True):
         """coverage_count on a resident set."""
@@ -526,12 +502,9 @@ class DeviceContext:
     def coverage_count(self, reads, start, stop, quality_threshold=15, fetch=True):
         """int32[4, stop - start] (rows A, C, G, T) counted on the device from a DecodedReads, by the rules of pysam's
         count_coverage; None unless fetched (the window stays on the device for coverage_candidates).  The resident problem stays."""
-        arrays = reads.arrays()  # kept alive until the call returns
-        desc = _lib.DecodedReadsStruct(n_reads=reads.n_reads, n_cigar_ops=len(arrays['cigar']), n_bases=len(arrays['seq']),
-                                       **{name: ptr(a) for name, a in arrays.items()})
+        desc, _keep_alive = self._reads_descriptor(reads)
         out = np.empty((4, max(0, int(stop) - int(start))), dtype=np.int32) if fetch else None
-        check(self._lib.dmx_coverage_count(self._h, ctypes.cast(ctypes.byref(desc), ctypes.c_void_p), int(start), int(stop),
-                                           int(quality_threshold), ptr(out)))
+        check(self._lib.dmx_coverage_count(self._h, desc, int(start), int(stop), int(quality_threshold), ptr(out)))
         return out
 
     def coverage_candidates(self, minimum_coverage, minimum_alternative_fraction, minimum_alternative_coverage,
@@ -725,7 +698,6 @@ class DeviceContext:
     def estep_form(self):
         """(form, distinct) of the last E-step: form 'direct' | 'packed' | 'dict' | 'dict_block' | None, distinct = most distinct
         values in a row of genotype_prob as counted by the last dictionary build (0: none was tried, 9: too many)."""
-        import ctypes
         form, distinct = ctypes.c_int32(0), ctypes.c_int32(0)
         check(self._lib.dmx_get_estep_form(self._h, ctypes.byref(form), ctypes.byref(distinct)))
         return {0: None, 1: 'direct', 2: 'dict', 3: 'dict_block', 4: 'packed'}[form.value], distinct.value
