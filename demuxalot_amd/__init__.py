@@ -4,8 +4,8 @@ Drop-in names of the reference package (demuxalot/__init__.py:3-7) that belong t
 """
 __version__ = '0.1.0'
 
-from .utils import BarcodeHandler
-from .snp_counter import (CompressedSNPCalls, DecodedReads, ReadCounter, ResidentReads, count_snps_from_read_chunks,
+from .utils import BarcodeHandler, calls_per_barcode, summarize_counted_SNPs
+from .snp_counter import (CompressedSNPCalls, DecodedReads, ReadCounter, ResidentCalls, ResidentReads, count_snps_from_read_chunks,
                           count_snps_from_reads)
 from .genotypes import ProbabilisticGenotypes
 from .demux import Demultiplexer, DevicePosteriors, invalidate_resident
@@ -13,5 +13,5 @@ from .snp_detection import (coverage_from_reads, detect_snps_positions_from_call
                             find_candidate_positions, select_snps_from_calls)
 
 __all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'invalidate_resident',
-           'detect_snps_positions_from_calls', 'select_snps_from_calls', 'DecodedReads', 'ResidentReads', 'count_snps_from_reads', 'count_snps_from_read_chunks', 'ReadCounter', 'coverage_from_reads',
+           'detect_snps_positions_from_calls', 'select_snps_from_calls', 'DecodedReads', 'ResidentReads', 'ResidentCalls', 'calls_per_barcode', 'summarize_counted_SNPs', 'count_snps_from_reads', 'count_snps_from_read_chunks', 'ReadCounter', 'coverage_from_reads',
            'find_candidate_positions', 'detect_snps_positions_from_reads']

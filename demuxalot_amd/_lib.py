@@ -138,12 +138,31 @@ DEBUG_SIGNATURES = {
     'dmx_coverage_count_resident': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P]),
     'dmx_count_reads_push_resident': (c_int, [_P, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]),
     'dmx_get_reads_upload_bytes': (c_int, [_P, POINTER(c_int64)]),
+    'dmx_calls_upload': (c_int, [_P, _P, POINTER(c_int64)]),
+    'dmx_calls_open': (c_int, [_P, POINTER(c_int64)]),
+    'dmx_calls_append_counted': (c_int, [_P, c_int64]),
+    'dmx_calls_seal': (c_int, [_P, c_int64]),
+    'dmx_calls_concatenate': (c_int, [_P, POINTER(c_int64), c_int32, POINTER(c_int64)]),
+    'dmx_calls_view': (c_int, [_P, c_int64, _P]),
+    'dmx_calls_info': (c_int, [_P, c_int64, POINTER(c_int64)]),
+    'dmx_calls_fetch': (c_int, [_P, c_int64, _P, _P]),
+    'dmx_calls_release': (c_int, [_P, c_int64]),
+    'dmx_calls_barcode_counts': (c_int, [_P, c_int64, c_int64, _P, _P]),
+    'dmx_stage_device_containers': (c_int, [_P, _P, c_int32]),
+    'dmx_snp_count_device': (c_int, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, c_int32, POINTER(c_int64)]),
+    'dmx_get_calls_transfer_bytes': (c_int, [_P, POINTER(c_int64)]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings
 COVERAGE_ATOMIC, COVERAGE_TILED = 0, 1  # dmx_set_coverage_form
+CALLS_INFO = ('n_molecules', 'n_snp_calls', 'nbytes', 'sealed')  # dmx_calls_info
 READS_INFO = ('n_reads', 'n_cigar_ops', 'n_bases', 'nbytes', 'reference_length')  # dmx_reads_info
 COUNT_READS_STAGES = ('upload', 'walk', 'molecules', 'duplicates', 'observations', 'fold', 'order')  # dmx_get_count_reads_timings
+
+
+class CallContainerStruct(ctypes.Structure):
+    """dmx_call_container of include/demux_hip.h."""
+    _fields_ = [('snp_calls', _P), ('n_snp_calls', c_int64), ('molecules', _P), ('n_molecules', c_int64), ('chrom', c_int32)]
 
 
 class DecodedReadsStruct(ctypes.Structure):

@@ -1180,6 +1180,7 @@ int dmx_count_reads_fetch(dmx_ctx *c, void *molecules_out, void *snp_calls_out)
     if (c->cr_calls)
         HIP_TRY(hipMemcpyAsync(snp_calls_out, c->d_cr_calls.p, (size_t)c->cr_calls * SNP_CALL_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->calls_transfer_bytes[1] += dmx::host::call_record_bytes(c->cr_molecules, c->cr_calls);
     return 0;
 }
 

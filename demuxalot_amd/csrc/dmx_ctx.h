@@ -103,6 +103,16 @@ struct ResidentReads {
     int64_t bytes = 0;               // device bytes held
 };
 
+// A resident call set (include/demux_hip_debug.h "Resident calls"; csrc/resident_calls.hip): the two record arrays of one
+// CompressedSNPCalls, bytewise the host records, in blocks of the context's cache.  Open while it is filled, read-only once sealed.
+// Its blocks are NOT counted in dmx_ctx::bytes (dmx_device_bytes is the problem's and the passes'; dmx_calls_info reports a set's).
+struct ResidentCalls {
+    unsigned char *molecules = nullptr, *calls = nullptr;  // [cap_molecules * 12], [cap_calls * 13]
+    long long n_molecules = 0, n_calls = 0;
+    long long cap_molecules = 0, cap_calls = 0;  // records the blocks have room for (0: no block)
+    bool sealed = false;
+};
+
 struct dmx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -284,6 +294,9 @@ struct dmx_ctx {
     // resident read sets (resident_reads.hip): the caller's, by handle; they outlive dmx_release_problem, dmx_destroy frees them
     std::map<int64_t, ResidentReads> resident_reads;
     int64_t reads_upload_bytes = 0;  // decoded-read arrays copied host to device so far (dmx_get_reads_upload_bytes)
+    // resident call sets (resident_calls.hip): the caller's, by handle, with the life cycle of the resident read sets
+    std::map<int64_t, ResidentCalls> resident_calls;
+    int64_t calls_transfer_bytes[2] = {0, 0};  // call records copied host to device / device to host so far (dmx_get_calls_transfer_bytes)
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at
@@ -472,6 +485,8 @@ int plan_mstep_shifts(dmx_ctx *c);  // the tiles' fixed-point exponents per vari
 void release_mstep_tiles(dmx_ctx *c);
 int build_snp_groups(dmx_ctx *c, const unsigned long long *vb_keys, const unsigned *src_idx, const float *src_p, long long m);
 int stage_containers_on_device(dmx_ctx *c, const dmx_call_container *parts, int n_parts);
+// the same from views of resident call sets: the pointers are device memory (checked by the caller), nothing is uploaded
+int stage_device_containers(dmx_ctx *c, const dmx_call_container *views, int n_views);
 int pack_staged_on_device(dmx_ctx *c, long long V, const int *var_chrom, const int *var_pos, const unsigned char *var_base,
                           const int *chrom_table, int n_table, long long *n_matched, long long *n_unique, long long *mol_per_variant);
 void release_staged_calls(dmx_ctx *c);

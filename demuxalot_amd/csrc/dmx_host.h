@@ -29,6 +29,14 @@ void release_coverage(dmx_ctx *c);       // the window and the candidates of dmx
 void release_resident_reads(dmx_ctx *c, ResidentReads &set);  // the buffers of one resident read set (resident_reads.hip)
 // the set behind a handle of dmx_reads_upload on this context; a stale or foreign handle: DMX_ERR_INVALID
 int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentReads **set);
+void release_resident_calls(dmx_ctx *c, ResidentCalls &set);  // the blocks of one resident call set (resident_calls.hip)
+// the set behind a handle of dmx_calls_upload / _open / _concatenate on this context; a stale or foreign handle: DMX_ERR_INVALID
+int find_resident_calls(dmx_ctx *c, int64_t handle, const char *who, ResidentCalls **set);
+// device views of call containers (dmx_stage_device_containers, dmx_snp_count_device): sizes, and every pointer device memory of
+// the context's device (resident_calls.hip)
+int check_device_containers(dmx_ctx *c, const dmx_call_container *views, int n_views, const char *who);
+// bytes of the two record arrays of a container
+inline int64_t call_record_bytes(long long n_molecules, long long n_calls) { return 12 * (int64_t)n_molecules + 13 * (int64_t)n_calls; }
 // bytes of the decoded-read arrays a call copies to the device: the eight a coverage pass reads, or all twelve
 int64_t decoded_reads_bytes(long long n_reads, long long n_ops, long long n_bases, bool with_counting_columns);
 int build_row_segments(dmx_ctx *c);

@@ -623,6 +623,22 @@ int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentRea
     return 0;
 }
 
+void release_resident_calls(dmx_ctx *c, ResidentCalls &set)
+{
+    ctx_free(c, set.molecules);
+    ctx_free(c, set.calls);
+    set = ResidentCalls();
+}
+
+int find_resident_calls(dmx_ctx *c, int64_t handle, const char *who, ResidentCalls **set)
+{
+    const auto it = c->resident_calls.find(handle);
+    if (it == c->resident_calls.end())
+        return fail(DMX_ERR_INVALID, "%s: %lld is no resident call set of this context (released, or another context's)", who, (long long)handle);
+    *set = &it->second;
+    return 0;
+}
+
 int64_t decoded_reads_bytes(long long n_reads, long long n_ops, long long n_bases, bool with_counting_columns)
 {
     ReadColumns shape;  // (for the columns' extents and element types)
@@ -709,6 +725,8 @@ int dmx_destroy(dmx_ctx *c)
     release_coverage(c);
     for (auto &entry : c->resident_reads) release_resident_reads(c, entry.second);
     c->resident_reads.clear();
+    for (auto &entry : c->resident_calls) release_resident_calls(c, entry.second);
+    c->resident_calls.clear();
     if (c->d_scratch.p) (void)hipFree(c->d_scratch.p);
     dmx::release_staged_calls(c);
     (void)hipDeviceSynchronize();  // the exchange stream too

@@ -1255,7 +1255,8 @@ void release_staged_calls(dmx_ctx *c)
 
 // Upload + field extraction of the containers' records (everything of the pack that does not need the variant keys):
 // the flat call arrays stay with the context until pack_staged_on_device (or the next staging) takes them.
-int stage_containers_on_device(dmx_ctx *c, const dmx_call_container *parts, int n_parts)
+// on_device: the parts' pointers are device memory already (views of resident call sets): nothing is uploaded.
+static int stage_parts(dmx_ctx *c, const dmx_call_container *parts, int n_parts, bool on_device)
 {
     hipStream_t st = c->stream;
     release_staged_calls(c);
@@ -1275,9 +1276,14 @@ int stage_containers_on_device(dmx_ctx *c, const dmx_call_container *parts, int 
     for (int k = 0; k < n_parts; k++) {
         const dmx_call_container &part = parts[k];
         if (part.n_snp_calls == 0) continue;
-        unsigned char *d_calls, *d_molecules;
-        DMX_TRY(upload(sc, &d_calls, (const unsigned char *)part.snp_calls, (size_t)part.n_snp_calls * SNP_CALL_BYTES, st));
-        DMX_TRY(upload(sc, &d_molecules, (const unsigned char *)part.molecules, (size_t)part.n_molecules * MOLECULE_BYTES, st));
+        const unsigned char *d_calls = (const unsigned char *)part.snp_calls, *d_molecules = (const unsigned char *)part.molecules;
+        if (!on_device) {
+            unsigned char *up_calls, *up_molecules;
+            DMX_TRY(upload(sc, &up_calls, d_calls, (size_t)part.n_snp_calls * SNP_CALL_BYTES, st));
+            DMX_TRY(upload(sc, &up_molecules, d_molecules, (size_t)part.n_molecules * MOLECULE_BYTES, st));
+            d_calls = up_calls, d_molecules = up_molecules;
+            c->calls_transfer_bytes[0] += MOLECULE_BYTES * (int64_t)part.n_molecules + SNP_CALL_BYTES * (int64_t)part.n_snp_calls;
+        }
         hipLaunchKernelGGL(k_flatten_container, dim3(grid_for(part.n_snp_calls)), dim3(256), 0, st, d_calls, part.n_snp_calls,
                            d_molecules, part.n_molecules, part.chrom, c->st_chrom + at, c->st_pos + at, c->st_base + at, c->st_cb + at,
                            c->st_p + at, bad);
@@ -1294,6 +1300,10 @@ int stage_containers_on_device(dmx_ctx *c, const dmx_call_container *parts, int 
     c->n_staged = n_calls;
     return 0;
 }
+
+int stage_containers_on_device(dmx_ctx *c, const dmx_call_container *parts, int n_parts) { return stage_parts(c, parts, n_parts, false); }
+
+int stage_device_containers(dmx_ctx *c, const dmx_call_container *views, int n_views) { return stage_parts(c, views, n_views, true); }
 
 // The rest of the pack on the staged calls.  chrom_table (nullable): var_chrom's number of the chromosome every staged
 // call carries provisionally (-1: no variant on it - calls there are an error, demux.py:339-341, 359).

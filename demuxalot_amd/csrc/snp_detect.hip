@@ -299,7 +299,8 @@ __global__ __launch_bounds__(256) void k_sd_gather(const unsigned char *__restri
     selected[at[p] - 1] = p;
 }
 
-int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const int32_t *donor_of_barcode, long long B, int D,
+// on_device: the parts' pointers are device memory already (views of resident call sets): nothing of them is uploaded
+int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, bool on_device, const int32_t *donor_of_barcode, long long B, int D,
               float threshold, long long cap, long long *n_positions)
 {
     hipStream_t st = c->stream;
@@ -326,9 +327,14 @@ int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const in
     for (int k = 0; k < n_parts; k++) {
         const dmx_call_container &part = parts[k];
         if (part.n_snp_calls == 0) continue;
-        unsigned char *d_calls, *d_molecules;
-        DMX_TRY(upload(sc, &d_calls, (const unsigned char *)part.snp_calls, (size_t)part.n_snp_calls * SNP_CALL_BYTES, st));
-        DMX_TRY(upload(sc, &d_molecules, (const unsigned char *)part.molecules, (size_t)part.n_molecules * MOLECULE_BYTES, st));
+        const unsigned char *d_calls = (const unsigned char *)part.snp_calls, *d_molecules = (const unsigned char *)part.molecules;
+        if (!on_device) {
+            unsigned char *up_calls, *up_molecules;
+            DMX_TRY(upload(sc, &up_calls, d_calls, (size_t)part.n_snp_calls * SNP_CALL_BYTES, st));
+            DMX_TRY(upload(sc, &up_molecules, d_molecules, (size_t)part.n_molecules * MOLECULE_BYTES, st));
+            d_calls = up_calls, d_molecules = up_molecules;
+            c->calls_transfer_bytes[0] += dmx::host::call_record_bytes(part.n_molecules, part.n_snp_calls);
+        }
         hipLaunchKernelGGL(k_sd_calls, dim3(grid_for(part.n_snp_calls)), dim3(256), 0, st, d_calls, part.n_snp_calls, d_molecules,
                            part.n_molecules, part.chrom, d_donor, B, threshold, keep + at, pos_key + at, base_cb + at, bad);
         DMX_TRY(launched("k_sd_calls"));
@@ -391,8 +397,9 @@ int snp_count(dmx_ctx *c, const dmx_call_container *parts, int n_parts, const in
 
 extern "C" {
 
-int dmx_snp_count(dmx_ctx *c, const dmx_call_container *containers, int32_t n_containers, const int32_t *donor_of_barcode,
-                  int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions)
+// what dmx_snp_count and dmx_snp_count_device share: the arguments, the pass, its clean-up
+static int snp_count_entry(dmx_ctx *c, const dmx_call_container *containers, int32_t n_containers, bool on_device, const int32_t *donor_of_barcode,
+                           int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions)
 {
     DMX_TRY(bind(c));
     if (n_containers < 0 || (n_containers && !containers)) return fail(DMX_ERR_INVALID, "bad container list");
@@ -404,7 +411,8 @@ int dmx_snp_count(dmx_ctx *c, const dmx_call_container *containers, int32_t n_co
     for (int64_t b = 0; b < n_barcodes; b++)
         if (donor_of_barcode[b] < -1 || donor_of_barcode[b] >= n_donors) return fail(DMX_ERR_INVALID, "donor_of_barcode[%lld] out of range", (long long)b);
     long long P = 0;
-    const int rc = snp_count(c, containers, n_containers, donor_of_barcode, n_barcodes, n_donors, p_threshold, cap, &P);
+    if (on_device) DMX_TRY(dmx::host::check_device_containers(c, containers, n_containers, "snp_count_device"));
+    const int rc = snp_count(c, containers, n_containers, on_device, donor_of_barcode, n_barcodes, n_donors, p_threshold, cap, &P);
     if (rc) {
         (void)hipStreamSynchronize(c->stream);
         dmx::host::release_snp_detection(c);
@@ -412,6 +420,18 @@ int dmx_snp_count(dmx_ctx *c, const dmx_call_container *containers, int32_t n_co
     }
     *n_positions = P;
     return 0;
+}
+
+int dmx_snp_count(dmx_ctx *c, const dmx_call_container *containers, int32_t n_containers, const int32_t *donor_of_barcode,
+                  int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions)
+{
+    return snp_count_entry(c, containers, n_containers, false, donor_of_barcode, n_barcodes, n_donors, p_threshold, cap, n_positions);
+}
+
+int dmx_snp_count_device(dmx_ctx *c, const dmx_call_container *views, int32_t n_views, const int32_t *donor_of_barcode,
+                         int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions)
+{
+    return snp_count_entry(c, views, n_views, true, donor_of_barcode, n_barcodes, n_donors, p_threshold, cap, n_positions);
 }
 
 int dmx_snp_score(dmx_ctx *c, double regularization, int32_t *chrom, int32_t *pos, int32_t *counts, double *importances,

@@ -296,10 +296,13 @@ def _pack_on_device(chromosome2compressed_snp_calls, genotypes, n_barcodes, add_
     context (the caller holds shared_context_lock).  `reduce_molecule_counts` (barcode-sharded runs): maps this
     shard's molecule counts per variant to the counts of the whole experiment, which the data term of the
     prior is made of (demux.py:381-384)."""
-    from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+    from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE, split_call_sets
     if ctx is None:
         ctx = get_context()
     shared = bool(getattr(ctx, '_is_shared', False))  # the process-wide context (its users hold shared_context_lock)
+    if split_call_sets(chromosome2compressed_snp_calls):
+        return _pack_resident_calls(ctx, shared, chromosome2compressed_snp_calls, genotypes, n_barcodes, add_data_prior, fetch_betas,
+                                    reduce_molecule_counts)
     containers = list(chromosome2compressed_snp_calls.values())
     raw = all(c.snp_calls.dtype == SNP_CALL_DTYPE and c.molecules.dtype == MOLECULE_DTYPE for c in containers)
     # The packed problem stays resident on the shared context: predict_posteriors followed by learn_genotypes on the same
@@ -404,6 +407,51 @@ def _pack_on_device(chromosome2compressed_snp_calls, genotypes, n_barcodes, add_
             thread, box, meta, sampled = hashes_later
             thread.join()
             ctx._resident_key = ('full', meta, sampled, box[0]) if box else None   # (a hash that failed: nothing is kept)
+    return ctx, betas
+
+
+def _resident_calls_key(named, genotypes, n_barcodes, keep_molecule_calls):
+    """What a problem packed from ResidentCalls is kept under on the shared context.  named: [(chromosome, ResidentCalls)].  No
+    record is looked at: a handle is never reused and a sealed set never changes, so (chromosome, handle) is exact."""
+    return ('resident-calls', tuple((chrom, int(calls._handle)) for chrom, calls in named), _var2varid_fingerprint(genotypes.var2varid),
+            genotypes.n_variants, genotypes.n_genotypes, int(n_barcodes), bool(keep_molecule_calls))
+
+
+def _pack_resident_calls(ctx, shared, chromosome2resident_calls, genotypes, n_barcodes, add_data_prior, fetch_betas, reduce_molecule_counts):
+    """_pack_on_device for a dict of ResidentCalls (snp_counter.py): the sets' device views are staged where the host path uploads
+    the records - no call record crosses the link, none is read on the host - and the rest is the host path's.  The sets may live
+    on another context of ctx's device.  The resident key on the shared context needs no hash: handles are never reused and a
+    sealed set never changes, so (chromosome, handle) names the records exactly."""
+    named = list(chromosome2resident_calls.items())
+    views = [(k, calls._view(ctx.device)) for k, (_chrom, calls) in enumerate(named)]  # (a closed set raises here, before any reuse)
+    key = None
+    if shared and reduce_molecule_counts is None and resident_policy() != '0':
+        key = _resident_calls_key(named, genotypes, n_barcodes, getattr(ctx, '_keep_molecule_calls', False))
+    if key is not None and getattr(ctx, '_resident_key', None) == key:
+        molecules = None  # (the counts per variant are on the device: dmx_set_prior_betas takes them from there)
+    else:
+        ctx.stage_device_containers(views)
+        try:
+            _fp, v2snp, (var_chrom, var_pos, var_base), chrom_index = _cached_variant_keys(genotypes)
+            chrom_of_container = []
+            for chrom, calls in named:
+                if chrom not in chrom_index:  # demux.py:339-341, 359: calls on a chromosome without variants trip the reference's final assert
+                    assert calls.n_snp_calls == 0
+                chrom_of_container.append(chrom_index.get(chrom, -1))
+        except BaseException:
+            try:  # the staged calls (~17 bytes per call on the GPU) go back before unwinding
+                ctx.release_problem()
+            except Exception:  # noqa: BLE001
+                pass
+            raise
+        _m, _u, molecules = ctx.pack_staged_and_set_problem(n_barcodes, genotypes.n_genotypes, var_chrom, var_pos, var_base, v2snp,
+                                                            chrom_of_container)
+        ctx._resident_key = key
+    if reduce_molecule_counts is not None and add_data_prior:
+        molecules = reduce_molecule_counts(molecules)
+    else:
+        molecules = None
+    betas = ctx.set_prior_betas(genotypes.get_betas(), genotypes.default_prior, add_data_prior, mol_per_variant=molecules, fetch=fetch_betas)
     return ctx, betas
 
 
@@ -829,6 +877,9 @@ class Demultiplexer:
     def pack_calls(chromosome2compressed_snp_calls, genotypes, add_data_prior: bool):
         """demux.py:303-392: returns (variant_index2snp_index, regularised betas (read-only),
         matched molecule calls, unique barcode calls)."""
+        from .snp_counter import split_call_sets
+        if split_call_sets(chromosome2compressed_snp_calls):  # the public host twin: the records come to the host
+            chromosome2compressed_snp_calls = {chrom: calls.to_host() for chrom, calls in chromosome2compressed_snp_calls.items()}
         packed = _pack(chromosome2compressed_snp_calls, genotypes, add_data_prior, want_molecule_table=True)
         barcode_calls = Demultiplexer.molecule_calls2barcode_calls(
             packed.molecule_calls,

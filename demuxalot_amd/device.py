@@ -411,22 +411,26 @@ class DeviceContext:
         assert qual_table.shape == (41,), 'qual_table holds the qualities 0 .. 40'
         return positions, qual_table
 
-    def _counted(self, entry, *args):
-        """(molecules, snp_calls) of a counting entry point: the call reports how many there are, dmx_count_reads_fetch copies them."""
+    def _counted(self, entry, *args, fetch=True):
+        """(molecules, snp_calls) of a counting entry point: the call reports how many there are, dmx_count_reads_fetch copies them.
+        fetch=False: (n_molecules, n_snp_calls), the records stay on the device (calls_append_counted takes them from there)."""
         from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
         n_molecules, n_calls = ctypes.c_int64(0), ctypes.c_int64(0)
         check(entry(self._h, *args, ctypes.byref(n_molecules), ctypes.byref(n_calls)))
+        if not fetch:
+            return n_molecules.value, n_calls.value
         molecules = np.empty(n_molecules.value, dtype=MOLECULE_DTYPE)
         snp_calls = np.empty(n_calls.value, dtype=SNP_CALL_DTYPE)
         check(self._lib.dmx_count_reads_fetch(self._h, ptr(molecules), ptr(snp_calls)))
         return molecules, snp_calls
 
-    def count_reads(self, reads, positions, qual_table):
+    def count_reads(self, reads, positions, qual_table, fetch=True):
         """(molecules, snp_calls) structured arrays (snp_counter.MOLECULE_DTYPE / SNP_CALL_DTYPE) counted on the device from a
-        DecodedReads at the strictly ascending int32 `positions`; qual_table float64[41].  The resident problem stays."""
+        DecodedReads at the strictly ascending int32 `positions`; qual_table float64[41].  The resident problem stays.
+        fetch=False (here and in the three calls below): (n_molecules, n_snp_calls), the records stay on the device."""
         positions, qual_table = self._count_inputs(positions, qual_table)
         desc, _keep_alive = self._reads_descriptor(reads)
-        return self._counted(self._lib.dmx_count_reads, desc, ptr(positions), len(positions), ptr(qual_table))
+        return self._counted(self._lib.dmx_count_reads, desc, ptr(positions), len(positions), ptr(qual_table), fetch=fetch)
 
     def count_reads_timings(self):
         """{stage: milliseconds} of the last count_reads or count_reads_push (include/demux_hip_debug.h: dmx_get_count_reads_timings)."""
@@ -439,10 +443,10 @@ class DeviceContext:
         positions, qual_table = self._count_inputs(positions, qual_table)
         check(self._lib.dmx_count_reads_begin(self._h, ptr(positions), len(positions), ptr(qual_table)))
 
-    def count_reads_push(self, reads, final=False):
+    def count_reads_push(self, reads, final=False, fetch=True):
         """(molecules, snp_calls) this push emitted, molecule_index counting on across the stream; reads: a DecodedReads or None."""
         desc, _keep_alive = (None, None) if reads is None else self._reads_descriptor(reads)
-        return self._counted(self._lib.dmx_count_reads_push, desc, 1 if final else 0)
+        return self._counted(self._lib.dmx_count_reads_push, desc, 1 if final else 0, fetch=fetch)
 
     def count_reads_end(self):
         check(self._lib.dmx_count_reads_end(self._h))
@@ -483,14 +487,105 @@ class DeviceContext:
         check(self._lib.dmx_get_reads_upload_bytes(self._h, ctypes.byref(n)))
         return n.value
 
-    def count_reads_resident(self, handle, positions, qual_table):
+    def count_reads_resident(self, handle, positions, qual_table, fetch=True):
         """count_reads on a resident set."""
         positions, qual_table = self._count_inputs(positions, qual_table)
-        return self._counted(self._lib.dmx_count_reads_resident, int(handle), ptr(positions), len(positions), ptr(qual_table))
+        return self._counted(self._lib.dmx_count_reads_resident, int(handle), ptr(positions), len(positions), ptr(qual_table), fetch=fetch)
 
-    def count_reads_push_resident(self, handle, first_read, last_read, final=False):
+    def count_reads_push_resident(self, handle, first_read, last_read, final=False, fetch=True):
         """count_reads_push with the reads [first_read, last_read) of a resident set as the chunk."""
-        return self._counted(self._lib.dmx_count_reads_push_resident, int(handle), int(first_read), int(last_read), 1 if final else 0)
+        return self._counted(self._lib.dmx_count_reads_push_resident, int(handle), int(first_read), int(last_read), 1 if final else 0,
+                             fetch=fetch)
+
+    # ---- resident calls (include/demux_hip_debug.h "Resident calls"; snp_counter.ResidentCalls is the front) ----
+    def calls_upload(self, snp_calls, molecules):
+        """Handle of a sealed set holding copies of the two record arrays (SNP_CALL_DTYPE / MOLECULE_DTYPE) of one container."""
+        parts, _keep_alive = self._container_list([(0, snp_calls, molecules)])
+        handle = ctypes.c_int64(0)
+        check(self._lib.dmx_calls_upload(self._h, ctypes.cast(parts, ctypes.c_void_p), ctypes.byref(handle)))
+        return handle.value
+
+    def calls_open(self):
+        """Handle of a new, empty, open set (calls_append_counted fills it, calls_seal closes it)."""
+        handle = ctypes.c_int64(0)
+        check(self._lib.dmx_calls_open(self._h, ctypes.byref(handle)))
+        return handle.value
+
+    def calls_append_counted(self, handle):
+        """Appends the records of the last count_reads / count_reads_push (any of the four) of this context, device to device."""
+        check(self._lib.dmx_calls_append_counted(self._h, int(handle)))
+
+    def calls_seal(self, handle):
+        check(self._lib.dmx_calls_seal(self._h, int(handle)))
+
+    def calls_concatenate(self, handles):
+        """Handle of a new sealed set: the sets in list order, molecule_index shifted by the molecules before each."""
+        handles = as_c(list(handles), np.int64)
+        out = ctypes.c_int64(0)
+        check(self._lib.dmx_calls_concatenate(self._h, handles.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(handles), ctypes.byref(out)))
+        return out.value
+
+    def calls_view(self, handle):
+        """_lib.CallContainerStruct with the device pointers and sizes of a sealed set (chrom 0)."""
+        view = _lib.CallContainerStruct()
+        check(self._lib.dmx_calls_view(self._h, int(handle), ctypes.cast(ctypes.byref(view), ctypes.c_void_p)))
+        return view
+
+    def calls_info(self, handle):
+        """{n_molecules, n_snp_calls, nbytes, sealed} of a set (dmx_calls_info)."""
+        info = (ctypes.c_int64 * len(_lib.CALLS_INFO))()
+        check(self._lib.dmx_calls_info(self._h, int(handle), info))
+        return dict(zip(_lib.CALLS_INFO, (int(v) for v in info)))
+
+    def calls_fetch(self, handle):
+        """(molecules, snp_calls) structured arrays of a sealed set."""
+        from .snp_counter import MOLECULE_DTYPE, SNP_CALL_DTYPE
+        info = self.calls_info(handle)
+        molecules = np.empty(info['n_molecules'], dtype=MOLECULE_DTYPE)
+        snp_calls = np.empty(info['n_snp_calls'], dtype=SNP_CALL_DTYPE)
+        check(self._lib.dmx_calls_fetch(self._h, int(handle), ptr(molecules), ptr(snp_calls)))
+        return molecules, snp_calls
+
+    def calls_release(self, handle):
+        check(self._lib.dmx_calls_release(self._h, int(handle)))
+
+    def calls_barcode_counts(self, handle, n_barcodes):
+        """(calls int64[B], molecules int64[B]) per compressed_cb of a sealed set (dmx_calls_barcode_counts)."""
+        calls, molecules = np.zeros(int(n_barcodes), dtype=np.int64), np.zeros(int(n_barcodes), dtype=np.int64)
+        check(self._lib.dmx_calls_barcode_counts(self._h, int(handle), int(n_barcodes), ptr(calls), ptr(molecules)))
+        return calls, molecules
+
+    @staticmethod
+    def _view_list(views):
+        """[(chromosome number, CallContainerStruct view)] as the array of dmx_call_container the device entry points take."""
+        parts = (_lib.CallContainerStruct * max(1, len(views)))()
+        for k, (chrom, view) in enumerate(views):
+            parts[k] = _lib.CallContainerStruct(view.snp_calls, view.n_snp_calls, view.molecules, view.n_molecules, int(chrom))
+        return parts
+
+    def stage_device_containers(self, views):
+        """stage_containers from views of sealed resident call sets ([(provisional chromosome number, view)]): nothing is uploaded.
+        The sets may belong to another context of this device.  include/demux_hip_debug.h: dmx_stage_device_containers."""
+        self._resident_key = None  # (demux.py: _pack_on_device keeps the packed problem of the shared context across calls)
+        parts = self._view_list(views)
+        check(self._lib.dmx_stage_device_containers(self._h, ctypes.cast(parts, ctypes.c_void_p), len(views)))
+
+    def snp_count_device(self, views, donor_of_barcode, n_donors, p_threshold=0.01, cap=3):
+        """snp_count from views of sealed resident call sets ([(chromosome number, view)]); nothing of the calls is uploaded."""
+        parts = self._view_list(views)
+        donor_of_barcode = as_c(donor_of_barcode, np.int32)
+        n = ctypes.c_int64(0)
+        check(self._lib.dmx_snp_count_device(self._h, ctypes.cast(parts, ctypes.c_void_p), len(views), ptr(donor_of_barcode),
+                                             len(donor_of_barcode), int(n_donors), float(np.float32(p_threshold)), int(cap),
+                                             ctypes.byref(n)))
+        self._snp_shape = (n.value, int(n_donors))
+        return n.value
+
+    def calls_transfer_bytes(self):
+        """(host to device, device to host): bytes of call records this context has copied so far (dmx_get_calls_transfer_bytes)."""
+        n = (ctypes.c_int64 * 2)()
+        check(self._lib.dmx_get_calls_transfer_bytes(self._h, n))
+        return int(n[0]), int(n[1])
 
     def coverage_count_resident(self, handle, start, stop, quality_threshold=15, fetch=True):
         """coverage_count on a resident set."""

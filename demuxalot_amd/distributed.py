@@ -277,6 +277,9 @@ def _install_shard(chromosome2compressed_snp_calls, genotypes, barcode_handler, 
     them)."""
     from .demux import _pack_on_device
     from .device import DeviceContext, default_device
+    from .snp_counter import ResidentCalls
+    if any(isinstance(calls, ResidentCalls) for calls in chromosome2compressed_snp_calls.values()):
+        raise TypeError('ResidentCalls are out of scope for the multi-GPU entry points (the shards are cut on the host): pass to_host()')
     n_barcodes = barcode_handler.n_barcodes
     bounds = partition_barcodes(calls_per_barcode(chromosome2compressed_snp_calls, n_barcodes), plane.world)
     lo, hi = int(bounds[plane.rank]), int(bounds[plane.rank + 1])

@@ -257,6 +257,157 @@ class ResidentReads:
             pass
 
 
+class ResidentCalls:
+    """The two record arrays of one chromosome's CompressedSNPCalls held on a device context and accepted wherever the container
+    is: Demultiplexer.predict_posteriors / learn_genotypes / staged_genotype_learning, select_snps_from_calls,
+    detect_snps_positions_from_calls, calls_per_barcode, summarize_counted_SNPs - none of which then moves a call record over the
+    link (include/demux_hip_debug.h "Resident calls"; DESIGN.md "Resident calls").  ResidentCalls(container) uploads a host
+    container; count_snps_from_reads(..., resident_calls=True) and ReadCounter(keep_calls=True) leave the counted records in such
+    sets without a download.  A set is immutable; a context manager:
+
+        with ResidentCalls(container) as resident:
+            logits, probs = Demultiplexer.predict_posteriors({'chr1': resident}, genotypes, handler)
+
+    Without on_context the set lives on the shared context.  Consumers may run on another context of the same device.  There is no
+    .snp_calls / .molecules: to_host() is the (explicit) download.  Every use after close() raises RuntimeError."""
+
+    def __init__(self, container, on_context=None):
+        self._ctx = self._handle = None
+        if isinstance(container, ResidentCalls):
+            raise TypeError('container is a ResidentCalls already (concatenate([it]) makes a copy on the device)')
+        try:
+            n_calls, n_molecules = int(container.n_snp_calls), int(container.n_molecules)
+            snp_calls, molecules = container.snp_calls, container.molecules
+        except AttributeError:
+            raise TypeError('container must be a CompressedSNPCalls (snp_calls, n_snp_calls, molecules, n_molecules)') from None
+        if getattr(snp_calls, 'dtype', None) != SNP_CALL_DTYPE or getattr(molecules, 'dtype', None) != MOLECULE_DTYPE:
+            raise TypeError("the container's record arrays must have the dtypes SNP_CALL_DTYPE and MOLECULE_DTYPE")
+        if not (0 <= n_calls <= len(snp_calls) and 0 <= n_molecules <= len(molecules)):
+            raise ValueError('n_snp_calls / n_molecules do not fit the record arrays')
+        if on_context is None:
+            with shared_context_lock:
+                ctx = get_context()
+                self._adopt_handle(ctx, ctx.calls_upload(snp_calls[:n_calls], molecules[:n_molecules]))
+        else:
+            self._adopt_handle(on_context, on_context.calls_upload(snp_calls[:n_calls], molecules[:n_molecules]))
+
+    def _adopt_handle(self, ctx, handle):
+        """Takes over a SEALED set of ctx (the caller holds ctx)."""
+        self._shared = bool(getattr(ctx, '_is_shared', False))
+        try:
+            self._info, self._device_view = ctx.calls_info(handle), ctx.calls_view(handle)
+        except BaseException:
+            ctx.calls_release(handle)
+            raise
+        self._ctx, self._handle = ctx, handle
+
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        out = cls.__new__(cls)
+        out._ctx = out._handle = None
+        out._adopt_handle(ctx, handle)
+        return out
+
+    def __getattr__(self, name):  # (only reached for names that are not there)
+        if name in ('snp_calls', 'molecules'):
+            raise AttributeError(f'a ResidentCalls keeps its records on the device and has no .{name}: to_host() downloads them')
+        raise AttributeError(f'{type(self).__name__!r} object has no attribute {name!r}')
+
+    def _check(self):
+        if self._handle is None:
+            raise RuntimeError('this ResidentCalls is closed')
+        if getattr(self._ctx, '_h', None) is None:
+            raise RuntimeError('the device context of this ResidentCalls was destroyed, and the set with it')
+
+    def _locked(self, run):
+        self._check()
+        if self._shared:
+            with shared_context_lock:
+                return run(self._ctx)
+        return run(self._ctx)
+
+    def _view(self, on_device=None):
+        """The set's device pointers and sizes, for a consumer on `on_device` (another device: TypeError)."""
+        self._check()
+        if on_device is not None and int(on_device) != self._ctx.device:
+            raise TypeError(f'this ResidentCalls lives on device {self._ctx.device}, the call runs on device {int(on_device)}')
+        return self._device_view
+
+    @property
+    def closed(self):
+        """True once close() has run (or the with block was left)."""
+        return self._handle is None
+
+    @property
+    def n_molecules(self):
+        self._check()
+        return self._info['n_molecules']
+
+    @property
+    def n_snp_calls(self):
+        self._check()
+        return self._info['n_snp_calls']
+
+    @property
+    def nbytes(self):
+        """Device bytes the set holds."""
+        self._check()
+        return self._info['nbytes']
+
+    def to_host(self) -> 'CompressedSNPCalls':
+        """The records as a CompressedSNPCalls: the one download of a set."""
+        return _container(*self._locked(lambda ctx: ctx.calls_fetch(self._handle)))
+
+    def barcode_counts(self, n_barcodes):
+        """(calls int64[n_barcodes], molecules int64[n_barcodes]) per compressed_cb, counted on the device."""
+        return self._locked(lambda ctx: ctx.calls_barcode_counts(self._handle, n_barcodes))
+
+    @staticmethod
+    def concatenate(resident_calls_list) -> 'ResidentCalls':
+        """CompressedSNPCalls.concatenate on the device: a new set on the parts' context, the parts in list order."""
+        parts = list(resident_calls_list)
+        if not parts or not all(isinstance(part, ResidentCalls) for part in parts):
+            raise TypeError('concatenate takes a non-empty list of ResidentCalls')
+        for part in parts:
+            part._check()
+            if part._ctx is not parts[0]._ctx:
+                raise ValueError('the ResidentCalls of one concatenate must live on one context')
+        if sum(part.n_molecules for part in parts) >= 2 ** 31:
+            raise ValueError('2^31 molecules or more: molecule_index is an int32')
+        return parts[0]._locked(lambda ctx: ResidentCalls._adopt(ctx, ctx.calls_concatenate([part._handle for part in parts])))
+
+    def close(self):
+        ctx, handle, self._handle = self._ctx, self._handle, None
+        if handle is None or getattr(ctx, '_h', None) is None:  # (a destroyed context has freed its sets)
+            return
+        if self._shared:
+            with shared_context_lock:
+                ctx.calls_release(handle)
+        else:
+            ctx.calls_release(handle)
+
+    def __enter__(self):
+        self._check()
+        return self
+
+    def __exit__(self, *_exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def split_call_sets(chromosome2calls, what='chromosome2compressed_snp_calls'):
+    """True when every value of the dict is a ResidentCalls, False when none is; a dict that mixes the two kinds is a TypeError."""
+    kinds = {isinstance(calls, ResidentCalls) for calls in chromosome2calls.values()}
+    if len(kinds) == 2:
+        raise TypeError(f'{what} mixes ResidentCalls and host containers: pass one kind (to_host() / ResidentCalls(container) convert)')
+    return kinds == {True}
+
+
 def _container(molecules, snp_calls):
     out = CompressedSNPCalls(start_snps_size=1, start_molecule_size=1)
     out.molecules, out.snp_calls = molecules, snp_calls
@@ -279,13 +430,18 @@ class ReadCounter:
 
     push returns the records of the molecules that chunk's reads flushed, finish the rest; concatenated they are the records of
     count_snps_from_reads on all the reads (molecule_index counts on across the pushes).  Without on_context the shared context
-    is used and its lock is held from __enter__ to __exit__.  One stream per context."""
+    is used and its lock is held from __enter__ to __exit__.  One stream per context.
+    keep_calls=True: the records stay on the device - push and finish return (n_molecules, n_snp_calls) of that push, and after
+    finish() `.calls` is the sealed ResidentCalls of the whole stream (the caller's: it outlives the with block)."""
 
-    def __init__(self, positions, on_context=None):
+    def __init__(self, positions, on_context=None, keep_calls=False):
         self._positions = np.ascontiguousarray(positions, dtype=np.int32)
         self._on_context = on_context
         self._ctx = None
         self._finished = False
+        self._keep_calls = bool(keep_calls)
+        self._set = None   # handle of the open set the pushes fill (keep_calls)
+        self.calls = None  # keep_calls: the sealed ResidentCalls, once finish() has run
 
     def __enter__(self):
         if self._ctx is not None:
@@ -296,17 +452,29 @@ class ReadCounter:
         try:
             ctx = get_context() if locked else self._on_context
             ctx.count_reads_begin(self._positions, quality_table())
+            if self._keep_calls:
+                try:
+                    self._set = ctx.calls_open()
+                except BaseException:
+                    ctx.count_reads_end()
+                    raise
         except BaseException:
             if locked:
                 shared_context_lock.release()
             raise
         self._ctx, self._finished = ctx, False
+        self.calls = None
         return self
 
     def __exit__(self, *_exc):
         ctx, self._ctx = self._ctx, None
+        handle, self._set = self._set, None
         try:
-            ctx.count_reads_end()
+            try:
+                if handle is not None:  # left before finish(): the half-filled set goes
+                    ctx.calls_release(handle)
+            finally:
+                ctx.count_reads_end()
         finally:
             if self._on_context is None:
                 shared_context_lock.release()
@@ -323,11 +491,17 @@ class ReadCounter:
                 raise TypeError('a device range is (ResidentReads, first_read, last_read)')
             resident, lo, hi = reads
             resident._check(self._ctx)
-            out = self._ctx.count_reads_push_resident(resident._handle, lo, hi, final=final)
+            out = self._ctx.count_reads_push_resident(resident._handle, lo, hi, final=final, fetch=not self._keep_calls)
         elif reads is not None and not isinstance(reads, DecodedReads):
             raise TypeError('a chunk must be a DecodedReads, a ResidentReads or a (ResidentReads, first_read, last_read) range')
         else:
-            out = self._ctx.count_reads_push(reads, final=final)
+            out = self._ctx.count_reads_push(reads, final=final, fetch=not self._keep_calls)
+        if self._keep_calls:
+            self._ctx.calls_append_counted(self._set)
+            if final:
+                self._ctx.calls_seal(self._set)
+                handle, self._set = self._set, None
+                self.calls = ResidentCalls._adopt(self._ctx, handle)
         self._finished = final
         return out
 
@@ -346,10 +520,10 @@ class ReadCounter:
         return 0 if self._ctx is None else self._ctx.count_reads_carry()
 
 
-def _count_chunks(ctx, chunks, positions):
-    """One chromosome's container from an iterable of chunks, one chunk alive at a time."""
+def _count_chunks(ctx, chunks, positions, resident_calls=False):
+    """One chromosome's container (resident_calls: ResidentCalls) from an iterable of chunks, one chunk alive at a time."""
     molecules, snp_calls = [], []
-    with ReadCounter(positions, on_context=ctx) as counter:
+    with ReadCounter(positions, on_context=ctx, keep_calls=resident_calls) as counter:
         iterator = iter(chunks)
         while True:
             chunk = next(iterator, None)
@@ -359,7 +533,43 @@ def _count_chunks(ctx, chunks, positions):
             if chunk is None:
                 break
             del chunk
+    if resident_calls:
+        return counter.calls
     return _container(np.concatenate(molecules), np.concatenate(snp_calls))
+
+
+def _empty_resident(ctx):
+    handle = ctx.calls_open()
+    ctx.calls_seal(handle)
+    return ResidentCalls._adopt(ctx, handle)
+
+
+def _counted_resident(ctx, count):
+    """The records count(fetch=False) leaves on ctx, as a sealed ResidentCalls."""
+    count(fetch=False)
+    handle = ctx.calls_open()
+    try:
+        ctx.calls_append_counted(handle)
+        ctx.calls_seal(handle)
+    except BaseException:
+        ctx.calls_release(handle)
+        raise
+    return ResidentCalls._adopt(ctx, handle)
+
+
+def _closing_on_failure(run):
+    """run(ctx) -> dict of results; the ResidentCalls it had made are closed when it raises."""
+    def guarded(ctx):
+        result = {}
+        try:
+            run(ctx, result)
+        except BaseException:
+            for calls in result.values():
+                if isinstance(calls, ResidentCalls):
+                    calls.close()
+            raise
+        return result
+    return guarded
 
 
 def _on(on_context, run, reads=()):
@@ -381,32 +591,34 @@ def _on(on_context, run, reads=()):
         return run(ctx)
 
 
-def count_snps_from_read_chunks(chromosome2chunks, chromosome2positions, *, on_context=None):
+def count_snps_from_read_chunks(chromosome2chunks, chromosome2positions, *, on_context=None, resident_calls=False):
     """count_snps_from_reads for reads that arrive in batches: chromosome2chunks maps a chromosome to an iterable of
     DecodedReads (a generator is fine), the chunks of that chromosome in read order.  Every iterable is consumed lazily, one
     chunk alive at a time, so neither the host nor the device ever holds a whole chromosome (ReadCounter).
 
+    :param resident_calls: as for count_snps_from_reads
     :return: what count_snps_from_reads returns on the concatenated chunks.  A chromosome without chunks gives an empty
         container; the chunks of a chromosome without positions are consumed and skipped.
     """
     if not isinstance(chromosome2chunks, dict) or not isinstance(chromosome2positions, dict):
         raise TypeError('chromosome2chunks and chromosome2positions must be dicts keyed by chromosome')
 
-    def run(ctx):
-        result = {}
+    def run(ctx, result):
         for chromosome, positions in chromosome2positions.items():
             chunks = chromosome2chunks.get(chromosome)
-            result[chromosome] = _empty_container() if chunks is None else _count_chunks(ctx, chunks, positions)
+            if chunks is None:
+                result[chromosome] = _empty_resident(ctx) if resident_calls else _empty_container()
+            else:
+                result[chromosome] = _count_chunks(ctx, chunks, positions, resident_calls)
         for chromosome, chunks in chromosome2chunks.items():
             if chromosome not in chromosome2positions:
                 for _chunk in chunks:
                     pass
-        return result
 
-    return _on(on_context, run)
+    return _on(on_context, _closing_on_failure(run))
 
 
-def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=None, max_reads_per_call=None):
+def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=None, max_reads_per_call=None, resident_calls=False):
     """count_snps (snp_counter.py:279-327) with the BAM reading replaced by reads the caller has decoded: per chromosome of
     chromosome2positions (in its order) one device call that groups the reads into molecules, walks the CIGARs to the
     SNP positions, multiplies the base-error probabilities and resolves conflicting bases (DESIGN.md "Read counting").
@@ -418,6 +630,8 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
     :param max_reads_per_call: None: one device call per chromosome.  A number: every chromosome is cut into slices of at most
         that many reads and streamed (ReadCounter), which bounds the device memory by the slice; the result is the same.  The
         slices of a ResidentReads are ranges on the device, cut where the host slices are.
+    :param resident_calls: True: the values of the result are ResidentCalls on the counting context - the records stay on the
+        device, nothing is fetched; they are the caller's to close()
     :return: dict chromosome -> CompressedSNPCalls, record for record what the reference's count_call_variants_for_chromosome
         returns.  A chromosome without reads gives an empty container; reads of a chromosome without positions are skipped.
     """
@@ -427,25 +641,26 @@ def count_snps_from_reads(chromosome2reads, chromosome2positions, *, on_context=
         raise ValueError('max_reads_per_call must be at least 1')
     table = quality_table()
 
-    def run(ctx):
-        result = {}
+    def run(ctx, result):
         for chromosome, positions in chromosome2positions.items():
             reads = chromosome2reads.get(chromosome)
             if reads is not None and not isinstance(reads, (DecodedReads, ResidentReads)):
                 raise TypeError(f'chromosome2reads[{chromosome!r}] must be a DecodedReads or a ResidentReads')
             resident = isinstance(reads, ResidentReads)
             if reads is None or reads.n_reads == 0:
-                result[chromosome] = _empty_container()
+                result[chromosome] = _empty_resident(ctx) if resident_calls else _empty_container()
             elif max_reads_per_call is None:
-                counted = ctx.count_reads_resident(reads._handle, positions, table) if resident else ctx.count_reads(reads, positions, table)
-                result[chromosome] = _container(*counted)
+                def count(fetch=True, reads=reads, positions=positions):
+                    if resident:
+                        return ctx.count_reads_resident(reads._handle, positions, table, fetch=fetch)
+                    return ctx.count_reads(reads, positions, table, fetch=fetch)
+                result[chromosome] = _counted_resident(ctx, count) if resident_calls else _container(*count())
             else:
                 step, n = int(max_reads_per_call), reads.n_reads
                 if resident:
                     chunks = ((reads, lo, min(lo + step, n)) for lo in range(0, n, step))
                 else:
                     chunks = (reads.slice(lo, lo + step) for lo in range(0, n, step))
-                result[chromosome] = _count_chunks(ctx, chunks, positions)
-        return result
+                result[chromosome] = _count_chunks(ctx, chunks, positions, resident_calls)
 
-    return _on(on_context, run, [chromosome2reads.get(chromosome) for chromosome in chromosome2positions])
+    return _on(on_context, _closing_on_failure(run), [chromosome2reads.get(chromosome) for chromosome in chromosome2positions])

@@ -36,7 +36,7 @@ import pandas as pd
 
 from .demux import Demultiplexer, DevicePosteriors
 from .device import get_context, shared_context_lock
-from .snp_counter import DecodedReads, ResidentReads, _on, count_snps_from_reads
+from .snp_counter import DecodedReads, ResidentCalls, ResidentReads, _on, count_snps_from_reads, split_call_sets
 
 P_BASE_WRONG_BELOW = np.float32(0.01)  # calls['p_base_wrong'] < 0.01 compares in float32 (snp_detection.py:111)
 ASSIGNMENT_THRESHOLD = 0.8             # posterior above which a barcode counts for its donor (snp_detection.py:166)
@@ -84,7 +84,11 @@ def _select_on(ctx, candidate_calls, sorted_donors, donor_of_barcode, regulariza
                n_additional_best_snps, cap):
     if len(sorted_donors) == 0:
         return []
-    n_positions = ctx.snp_count(_containers(candidate_calls), donor_of_barcode, len(sorted_donors), P_BASE_WRONG_BELOW, int(cap))
+    if split_call_sets(candidate_calls, 'candidate_calls'):  # views of the sets (this or another context of the device): no upload
+        views = [(k, calls._view(ctx.device)) for k, calls in enumerate(candidate_calls.values())]
+        n_positions = ctx.snp_count_device(views, donor_of_barcode, len(sorted_donors), P_BASE_WRONG_BELOW, int(cap))
+    else:
+        n_positions = ctx.snp_count(_containers(candidate_calls), donor_of_barcode, len(sorted_donors), P_BASE_WRONG_BELOW, int(cap))
     if n_positions == 0:
         return []
     scored = ctx.snp_score(regularization, fetch_counts=False, fetch_importances=True)
@@ -114,7 +118,7 @@ def select_snps_from_calls(candidate_calls, barcode_handler, barcode2donor, *, r
     """Scores every candidate position per donor and selects the best (snp_detection.py:78-125, 204-227).
 
     :param candidate_calls: dict chromosome -> CompressedSNPCalls at the candidate positions (what the reference's stage-2
-        count_snps returns)
+        count_snps returns), or -> ResidentCalls (all of them: the records are read where they lie)
     :param barcode2donor: dict or pandas Series barcode -> donor name, or a DevicePosteriors (its assignments(0.8))
     :param genotypes: with ignore_known_snps, positions these genotypes already hold are dropped from the result
     :return: [(chromosome, position, importances float64[D], {ref base: count, alt base: count})] of the selected positions,
@@ -138,7 +142,7 @@ def detect_snps_positions_from_calls(known_calls, candidate_calls, genotypes, ba
     """detect_snps_positions (snp_detection.py:128-215) with the BAM reading replaced by calls the caller supplies:
     known_calls at the genotypes' positions (step 1), candidate_calls at the candidate positions (step 2).
     Step 1 is predict_posteriors without doublets; its posteriors stay on the GPU, and the detection runs on the same
-    device context."""
+    device context.  known_calls and candidate_calls may (each) be dicts of ResidentCalls."""
     _check_arguments(candidate_calls, regularization, n_best_snps_per_donor, n_additional_best_snps,
                      max_contribution_to_base_count_from_barcode)
     posteriors = Demultiplexer.predict_posteriors(known_calls, genotypes, barcode_handler, doublet_prior=0.0, on_device=True)
@@ -298,7 +302,9 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
     Steps 2 to 5 run on the posteriors' device context.  Chromosomes are taken in the order of chromosome2reads; a
     chromosome without candidates is left out (the reference's `return []`).
     chromosome2reads and coverage_reads may hold ResidentReads: the three read passes (steps 1, 3 and 4) then run on the sets'
-    context and upload nothing, steps 2 and 5 on the posteriors' context; the candidate calls cross as host containers.
+    context and upload nothing, steps 2 and 5 on the posteriors' context.  Both call sets (steps 1 and 4) stay on the device as
+    ResidentCalls of the context that counted them, are read from there by steps 2 and 5, and are released before the function
+    returns: no call record crosses the link in either direction.
 
     :param coverage_reads: dict chromosome -> DecodedReads for step 3 when they differ from chromosome2reads.  The reference's
         stage 1 counts every read parse_read accepts, while DecodedReads by contract also drop the reads without a whitelisted
@@ -312,8 +318,19 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
         coverage_reads = chromosome2reads
     # reads that are resident decide where the read passes run; host arrays go to the posteriors' context, as ever
     resident = any(isinstance(reads, ResidentReads) for reads in list(chromosome2reads.values()) + list(coverage_reads.values()))
-    known_calls = count_snps_from_reads(chromosome2reads, genotypes.get_chromosome2positions())
-    posteriors = Demultiplexer.predict_posteriors(known_calls, genotypes, barcode_handler, doublet_prior=0.0, on_device=True)
+    call_sets = []  # the ResidentCalls of steps 1 and 4
+
+    def release_call_sets():
+        for calls in call_sets:
+            calls.close()
+
+    known_calls = count_snps_from_reads(chromosome2reads, genotypes.get_chromosome2positions(), resident_calls=True)
+    call_sets.extend(known_calls.values())
+    try:
+        posteriors = Demultiplexer.predict_posteriors(known_calls, genotypes, barcode_handler, doublet_prior=0.0, on_device=True)
+    except BaseException:
+        release_call_sets()
+        raise
     try:
         ctx = posteriors._ctx
         sorted_donors, donor_of_barcode = _donor_of_barcode(posteriors.assignments(ASSIGNMENT_THRESHOLD), barcode_handler)
@@ -324,10 +341,12 @@ def detect_snps_positions_from_reads(chromosome2reads, genotypes, barcode_handle
             minimum_fraction_of_ref_and_alt=minimum_fraction_of_ref_and_alt, max_fragment_step=max_fragment_step,
             chromosome2length=chromosome2length, quality_threshold=quality_threshold, on_context=None if resident else ctx)
         candidates = {chromosome: positions for chromosome, positions in candidates.items() if len(positions)}
-        candidate_calls = count_snps_from_reads(chromosome2reads, candidates, on_context=None if resident else ctx)
+        candidate_calls = count_snps_from_reads(chromosome2reads, candidates, on_context=None if resident else ctx, resident_calls=True)
+        call_sets.extend(candidate_calls.values())
         selected = _select_on(ctx, candidate_calls, sorted_donors, donor_of_barcode, regularization, n_best_snps_per_donor,
                               n_additional_best_snps, max_contribution_to_base_count_from_barcode)
     finally:
+        release_call_sets()  # (before the posteriors' context goes back to its pool: the candidate sets may live on it)
         posteriors.close()
     return _finish(selected, genotypes, ignore_known_snps, result_beta_prior_filename)
 

@@ -292,6 +292,62 @@ int dmx_count_reads_push_resident(dmx_ctx *ctx, int64_t handle, int64_t first_re
                                   int64_t *n_calls);
 int dmx_get_reads_upload_bytes(dmx_ctx *ctx, int64_t *bytes);
 
+/* ------------------------------------------------------------------------- *
+ * Resident calls (product API; declared here because demux_hip.h is kept to 64 entry points).
+ * The two record arrays of one CompressedSNPCalls (one chromosome) held in blocks the context owns, named by a handle, and taken
+ * by the pack and by the SNP counts in place of host containers: a run from reads to posteriors, or from reads to selected SNPs,
+ * then moves no call record over the link (DESIGN.md "Resident calls").  The records are bytewise the host records: 12-byte
+ * molecules, 13-byte snp_calls, unaligned.  A set is OPEN while it is filled and IMMUTABLE once sealed; view, fetch, concatenate
+ * and the counts take sealed sets only (an open one answers DMX_ERR_INVALID).  Handles are unique in the process and never
+ * reused: a released handle and a handle of another context answer DMX_ERR_INVALID everywhere.  The sets are the caller's:
+ * dmx_release_problem leaves them, dmx_destroy frees what is left.  Their blocks are not part of dmx_device_bytes.
+ *   dmx_calls_upload          copies the two arrays of a host container and seals the set.  One lane per call checks
+ *                             0 <= molecule_index < n_molecules; status and message are those of dmx_stage_containers on the same
+ *                             container.  The caller's arrays are free when it returns.
+ *   dmx_calls_open            a new, empty, open set.
+ *   dmx_calls_append_counted  appends the records of the last dmx_count_reads, dmx_count_reads_resident, dmx_count_reads_push or
+ *                             dmx_count_reads_push_resident of this context, device to device (molecule_index counts on across the
+ *                             pushes of a stream, so an append is a copy; the blocks grow by doubling).  A push that emitted
+ *                             nothing appends nothing.  DMX_ERR_INVALID: a sealed set, no records (none counted, or the last
+ *                             count or push failed), records whose molecules do not count on from the set's.
+ *   dmx_calls_seal            waits for the stream; from then on the set is read-only.
+ *   dmx_calls_concatenate     CompressedSNPCalls.concatenate on the device: a new sealed set, the parts (sealed sets of this
+ *                             context) in list order, every part's molecule_index shifted by the molecules before it.
+ *                             DMX_ERR_UNSUPPORTED: 2^31 molecules or more in all.
+ *   dmx_calls_view            device pointers and sizes of a sealed set (chrom 0), as dmx_stage_device_containers and
+ *                             dmx_snp_count_device take them; valid until the set is released.
+ *   dmx_calls_info            info[4] = n_molecules, n_snp_calls, device bytes held, sealed (0 / 1).
+ *   dmx_calls_fetch           copies the records of a sealed set to the host.
+ *   dmx_calls_release         frees one set.
+ *   dmx_calls_barcode_counts  the counters of the reference's summarize_counted_SNPs (utils.py:163-180): molecules per
+ *                             compressed_cb, and calls per compressed_cb of their molecule, int64[n_barcodes] each (integer
+ *                             atomics).  DMX_ERR_INVALID: a compressed_cb outside [0, n_barcodes).
+ *   dmx_stage_device_containers  dmx_stage_containers with DEVICE pointers (views): no upload, the same field extraction, the
+ *                             same check and message; dmx_pack_staged_and_set_problem follows unchanged.  A set may belong to
+ *                             another context of the same device (a sealed set's stream has been waited for).  Every pointer must
+ *                             be device memory of the context's device and the records must lie inside its allocation
+ *                             (hipPointerGetAttributes), else DMX_ERR_INVALID.  The stream is drained before it returns, so the
+ *                             owner may release the set afterwards.
+ *   dmx_snp_count_device      dmx_snp_count with device views, under the same rules.
+ *   dmx_get_calls_transfer_bytes  bytes[2] = cumulative bytes of call records this context copied host to device (dmx_stage_containers,
+ *                             dmx_pack_containers_and_set_problem, dmx_snp_count, dmx_calls_upload) and device to host
+ *                             (dmx_count_reads_fetch, dmx_calls_fetch).  The resident entry points add nothing.
+ * ------------------------------------------------------------------------- */
+int dmx_calls_upload(dmx_ctx *ctx, const dmx_call_container *host, int64_t *handle);
+int dmx_calls_open(dmx_ctx *ctx, int64_t *handle);
+int dmx_calls_append_counted(dmx_ctx *ctx, int64_t handle);
+int dmx_calls_seal(dmx_ctx *ctx, int64_t handle);
+int dmx_calls_concatenate(dmx_ctx *ctx, const int64_t *handles, int32_t n_handles, int64_t *handle);
+int dmx_calls_view(dmx_ctx *ctx, int64_t handle, dmx_call_container *view);
+int dmx_calls_info(dmx_ctx *ctx, int64_t handle, int64_t *info);
+int dmx_calls_fetch(dmx_ctx *ctx, int64_t handle, void *molecules_out, void *snp_calls_out);
+int dmx_calls_release(dmx_ctx *ctx, int64_t handle);
+int dmx_calls_barcode_counts(dmx_ctx *ctx, int64_t handle, int64_t n_barcodes, int64_t *calls_per_barcode, int64_t *molecules_per_barcode);
+int dmx_stage_device_containers(dmx_ctx *ctx, const dmx_call_container *views, int32_t n_views);
+int dmx_snp_count_device(dmx_ctx *ctx, const dmx_call_container *views, int32_t n_views, const int32_t *donor_of_barcode,
+                         int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions);
+int dmx_get_calls_transfer_bytes(dmx_ctx *ctx, int64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif
