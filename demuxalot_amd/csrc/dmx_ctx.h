@@ -196,7 +196,7 @@ struct dmx_ctx {
     int msteps_ahead = 0;           // M-steps the running dmx_em / dmx_run_iterations call still has to do (0 outside)
     long long msteps_expected = 0;  // dmx_set_msteps_expected: M-steps the caller says it will still run (counted down as they run)
     double mt_build_ms = 0.0;       // host wall time of the last build of the tile-major records
-    int mstep_form = 0;             // form of the last M-step launch: 0 none, 1 work items, 2 tiles (dmx_get_mstep_form)
+    int mstep_form = 0;             // form of the last M-step launch: 0 none, 1 work items, 2 tiles, 3 fixed-point work items (dmx_get_mstep_form; mstep_plan.h)
     DevBuf<int> d_sum_plan;  // np.sum over a row of K values as a leaf / level plan (dmx_api.cpp: ensure_options)
     long long sum_plan_k = -1;
     int sum_plan_values = 0;    // leaves + inner nodes

@@ -20,6 +20,7 @@
 
 #include "dmx_ctx.h"
 #include "dmx_host.h"
+#include "mstep_plan.h"
 
 using namespace dmx::host;
 
@@ -568,6 +569,48 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
     return 0;
 }
 
+// the incremental M-step's device state over incr_rows barcode rows: allocated at first use, reset when there is nothing to build on
+static int ensure_incremental_state(dmx_ctx *c, bool sharded, long long incr_rows, float power)
+{
+    if (!c->d_acc64.p) {
+        c->incr_rows = incr_rows;
+        DMX_TRY(dev_alloc(c, c->d_acc64, (size_t)c->V * c->G));
+        DMX_TRY(dev_alloc(c, c->d_prev_post, (size_t)incr_rows * c->G));
+        DMX_TRY(dev_alloc(c, c->d_prev_first, (size_t)incr_rows));
+        DMX_TRY(dev_alloc(c, c->d_incr_list, (size_t)incr_rows));
+        if (sharded) {
+            DMX_TRY(dmx::build_slice_row_index(c));  // (the slice's records by barcode row; without it: the masked walk and its byte map)
+            if (c->d_slice_rec.p == nullptr) {
+                DMX_TRY(dev_alloc(c, c->d_incr_map, (size_t)incr_rows));
+                HIP_TRY(hipMemsetAsync(c->d_incr_map.p, 0, (size_t)incr_rows, c->stream));
+            }
+        }
+        DMX_TRY(dev_alloc(c, c->d_incr_touched, (size_t)c->V));
+        DMX_TRY(dev_alloc(c, c->d_incr_state, (size_t)(3 * dmx::IS_WORDS)));  // two alternating sets + the counters
+        HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 3 * dmx::IS_WORDS, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_incr_touched.p, 0, (size_t)c->V, c->stream));
+        c->incr_valid = false;
+    }
+    if (!c->incr_valid || c->incr_power != power) {  // (nothing to build on: zeroed state words ask for the full pass)
+        HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 2 * dmx::IS_WORDS, c->stream));
+        if (c->mstep_incremental == 2 && !c->attached()) {  // (measurement: the sums built from nothing by the delta pass instead of the full pass)
+            const unsigned on[2] = {1u, 1u};
+            HIP_TRY(hipMemsetAsync(c->d_acc64.p, 0, sizeof(unsigned long long) * (size_t)c->V * c->G, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_prev_post.p, 0, sizeof(float) * (size_t)incr_rows * c->G, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_prev_first.p, 0xFF, sizeof(uint2) * (size_t)incr_rows, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (size_t)c->V * c->G, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_incr_state.p + dmx::IS_VALID, &on[0], sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_incr_state.p + dmx::IS_FORCE, &on[1], sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        c->incr_parity = 0;
+        c->incr_valid = true;
+        c->incr_power = power;
+    }
+    return 0;
+}
+
+// Every decision is mstep_plan.h's (the table: DESIGN.md 2.7); this is the sequence: gather, probe, plan, build, state, arguments, launch, combine.
 int run_mstep(dmx_ctx *c, float power)
 {
     const bool mshard = c->mshard;
@@ -605,137 +648,76 @@ int run_mstep(dmx_ctx *c, float power)
     c->add_is_zero = false;
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
-    const bool dist = c->attached();  // also with one rank: keeps the collective path testable on one GPU
-    unsigned long long *redo = c->exact_additions ? c->d_redo.p : nullptr;
-    a.item_variant = nullptr;
-    a.item_ptr = c->d_item_ptr.p;
-    a.prow = nullptr;
-    a.out32 = nullptr;
-    a.out64 = nullptr;
-    const bool f64 = c->reduce_dtype == DMX_F64;
-    // where k_mcombine writes: the variants of one work item are written there by the M-step kernels themselves
-    a.item_variant = c->d_item_variant.p;
-    a.redo_cap = c->d_redo.n;
-    a.fixed_shift_v = nullptr;
-    a.fixed_acc64 = nullptr;
-    a.fixed_state = nullptr;
-    a.incr_total = 0ull;
-    // tile-major form (kernels.h: MTileArgs): sums in any order, so not with the exact additions; built on first use
-    a.tiles_done = false;
-    dmx::MTileArgs tiles{};
-    // Building the records (a sort of the calls: 2.6 ms on 200k x 100k x 64, where an M-step + combine then takes 0.34 instead of
-    // 0.70 ms) pays from MSTEP_TILES_PAY M-steps on: taken when that many are still to come - in the running dmx_em /
-    // dmx_run_iterations call, or as the caller announced (dmx_set_msteps_expected) -, or the problem has seen that many
-    // already (somebody iterates call by call), or always (dmx_set_mstep_tiles(ctx, 2)).
-    // Under the INCREMENTAL M-step only the full passes cost anything, and since round 6 the work items can make them with the tile
-    // form's arithmetic (fixed_items below: 0.71 instead of 0.33 ms, no records): the records then pay only where full passes keep
-    // coming - a workload whose posteriors keep moving.  So a context that can go incremental starts on the work items and reads the
-    // device's count of full passes ONCE at its 4th, 16th and 64th M-step (a 4-byte download: the only host synchronisation of the
-    // policy); three full passes in the first four M-steps, or half of them later, and the records are built as before.  A converging
-    // 25-iteration call: M-steps 0.71 + 23 x 0.03 ms instead of 2.6 (build) + 0.33 + 23 x 0.03.
-    constexpr int MSTEP_TILES_PAY = 8;
-    const long long ahead = std::max<long long>(c->msteps_ahead, c->msteps_expected);
-    // (a rank that exchanges SUMS - reduce-scatter of the partial sums of its own barcodes - is one context with all calls of its barcodes
-    // too: its partial sums stay in the exchange buffer between two M-steps, the delta pass updates the rows it touched.  Not the all-reduce,
-    // which sums in place.)
-    const bool own_sums = !mshard && (!dist || c->sliced);
-    const bool can_go_incremental = c->mstep_incremental && c->mstep_tiles == 1 && !c->exact_additions && c->G <= 64 && c->n_csc > 0 && power > 0.0f &&
-                                    own_sums && c->d_call_pairs.p != nullptr && c->d_item_variant.p != nullptr;
-    if (can_go_incremental && !c->incr_heavy && c->n_mt == 0 && c->d_incr_state.p != nullptr &&
-        (c->msteps_done == 4 || c->msteps_done == 16 || c->msteps_done == 64)) {
+    mplan::Facts f{};
+    f.mstep_tiles = c->mstep_tiles;
+    f.mstep_incremental = c->mstep_incremental;
+    f.exact_additions = c->exact_additions;
+    f.G = c->G;
+    f.has_calls = c->n_csc > 0;
+    f.power = power;
+    f.attached = c->attached();  // also with one rank: keeps the collective path testable on one GPU
+    f.mshard = c->mshard;
+    f.sliced = c->sliced;
+    f.reduce_f64 = c->reduce_dtype == DMX_F64;
+    f.has_call_pairs = c->d_call_pairs.p != nullptr;
+    f.has_item_variant = c->d_item_variant.p != nullptr;
+    f.has_shift_v = c->d_mt_shift_v.p != nullptr;
+    f.has_incr_state = c->d_incr_state.p != nullptr;
+    f.has_slice_rec = c->d_slice_rec.p != nullptr;
+    f.n_mt = c->n_mt;
+    f.mt_tried = c->mt_tried;
+    f.msteps_done = c->msteps_done;
+    f.msteps_ahead = c->msteps_ahead;
+    f.msteps_expected = c->msteps_expected;
+    f.incr_heavy = c->incr_heavy;
+    f.rows_total = c->rows_total;
+    if (mplan::probe_due(f)) {
         unsigned full_passes = 0;
         HIP_TRY(hipMemcpyAsync(&full_passes, c->d_incr_state.p + 2 * dmx::IS_WORDS + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->incr_heavy = c->msteps_done == 4 ? full_passes >= 3u : 2ull * full_passes >= (unsigned long long)c->msteps_done;
+        f.incr_heavy = c->incr_heavy = mplan::heavy_after_probe(f, full_passes);
     }
-    const bool tiles_wanted = c->mstep_tiles == 2 || (c->mstep_tiles == 1 && (c->n_mt > 0 || ((ahead >= MSTEP_TILES_PAY || c->msteps_done >= MSTEP_TILES_PAY) &&
-                                                                                            (!can_go_incremental || c->incr_heavy))));
-    if (c->msteps_expected > 0) c->msteps_expected--;
+    if (c->msteps_expected > 0) c->msteps_expected--;  // (the plan reads the counters as they stood: f)
     c->msteps_done++;
-    if (!c->exact_additions && tiles_wanted && c->G <= 64 && c->n_csc > 0 && power > 0.0f) {  // (power > 0: contributions in [0, 1])
-        if (!c->mt_tried) {
-            HIP_TRY(hipStreamSynchronize(c->stream));  // (the build synchronises anyway; this makes its wall time its own)
-            const auto t0 = std::chrono::steady_clock::now();
-            DMX_TRY(dmx::build_mstep_tiles(c, mshard ? c->cut[c->rank] : 0, mshard ? c->cut[c->rank + 1] : c->V));
-            c->mt_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        if (c->n_mt > 0) {
-            tiles.stream = c->d_mt_stream.p;
-            tiles.ptr = c->d_mt_ptr.p;
-            tiles.first = c->d_mt_first.p;
-            tiles.order = c->d_mt_order.p;
-            tiles.shift = c->d_mt_shift.p;
-            tiles.n_tiles = c->n_mt;
-            tiles.tv = c->mt_tv;
-            a.tiles_done = true;
-        }
+    const mplan::Range own = mplan::variant_range(f, c->cut.data(), c->rank, c->V);
+    if (mplan::build_due(f)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (the build synchronises anyway; this makes its wall time its own)
+        const auto t0 = std::chrono::steady_clock::now();
+        DMX_TRY(dmx::build_mstep_tiles(c, own.v0, own.v1));
+        c->mt_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        f.n_mt = c->n_mt;
     }
-    if (!dist || mshard) {
-        a.out32 = c->d_add.p;
-    } else if (c->sliced) {
-        a.prow = c->d_prow.p;
-        if (f64) a.out64 = (double *)c->d_exch.p;
-        else a.out32 = (float *)c->d_exch.p;
-    } else {
-        if (f64) a.out64 = c->d_add64.p;
-        else a.out32 = c->d_add.p;
+    if (mplan::shifts_wanted(f)) DMX_TRY(dmx::plan_mstep_shifts(c));
+    f.has_shift_v = c->d_mt_shift_v.p != nullptr;
+    const mplan::Launch plan = mplan::launch(f);
+    const mplan::Dest dest = mplan::destination(f);
+    const bool incremental = plan.incr != mplan::INCR_NONE, sharded = plan.incr == mplan::INCR_SHARDED;
+    const long long incr_rows = sharded ? c->rows_total : c->B;
+    if (incremental) DMX_TRY(ensure_incremental_state(c, sharded, incr_rows, power));
+    else c->incr_valid = false;  // (another form writes the addition: the kept sums no longer describe it)
+    f.has_slice_rec = c->d_slice_rec.p != nullptr;
+    const bool by_rows = sharded && mplan::sharded_by_row_index(f);
+    // where k_mcombine writes: the variants of one work item are written there by the M-step kernels themselves
+    a.item_variant = c->d_item_variant.p;
+    a.item_ptr = c->d_item_ptr.p;
+    a.prow = dest.exchange_buffer ? c->d_prow.p : nullptr;
+    a.out32 = dest.f64 ? nullptr : dest.exchange_buffer ? (float *)c->d_exch.p : c->d_add.p;
+    a.out64 = !dest.f64 ? nullptr : dest.exchange_buffer ? (double *)c->d_exch.p : c->d_add64.p;
+    a.redo_cap = c->d_redo.n;
+    a.tiles_done = plan.form == 2;
+    a.incr_total = !sharded ? 0ull : by_rows ? (unsigned long long)c->n_csc : 2ull * (unsigned long long)incr_rows;
+    dmx::MTileArgs tiles{};
+    if (a.tiles_done) {
+        tiles.stream = c->d_mt_stream.p;
+        tiles.ptr = c->d_mt_ptr.p;
+        tiles.first = c->d_mt_first.p;
+        tiles.order = c->d_mt_order.p;
+        tiles.shift = c->d_mt_shift.p;
+        tiles.n_tiles = c->n_mt;
+        tiles.tv = c->mt_tv;
     }
-    // Fixed-point WORK-ITEM form (kernels.h: MstepArgs::fixed_shift_v): where the tile-major records are not there - a call too short
-    // to pay for their sort, learn_genotypes' default of 5 iterations among them - the work items add the tile-major form's integers
-    // with the tile cut's exponents (plan_mstep_shifts: the host's cut, no sort), so that their sums are the tile-major form's bit for
-    // bit and the incremental M-step builds on them: one full pass of 0.7 ms, then delta passes, instead of 0.7 ms per M-step.
-    // (dmx_set_mstep_tiles(ctx, 0) or dmx_set_mstep_incremental(ctx, 0): the float64 work-item form, as before.)
-    bool fixed_items = !a.tiles_done && c->mstep_tiles != 0 && c->mstep_incremental && !c->exact_additions && c->G <= 64 && c->n_csc > 0 &&
-                       power > 0.0f && own_sums && c->d_call_pairs.p != nullptr && c->d_item_variant.p != nullptr;
-    if (fixed_items) {
-        DMX_TRY(dmx::plan_mstep_shifts(c));
-        fixed_items = c->d_mt_shift_v.p != nullptr;
-    }
-    // Incremental form (kernels.h: MIncrArgs): one context with all calls of its barcodes, the tiles' per-variant exponents at hand.
-    // ... or a variant-sharded rank with the tile-major records of its slice (round 6): the same sums over the barcodes of ALL ranks, the
-    // changed barcodes found in the gathered tables, the delta pass a masked walk of the slice's variant-major records (MIncrArgs::changed_map).
-    const bool sharded_incr = a.tiles_done && c->mstep_incremental == 1 && mshard && c->d_mt_shift_v.p != nullptr && a.out32 == c->d_add.p && c->G <= 64 &&
-                              c->d_item_variant.p != nullptr && c->rows_total > 0;
-    const bool incremental = sharded_incr || ((a.tiles_done || fixed_items) && c->mstep_incremental && own_sums && c->d_mt_shift_v.p != nullptr &&
-                                              c->d_call_pairs.p != nullptr);
-    const long long incr_rows = sharded_incr ? c->rows_total : c->B;
     dmx::MIncrArgs incr{};
     if (incremental) {
-        if (!c->d_acc64.p) {
-            c->incr_rows = incr_rows;
-            DMX_TRY(dev_alloc(c, c->d_acc64, (size_t)c->V * c->G));
-            DMX_TRY(dev_alloc(c, c->d_prev_post, (size_t)incr_rows * c->G));
-            DMX_TRY(dev_alloc(c, c->d_prev_first, (size_t)incr_rows));
-            DMX_TRY(dev_alloc(c, c->d_incr_list, (size_t)incr_rows));
-            if (sharded_incr) {
-                DMX_TRY(dmx::build_slice_row_index(c));  // (the slice's records by barcode row; without it: the masked walk and its byte map)
-                if (c->d_slice_rec.p == nullptr) {
-                    DMX_TRY(dev_alloc(c, c->d_incr_map, (size_t)incr_rows));
-                    HIP_TRY(hipMemsetAsync(c->d_incr_map.p, 0, (size_t)incr_rows, c->stream));
-                }
-            }
-            DMX_TRY(dev_alloc(c, c->d_incr_touched, (size_t)c->V));
-            DMX_TRY(dev_alloc(c, c->d_incr_state, (size_t)(3 * dmx::IS_WORDS)));  // two alternating sets + the counters
-            HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 3 * dmx::IS_WORDS, c->stream));
-            HIP_TRY(hipMemsetAsync(c->d_incr_touched.p, 0, (size_t)c->V, c->stream));
-            c->incr_valid = false;
-        }
-        if (!c->incr_valid || c->incr_power != power) {  // (nothing to build on: zeroed state words ask for the full pass)
-            HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 2 * dmx::IS_WORDS, c->stream));
-            if (c->mstep_incremental == 2 && !dist) {  // (measurement: the sums built from nothing by the delta pass instead of the full pass)
-                const unsigned on[2] = {1u, 1u};
-                HIP_TRY(hipMemsetAsync(c->d_acc64.p, 0, sizeof(unsigned long long) * (size_t)c->V * c->G, c->stream));
-                HIP_TRY(hipMemsetAsync(c->d_prev_post.p, 0, sizeof(float) * (size_t)incr_rows * c->G, c->stream));
-                HIP_TRY(hipMemsetAsync(c->d_prev_first.p, 0xFF, sizeof(uint2) * (size_t)incr_rows, c->stream));
-                HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (size_t)c->V * c->G, c->stream));
-                HIP_TRY(hipMemcpyAsync(c->d_incr_state.p + dmx::IS_VALID, &on[0], sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpyAsync(c->d_incr_state.p + dmx::IS_FORCE, &on[1], sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            }
-            c->incr_parity = 0;
-            c->incr_valid = true;
-            c->incr_power = power;
-        }
         incr.state = c->d_incr_state.p + c->incr_parity * dmx::IS_WORDS;
         incr.next = c->d_incr_state.p + (c->incr_parity ^ 1) * dmx::IS_WORDS;
         c->incr_parity ^= 1;
@@ -746,82 +728,46 @@ int run_mstep(dmx_ctx *c, float power)
         incr.list = c->d_incr_list.p;
         incr.touched = c->d_incr_touched.p;
         incr.shift_v = c->d_mt_shift_v.p;
-        incr.pairs = sharded_incr ? nullptr : c->d_call_pairs.p;
-        incr.call_rows = sharded_incr ? nullptr : c->d_call_rows.p;
-        incr.pair_ptr = sharded_incr ? nullptr : c->d_pair_ptr.p;
-        incr.changed_map = sharded_incr ? c->d_incr_map.p : nullptr;  // (null with the row index)
-        incr.rec = sharded_incr ? c->d_slice_rec.p : nullptr;
-        incr.rec_ptr = sharded_incr && c->d_slice_rec.p != nullptr ? c->d_slice_ptr.p : nullptr;
-        incr.row_variant = !sharded_incr && c->sliced ? c->d_row_variant.p : nullptr;
+        incr.pairs = sharded ? nullptr : c->d_call_pairs.p;
+        incr.call_rows = sharded ? nullptr : c->d_call_rows.p;
+        incr.pair_ptr = sharded ? nullptr : c->d_pair_ptr.p;
+        incr.changed_map = sharded ? c->d_incr_map.p : nullptr;  // (null with the row index)
+        incr.rec = sharded ? c->d_slice_rec.p : nullptr;
+        incr.rec_ptr = by_rows ? c->d_slice_ptr.p : nullptr;
+        incr.row_variant = plan.row_variant ? c->d_row_variant.p : nullptr;
         incr.B = incr_rows;
         incr.V = c->V;
         incr.floor = dmx::mincr_floor(power);
-        a.incr_total = !sharded_incr ? 0ull : incr.rec_ptr != nullptr ? (unsigned long long)c->n_csc : 2ull * (unsigned long long)incr_rows;
         tiles.acc64 = c->d_acc64.p;
         tiles.incr_state = incr.state;
-        if (fixed_items) {
-            a.fixed_shift_v = c->d_mt_shift_v.p;
-            a.fixed_acc64 = c->d_acc64.p;
-            a.fixed_state = incr.state;
-        }
         c->mstep_incr_launches++;
-    } else {
-        c->incr_valid = false;  // (another form writes the addition: the kept sums no longer describe it)
     }
+    const bool fixed = plan.incr == mplan::INCR_WORK_ITEMS;  // (their full pass adds the tile form's integers: MstepArgs::fixed_shift_v)
+    a.fixed_shift_v = fixed ? c->d_mt_shift_v.p : nullptr;
+    a.fixed_acc64 = fixed ? c->d_acc64.p : nullptr;
+    a.fixed_state = fixed ? incr.state : nullptr;
     timer_begin(c, DMX_T_MSTEP, &ev);
-    if (sharded_incr) HIP_TRY(dmx::launch_mstep_incremental_sharded(c->stream, a, tiles, incr));
-    else if (incremental && fixed_items) HIP_TRY(dmx::launch_mstep_items_incremental(c->stream, a, incr));
-    else if (incremental) HIP_TRY(dmx::launch_mstep_incremental(c->stream, a, tiles, incr));
-    else if (a.tiles_done) HIP_TRY(dmx::launch_mstep_tiles(c->stream, a, tiles));
-    else HIP_TRY(dmx::launch_mstep(c->stream, a));
-    c->mstep_form = a.tiles_done ? 2 : (incremental && fixed_items ? 3 : 1);
+    HIP_TRY(incremental ? dmx::launch_mstep_incremental(c->stream, a, a.tiles_done ? &tiles : nullptr, incr)
+            : a.tiles_done ? dmx::launch_mstep_tiles(c->stream, a, tiles) : dmx::launch_mstep(c->stream, a));
+    c->mstep_form = plan.form;
     timer_end(c, DMX_T_MSTEP, ev);
-    if (!dist) {
-        timer_begin(c, DMX_T_MCOMBINE, &ev);
-        HIP_TRY(dmx::launch_mcombine(c->stream, a, c->d_item_ptr.p, 0, c->V, nullptr, c->d_add.p, nullptr, redo, c->d_n_redo.p, nullptr, true));
-        timer_end(c, DMX_T_MCOMBINE, ev);
-        return 0;
-    }
-    if (mshard) {
-        // this rank's variant slice, summed over the barcodes of all ranks: final, exact, nothing to reduce
-        timer_begin(c, DMX_T_MCOMBINE, &ev);
-        HIP_TRY(dmx::launch_mcombine(c->stream, a, c->d_item_ptr.p, c->cut[c->rank], c->cut[c->rank + 1], nullptr, c->d_add.p, nullptr, redo,
-                                     c->d_n_redo.p, nullptr, true));
-        timer_end(c, DMX_T_MCOMBINE, ev);
-        c->add_partial = c->nranks > 1;
-        return 0;
-    }
-    int rc = 0;
-    if (c->sliced) {
-        // partial sums straight into the padded exchange buffer, reduce-scatter, this rank's slice rounded into d_add
-        timer_begin(c, DMX_T_MCOMBINE, &ev);
-        HIP_TRY(dmx::launch_mcombine(c->stream, a, c->d_item_ptr.p, 0, c->V, c->d_prow.p, f64 ? nullptr : (float *)c->d_exch.p,
-                                     f64 ? (double *)c->d_exch.p : nullptr, redo, c->d_n_redo.p, nullptr, true));
-        timer_end(c, DMX_T_MCOMBINE, ev);
-        timer_begin(c, DMX_T_ALLREDUCE, &ev);
-        const size_t block = (size_t)c->slice_rows * c->G;
-        rc = coll_reduce_scatter(c, c->d_exch.p, c->d_recv.p, block, f64, c->stream);
-        if (rc == 0)
-            HIP_TRY(dmx::launch_store_slice(c->stream, c->d_recv.p, f64, c->cut[c->rank], c->cut[c->rank + 1] - c->cut[c->rank], c->G, c->d_add.p));
-        timer_end(c, DMX_T_ALLREDUCE, ev);
-        if (rc) return rc;
-        c->add_partial = c->nranks > 1;
-        return 0;
-    }
-    // SNPs with scattered variants: all-reduce of the dense sums, P-step on every rank
+    // combine into the plan's destination, then the exchange it names
     timer_begin(c, DMX_T_MCOMBINE, &ev);
-    HIP_TRY(dmx::launch_mcombine(c->stream, a, c->d_item_ptr.p, 0, c->V, nullptr, f64 ? nullptr : c->d_add.p, f64 ? c->d_add64.p : nullptr, redo,
+    HIP_TRY(dmx::launch_mcombine(c->stream, a, c->d_item_ptr.p, own.v0, own.v1, a.prow, a.out32, a.out64, c->exact_additions ? c->d_redo.p : nullptr,
                                  c->d_n_redo.p, nullptr, true));
     timer_end(c, DMX_T_MCOMBINE, ev);
-    timer_begin(c, DMX_T_ALLREDUCE, &ev);
-    const size_t cnt = (size_t)c->V * c->G;
-    if (f64) {
-        rc = coll_all_reduce(c, c->d_add64.p, cnt, true);
-        if (rc == 0) HIP_TRY(dmx::launch_f64_to_f32(c->stream, c->d_add64.p, c->d_add.p, (long long)cnt));
-    } else {
-        rc = coll_all_reduce(c, c->d_add.p, cnt, false);
+    int rc = 0;
+    if (dest.then != mplan::EXCH_NONE) timer_begin(c, DMX_T_ALLREDUCE, &ev);
+    if (dest.then == mplan::EXCH_REDUCE_SCATTER) {  // this rank's slice of the summed exchange buffer, rounded into d_add
+        rc = coll_reduce_scatter(c, c->d_exch.p, c->d_recv.p, (size_t)c->slice_rows * c->G, dest.f64, c->stream);
+        if (rc == 0)
+            HIP_TRY(dmx::launch_store_slice(c->stream, c->d_recv.p, dest.f64, c->cut[c->rank], c->cut[c->rank + 1] - c->cut[c->rank], c->G, c->d_add.p));
+    } else if (dest.then == mplan::EXCH_ALL_REDUCE) {
+        rc = coll_all_reduce(c, dest.f64 ? (void *)c->d_add64.p : (void *)c->d_add.p, (size_t)c->V * c->G, dest.f64);
+        if (rc == 0 && dest.f64) HIP_TRY(dmx::launch_f64_to_f32(c->stream, c->d_add64.p, c->d_add.p, (long long)c->V * c->G));
     }
-    timer_end(c, DMX_T_ALLREDUCE, ev);
+    if (dest.then != mplan::EXCH_NONE) timer_end(c, DMX_T_ALLREDUCE, ev);
+    if (rc == 0 && dest.slice_only) c->add_partial = c->nranks > 1;
     return rc;
 }
 

@@ -400,11 +400,9 @@ enum { IS_N = 0,        // changed barcodes of this M-step
 // posteriors below this contribute exactly 0 on every tile's grid (shift <= 50): p^power 2^50 <= 2^-2 for p <= 2^(-52 / power) - 2^-26 for the
 // reference's power of 2; powers for which that is not a normal float32: 0 (every bit counts)
 inline float mincr_floor(float power) { return power * 126.0f > 52.0f ? exp2f(-52.0f / power) : 0.0f; }
-hipError_t launch_mstep_incremental(hipStream_t st, const MstepArgs &a, const MTileArgs &t, const MIncrArgs &x);
-// the same with the fixed-point work-item form as the full pass (MstepArgs::fixed_shift_v): no tile-major records needed
-hipError_t launch_mstep_items_incremental(hipStream_t st, const MstepArgs &a, const MIncrArgs &x);
-// ... of a variant-sharded rank: changes over the gathered tables -> masked walk of the slice's records | the tile-major full pass -> finish
-hipError_t launch_mstep_incremental_sharded(hipStream_t st, const MstepArgs &a, const MTileArgs &t, const MIncrArgs &x);
+// t: the tile-major records of the full pass, or null: the fixed-point work-item form (MstepArgs::fixed_shift_v) is the full pass.  The delta
+// pass follows from x: rec_ptr / changed_map of a variant-sharded rank, else the context's own records
+hipError_t launch_mstep_incremental(hipStream_t st, const MstepArgs &a, const MTileArgs *t, const MIncrArgs &x);
 constexpr int MTILE_LDS_BYTES = 64 * 1024;  // accumulators of a tile: with the 12 KB of dense-call queues, two workgroups of 1024 threads per CU
 constexpr int MTILE_MAX_VARIANTS = 128;     // 7 bits of the record
 hipError_t launch_mstep_tiles(hipStream_t st, const MstepArgs &a, const MTileArgs &t);

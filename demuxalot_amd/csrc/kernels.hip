@@ -3425,54 +3425,30 @@ hipError_t launch_mstep(hipStream_t st, const MstepArgs &a)
     return hipGetLastError();
 }
 
-// changes -> delta pass | full pass (exactly one of them works) -> conversion / snapshot; the dense regime's kernel as in launch_mstep_tiles
-hipError_t launch_mstep_incremental(hipStream_t st, const MstepArgs &a, const MTileArgs &t, const MIncrArgs &x)
+// changes -> delta pass | full pass (exactly one of them works; behind the work items' full pass k_mcombine, launched by the caller, stands back
+// with it) -> conversion / snapshot; which delta pass and which full pass: kernels.h.  The refusals: nothing dmx_steps.cpp: run_mstep can ask for.
+hipError_t launch_mstep_incremental(hipStream_t st, const MstepArgs &a, const MTileArgs *t, const MIncrArgs &x)
 {
-    if (t.n_tiles == 0 || x.B == 0) return hipSuccess;
+    // (one context's records on tiles, nothing to do - the former launch_mstep_incremental: success)
+    if (t != nullptr && x.pairs != nullptr && (t->n_tiles == 0 || x.B == 0)) return hipSuccess;
+    // (no rows; no tiles - the former launch_mstep_incremental_sharded; no work items or no exponents - launch_mstep_items_incremental)
+    if (x.B == 0 || (t != nullptr ? t->n_tiles == 0 : a.n_items == 0 || a.fixed_shift_v == nullptr)) return hipErrorInvalidValue;
+    // (no records for the delta pass to walk: neither the context's own nor a sharded rank's row index or byte map - ..._sharded)
+    if (x.pairs == nullptr && x.changed_map == nullptr && x.rec_ptr == nullptr) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mincr_changes, dim3(blocks_for(x.B, 64)), dim3(256), 0, st, a, x);
-    if (a.square)
-        hipLaunchKernelGGL((k_mincr_delta<true>), dim3(4096), dim3(256), 0, st, a, x);
-    else
-        hipLaunchKernelGGL((k_mincr_delta<false>), dim3(4096), dim3(256), 0, st, a, x);
-    const hipError_t e = launch_mstep_tiles(st, a, t);  // (stands back unless the full pass is due; + the dense regime's kernel)
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mincr_finish, dim3(2048), dim3(256), 0, st, a, x);
-    return hipGetLastError();
-}
-
-// the same sequence with the fixed-point work-item form as the full pass (no tile-major records): changes -> delta pass | the items'
-// full pass (exactly one of them works; k_mcombine, launched by the caller behind this, stands back with it) -> conversion / snapshot
-hipError_t launch_mstep_items_incremental(hipStream_t st, const MstepArgs &a, const MIncrArgs &x)
-{
-    if (a.n_items == 0 || x.B == 0 || a.fixed_shift_v == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mincr_changes, dim3(blocks_for(x.B, 64)), dim3(256), 0, st, a, x);
-    if (a.square)
-        hipLaunchKernelGGL((k_mincr_delta<true>), dim3(4096), dim3(256), 0, st, a, x);
-    else
-        hipLaunchKernelGGL((k_mincr_delta<false>), dim3(4096), dim3(256), 0, st, a, x);
-    const hipError_t e = launch_mstep(st, a);  // (stands back unless the full pass is due; + the dense regime's kernel)
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mincr_finish, dim3(2048), dim3(256), 0, st, a, x);
-    return hipGetLastError();
-}
-
-hipError_t launch_mstep_incremental_sharded(hipStream_t st, const MstepArgs &a, const MTileArgs &t, const MIncrArgs &x)
-{
-    if (t.n_tiles == 0 || x.B == 0 || (x.changed_map == nullptr && x.rec_ptr == nullptr)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mincr_changes, dim3(blocks_for(x.B, 64)), dim3(256), 0, st, a, x);
-    const dim3 grid(std::min(blocks_for(a.n_items, 4), 8192u));
-    if (x.rec_ptr != nullptr) {  // the slice's records by barcode row: the changed barcodes' calls only
+    if (x.rec_ptr != nullptr || x.changed_map == nullptr) {
         if (a.square)
             hipLaunchKernelGGL((k_mincr_delta<true>), dim3(4096), dim3(256), 0, st, a, x);
         else
             hipLaunchKernelGGL((k_mincr_delta<false>), dim3(4096), dim3(256), 0, st, a, x);
     } else if (a.n_items) {
+        const dim3 grid(std::min(blocks_for(a.n_items, 4), 8192u));
         if (a.square)
             hipLaunchKernelGGL((k_mincr_delta_masked<true>), grid, dim3(256), 0, st, a, x);
         else
             hipLaunchKernelGGL((k_mincr_delta_masked<false>), grid, dim3(256), 0, st, a, x);
     }
-    const hipError_t e = launch_mstep_tiles(st, a, t);  // (stands back unless the full pass is due; + the dense regime's kernel)
+    const hipError_t e = t != nullptr ? launch_mstep_tiles(st, a, *t) : launch_mstep(st, a);  // (stands back unless the full pass is due; + the dense regime's kernel)
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_mincr_finish, dim3(2048), dim3(256), 0, st, a, x);
     return hipGetLastError();
