@@ -60,7 +60,6 @@ int layout_exchange(dmx_ctx *c);
 int copy_prob_out(dmx_ctx *c, float *dst);
 int copy_prob_in(dmx_ctx *c, const float *src);
 int ensure_full_addition(dmx_ctx *c);
-bool coarse_capable(const dmx_ctx *c, int with_doublets, float lo);
 int ensure_prob16(dmx_ctx *c);
 int run_pstep(dmx_ctx *c, float lo, float hi, bool with_addition, bool with_half = false);
 int prepare_dictionary(dmx_ctx *c, bool pairs, dmx::EstepArgs &a, int *form);

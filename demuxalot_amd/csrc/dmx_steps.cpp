@@ -20,6 +20,7 @@
 
 #include "dmx_ctx.h"
 #include "dmx_host.h"
+#include "estep_plan.h"
 #include "mstep_plan.h"
 
 using namespace dmx::host;
@@ -176,15 +177,6 @@ int ensure_full_addition(dmx_ctx *c)
     return 0;
 }
 
-// Whether the E-step behind a P-step with clip `lo` can take the coarse pass (kernels.hip: k_estep_tiled_coarse) - what run_estep asks
-// again, of the table it finds.
-bool coarse_capable(const dmx_ctx *c, int with_doublets, float lo)
-{
-    // (its records are there, or can be built from the tile-major stream: dmx_set_lean_memory releases that one behind the build)
-    return c->coarse_pass && c->estep_mode == DMX_ESTEP_GUARDED && !with_doublets && c->K > 16 && c->K <= 128 && c->tiled_estep && c->n_bins > 0 &&
-           (c->coarse_ready || c->d_tile_stream.p != nullptr) && lo >= 6.2e-5f && ((unsigned long long)c->prob_rows + 1ull) * (unsigned long long)c->G * 4ull < (1ull << 32);
-}
-
 // the table as binary16 + the all-zero row the padding calls gather (EstepArgs::prob16)
 int ensure_prob16(dmx_ctx *c)
 {
@@ -276,30 +268,56 @@ int run_pstep(dmx_ctx *c, float lo, float hi, bool with_addition, bool with_half
     return 0;
 }
 
+namespace ep = dmx::eplan;
+static_assert(ep::MODE_EXACT == DMX_ESTEP_EXACT && ep::MODE_FAST == DMX_ESTEP_FAST && ep::MODE_GUARDED == DMX_ESTEP_GUARDED, "estep_plan.h: Mode");
+
+// what the E-step's decisions read (estep_plan.h), as the context stands
+static ep::Facts estep_facts(const dmx_ctx *c, int with_doublets, bool with_prior, bool logits_kept)
+{
+    ep::Facts f{};
+    f.mode = (ep::Mode)c->estep_mode;
+    f.with_doublets = with_doublets != 0;
+    f.with_prior = with_prior;
+    f.logits_kept = logits_kept;
+    f.G = c->G;
+    f.K = c->K;
+    f.B = c->B;
+    f.table_rows = c->prob_rows;
+    f.schedule = c->tiled_estep;
+    f.n_bins = c->n_bins;
+    f.tile_stream = c->d_tile_stream.p != nullptr;
+    f.coarse_ready = c->coarse_ready;
+    f.coarse_pass = c->coarse_pass;
+    f.guard_adaptive = c->guard_adaptive != 0;
+    f.lean_memory = c->lean_memory != 0;
+    f.lo = c->p_clip_lo;
+    f.prob16_valid = c->prob16_valid;
+    f.sliced = c->sliced;
+    f.table_lists = c->prob_list_words != 0;
+    f.dict_mode = c->dict_mode;
+    f.dict_candidate = c->dict_candidate;
+    f.call_rows = c->d_call_rows.p != nullptr;
+    f.records_below_4g = ((unsigned long long)c->n_pairs + dmx::CALL_PAD_PAIRS) * sizeof(dmx::CallPair) < (1ull << 32);
+    f.packing = c->estep_packing;
+    f.row_statistic = c->max_row_calls > 0;
+    for (int k = 0; k < 3; k++) f.n_long_rows[k] = c->n_long_rows[k];
+    f.segments = c->n_segs > 0;
+    f.n_pair_blocks = with_doublets && c->d_pair_blocks.p != nullptr ? c->n_pair_blocks : 0;
+    return f;
+}
+
 // Dictionary form of the E-step (estep_dict.hip): distinct values per row of the current genotype table.  Returns
 // the form to run in *form (DMX_FORM_DIRECT when some row does not fit or the form does not exist for the shape).
+// The allocations, the build and its one download; estep_plan.h says before whether to build and behind which form the result allows.
 int prepare_dictionary(dmx_ctx *c, bool pairs, dmx::EstepArgs &a, int *form)
 {
+    const ep::Facts f = estep_facts(c, pairs, false, true);  // (neither a prior nor who reads the logits matters to the dictionary)
     *form = DMX_FORM_DIRECT;
     a.dict_n = 0;
     c->dict_distinct = 0;
-    const bool wanted = c->dict_mode == 2 || (c->dict_mode == 1 && c->dict_candidate);
-    if (!wanted || c->estep_mode == DMX_ESTEP_FAST || c->B == 0 || c->prob_rows == 0) return 0;  // (guarded: exact and faster)
+    if (!ep::dictionary_admissible(f)) return 0;
     const int G = c->G;
     const long long K = c->K, rows = c->prob_rows;
-    const bool block_form = pairs && K > dmx::DICT_LANE_K;  // wide doublet tables: workgroup per barcode
-    if (a.call_rows == nullptr) return 0;  // (dmx_set_lean_memory: the form's row array was released)
-    if (!block_form && (K > dmx::DICT_LANE_K || rows >= (1 << 24) || a.pairs_bytes == 0)) return 0;  // singlet tables beyond 256: the direct forms; 24-bit row x pitch; 32-bit record offsets
-    if (block_form && (size_t)G * 72 + 9 * 1024 > 160 * 1024) return 0;  // the code rows of a chunk must fit the LDS
-    if (G > 1024) return 0;  // widest k_build_dict instantiation (ensure_options refuses such runs anyway)
-    if (c->dict_mode == 1 && !block_form) {
-        // Where the lane form pays (measured): singlet runs with enough barcodes for several rounds of
-        // wavefronts.  A launch of one round lasts as long as its longest barcode, whose calls this form walks in
-        // batches with a memory latency each (20k x 10k x 64: 0.31 ms against 0.25 ms direct), and the 16 entry slots of
-        // a doublet run leave two calls per barcode and batch (20k x 20k x 8 with doublets: 0.60 against 0.28 ms).
-        const long long lanes = K <= 16 ? 4 : K <= 32 ? 8 : K <= 64 ? 16 : K <= 128 ? 32 : 64;
-        if (pairs || c->B * lanes / 64 < 8192) return 0;
-    }
     const size_t code_pitch = (size_t)dmx::dict_code_pitch(G);
     DMX_TRY(dev_grow(c, c->d_dict, (size_t)rows * dmx::DICT_CAP));
     DMX_TRY(dev_grow(c, c->d_codes, (size_t)rows * code_pitch));
@@ -309,18 +327,22 @@ int prepare_dictionary(dmx_ctx *c, bool pairs, dmx::EstepArgs &a, int *form)
     HIP_TRY(hipMemcpyAsync(&distinct, c->d_dict_stat.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->dict_distinct = (int)distinct;
-    if (distinct == 0 || (int)distinct > (pairs ? dmx::DICT_PAIR_CAP : dmx::DICT_CAP)) return 0;
-    if (block_form) {
+    const size_t pitch = ep::dictionary_candidate_form(f, distinct) == ep::DICT_LANE ? (size_t)dmx::dict_table_pitch((int)distinct, (int)K, f.with_doublets) : 0;
+    switch (ep::dictionary_form(f, distinct, pitch)) {
+    case ep::DICT_NONE:
+        return 0;
+    case ep::DICT_BLOCK:
         a.dict_n = (int)distinct;
         a.dict = c->d_dict.p;
         a.codes = c->d_codes.p;
         *form = DMX_FORM_DICT_BLOCK;
         return 0;
+    case ep::DICT_LANE:
+        break;
     }
-    const size_t pitch = (size_t)dmx::dict_table_pitch((int)distinct, (int)K, pairs), need_bytes = (size_t)rows * pitch;
-    if (need_bytes >= (1ull << 32)) return 0;  // buffer addressing
+    const size_t need_bytes = (size_t)rows * pitch;
     DMX_TRY(dev_grow(c, c->d_dtab, need_bytes));
-    HIP_TRY(dmx::launch_pack_rows(c->stream, c->d_dict.p, c->d_codes.p, c->d_pairs.p, rows, G, (int)K, pairs, (int)distinct, c->d_dtab.p));
+    HIP_TRY(dmx::launch_pack_rows(c->stream, c->d_dict.p, c->d_codes.p, c->d_pairs.p, rows, G, (int)K, f.with_doublets, (int)distinct, c->d_dtab.p));
     a.dict_n = (int)distinct;
     a.dtab = c->d_dtab.p;
     a.dtab_pitch = (int)pitch;
@@ -329,11 +351,10 @@ int prepare_dictionary(dmx_ctx *c, bool pairs, dmx::EstepArgs &a, int *form)
     return 0;
 }
 
-// logits_kept: somebody can read this E-step's logits (it is the last one of the call); else the next E-step of the same call
-// overwrites them, and the guarded mode may take the coarse pass (kernels.hip: k_estep_tiled_coarse)
-int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, float power, bool logits_kept)
+// the argument block of the E-step's kernels as the context stands: no launch chosen yet (fast, segs, the guard's fields and what a
+// launch walks are run_estep's to set from the plan)
+static void fill_estep_args(dmx_ctx *c, dmx::EstepArgs &a, int with_doublets, bool with_prior, int prior_dtype, float power)
 {
-    dmx::EstepArgs a;
     a.pair_ptr = c->d_pair_ptr.p;
     a.order = c->d_bc_order.p;
     a.pairs = c->d_call_pairs.p;
@@ -361,25 +382,15 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
     a.nz = c->mshard ? c->d_nz_g.p + row_base * ((c->G + 63) / 64) : c->d_nz.p;
     a.first = c->G <= 64 ? (c->mshard ? c->d_first_g.p + row_base : c->d_first.p) : nullptr;
     a.post_singlets = c->mshard ? c->d_post_g.p + row_base * c->G : nullptr;
-    c->post_gathered = false;
     a.dense_calls = c->G <= 64 ? c->d_dense_calls.p : nullptr;
-    // (the slots are zero: set at the install, left so by k_sum_dense at the end of every E-step that used them)
-    c->dense_stat_valid = a.dense_calls != nullptr;
     a.nz_floor = power == 2.0f ? dmx::NZ_FLOOR_SQUARE : 0.0f;
-    c->nz_floor = a.nz_floor;
     a.B = c->B;
     a.prob_bytes = (unsigned)((unsigned long long)c->prob_rows * c->G * 4ull);
     a.G = c->G;
     a.K = c->K;
-    // Guarded mode: the tolerance-mode kernels wherever a lane-per-option one exists (estep_epilogue.h: estep_guard), the
-    // exact mode for the workgroup-per-barcode shapes
-    // (the workgroup-per-barcode forms - option tables beyond 1024, doublet tables beyond 256 - evaluate the guard in
-    // k_softmax_rows from the logits alone, which does not cover prior logits: with a prior they run the exact mode)
-    const bool block_shape = c->K > 1024 || (with_doublets && c->K > 256);
-    const bool guarded = c->estep_mode == DMX_ESTEP_GUARDED && !(block_shape && with_prior);
-    a.fast = c->estep_mode == DMX_ESTEP_FAST || guarded;
+    a.fast = 0;
     a.guard = 0;
-    a.guard_per_call = 7.0e-8f;  // estep_epilogue.h: GUARD_PER_CALL (launch_estep raises it for the form with pre-scaled rows)
+    a.guard_per_call = ep::GUARD_PER_CALL_PLAIN;  // estep_epilogue.h: GUARD_PER_CALL (launch_estep raises it for the form with pre-scaled rows)
     a.guard_count = c->d_guard_count.p;
     a.guard_list = c->d_guard_list.p;
     a.guard_sub = c->d_guard_sub.p;
@@ -387,14 +398,13 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
     a.order_count = nullptr;
     a.direct = nullptr;
     a.order_direct = nullptr;
-    a.segs = c->n_segs > 0 && c->K <= 1024 ? c->d_segs.p : nullptr;
+    a.segs = nullptr;
     a.n_segs = c->n_segs;
     a.n_split = c->n_split;
     a.split_first = c->d_split_first.p;
     a.seg_sums = c->d_seg_sums.p;
-    c->guard_ran = false;
     a.tiled = c->tiled_estep;
-    a.n_bins = c->tiled_estep ? c->n_bins : 0;
+    a.n_bins = 0;
     a.bin_rows_cap = c->bin_rows_cap;
     a.bin_order = c->d_bin_order.p;
     a.bin_rows = c->d_bin_rows.p;
@@ -410,154 +420,144 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
     a.dtab_pitch = 0;
     a.dict = nullptr;
     a.codes = nullptr;
-    if (c->lean_memory && with_doublets && c->d_tile_stream.p != nullptr && !c->coarse_ready) {
-        // (dmx_set_lean_memory: the tile-major schedule is the singlet runs'; a run with doublets never reads its stream - 6.4 GB of configs[4])
+}
+
+// what a launch walks and whether it is the coarse level's, handed to the kernels as the arrays themselves (estep_plan.h: handover;
+// kernels.hip: launch_estep reads it back through request_of)
+static void set_walk(const dmx_ctx *c, dmx::EstepArgs &a, ep::Walk walk, bool coarse = false)
+{
+    const ep::Handover h = ep::handover(walk, coarse);
+    a.tile_stream = c->d_tile_stream.p;
+    if (!h.bins) a.n_bins = 0;
+    if (h.coarse_records) {
+        a.coarse_stream = c->d_coarse_stream.p;
+        a.coarse_bin_ptr = c->d_coarse_bin_ptr.p;
+        a.log2_keep = c->d_log2_keep.p;
+    }
+    if (h.prob16) a.prob16 = c->d_prob16.p;
+}
+
+// The guarded step: fast kernels with the guard evaluated per barcode, then the exact kernel over the barcodes they queued (their
+// number is only known on the device: a launch sized for all of them, the wavefronts past the queue's end
+// return at once); the redo rewrites logits, posteriors, bitmaps and codes of those barcodes.  Adaptive
+// (kernels.hip: k_guard_begin): the passes are timed on the device, and an E-step for which pass + redo would cost
+// more than the exact kernel over every barcode runs that kernel directly - the fast kernels stand back.
+// What is built, released and converted, and what the fine level walks: estep_plan.h, "the guarded step".
+static int guarded_estep(dmx_ctx *c, ep::Facts &f, dmx::EstepArgs &a)
+{
+    const bool capable = ep::coarse_capable(f, f.lo), allow_coarse = ep::allow_coarse(f), release = ep::lean_release_due(f);
+    // (the coarse guard's estimate of the fine level reads the fine level's allowance too: priced for the walk this E-step found, which is
+    // not the one it leaves behind when the release comes with it)
+    const float fine_allowance_found = ep::fine_allowance(f, ep::walk(f));
+    if (ep::coarse_build_due(f)) {
+        // ahead of k_guard_begin's time stamp (not part of the pass the device times)
+        const int cpg = ep::coarse_calls_per_gather(f.K), bpr = ep::coarse_batches_per_record(cpg);
+        const size_t words = (((size_t)c->n_pairs / 4 + (size_t)c->n_bins * (bpr - 1)) / bpr + 1) * (size_t)(cpg * 16);
+        DMX_TRY(dev_alloc(c, c->d_coarse_stream, words));
+        DMX_TRY(dev_alloc(c, c->d_coarse_bin_ptr, (size_t)c->n_bins + 1));
+        DMX_TRY(dev_alloc(c, c->d_log2_keep, (size_t)c->B));
+        // (the barcodes' sums of log2 keep come out of the same pass: every call's keep factor is read there once)
+        HIP_TRY(dmx::launch_build_coarse_stream(c->stream, c->d_tile_stream.p, c->d_bin_ptr.p, c->n_bins, a.prob_bytes, cpg, c->d_coarse_bin_ptr.p, c->d_coarse_stream.p,
+                                                c->d_bin_rows.p, c->bin_rows_cap, c->d_log2_keep.p));
+        c->coarse_ready = f.coarse_ready = true;
+        if (release) {  // (the blocks return to the context's cache behind the build, stream-ordered; the incremental M-step reads the rows from the records)
+            dev_free(c, c->d_tile_stream);
+            dev_free(c, c->d_call_rows);
+            a.tile_stream = nullptr;
+            a.call_rows = nullptr;
+            f.tile_stream = f.call_rows = false;
+        }
+    }
+    if (allow_coarse) DMX_TRY(ensure_prob16(c));
+    HIP_TRY(dmx::launch_guard_begin(c->stream, c->d_guard_count.p, c->B, c->K, c->guard_adaptive, capable, allow_coarse));
+    a.guard = 1;
+    a.guard_per_call = fine_allowance_found;
+    a.order_direct = c->d_bc_order.p;
+    a.guard_main_coarse = 0;
+    a.guard_alt_per_call = capable ? dmx::GUARD_PER_CALL_COARSE : 0.0f;
+    a.guard_alt_accum = capable ? dmx::GUARD_ACCUM_F32 : 0.0f;
+    if (allow_coarse) {
+        if (ep::prob16_conversion_due(f)) {
+            const bool kept = ep::prob16_stays_valid(f);
+            HIP_TRY(dmx::launch_prob_to_half(c->stream, c->d_prob.p, c->prob_rows, c->G, c->d_prob16.p, kept ? nullptr : c->d_guard_count.p + dmx::GS_SKIP_COARSE));
+            c->prob16_valid = kept;
+        }
+        dmx::EstepArgs coarse = a;
+        set_walk(c, coarse, ep::WALK_COARSE_RECORDS, true);
+        coarse.guard_per_call = dmx::GUARD_PER_CALL_COARSE;
+        coarse.guard_accum = dmx::GUARD_ACCUM_F32;
+        coarse.guard_main_coarse = 1;
+        coarse.guard_alt_per_call = a.guard_per_call;
+        coarse.guard_alt_accum = 0.0f;
+        coarse.direct = c->d_guard_count.p + dmx::GS_SKIP_COARSE;
+        HIP_TRY(dmx::launch_estep(c->stream, coarse, false));
+    }
+    a.direct = c->d_guard_count.p + dmx::GS_SKIP_FINE;
+    const ep::Walk walk = ep::walk(f);  // (behind the release, where it came with this E-step)
+    set_walk(c, a, walk);
+    a.guard_per_call = ep::fine_allowance(f, walk);
+    HIP_TRY(dmx::launch_estep(c->stream, a, f.with_doublets));
+    a.coarse_stream = nullptr;  // (the redo below is the exact kernel's)
+    HIP_TRY(dmx::launch_guard_compact(c->stream, c->d_guard_count.p, c->d_guard_sub.p, c->guard_sub_cap, c->d_guard_list.p, c->d_bc_order.p, c->B));
+    dmx::EstepArgs redo = a;
+    set_walk(c, redo, ep::WALK_BARCODE_MAJOR);
+    redo.direct = c->d_guard_count.p + dmx::GS_DIRECT;
+    redo.fast = 0;
+    redo.guard = 2;
+    redo.order = c->d_guard_list.p;
+    redo.order_count = c->d_guard_count.p + dmx::GS_COUNT;
+    HIP_TRY(dmx::launch_estep(c->stream, redo, f.with_doublets));
+    c->guard_rows_total += c->B;
+    c->guard_ran = true;
+    return 0;
+}
+
+// logits_kept: somebody can read this E-step's logits (it is the last one of the call); else the next E-step of the same call
+// overwrites them, and the guarded mode may take the coarse pass (kernels.hip: k_estep_tiled_coarse).
+// Every decision is estep_plan.h's (the table: DESIGN.md 4.1); this is the sequence: arguments, facts, plan, builds and releases, launches, bookkeeping.
+int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, float power, bool logits_kept)
+{
+    dmx::EstepArgs a;
+    fill_estep_args(c, a, with_doublets, with_prior, prior_dtype, power);
+    c->post_gathered = false;
+    // (the slots are zero: set at the install, left so by k_sum_dense at the end of every E-step that used them)
+    c->dense_stat_valid = a.dense_calls != nullptr;
+    c->nz_floor = a.nz_floor;
+    c->guard_ran = false;
+    ep::Facts f = estep_facts(c, with_doublets, with_prior, logits_kept);
+    if (ep::unused_stream_release_due(f)) {
         dev_free(c, c->d_tile_stream);
         a.tile_stream = nullptr;
+        f.tile_stream = false;
     }
+    a.fast = ep::tolerance_arithmetic(f);
+    a.segs = ep::segments_offered(f) ? c->d_segs.p : nullptr;
+    a.n_bins = ep::bins(f);
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
     timer_begin(c, DMX_T_ESTEP, &ev);
     int form = DMX_FORM_DIRECT;
-    // The dictionary form is exact and faster than the fine pass, but not than the COARSE pass (200k x 100k x 64: 1.1 ms with its
-    // dictionary build against 0.75): an E-step whose logits nobody reads - the first of a dmx_em call of several iterations - takes
-    // the coarse pass like the ones behind it (its records are built here instead of one E-step later).
-    // dmx_set_lean_memory has released the tile-major stream: the tolerance kernels of this E-step walk the coarse pass's records where they
-    // exist (k_estep_tiled_fine8: the float32 table, float64 sums), else the barcode-major ones (n_bins = 0 where they launch)
-    const bool fine8 = c->d_tile_stream.p == nullptr && c->coarse_ready && !with_doublets && a.n_bins > 0 && c->K > 16 && c->K <= 128;
-    const bool coarse_first = c->estep_mode == DMX_ESTEP_GUARDED && !logits_kept && c->guard_adaptive && coarse_capable(c, with_doublets, c->p_clip_lo) &&
-                              a.n_bins > 0 && c->dict_mode == 1;
-    if (!coarse_first) DMX_TRY(prepare_dictionary(c, with_doublets != 0, a, &form));  // part of the E-step's time
+    if (!ep::coarse_first(f)) DMX_TRY(prepare_dictionary(c, f.with_doublets, a, &form));  // part of the E-step's time
     if (form == DMX_FORM_DICT)
-        HIP_TRY(dmx::launch_estep_dict(c->stream, a, with_doublets != 0));
+        HIP_TRY(dmx::launch_estep_dict(c->stream, a, f.with_doublets));
     else if (form == DMX_FORM_DICT_BLOCK)
         HIP_TRY(dmx::launch_estep_dict_block(c->stream, a));
     else {
-        // Several option slots per lane (estep_packed.hip) make a barcode's serial walk `slots` times longer, and a launch
-        // lasts at least as long as its longest barcode.  So the barcodes with more calls than a third of what a SIMD
-        // gets on average (counted by the repack) walk on 64 lanes inside the same launch; when that is more than an
-        // eighth of them the problem is one of few, long rows and the direct form takes it.  20k x 20k x 8 with
-        // doublets (longest row 3 500 calls): all packed 0.72 ms, split at 1 000 / 2 000 rows 0.32 / 0.30 ms, direct
-        // 0.28 ms - the wavefronts of a launch that fits the chip at once stay where they were placed, the heaviest
-        // 64-lane walks next to the heaviest packed ones; see DESIGN.md 4.1c.  Mode 2: every barcode packed; 3: the split
-        // wherever the shape exists.
-        int lanes = 0, slots = 0;
-        // (guarded mode: where the packed form is taken it is exact AND faster than the tolerance-mode kernel on 64 lanes -
-        // 200k x 20k x 8 with doublets: 1.94 against 2.08 ms -, so it runs as it is, without guard)
-        bool packed = c->estep_packing && with_doublets && c->estep_mode != DMX_ESTEP_FAST && a.pairs_bytes && dmx::estep_packed_shape(a.K, a.G, &lanes, &slots);
-        if (packed && c->estep_packing != 2) {
-            const int k = lanes == 8 ? 0 : lanes == 16 ? 1 : 2;
-            a.n_long = c->max_row_calls > 0 ? c->n_long_rows[k] : c->B;  // no statistic (host-packed problem): not packed
+        ep::Packed packed = ep::packed_candidate(f);
 #ifdef DMX_EXPERIMENTS  // experiment builds only (make EXPERIMENTS=1)
-            if (const char *e = std::getenv("DEMUXALOT_AMD_PACKED_LONG")) a.n_long = std::min<long long>(c->B, std::max(0ll, atoll(e)));
+        if (const char *e = std::getenv("DEMUXALOT_AMD_PACKED_LONG"))
+            if (packed.split) packed.n_long = std::min<long long>(c->B, std::max(0ll, atoll(e)));
 #endif
-            if (c->estep_packing == 1 && 8 * a.n_long > c->B) packed = false;
-            if (!packed) a.n_long = 0;
-        }
-        if (packed) {
+        if (ep::packed_runs(f, packed)) {
+            a.n_long = packed.n_long;
             a.fast = 0;
             HIP_TRY(dmx::launch_estep_packed(c->stream, a));
             form = DMX_FORM_PACKED;
-        } else if (guarded) {
-            // fast kernels with the guard evaluated per barcode, then the exact kernel over the barcodes they queued (their
-            // number is only known on the device: a launch sized for all of them, the wavefronts past the queue's end
-            // return at once); the redo rewrites logits, posteriors, bitmaps and codes of those barcodes.  Adaptive
-            // (kernels.hip: k_guard_begin): the passes are timed on the device, and an E-step for which pass + redo would cost
-            // more than the exact kernel over every barcode runs that kernel directly - the fast kernels stand back.
-            // The coarse pass (kernels.hip: k_estep_tiled_coarse; singlets, 17 .. 128 genotypes, the tile-major schedule, a P-step's
-            // table whose clip keeps binary16 normal) is admissible when nobody can read this E-step's logits.  Which of coarse pass,
-            // fine pass and the direct form runs is the device's choice (k_guard_begin): both fast launches are issued, the one
-            // that is not taken stands back.
-            const bool capable = coarse_capable(c, with_doublets, c->p_clip_lo) && a.n_bins > 0;
-            const bool allow_coarse = capable && (!logits_kept || c->coarse_pass == 2);
-            if (allow_coarse && !c->coarse_ready) {
-                // once per problem, ahead of k_guard_begin's time stamp (not part of the pass the device times): the coarse pass's
-                // records - 8 bytes per call where the tile-major stream has 16 - and the log2 of the keep factors per barcode
-                const int cpg = dmx::coarse_calls_per_gather((int)c->K), bpr = dmx::coarse_batches_per_record(cpg);
-                const size_t words = (((size_t)c->n_pairs / 4 + (size_t)c->n_bins * (bpr - 1)) / bpr + 1) * (size_t)(cpg * 16);
-                DMX_TRY(dev_alloc(c, c->d_coarse_stream, words));
-                DMX_TRY(dev_alloc(c, c->d_coarse_bin_ptr, (size_t)c->n_bins + 1));
-                DMX_TRY(dev_alloc(c, c->d_log2_keep, (size_t)c->B));
-                // (the barcodes' sums of log2 keep come out of the same pass: every call's keep factor is read there once)
-                HIP_TRY(dmx::launch_build_coarse_stream(c->stream, c->d_tile_stream.p, c->d_bin_ptr.p, c->n_bins, a.prob_bytes, cpg, c->d_coarse_bin_ptr.p, c->d_coarse_stream.p,
-                                                        c->d_bin_rows.p, c->bin_rows_cap, c->d_log2_keep.p));
-                c->coarse_ready = true;
-                // dmx_set_lean_memory: the tile-major stream has done its last job (the block returns to the context's cache behind the build,
-                // stream-ordered); the fine level is the barcode-major tolerance kernel from here on (below)
-                if (c->lean_memory) {
-                    dev_free(c, c->d_tile_stream);
-                    // ... and the compact row array of the dictionary form with it (4 bytes per call): an E-step that keeps its logits on the
-                    // prior table then runs the tolerance kernel too, the incremental M-step reads the rows from the records
-                    dev_free(c, c->d_call_rows);
-                    a.call_rows = nullptr;
-                }
-            }
-            if (allow_coarse) DMX_TRY(ensure_prob16(c));
-            HIP_TRY(dmx::launch_guard_begin(c->stream, c->d_guard_count.p, c->B, c->K, c->guard_adaptive, capable, allow_coarse));
-            a.guard = 1;
-            if (fine8) a.guard_per_call = dmx::guard_per_call_fine8(dmx::coarse_calls_per_gather((int)c->K));  // (the coarse guard's estimate of the fine level reads it too)
-            a.order_direct = c->d_bc_order.p;
-            a.guard_main_coarse = 0;
-            a.guard_alt_per_call = capable ? dmx::GUARD_PER_CALL_COARSE : 0.0f;
-            a.guard_alt_accum = capable ? dmx::GUARD_ACCUM_F32 : 0.0f;
-            if (allow_coarse) {
-                if (!c->prob16_valid) {  // (the P-step of a dmx_em / dmx_run_iterations call has written it already)
-                    // a sliced run whose slices travel as lists of changed rows keeps the binary16 table up to date row by row from here on
-                    // (run_pstep): converted whatever level the device takes, so that the host knows it valid
-                    const bool kept = c->sliced && c->prob_list_words != 0;
-                    HIP_TRY(dmx::launch_prob_to_half(c->stream, c->d_prob.p, c->prob_rows, c->G, c->d_prob16.p, kept ? nullptr : c->d_guard_count.p + dmx::GS_SKIP_COARSE));
-                    c->prob16_valid = kept;
-                }
-                dmx::EstepArgs coarse = a;
-                coarse.prob16 = c->d_prob16.p;
-                coarse.coarse_stream = c->d_coarse_stream.p;
-                coarse.coarse_bin_ptr = c->d_coarse_bin_ptr.p;
-                coarse.log2_keep = c->d_log2_keep.p;
-                coarse.guard_per_call = dmx::GUARD_PER_CALL_COARSE;
-                coarse.guard_accum = dmx::GUARD_ACCUM_F32;
-                coarse.guard_main_coarse = 1;
-                coarse.guard_alt_per_call = a.guard_per_call;
-                coarse.guard_alt_accum = 0.0f;
-                coarse.direct = c->d_guard_count.p + dmx::GS_SKIP_COARSE;
-                HIP_TRY(dmx::launch_estep(c->stream, coarse, false));
-            }
-            a.direct = c->d_guard_count.p + dmx::GS_SKIP_FINE;
-            a.tile_stream = c->d_tile_stream.p;
-            if (c->d_tile_stream.p == nullptr) {  // (released: the fine level walks the coarse pass's records, or a barcode per wavefront the barcode-major ones)
-                if (c->coarse_ready && !with_doublets && a.n_bins > 0 && c->K > 16 && c->K <= 128) {
-                    a.coarse_stream = c->d_coarse_stream.p;
-                    a.coarse_bin_ptr = c->d_coarse_bin_ptr.p;
-                    a.log2_keep = c->d_log2_keep.p;
-                    a.prob16 = nullptr;
-                    a.guard_per_call = dmx::guard_per_call_fine8(dmx::coarse_calls_per_gather((int)c->K));  // (also where the release came with this E-step)
-                } else {
-                    a.n_bins = 0;
-                }
-            }
-            HIP_TRY(dmx::launch_estep(c->stream, a, with_doublets != 0));
-            a.coarse_stream = nullptr;  // (the redo below is the exact kernel's)
-            HIP_TRY(dmx::launch_guard_compact(c->stream, c->d_guard_count.p, c->d_guard_sub.p, c->guard_sub_cap, c->d_guard_list.p, c->d_bc_order.p, c->B));
-            dmx::EstepArgs redo = a;
-            redo.direct = c->d_guard_count.p + dmx::GS_DIRECT;
-            redo.fast = 0;
-            redo.guard = 2;
-            redo.n_bins = 0;
-            redo.order = c->d_guard_list.p;
-            redo.order_count = c->d_guard_count.p + dmx::GS_COUNT;
-            HIP_TRY(dmx::launch_estep(c->stream, redo, with_doublets != 0));
-            c->guard_rows_total += c->B;
-            c->guard_ran = true;
+        } else if (ep::guarded(f)) {
+            DMX_TRY(guarded_estep(c, f, a));
         } else {
-            if (c->d_tile_stream.p == nullptr) {
-                if (fine8 && a.fast) {  // (the tolerance mode without the guard)
-                    a.coarse_stream = c->d_coarse_stream.p;
-                    a.coarse_bin_ptr = c->d_coarse_bin_ptr.p;
-                    a.log2_keep = c->d_log2_keep.p;
-                } else {
-                    a.n_bins = 0;
-                }
-            }
-            HIP_TRY(dmx::launch_estep(c->stream, a, with_doublets != 0));
+            set_walk(c, a, ep::walk(f));
+            HIP_TRY(dmx::launch_estep(c->stream, a, f.with_doublets));
         }
     }
     c->estep_form = form;
@@ -895,7 +895,7 @@ int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, 
     const bool keep_last = c->logits_needed || logits_out != nullptr;  // (dmx_set_logits_needed)
     for (int it = 0; it < n_iterations; it++) {
         const bool kept = it + 1 == n_iterations && keep_last;  // somebody can read this E-step's logits
-        DMX_TRY(run_pstep(c, lo, hi, true, !kept && it > 0 && coarse_capable(c, with_doublets, lo)));  // (iteration 0: the dictionary form)
+        DMX_TRY(run_pstep(c, lo, hi, true, !kept && it > 0 && ep::coarse_capable(estep_facts(c, with_doublets, false, kept), lo)));  // (iteration 0: the dictionary form)
         DMX_TRY(run_estep(c, with_doublets, it == 0 && prior_logits != nullptr, prior_dtype, power, kept));
         if (it + 1 < n_iterations) {  // the M-step after the last yield is dead
             c->msteps_ahead = n_iterations - 1 - it;
@@ -922,7 +922,7 @@ int dmx_run_iterations(dmx_ctx *c, int n_iterations, float lo, float hi, float p
     const int with_doublets = c->K != c->G;
     for (int it = 0; it < n_iterations; it++) {
         const bool kept = it + 1 == n_iterations && c->logits_needed;  // somebody can read this E-step's logits
-        DMX_TRY(run_pstep(c, lo, hi, true, !kept && coarse_capable(c, with_doublets, lo)));
+        DMX_TRY(run_pstep(c, lo, hi, true, !kept && ep::coarse_capable(estep_facts(c, with_doublets, false, kept), lo)));
         DMX_TRY(run_estep(c, with_doublets, false, DMX_F32, power, kept));
         c->msteps_ahead = n_iterations - it;
         const int rc_m = run_mstep(c, power);

@@ -591,10 +591,7 @@ hipError_t launch_estep_dict_block(hipStream_t st, const EstepArgs &a)
     return launch_softmax_rows(st, a);
 }
 
-static int dict_lanes(int K, bool pairs)  // lanes per barcode of the E-step kernel
-{
-    return K <= 16 && !pairs ? 4 : K <= 32 ? 8 : K <= 64 ? 16 : K <= 128 ? 32 : 64;
-}
+using eplan::dict_lanes;  // lanes per barcode of the E-step kernel
 
 // distinct: what launch_build_dict found (<= DICT_CAP; <= DICT_PAIR_CAP for doublet runs); returns the row pitch
 int dict_table_pitch(int distinct, int K, bool pairs)

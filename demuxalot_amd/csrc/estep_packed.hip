@@ -226,28 +226,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     estep_epilogue<L, A>(a, b, live, acc, kk, valid, lane, li, gbase, 2 * npairs);
 }
 
-// Lane-group shape for a doublet table of K options over G genotypes; false: the direct form is as good or better.
-bool estep_packed_shape(int K, int G, int *lanes, int *slots)
-{
-    static const int shapes[][2] = {{8, 3}, {8, 5}, {16, 3}, {16, 5}, {32, 3}, {32, 5}};
-    int direct = 4;  // slots the direct form spends on a row: next power of two up to 64, then multiples of 64 x {1, 2, 4, 8, 16}
-    while (direct < K && direct < 64) direct <<= 1;
-    while (direct < K) direct <<= 1;
-    int best = direct, bl = 0, ba = 0;
-    for (const auto &sh : shapes) {
-        const int cap = sh[0] * sh[1];
-        if (cap >= K && G <= sh[0] && cap < best) {
-            best = cap;
-            bl = sh[0];
-            ba = sh[1];
-        }
-    }
-    if (!bl) return false;
-    *lanes = bl;
-    *slots = ba;
-    return true;
-}
-
 template <int L, int A>
 static void launch_packed(hipStream_t st, const EstepArgs &a)
 {
@@ -260,6 +238,7 @@ hipError_t launch_estep_packed(hipStream_t st, const EstepArgs &a)
 {
     if (a.B == 0) return hipSuccess;
     int L = 0, A = 0;
+    // (refusals run_estep cannot reach: eplan::packed_candidate asks the same shape and record size, and the packed form never runs the tolerance arithmetic)
     if (a.fast || a.pairs_bytes == 0 || a.n_long < 0 || a.n_long > a.B || !estep_packed_shape(a.K, a.G, &L, &A)) return hipErrorInvalidValue;
     if (L == 8 && A == 3) launch_packed<8, 3>(st, a);
     else if (L == 8) launch_packed<8, 5>(st, a);

@@ -144,7 +144,6 @@ hipError_t launch_guard_compact(hipStream_t, unsigned *, const int *, unsigned, 
 hipError_t launch_mcombine(hipStream_t, const MstepArgs &, const long long *, long long, long long, const int *, float *, double *,
                            unsigned long long *, unsigned *, const int *, bool) { return hipSuccess; }
 hipError_t launch_store_slice(hipStream_t, const void *, bool, long long, long long, int, float *) { return hipSuccess; }
-bool estep_packed_shape(int, int, int *, int *) { return false; }
 hipError_t launch_estep_packed(hipStream_t, const EstepArgs &) { return hipSuccess; }
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {

@@ -4,6 +4,7 @@
 
 #include "demux_hip.h"
 #include "demux_hip_debug.h"
+#include "estep_plan.h"
 
 namespace dmx {
 
@@ -190,12 +191,7 @@ constexpr unsigned GS_UNKNOWN = 0xFFFFFFFFu;
 // so its error cancels in the posteriors and in every difference of two logits; in a logit served by a coarse E-step (dmx_set_coarse_pass(2)) it
 // is one more v_log_f32 error per call, 1.06e-5.  4.934e-4 + 1.06e-5 = 5.04e-4, rounded up (round 5: 4.94e-4, 0.1 % of headroom).
 constexpr float GUARD_PER_CALL_COARSE = 5.1e-4f;
-// The fine pass on the coarse pass's records (kernels.hip: k_estep_tiled_fine8; the tile-major stream released: dmx_set_lean_memory): float32 table,
-// float64 sums, a term keep (p + r): 4 x 2^-24 relative against the reference's float32 term (r's division, the sum's rounding, the
-// reference's two), the slot tag in one r of a block's 8 / cpg per batch (2^-19 of r <= 1.91e-6 of the term), the product's roundings and
-// the mantissa's log as GUARD_PER_CALL prices them.  Every block of a barcode's batch carries exactly one tagged r and the guard counts
-// padded calls, so the tag is charged to one call in 8 / cpg.
-inline float guard_per_call_fine8(int cpg) { return 1.91e-6f / (float)(8 / cpg) + 4.0f * 6.0e-8f + 7.0e-8f; }
+using eplan::guard_per_call_fine8;  // (the fine pass on the coarse pass's records: estep_plan.h)
 constexpr float GUARD_ACCUM_F32 = 6.0e-8f;  // 2^-24, rounded up: per float32 addition of the running sum (estep_epilogue.h)
 constexpr int GUARD_SLOTS = 256;   // hashed counters behind the state words: barcodes flagged by a guard whose pass does not run (a direct
                                    // E-step: both; a fine one: the coarse guard's; a coarse one: the fine guard's) - a set per guard
@@ -210,9 +206,9 @@ hipError_t launch_guard_begin(hipStream_t st, unsigned *state, long long B, int 
 hipError_t launch_guard_stamp(hipStream_t st, unsigned *state, int which);  // state[which] = the device's wall clock (GS_T_REDO, GS_T_END)
 
 constexpr int CALL_PAD_PAIRS = 64;     // readable neutral records behind the last barcode's row (pairs and call_rows)
-constexpr int DICT_CAP = 8;            // distinct values per row the dictionary form handles (singlet runs)
-constexpr int DICT_PAIR_CAP = 4;       // ... in doublet runs (10 pair values)
-constexpr int DICT_LANE_K = 256;       // option tables up to this width take the lane-per-four-options dictionary kernel
+using eplan::DICT_CAP;       // the dictionary form's caps and the width of its lane kernel: estep_plan.h
+using eplan::DICT_PAIR_CAP;
+using eplan::DICT_LANE_K;
 __host__ __device__ inline int dict_code_pitch(int n) { return (n + 3) & ~3; }  // bytes between the rows of a code table of n codes per row
 
 constexpr int DENSE_SLOTS = 1024;            // hashed counters of the dense-call statistic
@@ -311,10 +307,10 @@ hipError_t launch_probs_from_betas_f64(hipStream_t st, const double *betas, cons
 // sets flags[0] bit 0 when a value lies outside [0, 1] or is not finite
 hipError_t launch_check_unit_range(hipStream_t st, const float *x, long long n, int *flags);
 hipError_t launch_estep(hipStream_t st, const EstepArgs &a, bool pairs);
-// the coarse pass's records from the tile-major stream (coarse_bin_ptr first, one block; then the stream); cpg = calls per gather: 1 for
-// 65 .. 128 genotypes, 2 for 33 .. 64, 4 for 17 .. 32; zero_off = byte offset of the all-zero row behind the table
-constexpr int coarse_calls_per_gather(int K) { return K > 64 ? 1 : K > 32 ? 2 : 4; }
-constexpr int coarse_batches_per_record(int cpg) { return cpg; }  // (kernels.hip: CoarseShape<CPG>::BPR)
+// the coarse pass's records from the tile-major stream (coarse_bin_ptr first, one block; then the stream); cpg = calls per gather
+// (estep_plan.h: coarse_calls_per_gather); zero_off = byte offset of the all-zero row behind the table
+using eplan::coarse_calls_per_gather;
+using eplan::coarse_batches_per_record;
 hipError_t launch_build_coarse_stream(hipStream_t st, const CallPair *stream, const long long *bin_ptr, long long n_bins, unsigned zero_off,
                                       int cpg, long long *coarse_bin_ptr, unsigned *out, const int *bin_rows, int R, double *log2_keep);
 hipError_t launch_prob_to_half(hipStream_t st, const float *prob, long long rows, int G, unsigned short *out, const unsigned *skip);  // EstepArgs::prob16; *skip != 0: nothing
@@ -413,7 +409,7 @@ hipError_t launch_mcombine(hipStream_t st, const MstepArgs &a, const long long *
 hipError_t launch_store_slice(hipStream_t st, const void *slice, bool f64, long long v_begin, long long n_rows, int G, float *add);
 // call_rows (nullable): the compact row array of the same records, rewritten as well
 // estep_packed.hip: exact E-step of narrow doublet tables, several option slots per lane (K = 36: 8 lanes x 5 slots)
-bool estep_packed_shape(int K, int G, int *lanes, int *slots);
+using eplan::estep_packed_shape;
 hipError_t launch_estep_packed(hipStream_t st, const EstepArgs &a);
 hipError_t launch_remap_row_offsets(hipStream_t st, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows,
                                     unsigned *call_rows);

@@ -3193,13 +3193,14 @@ hipError_t launch_check_unit_range(hipStream_t st, const float *x, long long n, 
 }
 
 template <int L, int A, int U>
-static void launch_direct(hipStream_t st, const EstepArgs &a_in, bool pairs)
+static void launch_direct(hipStream_t st, const EstepArgs &a_in, bool pairs, const eplan::Kernel &k)
 {
     EstepArgs a = a_in;
-    // the doublet tolerance kernel loads a call's row whole into PairRowShape<A>::GPAD lanes: every table of G (G + 1) / 2
-    // options that reaches this A has G <= GPAD; any other option table takes the exact kernel (always admissible)
-    const bool fast = a.fast && (!(pairs && L == 64 && A <= 8) || a.G <= PairRowShape<A>::GPAD);
-    const bool split = L == 64 && fast && a.segs != nullptr && a.n_segs > 0 && a.order_count == nullptr;
+    // The plan says "the tolerance arithmetic is wanted" (k.fast); whether the doublet tolerance kernel has a row shape for the table is
+    // asked here, where PairRowShape lives with the device code: it loads a call's row whole into PairRowShape<A>::GPAD lanes: every table
+    // of G (G + 1) / 2 options that reaches this A has G <= GPAD; any other option table takes the exact kernel (always admissible)
+    const bool fast = k.fast && (!(pairs && L == 64 && A <= 8) || a.G <= PairRowShape<A>::GPAD);
+    const bool split = k.kind == eplan::KERNEL_DIRECT_SPLIT && fast;
     if (!split) a.segs = nullptr;
     const dim3 grid(blocks_for(split ? a.n_segs + (a.B - a.n_split) : a.B, 4 * (64 / L))), block(256);
     if (fast) {
@@ -3238,119 +3239,90 @@ static hipError_t launch_block(hipStream_t st, const EstepArgs &a, int k_base)
     return hipGetLastError();
 }
 
-template <int A>
-static void launch_tiled(hipStream_t st, const EstepArgs &a)
+// the kernels of the tile-major schedule: a bin of barcodes per wavefront
+static void launch_tiled(hipStream_t st, const EstepArgs &a, const eplan::Kernel &k)
 {
     const dim3 grid(blocks_for(a.n_bins, 4)), block(256);
-    if (a.fast && a.prob16 == nullptr && a.coarse_stream != nullptr) {  // the fine pass on the coarse pass's records (the tile-major stream was released)
-        if constexpr (A == 2)
-            hipLaunchKernelGGL(k_estep_tiled_fine8<1>, grid, block, 0, st, a);
-        else if (a.K > 32)
-            hipLaunchKernelGGL(k_estep_tiled_fine8<2>, grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL(k_estep_tiled_fine8<4>, grid, block, 0, st, a);
-        return;
-    }
-    if constexpr (A == 1) {
-        if (a.fast && a.prob16 != nullptr) {  // the coarse pass (guarded mode only: dmx_api.cpp: run_estep)
-            if (a.K > 32)
-                hipLaunchKernelGGL(k_estep_tiled_coarse<2>, grid, block, 0, st, a);
-            else
-                hipLaunchKernelGGL(k_estep_tiled_coarse<4>, grid, block, 0, st, a);
-            return;
-        }
-        if (a.fast && a.K <= 32) {  // two calls per gather
-            hipLaunchKernelGGL((k_estep_tiled<1, true, true>), grid, block, 0, st, a);
-            return;
-        }
-    }
-    if constexpr (A == 2) {
-        if (a.fast && a.prob16 != nullptr) {  // the coarse pass for 65 .. 128 genotypes: one call per gather
-            hipLaunchKernelGGL(k_estep_tiled_coarse<1>, grid, block, 0, st, a);
-            return;
+    switch (k.kind) {
+    case eplan::KERNEL_FINE8:  // the fine pass on the coarse pass's records (the tile-major stream was released)
+        if (k.cpg == 1) hipLaunchKernelGGL(k_estep_tiled_fine8<1>, grid, block, 0, st, a);
+        else if (k.cpg == 2) hipLaunchKernelGGL(k_estep_tiled_fine8<2>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_estep_tiled_fine8<4>, grid, block, 0, st, a);
+        break;
+    case eplan::KERNEL_COARSE:  // the coarse pass (guarded mode only: dmx_steps.cpp: run_estep); 65 .. 128 genotypes: one call per gather
+        if (k.cpg == 1) hipLaunchKernelGGL(k_estep_tiled_coarse<1>, grid, block, 0, st, a);
+        else if (k.cpg == 2) hipLaunchKernelGGL(k_estep_tiled_coarse<2>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_estep_tiled_coarse<4>, grid, block, 0, st, a);
+        break;
+    case eplan::KERNEL_TILED_TWO_CALLS:  // two calls per gather
+        hipLaunchKernelGGL((k_estep_tiled<1, true, true>), grid, block, 0, st, a);
+        break;
+    default:
+        if (k.A == 1) {
+            if (k.fast) hipLaunchKernelGGL((k_estep_tiled<1, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_estep_tiled<1, false>), grid, block, 0, st, a);
+        } else {
+            if (k.fast) hipLaunchKernelGGL((k_estep_tiled<2, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_estep_tiled<2, false>), grid, block, 0, st, a);
         }
     }
-    if (a.fast)
-        hipLaunchKernelGGL((k_estep_tiled<A, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_estep_tiled<A, false>), grid, block, 0, st, a);
 }
 
+// 2 x 3 blocks of the option triangle, `THREADS` of them per launch (k_estep_pairblocks), then the softmax over complete rows
+template <int THREADS>
+static hipError_t launch_pairblocks(hipStream_t st, const EstepArgs &a, int launches)
+{
+    EstepArgs prescaled = a;
+    prescaled.guard_per_call = GUARD_PER_CALL_PRESCALED;
+    int C = ((THREADS == 512 ? 32768 : 16384) / (4 * a.G)) & ~7;  // calls staged per chunk (twice as many for 512 threads: 69.3 -> 67.9 ms at K = 8256)
+    C = C < 8 ? 8 : (C > 128 ? 128 : C);
+    size_t bytes = (size_t)(C + 2) * a.G * 4 + (size_t)C * 12;
+    bytes = (bytes + 15) & ~size_t(15);
+    const hipError_t e = hipFuncSetAttribute((const void *)k_estep_pairblocks<PAIRBLOCK_R1, PAIRBLOCK_R2, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < launches; i++)
+        hipLaunchKernelGGL((k_estep_pairblocks<PAIRBLOCK_R1, PAIRBLOCK_R2, THREADS>), dim3((unsigned)a.B), dim3(THREADS), bytes, st, prescaled, C, i * THREADS);
+    return launch_softmax_rows(st, prescaled);
+}
+
+// Which kernel a launch is: eplan::kernel (estep_plan.h), asked once.  EstepArgs is the kernels' argument block and has no field for the
+// plan's walk and level: run_estep hands them over as the arrays themselves (estep_plan.h: handover), read back by request_of and nowhere else.
 hipError_t launch_estep(hipStream_t st, const EstepArgs &a, bool pairs)
 {
     if (a.B == 0) return hipSuccess;
-    const int K = a.K;
-    // tile-major schedule (built by the repack for large singlet problems).  It pays in the tolerance mode, whose
-    // time is the row gathers (1.50 ms against 1.72 ms on 200k x 100k x 64: L2 hit rate 44 % -> 68 %); the exact mode
-    // is bound by its arithmetic and only pays the schedule's overhead (2.94 against 2.70 ms), so it keeps one
-    // barcode per wavefront unless the schedule is forced (a.tiled == 2: tests).
-    if (a.n_bins > 0 && !pairs && K <= 128 && ((a.fast && K > 16) || (a.tiled == 2 && K > 32))) {
-        if (K <= 64) launch_tiled<1>(st, a);
-        else launch_tiled<2>(st, a);
+    const eplan::Request r = eplan::request_of(a.K, pairs, a.fast != 0, a.tiled, a.n_bins, a.prob16 != nullptr, a.coarse_stream != nullptr,
+                                               a.segs != nullptr && a.n_segs > 0, a.order_count != nullptr, a.pair_blocks != nullptr ? a.n_pair_blocks : 0);
+    const eplan::Kernel k = eplan::kernel(r);
+    switch (k.kind) {
+    case eplan::KERNEL_REFUSED:  // K = G > 1024 singlets: not supported (checked by the caller)
+        return hipErrorInvalidValue;
+    case eplan::KERNEL_TILED:
+    case eplan::KERNEL_TILED_TWO_CALLS:
+    case eplan::KERNEL_COARSE:
+    case eplan::KERNEL_FINE8:
+        launch_tiled(st, a, k);
         return hipGetLastError();
-    }
-    if (K <= 256) {
-        if (K <= 4) launch_direct<4, 1, 4>(st, a, pairs);
-        else if (K <= 8) launch_direct<8, 1, 8>(st, a, pairs);
-        else if (K <= 16) launch_direct<16, 1, 8>(st, a, pairs);
-        else if (K <= 32) launch_direct<32, 1, 8>(st, a, pairs);
-        else if (K <= 64) launch_direct<64, 1, 8>(st, a, pairs);
-        else if (K <= 128) launch_direct<64, 2, 4>(st, a, pairs);
-        else launch_direct<64, 4, 2>(st, a, pairs);
+    case eplan::KERNEL_DIRECT:
+    case eplan::KERNEL_DIRECT_SPLIT:
+        if (k.L == 4) launch_direct<4, 1, 4>(st, a, pairs, k);
+        else if (k.L == 8) launch_direct<8, 1, 8>(st, a, pairs, k);
+        else if (k.L == 16) launch_direct<16, 1, 8>(st, a, pairs, k);
+        else if (k.L == 32) launch_direct<32, 1, 8>(st, a, pairs, k);
+        else if (k.A == 1) launch_direct<64, 1, 8>(st, a, pairs, k);
+        else if (k.A == 2) launch_direct<64, 2, 4>(st, a, pairs, k);
+        else if (k.A == 4) launch_direct<64, 4, 2>(st, a, pairs, k);
+        else if (k.A == 8) launch_direct<64, 8, 2>(st, a, pairs, k);
+        else launch_direct<64, 16, 2>(st, a, pairs, k);
         return hipGetLastError();
+    case eplan::KERNEL_PAIR_BLOCKS:
+        return k.threads == 512 ? launch_pairblocks<512>(st, a, k.launches) : launch_pairblocks<256>(st, a, k.launches);
+    case eplan::KERNEL_BLOCK_TILES:
+        break;
     }
-    // Doublet tables of more than 512 options (256 in the tolerance mode) already go to the workgroup-per-barcode form
-    // below: with 16 accumulators + two row offsets per lane the lane-per-option form is down to 2 (1) waves per SIMD
-    // (20k x 20k x 32 with doublets, K = 528: 3.50 -> 2.97 ms, tolerance mode 4.54 -> 1.49 ms; at K = 496 it is still
-    // ahead in the exact mode, 2.44 against 2.65 ms, and behind in the tolerance mode, 2.04 against 1.20 ms).
-    const bool to_block = pairs && (K > 512 || (a.fast && K > 256));
-    if (K <= 1024 && !to_block) {  // register-resident up to 16 options per lane; slots past K are skipped wave-uniformly
-        if (K <= 512) launch_direct<64, 8, 2>(st, a, pairs);
-        else launch_direct<64, 16, 2>(st, a, pairs);
-        return hipGetLastError();
-    }
-    if (!pairs) return hipErrorInvalidValue;  // K = G > 1024 singlets: not supported (checked by the caller)
-    // K > 1024: the options in tiles of up to 17 per thread, one launch of k_estep_block per tile leaving its logits,
-    // then the softmax over complete rows.  What this form runs on is registers per thread, i.e. resident wavefronts:
-    //   * the softmax fused into a single launch costs 40 VGPRs (3 waves per SIMD instead of 4): 12.2 ms against
-    //     10.4 ms on 20k x 20k x 64 with doublets (K = 2080);
-    //   * one launch with 33 accumulators per thread (236 VGPRs, 2 waves per SIMD) took 297 ms on 130k x 650k x 128 with
-    //     doublets (K = 8256); two launches of 17 take 257 ms although every tile stages the barcode's genotype rows
-    //     again; three of 12: 264 ms.
-    // (Tiles of 65 accumulators per thread -- 385 VGPRs plus SGPR spills -- ended in GPU memory faults that narrower
-    // tiles of the same source do not show: profiles/r2_block_tile65_experiment.txt.)
-    if (a.fast && pairs && a.pair_blocks != nullptr && a.n_pair_blocks > 0 && a.order_count == nullptr) {
-        EstepArgs prescaled = a;
-        prescaled.guard_per_call = GUARD_PER_CALL_PRESCALED;
-        // tolerance arithmetic: 2 x 3 blocks of the option triangle, 256 blocks per launch (k_estep_pairblocks)
-        const bool big = a.n_pair_blocks >= 1024;         // enough blocks for 512 threads to share the staging of a chunk
-        int C = ((big ? 32768 : 16384) / (4 * a.G)) & ~7;  // calls staged per chunk (twice as many for 512 threads: 69.3 -> 67.9 ms at K = 8256)
-        C = C < 8 ? 8 : (C > 128 ? 128 : C);
-        size_t bytes = (size_t)(C + 2) * a.G * 4 + (size_t)C * 12;
-        bytes = (bytes + 15) & ~size_t(15);
-        // 512 threads share the staging of a chunk where there are blocks for them (K = 8256: 1 450 blocks, 74.7 -> 69.7 ms;
-        // K = 528: 121 blocks, 1.24 ms with 256 threads against 1.84); 1024 threads: 103 ms
-        auto launch = [&](auto kernel, int threads) {
-            const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e != hipSuccess) return e;
-            for (int blk_base = 0; blk_base < a.n_pair_blocks; blk_base += threads)
-                hipLaunchKernelGGL(kernel, dim3((unsigned)a.B), dim3(threads), bytes, st, prescaled, C, blk_base);
-            return hipSuccess;
-        };
-        const hipError_t e = big ? launch(k_estep_pairblocks<PAIRBLOCK_R1, PAIRBLOCK_R2, 512>, 512)
-                                                     : launch(k_estep_pairblocks<PAIRBLOCK_R1, PAIRBLOCK_R2, 256>, 256);
-        if (e != hipSuccess) return e;
-        return launch_softmax_rows(st, prescaled);
-    }
-    const int need = (K + 255) / 256;
-    int tile = need <= 2 ? 2 : need <= 4 ? 4 : need <= 6 ? 6 : need <= 8 ? 8 : need <= 12 ? 12 : need <= 17 ? 17 : need <= 24 ? 12 : 17;
-    // the tolerance mode carries a running product and an exponent per option besides the accumulator: tiles of 6
-    // keep it at 4+ waves per SIMD (K = 8256: 170 ms with tiles of 17, 103 with 12, 87 with 6, 98 with 4; the exact
-    // mode does not care: 214 / 220 / 218 / 230 ms)
-    if (a.fast && need > 6) tile = 6;
-    for (int k_base = 0; k_base < K; k_base += tile * 256) {
-        const hipError_t e = tile == 2 ? launch_block<2>(st, a, k_base) : tile == 4 ? launch_block<4>(st, a, k_base) : tile == 6 ? launch_block<6>(st, a, k_base) : tile == 8 ? launch_block<8>(st, a, k_base)
-                           : tile == 12 ? launch_block<12>(st, a, k_base) : launch_block<17>(st, a, k_base);
+    for (int i = 0; i < k.launches; i++) {
+        const int k_base = i * k.tile * 256;
+        const hipError_t e = k.tile == 2 ? launch_block<2>(st, a, k_base) : k.tile == 4 ? launch_block<4>(st, a, k_base) : k.tile == 6 ? launch_block<6>(st, a, k_base) : k.tile == 8 ? launch_block<8>(st, a, k_base)
+                           : k.tile == 12 ? launch_block<12>(st, a, k_base) : launch_block<17>(st, a, k_base);
         if (e != hipSuccess) return e;
     }
     return launch_softmax_rows(st, a);

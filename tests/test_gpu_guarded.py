@@ -147,6 +147,19 @@ def test_guarded_mode_every_kernel_shape_against_the_exact_mode_and_the_oracle(o
     """All lane-group widths and slot counts, and the workgroup-per-barcode forms (K > 1024, doublet tables > 256): posteriors within the
     contract of the exact mode's = the oracle's, argmax identical, on EVERY barcode; the barcodes the guard queued carry
     the exact mode's bits."""
+    _every_barcode_of_a_kernel_shape(oracle, G, dp)
+
+
+@pytest.mark.parametrize('G,dp', [(4, 0.), (5, 0.), (8, 0.), (9, 0.), (17, 0.), (65, 0.), (129, 0.), (256, 0.), (257, 0.), (512, 0.), (513, 0.), (1024, 0.),
+                                  (23, 0.3), (31, 0.3), (44, 0.3)])
+def test_guarded_mode_on_either_side_of_every_routing_threshold(oracle, G, dp):
+    """The option tables next to the thresholds of the kernel choice (csrc/estep_plan.h: kernel) that the test above leaves out: singlets
+    at 4 | 5, 8 | 9, 16 | 17, 64 | 65, 128 | 129, 256 | 257, 512 | 513 and 1024, doublet tables of 276 (the first past 256), 496 and 990
+    options.  The same problem sizes, the same assertions."""
+    _every_barcode_of_a_kernel_shape(oracle, G, dp)
+
+
+def _every_barcode_of_a_kernel_shape(oracle, G, dp):
     from demuxalot_amd import synth
     B = 400
     p = synth.generate(n_barcodes=B, n_snps=300, n_genotypes=G, calls_per_barcode=60, doublets=dp > 0, seed=G)
