@@ -151,6 +151,8 @@ DEBUG_SIGNATURES = {
     'dmx_stage_device_containers': (c_int, [_P, _P, c_int32]),
     'dmx_snp_count_device': (c_int, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, c_int32, POINTER(c_int64)]),
     'dmx_get_calls_transfer_bytes': (c_int, [_P, POINTER(c_int64)]),
+    'dmx_get_donor_readout': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    'dmx_get_allowed_mass': (c_int, [_P, _P, _P, _P, _P]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings

@@ -26,7 +26,7 @@ from typing import Dict, Tuple
 import numpy as np
 import pandas as pd
 
-from . import _lib
+from . import _lib, donor_readout
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
 
@@ -489,8 +489,9 @@ class DevicePosteriors:
     released into the context's block cache - parked, re-used by the next call, and returned to the driver by
     demuxalot_amd.device.trim_device_caches() or by any allocation that would otherwise run out of device memory."""
 
-    def __init__(self, ctx, barcodes, column_names, index_name=None, pooled=True):
+    def __init__(self, ctx, barcodes, column_names, index_name=None, pooled=True, n_donors=None):
         self._ctx = ctx
+        self.n_donors = int(ctx.G if n_donors is None else n_donors)  # the singlet columns are the first n_donors
         self._pooled = pooled  # False: a context set up elsewhere (e.g. with a communicator attached): destroyed on close
         self.barcodes = list(barcodes)
         self.columns = list(column_names)
@@ -532,6 +533,50 @@ class DevicePosteriors:
     def option_sums(self) -> pd.Series:
         """probs.sum(axis=0) (`probs[genotype_names].sum()`, same notebook cells 19 / 21), float64."""
         return pd.Series(self._ctx.get_option_sums(), index=self.columns)
+
+    # ---- donor level: the pair columns of a doublet run folded back onto donors (donor_readout.py) ----
+    @property
+    def donor_names(self):
+        return self.columns[:self.n_donors]
+
+    def doublet_probability(self) -> pd.Series:
+        """Per barcode the posterior mass of the pair columns, float64 (0 for a run without doublets):
+        probs[pair columns].sum(axis=1) of the DataFrame, added in float64."""
+        return pd.Series(self._ctx.get_donor_readout()['doublet_mass'], index=self._index())
+
+    def donor_marginals(self) -> pd.DataFrame:
+        """float32 [B, G]: per barcode and donor the posterior mass of every option that contains the donor - its singlet and
+        its G - 1 pairs, added in float64 in ascending column order and rounded once.  Without doublets: the posteriors."""
+        return pd.DataFrame(self._ctx.get_donor_readout(marginals=True)['donor_marginals'], index=self._index(),
+                            columns=self.donor_names)
+
+    def droplet_calls(self, threshold=0.9) -> pd.DataFrame:
+        """Per barcode: status, donor_1, donor_2, probability, doublet_probability.
+        'singlet' when the best singlet posterior is > threshold (the strict float32 comparison of assignments()): donor_1 is
+        that donor, probability its posterior.  Otherwise 'doublet' when the mass of all pair columns is > threshold (float64):
+        donor_1, donor_2 are the donors of the most probable pair, probability is that mass.  Otherwise 'unassigned': no donors,
+        probability the larger of the two."""
+        r = self._ctx.get_donor_readout()
+        return donor_readout.compose_calls(self.donor_names, threshold, r['best_singlet'], r['best_singlet_prob'], r['best_pair'],
+                                           r['doublet_mass'], index=self._index())
+
+    def donor_summary(self, threshold=0.9) -> pd.DataFrame:
+        """Per donor: n_singlets, n_doublets (droplets droplet_calls(threshold) calls doublet whose best pair contains the
+        donor) and expected_cells, the float64 column sum of donor_marginals() - formed from option_sums(), a donor's own
+        column plus its pair columns, so that nothing of size [B, G] is downloaded."""
+        return donor_readout.compose_summary(self.donor_names, self.droplet_calls(threshold), self._ctx.get_option_sums())
+
+    def qualities(self, barcode2possible_options) -> dict:
+        """{'logloss', 'accuracy', 'error rate'} of the reference's utils._compute_qualities (utils.py:265-296) against the
+        options (column names, pairs as 'A+B') that are possible for each barcode: logloss is the mean of
+        -log(max(mass, 1e-4)) with mass the posterior of the barcode's possible options, accuracy the share of barcodes whose
+        most probable option is possible.  A barcode that is missing from the dict and a name that is not a column raise
+        ValueError (the reference asserts).
+        Differs from the reference in precision only: the reference adds the float32 posteriors in float32 and takes a float32
+        log; here the masses are float64 sums in list order, formed on the device, and log and mean are float64.  The
+        reference's check that the rows sum to one is not repeated."""
+        start, options = donor_readout.allowed_lists(self.barcodes, self.columns, barcode2possible_options)
+        return donor_readout.compose_qualities(*self._ctx.get_allowed_mass(start, options))
 
     def rows(self, lo, hi, what='probs') -> pd.DataFrame:
         """Rows [lo, hi) of the 'probs' or 'logits' matrix as a DataFrame."""
@@ -615,7 +660,7 @@ class Demultiplexer:
                 ctx.close()
                 raise
             learnt_genotypes = genotypes._with_betas(learnt_betas, _take=True)
-            return learnt_genotypes, DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names)
+            return learnt_genotypes, DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names, n_donors=n_genotypes)
         with shared_context_lock:
             ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
                                           fetch_betas=False)
@@ -730,7 +775,8 @@ class Demultiplexer:
             except BaseException:
                 ctx.close()
                 raise
-            return DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names, index_name='BARCODE')
+            return DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names, index_name='BARCODE',
+                                    n_donors=genotypes.n_genotypes)
         with shared_context_lock:
             logits, probs = run(get_context(), True)
 

@@ -639,6 +639,33 @@ class DeviceContext:
         check(self._lib.dmx_get_option_sums(self._h, ptr(out)))
         return out
 
+    def get_donor_readout(self, marginals=False):
+        """The pair columns folded back onto donors in one pass (include/demux_hip_debug.h: dmx_get_donor_readout): dict of
+        singlet_mass, doublet_mass (float64[B]), best_singlet, best_pair (int32[B] column indices, -1: no such column),
+        best_singlet_prob, best_pair_prob (float32[B]) and, with marginals=True, donor_marginals (float32[B, G])."""
+        B = self.B
+        out = dict(singlet_mass=np.zeros(B, np.float64), doublet_mass=np.zeros(B, np.float64),
+                   best_singlet=np.full(B, -1, np.int32), best_singlet_prob=np.full(B, np.nan, np.float32),
+                   best_pair=np.full(B, -1, np.int32), best_pair_prob=np.full(B, np.nan, np.float32))
+        if marginals:
+            out['donor_marginals'] = np.zeros((B, self.G), np.float32)
+        check(self._lib.dmx_get_donor_readout(self._h, ptr(out['singlet_mass']), ptr(out['doublet_mass']), ptr(out['best_singlet']),
+                                              ptr(out['best_singlet_prob']), ptr(out['best_pair']), ptr(out['best_pair_prob']),
+                                              ptr(out.get('donor_marginals'))))
+        return out
+
+    def get_allowed_mass(self, start, options):
+        """(mass float64[B], best_is_allowed int32[B]) of the CSR lists options[start[b]:start[b + 1]] of allowed option columns:
+        the listed posteriors added in float64 in list order, and whether the row's first maximum is listed
+        (include/demux_hip_debug.h: dmx_get_allowed_mass)."""
+        start, options = as_c(start, np.int64), as_c(options, np.int32)
+        assert start.shape == (self.B + 1,), 'one start per barcode and the end'
+        assert options.ndim == 1 and len(options) >= (start[-1] if len(start) else 0), 'allowed options shorter than start[-1]'
+        mass = np.zeros(self.B, np.float64)
+        hit = np.zeros(self.B, np.int32)
+        check(self._lib.dmx_get_allowed_mass(self._h, ptr(start), ptr(options), ptr(mass), ptr(hit)))
+        return mass, hit
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

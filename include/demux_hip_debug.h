@@ -348,6 +348,35 @@ int dmx_snp_count_device(dmx_ctx *ctx, const dmx_call_container *views, int32_t 
                          int64_t n_barcodes, int32_t n_donors, float p_threshold, int32_t cap, int64_t *n_positions);
 int dmx_get_calls_transfer_bytes(dmx_ctx *ctx, int64_t *bytes);
 
+/* ------------------------------------------------------------------------- *
+ * Donor-level read-outs of the posteriors (product API; declared here because demux_hip.h is kept to 64 entry points).
+ * Reductions of the resident float32 posteriors [B, K] of the last dmx_estep / dmx_em, like dmx_get_top_options and
+ * dmx_get_option_sums (call order: after dmx_estep / dmx_em; B == 0 returns 0), that fold the pair columns of a doublet run
+ * back onto donors (csrc/results.hip).  Columns as everywhere: singlets 0 .. G-1, pair (g1 < g2) at
+ * G + g1 (2G - g1 - 1) / 2 + (g2 - g1 - 1); a run without doublets has K == G and no pair columns.
+ *   dmx_get_donor_readout  one pass over the matrix; every output is B long but donor_marginals [B, G], and any may be NULL:
+ *                          singlet_mass / doublet_mass  float64 sums of the singlet / of the pair columns (0 without pairs), in
+ *                              a fixed order: the same bits from run to run, within (K - 1) 2^-53 relative of any other order;
+ *                          best_singlet / best_pair     the first maximum over the singlet / the pair columns, as a COLUMN index,
+ *                              with its posterior: ties go to the lower column and NaNs never win (the rule of
+ *                              dmx_get_top_options); -1 and NaN where there is no such column (best_pair without doublets);
+ *                          donor_marginals[b, g]        the posterior mass of every option that contains donor g: the float32
+ *                              values widened to float64 and added sequentially in ASCENDING COLUMN ORDER - singlet g, then
+ *                              (0, g) .. (g-1, g), then (g, g+1) .. (g, G-1) -, rounded to float32 once: reproducible and
+ *                              checkable bit for bit.  NULL: neither computed nor allocated.
+ *   dmx_get_allowed_mass   the device half of the reference's utils._compute_qualities (utils.py:265-296).  The options allowed
+ *                          for barcode b are allowed_options[allowed_start[b] .. allowed_start[b + 1]) (CSR, B + 1 starts).
+ *                          mass[b]: the listed posteriors widened to float64 and added sequentially in list order (an option
+ *                          listed twice is added twice, an empty list gives 0); best_is_allowed[b]: 1 when the first maximum of
+ *                          the whole row (dmx_get_top_options, k = 1) is in the list.  Either output may be NULL.
+ *                          DMX_ERR_INVALID before anything is launched: allowed_start[0] != 0, a decreasing allowed_start, an
+ *                          option outside [0, K).
+ * ------------------------------------------------------------------------- */
+int dmx_get_donor_readout(dmx_ctx *ctx, double *singlet_mass, double *doublet_mass, int32_t *best_singlet, float *best_singlet_prob,
+                          int32_t *best_pair, float *best_pair_prob, float *donor_marginals);
+int dmx_get_allowed_mass(dmx_ctx *ctx, const int64_t *allowed_start, const int32_t *allowed_options, double *mass,
+                         int32_t *best_is_allowed);
+
 #ifdef __cplusplus
 }
 #endif
