@@ -3026,7 +3026,8 @@ __global__ __launch_bounds__(256) void k_f32_to_f64(const float *__restrict__ in
     if (i < n) out[i] = (double)in[i];
 }
 
-// per-barcode argmax of the posterior (first maximum, like DataFrame.idxmax / np.argmax)
+// per-barcode argmax of the posterior (first maximum, like DataFrame.idxmax / np.argmax); NaNs never win, and a row without any
+// non-NaN posterior gets -1 / NaN: the rule of results.hip's k_top_options, so that every read-out answers such a row alike
 __global__ __launch_bounds__(256) void k_assign(const float *__restrict__ post, long long B, int K,
                                                 int *__restrict__ best, float *__restrict__ best_p)
 {
@@ -3038,7 +3039,7 @@ __global__ __launch_bounds__(256) void k_assign(const float *__restrict__ post, 
     int bi = 0x7FFFFFFF;
     for (int k = lane; k < K; k += 64) {
         const float v = row[k];
-        if (v > bv) {
+        if (v > bv || (v == bv && k < bi)) {
             bv = v;
             bi = k;
         }
@@ -3053,8 +3054,9 @@ __global__ __launch_bounds__(256) void k_assign(const float *__restrict__ post, 
         }
     }
     if (lane == 0) {
-        best[b] = bi;
-        best_p[b] = bv;
+        const bool have = bi != 0x7FFFFFFF;
+        best[b] = have ? bi : -1;
+        best_p[b] = have ? bv : __builtin_nanf("");
     }
 }
 

@@ -515,10 +515,11 @@ class DevicePosteriors:
         return pd.Series(names, index=self._index([self.barcodes[i] for i in rows]))
 
     def best(self) -> pd.DataFrame:
-        """Per barcode: the most probable option and its posterior (idxmax / max of every row)."""
+        """Per barcode: the most probable option and its posterior (idxmax / max of every row); None / NaN for a row
+        without any non-NaN posterior."""
         best, prob = self._ctx.get_assignments()
-        return pd.DataFrame({'option': np.asarray(self.columns, dtype=object)[best], 'probability': prob},
-                            index=self._index())
+        names = np.asarray(self.columns + [None], dtype=object)  # -1 (no non-NaN posterior in the row) -> None
+        return pd.DataFrame({'option': names[best], 'probability': prob}, index=self._index())
 
     def top_options(self, k=2) -> pd.DataFrame:
         """The k <= 4 best options per barcode, best first: columns option_1, probability_1, option_2, ..."""

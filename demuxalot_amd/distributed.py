@@ -344,7 +344,8 @@ class ShardedPosteriors:
         best, prob = self.local._ctx.get_assignments()
         best = self.plane.gather_rows(best.astype(np.int32))
         prob = self.plane.gather_rows(prob.astype(np.float32))
-        return pd.DataFrame({'option': np.asarray(self.columns, dtype=object)[best], 'probability': prob}, index=self._index())
+        names = np.asarray(list(self.columns) + [None], dtype=object)  # -1 (no non-NaN posterior in the row) -> None
+        return pd.DataFrame({'option': names[best], 'probability': prob}, index=self._index())
 
     def assignments(self, threshold=0.9) -> pd.Series:
         """probs[probs.max(axis=1).gt(threshold)].idxmax(axis=1) over all barcodes (snp_detection.py:166)."""

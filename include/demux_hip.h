@@ -294,7 +294,10 @@ int dmx_get_addition(dmx_ctx *ctx, float *addition_out);
 int dmx_get_block(dmx_ctx *ctx, int what, int64_t b0, int64_t b1, int64_t k0, int64_t k1, float *out);
 
 /* Per-barcode reduction of the posterior on the GPU: argmax option and its
- * probability (what users take from the DataFrame: probs.idxmax(axis=1)). */
+ * probability (what users take from the DataFrame: probs.idxmax(axis=1)): the first maximum; NaNs never win.
+ * A row without any non-NaN posterior (a non-finite prior logit makes one) gets best_option = -1 and
+ * best_prob = NaN - here, in dmx_get_assignments_above (which does not count it) and in dmx_get_top_options alike.
+ * Both outputs are nullable. */
 int dmx_get_assignments(dmx_ctx *ctx, int32_t *best_option, float *best_prob);
 
 /* The reductions users of the reference apply to the posterior DataFrame, done on the GPU so that the [B, K]
@@ -304,10 +307,13 @@ int dmx_get_assignments(dmx_ctx *ctx, int32_t *best_option, float *best_prob);
  *                              best_option[b] = first arg-max column if its posterior is > threshold, else -1;
  *                              best_prob[b] = the row maximum either way; *n_assigned = rows above the threshold.
  *   dmx_get_top_options        the k (1..4) best options of every barcode, best first, ties to the lower column:
- *                              options int32[B*k] (-1 past the end of a short row), probs float32[B*k].
+ *                              options int32[B*k] (-1 past the end of a short row), probs float32[B*k] (NaN there).
  *   dmx_get_option_sums        probs.sum(axis=0) (`probs[genotype_names].sum()`, same notebook cells 19/21) as
- *                              float64[K], added in a fixed order (reproducible run to run).
- * All outputs except the sums are nullable. */
+ *                              float64[K], added in a fixed order (reproducible run to run): float64 sums of 512 slabs
+ *                              of ceil(B / 512) consecutive rows each, in row order, then the slabs in order.
+ * NaN posteriors never win; a row without any non-NaN posterior gets -1 / NaN from both arg-max read-outs and is not
+ * counted in *n_assigned.  The outputs of dmx_get_assignments_above are nullable; those of dmx_get_top_options (when
+ * there are barcodes) and of dmx_get_option_sums are required: a null pointer is refused. */
 int dmx_get_assignments_above(dmx_ctx *ctx, float threshold, int32_t *best_option, float *best_prob,
                               int64_t *n_assigned);
 int dmx_get_top_options(dmx_ctx *ctx, int32_t k, int32_t *options, float *probs);
