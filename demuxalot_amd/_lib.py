@@ -153,6 +153,7 @@ DEBUG_SIGNATURES = {
     'dmx_get_calls_transfer_bytes': (c_int, [_P, POINTER(c_int64)]),
     'dmx_get_donor_readout': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     'dmx_get_allowed_mass': (c_int, [_P, _P, _P, _P, _P]),
+    'dmx_estep_pools': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings

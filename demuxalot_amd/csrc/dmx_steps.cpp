@@ -21,6 +21,7 @@
 #include "dmx_ctx.h"
 #include "dmx_host.h"
 #include "estep_plan.h"
+#include "estep_pools.h"
 #include "mstep_plan.h"
 
 using namespace dmx::host;
@@ -864,6 +865,71 @@ int dmx_estep(dmx_ctx *c, int with_doublets, const float *penalties, const void 
     DMX_TRY(copy_out(c, probs_out, c->d_post.p, bk));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// The pooled E-step (estep_pools.hip).  Everything is checked here, on the host, before anything is uploaded or launched; the
+// context's resident results of the last dmx_estep are not touched.
+int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                    const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                    float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass)
+{
+    DMX_TRY(bind(c));
+    DMX_TRY(need(c, c->have_problem && c->have_probs, "genotype probabilities (dmx_probs_from_betas / dmx_set_probs) before dmx_estep_pools"));
+    if (c->nranks > 1) return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: single GPU only");
+    if (with_doublets != 0 && with_doublets != 1) return fail(DMX_ERR_INVALID, "dmx_estep_pools: with_doublets must be 0 or 1");
+    if (n_pools < 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: negative n_pools");
+    if (!pool_start || !row_ptr) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_start / row_ptr");
+    if (n_pools > 0 && (!pool_donors || !pair_penalty)) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_donors / pair_penalty");
+    if (c->B > 0 && !pool_of_barcode) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_of_barcode");
+    if (pool_start[0] != 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_start[0] is %lld, not 0", (long long)pool_start[0]);
+    const long long B = c->B;
+    const int G = c->G;
+    dmx::PoolsPlan plan;
+    plan.with_doublets = with_doublets != 0;
+    plan.n_pools = n_pools;
+    plan.opt_ptr.assign(1, 0);
+    for (int p = 0; p < n_pools; p++) {
+        const long long first = pool_start[p], g = pool_start[p + 1] - first;
+        if (g < 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_start decreases at pool %d", p);
+        if (g == 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool %d is empty", p);
+        for (long long i = 0; i < g; i++) {
+            const long long d = pool_donors[first + i];
+            if (d < 0 || d >= G) return fail(DMX_ERR_INVALID, "dmx_estep_pools: donor %lld of pool %d is outside [0, %d)", d, p, G);
+            if (i > 0 && d <= pool_donors[first + i - 1])
+                return fail(DMX_ERR_INVALID, "dmx_estep_pools: the donors of pool %d are not strictly ascending", p);
+            if (d >= 65536) return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: donor index %lld does not fit the 16 bits of an option's column", d);
+        }
+        const long long options = with_doublets ? g * (g + 1) / 2 : g;
+        if (options > dmx::POOL_MAX_OPTIONS)
+            return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: pool %d has %lld options, more than %d (44 donors with doublets, 1024 without)", p,
+                        options, dmx::POOL_MAX_OPTIONS);
+        // the reference's options for the genotype list (demux.py:175-191): singlets in list order, then the pairs i < j, i-major
+        const int32_t *d = pool_donors + first;
+        for (long long i = 0; i < g; i++) plan.opts.push_back((unsigned)d[i] | (unsigned)d[i] << 16);
+        if (with_doublets)
+            for (long long i = 0; i < g; i++)
+                for (long long j = i + 1; j < g; j++) plan.opts.push_back((unsigned)d[i] | (unsigned)d[j] << 16);
+        plan.pool_size.push_back((int)g);
+        plan.opt_ptr.push_back((long long)plan.opts.size());
+    }
+    if (row_ptr[0] != 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: row_ptr[0] is %lld, not 0", (long long)row_ptr[0]);
+    for (long long b = 0; b < B; b++) {
+        const int p = pool_of_barcode[b];
+        if (p < -1 || p >= n_pools) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_of_barcode[%lld] = %d is outside [-1, %d)", b, p, (int)n_pools);
+        const long long options = p < 0 ? 0 : plan.opt_ptr[(size_t)p + 1] - plan.opt_ptr[(size_t)p];
+        if (row_ptr[b + 1] - row_ptr[b] != options)
+            return fail(DMX_ERR_INVALID, "dmx_estep_pools: row_ptr gives barcode %lld %lld entries, its pool has %lld options", b,
+                        (long long)(row_ptr[b + 1] - row_ptr[b]), options);
+    }
+    plan.pair_penalty = pair_penalty;
+    plan.pool_of_barcode = pool_of_barcode;
+    plan.row_ptr = row_ptr;
+    plan.logits_out = logits_out;
+    plan.probs_out = probs_out;
+    plan.best_option = best_option;
+    plan.best_prob = best_prob;
+    plan.doublet_mass = doublet_mass;
+    return dmx::run_estep_pools(c, plan);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)

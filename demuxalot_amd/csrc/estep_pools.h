@@ -1,0 +1,66 @@
+// estep_pools.h -- the pooled E-step (estep_pools.hip; dmx_steps.cpp: dmx_estep_pools): every barcode is scored against the
+// donors of its own pool only, all pools in one pass over the resident call records and the one resident genotype table.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+struct dmx_ctx;
+
+namespace dmx {
+
+constexpr int POOL_MAX_OPTIONS = 1024;  // the register-resident row of the exact epilogue (estep_epilogue.h: reg_row_sum)
+constexpr int POOL_BUCKETS = 5;         // option slots per lane of a launch: 1, 2, 4, 8, 16
+inline int pool_bucket_slots(int bucket) { return 1 << bucket; }
+inline int pool_bucket_of(int n_options)  // the narrowest instantiation that holds ceil(n_options / 64) slots
+{
+    const int slots = (n_options + 63) / 64;
+    int bucket = 0;
+    while (pool_bucket_slots(bucket) < slots) bucket++;
+    return bucket;
+}
+
+// argument block of k_estep_pools: one launch walks the barcodes of `list`
+struct PoolEstepArgs {
+    const long long *pair_ptr;  // [B + 1] the resident problem's records, as EstepArgs has them
+    const CallPair *pairs;
+    const float *prob;          // [rows, G]
+    unsigned prob_bytes;
+    const int *list;            // [n_list] barcodes of this launch, by decreasing row length
+    long long n_list;
+    const int *pool_of;          // [B] pool of every barcode (-1: none; such a barcode is in no list)
+    const long long *row_ptr;    // [B + 1] first entry of every barcode's compact row
+    const long long *opt_ptr;    // [P + 1] first option of every pool in `opts`
+    const unsigned *opts;        // d1 | d2 << 16 (table columns; a singlet: d1 == d2), the layout of EstepArgs::opt_pairs
+    const int *pool_size;        // [P] donors of the pool = its singlet options
+    const float *pair_penalty;   // [P] logit offset of the pool's pair options
+    float *logits, *post;        // compact rows
+    int *best;                   // [B] first arg-max option inside the pool's list
+    float *best_prob;            // [B]
+    double *pair_mass;           // [B] float64 sum of the pair posteriors in ascending option order
+};
+
+hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs);
+
+// what dmx_estep_pools has validated and laid out on the host
+struct PoolsPlan {
+    bool with_doublets;
+    long long n_pools;
+    std::vector<long long> opt_ptr;    // [P + 1]
+    std::vector<unsigned> opts;
+    std::vector<int> pool_size;        // [P]
+    const float *pair_penalty;         // [P]
+    const int32_t *pool_of_barcode;    // [B]
+    const int64_t *row_ptr;            // [B + 1]
+    float *logits_out, *probs_out;     // nullable
+    int32_t *best_option;              // nullable
+    float *best_prob;
+    double *doublet_mass;
+};
+// the device half: uploads, one launch per non-empty bucket, read-back; -1 / NaN for the barcodes of no pool
+int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan);
+
+}  // namespace dmx

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dmx_ctx.h"
+#include "estep_pools.h"
 
 // ------------------------------------------------------------------------------------
 // HIP runtime
@@ -145,6 +146,7 @@ hipError_t launch_mcombine(hipStream_t, const MstepArgs &, const long long *, lo
                            unsigned long long *, unsigned *, const int *, bool) { return hipSuccess; }
 hipError_t launch_store_slice(hipStream_t, const void *, bool, long long, long long, int, float *) { return hipSuccess; }
 hipError_t launch_estep_packed(hipStream_t, const EstepArgs &) { return hipSuccess; }
+int run_estep_pools(dmx_ctx *, const PoolsPlan &) { return 0; }  // (validated by dmx_estep_pools; nothing is written)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {
     // this one is cheap enough to do for real: it indexes new_rows with what the records hold

@@ -29,6 +29,7 @@ import pandas as pd
 from . import _lib, donor_readout
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
+from .pools import PooledPosteriors, resolve_pools
 
 _MOLECULE_CALL_DTYPE = [('variant_id', 'int32'), ('snp_id', 'int32'), ('compressed_cb', 'int32'),
                         ('molecule_id', 'int32'), ('p_base_wrong', 'float32'), ('p_molecule_aligned_wrong', 'float32')]
@@ -784,6 +785,40 @@ class Demultiplexer:
         logits_df = pd.DataFrame(data=logits, index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
         probs_df = pd.DataFrame(data=probs, index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)  # own Index object, shared labels
         return logits_df, probs_df
+
+    @staticmethod
+    def predict_posteriors_in_pools(chromosome2compressed_snp_calls,
+                                    genotypes,
+                                    barcode_handler,
+                                    barcode2pool,
+                                    pool2donors,
+                                    p_genotype_clip=0.01,
+                                    doublet_prior=0.35) -> PooledPosteriors:
+        """(not in the reference) predict_posteriors with every barcode scored against the donors of its own pool only - a
+        lane, hashtag group or sub-experiment that holds a known subset of the donors -, all pools in one pass over one packed
+        problem and one genotype table.  The frames of a pool (PooledPosteriors.to_dataframes) are, bit for bit, the rows of the
+        pool's barcodes in what the reference's predict_posteriors returns for the pool's genotype sub-list on the same table.
+        :param barcode2pool: barcode -> pool name, or None for "in no pool"; every barcode of the handler has an entry
+        :param pool2donors: pool name -> donor names, in any order (sorted into genotype order); at most 44 donors per pool
+            with doublets, 1024 without
+        ValueError: a duplicate or unknown donor, an empty pool, a barcode without an entry, an unknown pool."""
+        assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
+        assert 0 <= doublet_prior < 1
+        names = list(genotypes.genotype_names)
+        pool_names, pool_columns, pool_of_barcode = resolve_pools(names, barcode_handler.ordered_barcodes, barcode2pool, pool2donors)
+        option_names = [_option_names([names[g] for g in columns], doublet_prior) for columns in pool_columns]
+        # the reference's bonus for the pool's genotype list (demux.py:164-169): the prior doublet share is doublet_prior inside every pool
+        pair_penalty = np.array([Demultiplexer._doublet_penalties(len(columns), doublet_prior)[-1] if len(columns) > 1 else 0.0
+                                 for columns in pool_columns], dtype=np.float32)
+        with shared_context_lock:
+            ctx = get_context()
+            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
+            ctx.set_addition(None)
+            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+            assert np.isfinite(genotype_prob).all()
+            out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty)
+        return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
+                                out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
 
     # ------------------------------------------------------------------------------------
     @staticmethod

@@ -666,6 +666,34 @@ class DeviceContext:
         check(self._lib.dmx_get_allowed_mass(self._h, ptr(start), ptr(options), ptr(mass), ptr(hit)))
         return mass, hit
 
+    def estep_pools(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits=True, fetch_probs=True):
+        """The pooled E-step (include/demux_hip_debug.h: dmx_estep_pools): every barcode against the donors of its own pool.
+        pools: one strictly ascending list of table columns per pool; pool_of_barcode int32[B], -1: in no pool;
+        pair_penalty float32[n_pools].  Returns a dict: row_ptr int64[B + 1], logits / probs (compact float32[row_ptr[B]], or
+        None), best_option int32[B], best_prob float32[B], doublet_mass float64[B].  The resident results of the last
+        E-step are left as they are."""
+        B = self.B
+        sizes = np.array([len(d) for d in pools], dtype=np.int64)
+        pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        donors = as_c(np.concatenate([np.asarray(d, dtype=np.int64).reshape(-1) for d in pools]) if len(pools) else [], np.int32)
+        pool_of_barcode = as_c(pool_of_barcode, np.int32)
+        assert pool_of_barcode.shape == (B,), 'one pool id per barcode'
+        pair_penalty = as_c(pair_penalty, np.float32)
+        assert pair_penalty.shape == (len(pools),), 'one pair penalty per pool'
+        n_options = sizes * (sizes + 1) // 2 if with_doublets else sizes
+        in_pool = (pool_of_barcode >= 0) & (pool_of_barcode < len(pools))  # (ids outside: the library's error)
+        row_len = np.zeros(B, dtype=np.int64)
+        row_len[in_pool] = n_options[pool_of_barcode[in_pool]]
+        row_ptr = np.concatenate([[0], np.cumsum(row_len)]).astype(np.int64)
+        n = int(row_ptr[-1])
+        out = dict(row_ptr=row_ptr, logits=np.empty(n, np.float32) if fetch_logits else None,
+                   probs=np.empty(n, np.float32) if fetch_probs else None, best_option=np.full(B, -1, np.int32),
+                   best_prob=np.full(B, np.nan, np.float32), doublet_mass=np.full(B, np.nan, np.float64))
+        check(self._lib.dmx_estep_pools(self._h, int(bool(with_doublets)), len(pools), ptr(pool_start), ptr(donors), ptr(pair_penalty),
+                                        ptr(pool_of_barcode), ptr(row_ptr), ptr(out['logits']), ptr(out['probs']),
+                                        ptr(out['best_option']), ptr(out['best_prob']), ptr(out['doublet_mass'])))
+        return out
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

@@ -377,6 +377,36 @@ int dmx_get_donor_readout(dmx_ctx *ctx, double *singlet_mass, double *doublet_ma
 int dmx_get_allowed_mass(dmx_ctx *ctx, const int64_t *allowed_start, const int32_t *allowed_options, double *mass,
                          int32_t *best_is_allowed);
 
+/* ------------------------------------------------------------------------- *
+ * The pooled E-step (product API; declared here because demux_hip.h is kept to 64 entry points; csrc/estep_pools.hip).
+ * Every barcode is scored against the donors of its own POOL only - a lane, hashtag group or sub-experiment that holds a known
+ * subset of the donors -, all pools in one pass over the resident call records and the one resident genotype table
+ * (call order: a problem and dmx_probs_from_betas / dmx_set_probs; single GPU).
+ *   pools       pool p is the strictly ascending list pool_donors[pool_start[p] .. pool_start[p + 1]) of g_p >= 1 table columns.
+ *               Its options are the reference's for that genotype list (demux.py:175-191): the g_p singlets in list order, then,
+ *               with_doublets, the pairs (i < j), i-major: K_p = g_p or g_p (g_p + 1) / 2 options, at most 1024 (44 donors with
+ *               doublets, 1024 without).
+ *   logit       logit[b, k] = f32(f64(pen) + sum over the calls of b in their stored order of f64(log_f32(q keep + floor))),
+ *               q = prob[v, d] for a singlet and (prob[v, d1] + prob[v, d2]) * 0.5f for a pair, pen = 0 for a singlet and
+ *               pair_penalty[p] for a pair: the exact E-step's arithmetic, whatever dmx_set_estep_mode says.  The posterior
+ *               row is the float32 softmax of dmx_estep's exact forms.  So the row of a barcode of pool p equals, bit for bit,
+ *               what the reference computes for the genotype list of p on the column subset of the same table.
+ *   rows        compact: barcode b owns entries row_ptr[b] .. row_ptr[b + 1) of logits_out / probs_out (float32[row_ptr[B]],
+ *               nullable), K_p of them, none when pool_of_barcode[b] == -1 (in no pool).
+ *   read-outs   per barcode, each nullable: best_option = the first arg-max inside the pool's option list (ties to the lower
+ *               index, NaN never wins) with its posterior best_prob; doublet_mass = the pair posteriors widened to float64 and
+ *               added sequentially in ascending option order (0 without doublets).  A barcode in no pool gets -1 / NaN / NaN.
+ * Checked on the host before anything is launched.  DMX_ERR_INVALID: pool_start[0] != 0 or decreasing, an empty pool, donors not
+ * strictly ascending or outside [0, G), a pool id outside [-1, n_pools), a row_ptr other than the pool sizes imply, no problem or
+ * no table.  DMX_ERR_UNSUPPORTED: a pool of more than 1024 options, a communicator attached.  The resident results of the last
+ * dmx_estep / dmx_em are left as they are; the pass is counted in the DMX_T_ESTEP slot of dmx_get_timings.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_pools(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                    const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                    const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                    float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                    int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */);
+
 #ifdef __cplusplus
 }
 #endif
