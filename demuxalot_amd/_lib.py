@@ -154,6 +154,8 @@ DEBUG_SIGNATURES = {
     'dmx_get_donor_readout': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     'dmx_get_allowed_mass': (c_int, [_P, _P, _P, _P, _P]),
     'dmx_estep_pools': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'dmx_estep_pools_resident': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'dmx_em_pools': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings

@@ -867,41 +867,45 @@ int dmx_estep(dmx_ctx *c, int with_doublets, const float *penalties, const void 
     return 0;
 }
 
-// The pooled E-step (estep_pools.hip).  Everything is checked here, on the host, before anything is uploaded or launched; the
-// context's resident results of the last dmx_estep are not touched.
-int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
-                    const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
-                    float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass)
+// The pooled E-step (estep_pools.hip).  Everything is checked here, on the host, before anything is uploaded or launched: one
+// function for dmx_estep_pools, dmx_estep_pools_resident and dmx_em_pools.  resident: the entry leaves the dense singlet posteriors in
+// the context (single GPU, no communicator).
+static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_betas, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                      const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                      float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, dmx::PoolsPlan &plan)
 {
-    DMX_TRY(bind(c));
-    DMX_TRY(need(c, c->have_problem && c->have_probs, "genotype probabilities (dmx_probs_from_betas / dmx_set_probs) before dmx_estep_pools"));
-    if (c->nranks > 1) return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: single GPU only");
-    if (with_doublets != 0 && with_doublets != 1) return fail(DMX_ERR_INVALID, "dmx_estep_pools: with_doublets must be 0 or 1");
-    if (n_pools < 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: negative n_pools");
-    if (!pool_start || !row_ptr) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_start / row_ptr");
-    if (n_pools > 0 && (!pool_donors || !pair_penalty)) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_donors / pair_penalty");
-    if (c->B > 0 && !pool_of_barcode) return fail(DMX_ERR_INVALID, "dmx_estep_pools: null pool_of_barcode");
-    if (pool_start[0] != 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_start[0] is %lld, not 0", (long long)pool_start[0]);
+    if (need_betas) {
+        if (!(c->have_problem && c->have_betas)) return fail(DMX_ERR_INVALID, "call order: dmx_set_problem + dmx_set_betas before %s", who);
+    } else if (!(c->have_problem && c->have_probs)) {
+        return fail(DMX_ERR_INVALID, "call order: genotype probabilities (dmx_probs_from_betas / dmx_set_probs) before %s", who);
+    }
+    if (c->nranks > 1) return fail(DMX_ERR_UNSUPPORTED, "%s: single GPU only", who);
+    if (resident && c->attached()) return fail(DMX_ERR_UNSUPPORTED, "%s: a context with a communicator attached is not supported", who);
+    if (with_doublets != 0 && with_doublets != 1) return fail(DMX_ERR_INVALID, "%s: with_doublets must be 0 or 1", who);
+    if (n_pools < 0) return fail(DMX_ERR_INVALID, "%s: negative n_pools", who);
+    if (!pool_start || !row_ptr) return fail(DMX_ERR_INVALID, "%s: null pool_start / row_ptr", who);
+    if (n_pools > 0 && (!pool_donors || !pair_penalty)) return fail(DMX_ERR_INVALID, "%s: null pool_donors / pair_penalty", who);
+    if (c->B > 0 && !pool_of_barcode) return fail(DMX_ERR_INVALID, "%s: null pool_of_barcode", who);
+    if (pool_start[0] != 0) return fail(DMX_ERR_INVALID, "%s: pool_start[0] is %lld, not 0", who, (long long)pool_start[0]);
     const long long B = c->B;
     const int G = c->G;
-    dmx::PoolsPlan plan;
     plan.with_doublets = with_doublets != 0;
     plan.n_pools = n_pools;
     plan.opt_ptr.assign(1, 0);
     for (int p = 0; p < n_pools; p++) {
         const long long first = pool_start[p], g = pool_start[p + 1] - first;
-        if (g < 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_start decreases at pool %d", p);
-        if (g == 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool %d is empty", p);
+        if (g < 0) return fail(DMX_ERR_INVALID, "%s: pool_start decreases at pool %d", who, p);
+        if (g == 0) return fail(DMX_ERR_INVALID, "%s: pool %d is empty", who, p);
         for (long long i = 0; i < g; i++) {
             const long long d = pool_donors[first + i];
-            if (d < 0 || d >= G) return fail(DMX_ERR_INVALID, "dmx_estep_pools: donor %lld of pool %d is outside [0, %d)", d, p, G);
+            if (d < 0 || d >= G) return fail(DMX_ERR_INVALID, "%s: donor %lld of pool %d is outside [0, %d)", who, d, p, G);
             if (i > 0 && d <= pool_donors[first + i - 1])
-                return fail(DMX_ERR_INVALID, "dmx_estep_pools: the donors of pool %d are not strictly ascending", p);
-            if (d >= 65536) return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: donor index %lld does not fit the 16 bits of an option's column", d);
+                return fail(DMX_ERR_INVALID, "%s: the donors of pool %d are not strictly ascending", who, p);
+            if (d >= 65536) return fail(DMX_ERR_UNSUPPORTED, "%s: donor index %lld does not fit the 16 bits of an option's column", who, d);
         }
         const long long options = with_doublets ? g * (g + 1) / 2 : g;
         if (options > dmx::POOL_MAX_OPTIONS)
-            return fail(DMX_ERR_UNSUPPORTED, "dmx_estep_pools: pool %d has %lld options, more than %d (44 donors with doublets, 1024 without)", p,
+            return fail(DMX_ERR_UNSUPPORTED, "%s: pool %d has %lld options, more than %d (44 donors with doublets, 1024 without)", who, p,
                         options, dmx::POOL_MAX_OPTIONS);
         // the reference's options for the genotype list (demux.py:175-191): singlets in list order, then the pairs i < j, i-major
         const int32_t *d = pool_donors + first;
@@ -912,13 +916,13 @@ int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_
         plan.pool_size.push_back((int)g);
         plan.opt_ptr.push_back((long long)plan.opts.size());
     }
-    if (row_ptr[0] != 0) return fail(DMX_ERR_INVALID, "dmx_estep_pools: row_ptr[0] is %lld, not 0", (long long)row_ptr[0]);
+    if (row_ptr[0] != 0) return fail(DMX_ERR_INVALID, "%s: row_ptr[0] is %lld, not 0", who, (long long)row_ptr[0]);
     for (long long b = 0; b < B; b++) {
         const int p = pool_of_barcode[b];
-        if (p < -1 || p >= n_pools) return fail(DMX_ERR_INVALID, "dmx_estep_pools: pool_of_barcode[%lld] = %d is outside [-1, %d)", b, p, (int)n_pools);
+        if (p < -1 || p >= n_pools) return fail(DMX_ERR_INVALID, "%s: pool_of_barcode[%lld] = %d is outside [-1, %d)", who, b, p, (int)n_pools);
         const long long options = p < 0 ? 0 : plan.opt_ptr[(size_t)p + 1] - plan.opt_ptr[(size_t)p];
         if (row_ptr[b + 1] - row_ptr[b] != options)
-            return fail(DMX_ERR_INVALID, "dmx_estep_pools: row_ptr gives barcode %lld %lld entries, its pool has %lld options", b,
+            return fail(DMX_ERR_INVALID, "%s: row_ptr gives barcode %lld %lld entries, its pool has %lld options", who, b,
                         (long long)(row_ptr[b + 1] - row_ptr[b]), options);
     }
     plan.pair_penalty = pair_penalty;
@@ -929,7 +933,45 @@ int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_
     plan.best_option = best_option;
     plan.best_prob = best_prob;
     plan.doublet_mass = doublet_mass;
+    return 0;
+}
+
+// what a dense pooled E-step writes into: the context's own result arrays with K = G, the [B, G] posteriors zeroed once - the kernel
+// writes the columns of a barcode's pool only, and pool membership does not change inside a call
+static int begin_dense_pools(dmx_ctx *c)
+{
+    const std::vector<float> zeros((size_t)std::max(c->G, 1), 0.0f);
+    DMX_TRY(ensure_options(c, 0, zeros.data()));
+    const size_t bg = (size_t)c->B * c->G;
+    HIP_TRY(hipMemsetAsync(c->d_post.p, 0, sizeof(float) * (bg ? bg : 1), c->stream));
+    c->have_post = false;  // (until the first dense E-step has run)
+    return 0;
+}
+
+int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                    const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                    float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass)
+{
+    DMX_TRY(bind(c));
+    dmx::PoolsPlan plan;
+    DMX_TRY(plan_pools(c, "dmx_estep_pools", false, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
+                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
     return dmx::run_estep_pools(c, plan);
+}
+
+int dmx_estep_pools_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                             const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                             float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass)
+{
+    DMX_TRY(bind(c));
+    dmx::PoolsPlan plan;
+    DMX_TRY(plan_pools(c, "dmx_estep_pools_resident", true, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode,
+                       row_ptr, logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+    DMX_TRY(begin_dense_pools(c));
+    dmx::PoolsRunPtr run;
+    DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
+    DMX_TRY(dmx::launch_estep_pools_pass(c, *run, 2.0f));  // (the floor of a squaring M-step; run_mstep rebuilds for another power)
+    return dmx::read_back_estep_pools(c, *run);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)
@@ -977,6 +1019,39 @@ int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, 
     DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// dmx_em with the pooled E-step in place of the full-table one: P-step, dense pooled E-step, M-step, all on the device; the host
+// round trip of the pools (lists, uploads, result buffers) is paid once, the read-back once after the last E-step.
+int dmx_em_pools(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                 const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float power,
+                 float *logits_out, float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, float *addition_out)
+{
+    DMX_TRY(bind(c));
+    dmx::PoolsPlan plan;
+    DMX_TRY(plan_pools(c, "dmx_em_pools", true, true, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
+                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+    if (n_iterations < 1) return fail(DMX_ERR_INVALID, "dmx_em_pools: n_iterations must be >= 1");
+    DMX_TRY(begin_dense_pools(c));
+    const size_t vg = (size_t)c->V * c->G;
+    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));  // demux.py:86
+    c->incr_valid = false;
+    c->add_is_zero = true;
+    c->add_partial = false;
+    dmx::PoolsRunPtr run;
+    DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
+    for (int it = 0; it < n_iterations; it++) {
+        DMX_TRY(run_pstep(c, lo, hi, true, false));
+        DMX_TRY(dmx::launch_estep_pools_pass(c, *run, power));
+        if (it + 1 < n_iterations) {  // the M-step after the last yield is dead
+            c->msteps_ahead = n_iterations - 1 - it;
+            const int rc_m = run_mstep(c, power);
+            c->msteps_ahead = 0;
+            if (rc_m) return rc_m;
+        }
+    }
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
+    return dmx::read_back_estep_pools(c, *run);
 }
 
 int dmx_run_iterations(dmx_ctx *c, int n_iterations, float lo, float hi, float power)

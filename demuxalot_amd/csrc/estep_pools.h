@@ -2,6 +2,7 @@
 // donors of its own pool only, all pools in one pass over the resident call records and the one resident genotype table.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -41,9 +42,12 @@ struct PoolEstepArgs {
     int *best;                   // [B] first arg-max option inside the pool's list
     float *best_prob;            // [B]
     double *pair_mass;           // [B] float64 sum of the pair posteriors in ascending option order
+    float *dense;                // [B, G] the DENSE form only: a barcode's singlet posteriors at the table columns of its pool's donors.
+    int G;                       //        The kernel writes nothing else of the row: the host zeroes the matrix once per call.
 };
 
-hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs);
+// dense: the form that also leaves the singlet posteriors in a.dense (learning within pools: the M-step's input)
+hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs, bool dense = false);
 
 // what dmx_estep_pools has validated and laid out on the host
 struct PoolsPlan {
@@ -60,7 +64,22 @@ struct PoolsPlan {
     float *best_prob;
     double *doublet_mass;
 };
-// the device half: uploads, one launch per non-empty bucket, read-back; -1 / NaN for the barcodes of no pool
+// The device half in three parts, so that a call of several E-steps (dmx_em_pools) pays the host round trip once.
+//   prepare    the download of the context's `order`, the bucket lists, every upload, the compact result buffers; `plan` outlives the run
+//   launch     one launch per non-empty bucket.  A dense run writes the singlet posteriors into the context's own d_post as [B, G]
+//              (the caller has set K = G and zeroed it: dmx_steps.cpp, begin_dense_pools), rebuilds d_nz / d_first with the floor of
+//              `power` and leaves the context as run_estep leaves it for run_mstep
+//   read back  the compact rows and read-outs; -1 / NaN for the barcodes of no pool
+// The run holds its temporaries (device_scratch.h) until it is destroyed.
+struct PoolsRun;
+struct PoolsRunDeleter {
+    void operator()(PoolsRun *run) const;
+};
+typedef std::unique_ptr<PoolsRun, PoolsRunDeleter> PoolsRunPtr;
+int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunPtr &run);
+int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &run, float power);
+int read_back_estep_pools(dmx_ctx *c, PoolsRun &run);
+// the three in a row without the dense form: dmx_estep_pools
 int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan);
 
 }  // namespace dmx

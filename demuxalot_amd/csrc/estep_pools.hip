@@ -4,6 +4,9 @@
 // reference computes for the genotype list of its pool on the column subset of the same table.  What differs from
 // k_estep_direct's 64-lane path is where a lane's two table columns come from - the option list of the barcode's pool instead
 // of the one global list - and that the rows are compact: row_ptr[b] .. row_ptr[b + 1].
+// Learning within pools (dmx_estep_pools_resident, dmx_em_pools) runs the DENSE form of the same kernel, which also
+// leaves the singlet posteriors as a [B, G] matrix for the M-step; the host half is prepare / launch / read back, so that a call of
+// several E-steps prepares and reads back once.
 #include <hip/hip_runtime.h>
 
 #include <limits>
@@ -23,7 +26,9 @@ constexpr int NO_OPTION = 0x7FFFFFFF;
 // One wavefront per barcode.  Lane l, slot s takes option l + 64 s of the barcode's pool; slots entirely past the pool's last
 // option are skipped wave-uniformly.  Everything about the row and the pool lives in SGPRs: records by scalar loads, a call's row
 // offset as the scalar offset of the buffer loads on the table, the lane's two column offsets fixed for the whole row.
-template <int A, bool PAIRS, int U>
+// DENSE: the lanes that hold the pool's singlet options also store their posterior at the donor's table column of the barcode's row
+// of a.dense ([B, G]: what the M-step reads).  Nothing else of that row is written here - the other columns are the host's zeros.
+template <int A, bool PAIRS, int U, bool DENSE>
 __global__ __launch_bounds__(256) void k_estep_pools(PoolEstepArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -122,42 +127,78 @@ __global__ __launch_bounds__(256) void k_estep_pools(PoolEstepArgs a)
         a.best_prob[b] = bi != NO_OPTION ? bv : __builtin_nanf("");
         a.pair_mass[b] = mass;
     }
+    if (DENSE) {
+        // with pairs a pool has at most 44 donors (POOL_MAX_OPTIONS): its singlets are all in slot 0
+        static_assert(POOL_MAX_OPTIONS < 64 * 65 / 2, "a pool with pairs and 64 donors or more: singlets beyond slot 0");
+        constexpr int SINGLET_SLOTS = PAIRS ? 1 : A;
+        float *__restrict__ out = a.dense + (long long)b * a.G;
+#pragma unroll
+        for (int s = 0; s < SINGLET_SLOTS; s++)
+            if (valid[s] && kk[s] < n_single) out[o1[s] >> 2] = post[s];
+    }
 }
 
-template <int A, int U>
-void launch_one(hipStream_t st, const PoolEstepArgs &a, bool pairs)
+template <int A, int U, bool DENSE>
+void launch_form(hipStream_t st, const PoolEstepArgs &a, bool pairs)
 {
     const dim3 grid((unsigned)((a.n_list + 3) / 4)), block(256);
     if (pairs)
-        hipLaunchKernelGGL((k_estep_pools<A, true, U>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((k_estep_pools<A, true, U, DENSE>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((k_estep_pools<A, false, U>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((k_estep_pools<A, false, U, DENSE>), grid, block, 0, st, a);
+}
+
+template <int A, int U>
+void launch_one(hipStream_t st, const PoolEstepArgs &a, bool pairs, bool dense)
+{
+    if (dense)
+        launch_form<A, U, true>(st, a, pairs);
+    else
+        launch_form<A, U, false>(st, a, pairs);
 }
 
 }  // namespace
 
 // calls per batch as k_estep_direct's exact 64-lane launches have them (kernels.hip: launch_estep)
-hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs)
+hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs, bool dense)
 {
     if (a.n_list == 0) return hipSuccess;
+    if (dense && (a.dense == nullptr || a.G <= 0)) return hipErrorInvalidValue;
     switch (slots) {
-    case 1: launch_one<1, 8>(st, a, pairs); break;
-    case 2: launch_one<2, 4>(st, a, pairs); break;
-    case 4: launch_one<4, 2>(st, a, pairs); break;
-    case 8: launch_one<8, 2>(st, a, pairs); break;
-    case 16: launch_one<16, 2>(st, a, pairs); break;
+    case 1: launch_one<1, 8>(st, a, pairs, dense); break;
+    case 2: launch_one<2, 4>(st, a, pairs, dense); break;
+    case 4: launch_one<4, 2>(st, a, pairs, dense); break;
+    case 8: launch_one<8, 2>(st, a, pairs, dense); break;
+    case 16: launch_one<16, 2>(st, a, pairs, dense); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
+// what a pooled call keeps on the device between its parts (estep_pools.h)
+struct PoolsRun {
+    scratch::Scratch sc;
+    const PoolsPlan *plan;
+    PoolEstepArgs a = {};
+    int *d_lists[POOL_BUCKETS] = {};
+    long long n_lists[POOL_BUCKETS] = {};
+    long long n_values = 0;
+    bool dense = false;
+    PoolsRun(dmx_ctx *c, const PoolsPlan *p) : sc(c), plan(p) {}
+};
+
+void PoolsRunDeleter::operator()(PoolsRun *run) const { delete run; }
+
+int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunPtr &run)
 {
     using namespace dmx::scratch;
     using namespace dmx::host;
     const long long B = c->B, P = plan.n_pools;
     const hipStream_t st = c->stream;
-    const long long n_values = B > 0 ? (long long)plan.row_ptr[B] : 0;
+    run.reset(new PoolsRun(c, &plan));
+    PoolsRun &r = *run;
+    r.dense = dense;
+    r.n_values = B > 0 ? (long long)plan.row_ptr[B] : 0;
 
     // the barcodes of every bucket, longest rows first: the context's `order` filtered, so a launch's tail is its shortest rows
     std::vector<int> order((size_t)B);
@@ -173,8 +214,8 @@ int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
         lists[pool_bucket_of((int)(plan.opt_ptr[(size_t)p + 1] - plan.opt_ptr[(size_t)p]))].push_back(b);
     }
 
-    Scratch sc(c);
-    PoolEstepArgs a = {};
+    Scratch &sc = r.sc;
+    PoolEstepArgs &a = r.a;
     a.pair_ptr = c->d_pair_ptr.p;
     a.pairs = c->d_call_pairs.p;
     a.prob = c->d_prob.p;
@@ -196,24 +237,57 @@ int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
     a.pair_penalty = d_pen;
     a.pool_of = d_pool_of;
     a.row_ptr = d_row_ptr;
-    DMX_TRY(sc.get(&a.logits, (size_t)n_values));
-    DMX_TRY(sc.get(&a.post, (size_t)n_values));
+    DMX_TRY(sc.get(&a.logits, (size_t)r.n_values));
+    DMX_TRY(sc.get(&a.post, (size_t)r.n_values));
     DMX_TRY(sc.get(&a.best, (size_t)B));
     DMX_TRY(sc.get(&a.best_prob, (size_t)B));
     DMX_TRY(sc.get(&a.pair_mass, (size_t)B));
-    int *d_lists[POOL_BUCKETS];
-    for (int k = 0; k < POOL_BUCKETS; k++) DMX_TRY(upload(sc, &d_lists[k], lists[k].data(), lists[k].size(), st));
+    a.G = c->G;
+    for (int k = 0; k < POOL_BUCKETS; k++) {
+        DMX_TRY(upload(sc, &r.d_lists[k], lists[k].data(), lists[k].size(), st));
+        r.n_lists[k] = (long long)lists[k].size();
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // `lists` are locals
+    return 0;
+}
 
+int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &r, float power)
+{
+    using namespace dmx::host;
+    const hipStream_t st = c->stream;
+    PoolEstepArgs a = r.a;
+    a.dense = r.dense ? c->d_post.p : nullptr;  // [B, G]: K = G
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
     timer_begin(c, DMX_T_ESTEP, &ev);
     for (int k = 0; k < POOL_BUCKETS; k++) {
-        a.list = d_lists[k];
-        a.n_list = (long long)lists[k].size();
-        HIP_TRY(launch_estep_pools(st, a, pool_bucket_slots(k), plan.with_doublets));
+        a.list = r.d_lists[k];
+        a.n_list = r.n_lists[k];
+        HIP_TRY(launch_estep_pools(st, a, pool_bucket_slots(k), r.plan->with_doublets, r.dense));
+    }
+    if (r.dense) {
+        // the bitmap and the codes of the M-step from the [B, G] matrix, with the floor a full-table E-step of this power takes
+        // (dmx_steps.cpp: fill_estep_args); the context as run_estep leaves it, without statistics of the dense calls
+        const float floor = power == 2.0f ? NZ_FLOOR_SQUARE : 0.0f;
+        HIP_TRY(launch_rebuild_nz(st, c->d_post.p, c->B, c->G, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
+        c->post_gathered = false;
+        c->dense_stat_valid = false;
+        c->nz_floor = floor;
+        c->guard_ran = false;
+        c->have_post = true;
+        c->logits_readable = false;  // (d_logits holds nothing of this pass)
     }
     timer_end(c, DMX_T_ESTEP, ev);
+    return 0;
+}
 
+int read_back_estep_pools(dmx_ctx *c, PoolsRun &r)
+{
+    using namespace dmx::host;
+    const long long B = c->B, n_values = r.n_values;
+    const hipStream_t st = c->stream;
+    const PoolsPlan &plan = *r.plan;
+    const PoolEstepArgs &a = r.a;
     if (plan.logits_out && n_values) HIP_TRY(hipMemcpyAsync(plan.logits_out, a.logits, sizeof(float) * (size_t)n_values, hipMemcpyDeviceToHost, st));
     if (plan.probs_out && n_values) HIP_TRY(hipMemcpyAsync(plan.probs_out, a.post, sizeof(float) * (size_t)n_values, hipMemcpyDeviceToHost, st));
     if (plan.best_option && B) HIP_TRY(hipMemcpyAsync(plan.best_option, a.best, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
@@ -227,6 +301,14 @@ int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
         if (plan.doublet_mass) plan.doublet_mass[b] = std::numeric_limits<double>::quiet_NaN();
     }
     return 0;
+}
+
+int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
+{
+    PoolsRunPtr run;
+    DMX_TRY(prepare_estep_pools(c, plan, false, run));
+    DMX_TRY(launch_estep_pools_pass(c, *run, 2.0f));
+    return read_back_estep_pools(c, *run);
 }
 
 }  // namespace dmx

@@ -147,6 +147,19 @@ hipError_t launch_mcombine(hipStream_t, const MstepArgs &, const long long *, lo
 hipError_t launch_store_slice(hipStream_t, const void *, bool, long long, long long, int, float *) { return hipSuccess; }
 hipError_t launch_estep_packed(hipStream_t, const EstepArgs &) { return hipSuccess; }
 int run_estep_pools(dmx_ctx *, const PoolsPlan &) { return 0; }  // (validated by dmx_estep_pools; nothing is written)
+struct PoolsRun {};
+void PoolsRunDeleter::operator()(PoolsRun *run) const { delete run; }
+int prepare_estep_pools(dmx_ctx *, const PoolsPlan &, bool, PoolsRunPtr &run)
+{
+    run.reset(new PoolsRun);
+    return 0;
+}
+int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &, float)
+{
+    c->have_post = true;
+    return 0;
+}
+int read_back_estep_pools(dmx_ctx *, PoolsRun &) { return 0; }
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {
     // this one is cheap enough to do for real: it indexes new_rows with what the records hold

@@ -804,12 +804,8 @@ class Demultiplexer:
         ValueError: a duplicate or unknown donor, an empty pool, a barcode without an entry, an unknown pool."""
         assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
         assert 0 <= doublet_prior < 1
-        names = list(genotypes.genotype_names)
-        pool_names, pool_columns, pool_of_barcode = resolve_pools(names, barcode_handler.ordered_barcodes, barcode2pool, pool2donors)
-        option_names = [_option_names([names[g] for g in columns], doublet_prior) for columns in pool_columns]
-        # the reference's bonus for the pool's genotype list (demux.py:164-169): the prior doublet share is doublet_prior inside every pool
-        pair_penalty = np.array([Demultiplexer._doublet_penalties(len(columns), doublet_prior)[-1] if len(columns) > 1 else 0.0
-                                 for columns in pool_columns], dtype=np.float32)
+        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
         with shared_context_lock:
             ctx = get_context()
             _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
@@ -819,6 +815,90 @@ class Demultiplexer:
             out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty)
         return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                 out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
+
+    @staticmethod
+    def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):
+        """What the pooled entry points share: (pool names, per pool its table columns, pool_of_barcode, per pool its option names,
+        per pool the reference's bonus for its genotype list - demux.py:164-169: the prior doublet share is doublet_prior inside
+        every pool)."""
+        names = list(genotypes.genotype_names)
+        pool_names, pool_columns, pool_of_barcode = resolve_pools(names, barcode_handler.ordered_barcodes, barcode2pool, pool2donors)
+        option_names = [_option_names([names[g] for g in columns], doublet_prior) for columns in pool_columns]
+        pair_penalty = np.array([Demultiplexer._doublet_penalties(len(columns), doublet_prior)[-1] if len(columns) > 1 else 0.0
+                                 for columns in pool_columns], dtype=np.float32)
+        return pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty
+
+    @staticmethod
+    def learn_genotypes_in_pools(chromosome2compressed_snp_calls,
+                                 genotypes,
+                                 barcode_handler,
+                                 barcode2pool,
+                                 pool2donors,
+                                 n_iterations=5,
+                                 p_genotype_clip=0.01,
+                                 doublet_prior=0.) -> Tuple[object, PooledPosteriors]:
+        """(not in the reference) learn_genotypes with every barcode scored against the donors of its own pool only: the
+        reference's loop (demux.py:86-118) with the E-step of predict_posteriors_in_pools, and posterior 0 for the donors outside
+        a barcode's pool.  A barcode in no pool contributes nothing; a donor in no pool keeps its betas.  With one all-donor pool
+        this is learn_genotypes itself.  The whole loop runs on the GPU (dmx_em_pools).
+        :param barcode2pool, pool2donors: as in predict_posteriors_in_pools (same ValueErrors)
+        :return: learnt genotypes (betas = raw betas + the addition used by the last E-step) and the PooledPosteriors of the
+            last iteration."""
+        assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
+        assert 0 <= doublet_prior < 1
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        with shared_context_lock:
+            ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
+                                          fetch_betas=False)
+            out = ctx.em_pools(n_iterations, p_genotype_clip, pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty,
+                               contribution_power=Demultiplexer.contribution_power, fetch_addition=False)
+            learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
+        pooled = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
+                                  out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
+        return genotypes._with_betas(learnt_betas, _take=True), pooled
+
+    @staticmethod
+    def staged_genotype_learning_in_pools(chromosome2compressed_snp_calls,
+                                          genotypes,
+                                          barcode_handler,
+                                          barcode2pool,
+                                          pool2donors,
+                                          n_iterations=5,
+                                          p_genotype_clip=0.01,
+                                          doublet_prior=0.):
+        """Generator over the iterations of learn_genotypes_in_pools, shaped like staged_genotype_learning: yields
+        (PooledPosteriors, debug dict with 'genotype_prior', 'genotype_addition'); the yielded addition is the one the
+        iteration's E-step used.  The EM state lives on the GPU between yields, in a device context private to this generator."""
+        assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
+        assert 0 <= doublet_prior < 1
+        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+
+        ctx = acquire_private_context()
+        try:
+            _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
+            genotype_addition = np.zeros_like(prior_betas)
+            ctx.set_addition(None)
+            for _iteration in range(n_iterations):
+                ctx.probs_from_betas(p_genotype_clip, fetch=False)
+                out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, resident=True)
+                pooled = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
+                                          out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
+                yield pooled, {
+                    'genotype_prior': prior_betas,
+                    'genotype_addition': genotype_addition,
+                }
+                genotype_addition = ctx.mstep(Demultiplexer.contribution_power)
+        except GeneratorExit:  # the consumer stopped early: nothing wrong with the context
+            release_private_context(ctx)
+            raise
+        except BaseException:
+            release_private_context(ctx, failed=True)
+            raise
+        else:
+            release_private_context(ctx)
 
     # ------------------------------------------------------------------------------------
     @staticmethod

@@ -666,12 +666,8 @@ class DeviceContext:
         check(self._lib.dmx_get_allowed_mass(self._h, ptr(start), ptr(options), ptr(mass), ptr(hit)))
         return mass, hit
 
-    def estep_pools(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits=True, fetch_probs=True):
-        """The pooled E-step (include/demux_hip_debug.h: dmx_estep_pools): every barcode against the donors of its own pool.
-        pools: one strictly ascending list of table columns per pool; pool_of_barcode int32[B], -1: in no pool;
-        pair_penalty float32[n_pools].  Returns a dict: row_ptr int64[B + 1], logits / probs (compact float32[row_ptr[B]], or
-        None), best_option int32[B], best_prob float32[B], doublet_mass float64[B].  The resident results of the last
-        E-step are left as they are."""
+    def _pools_arguments(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs):
+        """(the pool arguments of the dmx_estep_pools family as ctypes pointers, the arrays behind them, the result dict)."""
         B = self.B
         sizes = np.array([len(d) for d in pools], dtype=np.int64)
         pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -689,9 +685,40 @@ class DeviceContext:
         out = dict(row_ptr=row_ptr, logits=np.empty(n, np.float32) if fetch_logits else None,
                    probs=np.empty(n, np.float32) if fetch_probs else None, best_option=np.full(B, -1, np.int32),
                    best_prob=np.full(B, np.nan, np.float32), doublet_mass=np.full(B, np.nan, np.float64))
-        check(self._lib.dmx_estep_pools(self._h, int(bool(with_doublets)), len(pools), ptr(pool_start), ptr(donors), ptr(pair_penalty),
-                                        ptr(pool_of_barcode), ptr(row_ptr), ptr(out['logits']), ptr(out['probs']),
-                                        ptr(out['best_option']), ptr(out['best_prob']), ptr(out['doublet_mass'])))
+        keep = (pool_start, donors, pair_penalty, pool_of_barcode, row_ptr)
+        pool_args = (len(pools), ptr(pool_start), ptr(donors), ptr(pair_penalty), ptr(pool_of_barcode), ptr(row_ptr))
+        return pool_args, keep, out
+
+    @staticmethod
+    def _pools_results(out):
+        return (ptr(out['logits']), ptr(out['probs']), ptr(out['best_option']), ptr(out['best_prob']), ptr(out['doublet_mass']))
+
+    def estep_pools(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits=True, fetch_probs=True, resident=False):
+        """The pooled E-step (include/demux_hip_debug.h: dmx_estep_pools): every barcode against the donors of its own pool.
+        pools: one strictly ascending list of table columns per pool; pool_of_barcode int32[B], -1: in no pool;
+        pair_penalty float32[n_pools].  Returns a dict: row_ptr int64[B + 1], logits / probs (compact float32[row_ptr[B]], or
+        None), best_option int32[B], best_prob float32[B], doublet_mass float64[B].  The resident results of the last
+        E-step are left as they are - unless resident=True (dmx_estep_pools_resident): then the singlet posteriors are left in
+        the context as a dense [B, G] matrix, zero outside a barcode's pool, so that mstep() may follow and get_probs() returns it."""
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        entry = self._lib.dmx_estep_pools_resident if resident else self._lib.dmx_estep_pools
+        check(entry(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out)))
+        if resident:
+            self.K = self.G
+        return out
+
+    def em_pools(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, contribution_power=2.,
+                 fetch_logits=True, fetch_probs=True, fetch_addition=True):
+        """n_iterations of P-step, pooled E-step and M-step on the device (include/demux_hip_debug.h: dmx_em_pools): em() with every
+        barcode scored against the donors of its own pool, and posterior 0 for the others.  Returns estep_pools()'s dict of the last
+        iteration with one more key, 'addition': float32[V, G], the addition its E-step used (None without fetch_addition).
+        get_learnt_betas() and get_probs() (the dense [B, G] singlet posteriors) work afterwards."""
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        out['addition'] = np.empty((self.V, self.G), dtype=np.float32) if fetch_addition else None
+        check(self._lib.dmx_em_pools(self._h, int(n_iterations), lo, hi, int(bool(with_doublets)), *pool_args, float(contribution_power),
+                                     *self._pools_results(out), ptr(out['addition'])))
+        self.K = self.G
         return out
 
     def synchronize(self):

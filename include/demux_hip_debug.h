@@ -407,6 +407,37 @@ int dmx_estep_pools(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int6
                     float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
                     int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */);
 
+/* ------------------------------------------------------------------------- *
+ * Learning within pools (product API).  The reference's EM loop (demux.py:86-118) with its E-step replaced by the
+ * pooled one: a donor outside a barcode's pool has posterior 0 for that barcode.
+ *   dense       the singlet posteriors of a pooled pass as the M-step reads them: float32[B, G], dense[b, d_p[i]] = row_b[i] for
+ *               i < g_p (p the pool of b), every other entry +0 - a barcode in no pool is a row of zeros and contributes nothing,
+ *               a donor in no pool keeps an all-zero addition column.
+ *   dmx_estep_pools_resident   the arguments, the pass and the results of dmx_estep_pools.  It also leaves `dense` as the context's
+ *               resident posteriors with K = G (and their bitmaps and codes), so that dmx_mstep may follow; dmx_get_probs then
+ *               returns that [B, G] matrix.  The logits of the pass are the compact ones only: dmx_get_logits is refused.
+ *   dmx_em_pools   n_iterations >= 1 of: genotype_prob from betas + addition clipped to [lo, hi] (the addition starts at 0), the
+ *               dense pooled E-step, addition = the M-step of `dense` with `power` - the loop of dmx_em, the M-step after the
+ *               last E-step left out.  The outputs (each nullable) are the last iteration's compact rows and read-outs, as
+ *               dmx_estep_pools defines them, and addition_out float32[V, G], the addition its E-step used.  dmx_get_learnt_betas
+ *               and dmx_get_probs work afterwards.  (call order: a problem and dmx_set_betas / dmx_set_prior_betas)
+ * Exactness: the pooled E-step has no tolerance arithmetic; with dmx_set_exact_additions(ctx, 1) posteriors, logits, additions and
+ * learnt betas are the restated loop's bit for bit; with the default additions the M-step is dmx_mstep's, with its bound.
+ * Both validate exactly as dmx_estep_pools does, before anything is uploaded or launched, and return DMX_ERR_UNSUPPORTED with a
+ * communicator attached (dmx_comm_init*) or more than one rank; dmx_em_pools returns DMX_ERR_INVALID for n_iterations < 1.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_pools_resident(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                             const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                             const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                             float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                             int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */);
+int dmx_em_pools(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools,
+                 const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                 const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */, float power,
+                 float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                 int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                 float *addition_out /* nullable, float32[V, G] */);
+
 #ifdef __cplusplus
 }
 #endif
