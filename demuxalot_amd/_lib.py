@@ -115,6 +115,9 @@ DEBUG_SIGNATURES = {
     'dmx_set_mstep_tiles': (c_int, [_P, c_int]),
     'dmx_get_mstep_form': (c_int, [_P, POINTER(c_int32)]),
     'dmx_get_mstep_tiles_info': (c_int, [_P, POINTER(c_int32), POINTER(c_double)]),
+    'dmx_set_live_floor_on_grid': (c_int, [_P, c_int]),
+    'dmx_get_live_floor': (c_int, [_P, POINTER(c_float), POINTER(c_int64)]),
+    'dmx_debug_get_live_counts': (c_int, [_P, _P]),
     'dmx_test_logf': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_logf_hot': (c_int, [_P, _P, _P, c_int64]),
     'dmx_test_expf': (c_int, [_P, _P, _P, c_int64]),

@@ -464,6 +464,34 @@ int dmx_get_mstep_form(dmx_ctx *c, int32_t *form)
     return 0;
 }
 
+int dmx_set_live_floor_on_grid(dmx_ctx *c, int on_grid)
+{
+    if (!c) return fail(DMX_ERR_INVALID, "null context");
+    c->live_floor_grid = on_grid != 0;
+    return 0;
+}
+
+int dmx_get_live_floor(dmx_ctx *c, float *floor, int64_t *rebuilds)
+{
+    if (!c) return fail(DMX_ERR_INVALID, "null context");
+    if (floor) *floor = c->nz_floor;
+    if (rebuilds) *rebuilds = (int64_t)c->nz_rebuilds;
+    return 0;
+}
+
+int dmx_debug_get_live_counts(dmx_ctx *c, int32_t *counts)
+{
+    DMX_TRY(bind(c));
+    DMX_TRY(need(c, c->have_problem && c->have_post, "an E-step before dmx_debug_get_live_counts"));
+    if (c->G > 64 || c->mshard) return fail(DMX_ERR_UNSUPPORTED, "dmx_debug_get_live_counts: barcode codes exist for G <= 64 on a context that holds its own");
+    if (!counts && c->B > 0) return fail(DMX_ERR_INVALID, "null argument");
+    std::vector<uint2> codes((size_t)c->B);
+    if (c->B) HIP_TRY(hipMemcpyAsync(codes.data(), c->d_first.p, sizeof(uint2) * (size_t)c->B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (long long b = 0; b < c->B; b++) counts[b] = (int32_t)(codes[(size_t)b].y & 127u);
+    return 0;
+}
+
 int dmx_set_mstep_wide_addresses(dmx_ctx *c, int wide)
 {
     if (!c) return fail(DMX_ERR_INVALID, "null context");

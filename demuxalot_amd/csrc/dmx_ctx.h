@@ -234,6 +234,8 @@ struct dmx_ctx {
     DevBuf<double> d_seg_sums;
     long long n_segs = 0, n_split = 0;
     float nz_floor = 0.0f;     // threshold the current d_nz / d_first were built with
+    int live_floor_grid = 1;   // dmx_set_live_floor_on_grid: an E-step ahead of a fixed-point M-step writes them at live_floor_fixed (kernels.h)
+    long long nz_rebuilds = 0; // launches of k_rebuild_nz by run_mstep since dmx_reset_timings (the codes' floor did not fit the M-step's form)
     DevBuf<uint2> d_first;  // [B] {posterior of the lowest live singlet column, count | first live columns} (G <= 64): EstepArgs::first
     DevBuf<unsigned long long> d_dense_calls;  // [1] E-step statistic read by the M-step kernels (kernels.h)
     bool dense_stat_valid = false;

@@ -816,6 +816,7 @@ int dmx_reset_timings(dmx_ctx *c)
     if (c->d_guard_count.p) HIP_TRY(hipMemsetAsync(c->d_guard_count.p + dmx::GS_COARSE_STEPS, 0, 2 * sizeof(unsigned), c->stream));  // + GS_PROBES
     if (c->d_incr_state.p) HIP_TRY(hipMemsetAsync(c->d_incr_state.p + 2 * dmx::IS_WORDS, 0, sizeof(unsigned) * 3, c->stream));  // (word 3: full passes since the install, kept)
     c->guard_rows_total = 0;
+    c->nz_rebuilds = 0;
     for (int s = 0; s < DMX_T_COUNT; s++) {
         timer_flush(c, s);
         c->timers[s].ms = 0.0;

@@ -352,6 +352,37 @@ int prepare_dictionary(dmx_ctx *c, bool pairs, dmx::EstepArgs &a, int *form)
     return 0;
 }
 
+// what the M-step's decisions read (mstep_plan.h), as the context stands: run_mstep's facts, and - asked ahead by run_estep, inside dmx_em /
+// dmx_run_iterations with msteps_ahead already set for it - those of the M-step that follows an E-step (the counters move behind the plan)
+static mplan::Facts mstep_facts(const dmx_ctx *c, float power)
+{
+    mplan::Facts f{};
+    f.mstep_tiles = c->mstep_tiles;
+    f.mstep_incremental = c->mstep_incremental;
+    f.exact_additions = c->exact_additions;
+    f.G = c->G;
+    f.has_calls = c->n_csc > 0;
+    f.power = power;
+    f.attached = c->attached();  // also with one rank: keeps the collective path testable on one GPU
+    f.mshard = c->mshard;
+    f.sliced = c->sliced;
+    f.reduce_f64 = c->reduce_dtype == DMX_F64;
+    f.has_call_pairs = c->d_call_pairs.p != nullptr;
+    f.has_item_variant = c->d_item_variant.p != nullptr;
+    f.has_shift_v = c->d_mt_shift_v.p != nullptr;
+    f.has_incr_state = c->d_incr_state.p != nullptr;
+    f.has_slice_rec = c->d_slice_rec.p != nullptr;
+    f.n_mt = c->n_mt;
+    f.mt_tried = c->mt_tried;
+    f.msteps_done = c->msteps_done;
+    f.msteps_ahead = c->msteps_ahead;
+    f.msteps_expected = c->msteps_expected;
+    f.incr_heavy = c->incr_heavy;
+    f.rows_total = c->rows_total;
+    f.shift_tried = c->mt_shift_tried;
+    return f;
+}
+
 // the argument block of the E-step's kernels as the context stands: no launch chosen yet (fast, segs, the guard's fields and what a
 // launch walks are run_estep's to set from the plan)
 static void fill_estep_args(dmx_ctx *c, dmx::EstepArgs &a, int with_doublets, bool with_prior, int prior_dtype, float power)
@@ -384,7 +415,9 @@ static void fill_estep_args(dmx_ctx *c, dmx::EstepArgs &a, int with_doublets, bo
     a.first = c->G <= 64 ? (c->mshard ? c->d_first_g.p + row_base : c->d_first.p) : nullptr;
     a.post_singlets = c->mshard ? c->d_post_g.p + row_base * c->G : nullptr;
     a.dense_calls = c->G <= 64 ? c->d_dense_calls.p : nullptr;
-    a.nz_floor = power == 2.0f ? dmx::NZ_FLOOR_SQUARE : 0.0f;
+    // codes and bitmap at the floor the M-step that follows admits (kernels.h: live_floor_fixed); the regime statistic at its own
+    a.dense_floor = dmx::live_floor_float64(power);
+    a.nz_floor = c->live_floor_grid && mplan::live_floor_on_grid(mstep_facts(c, power)) ? dmx::live_floor_fixed(power) : a.dense_floor;
     a.B = c->B;
     a.prob_bytes = (unsigned)((unsigned long long)c->prob_rows * c->G * 4ull);
     a.G = c->G;
@@ -638,40 +671,24 @@ int run_mstep(dmx_ctx *c, float power)
     a.power = power;
     a.dense_calls = c->dense_stat_valid && a.post_bytes < (1ull << 32) ? c->d_dense_calls.p : nullptr;
     a.total_calls = 2ull * (unsigned long long)c->n_pairs;
-    if (!a.square && c->nz_floor != 0.0f) {
-        // the E-step assumed a squaring M-step: rebuild the bitmap with the exact `!= 0` rule
-        HIP_TRY(dmx::launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->K, c->G, 0.0f, (mshard ? c->d_nz_g.p : c->d_nz.p) + row_base * Wn,
+    // The codes and the bitmap are rebuilt from the stored posteriors when their floor is above what this M-step admits (the regime
+    // statistic stays the E-step's: it has its own floor).  No launch in steady state: the E-step asked the plan ahead (run_estep).
+    auto rebuild_codes = [&](float floor) -> int {
+        HIP_TRY(dmx::launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->K, c->G, floor, (mshard ? c->d_nz_g.p : c->d_nz.p) + row_base * Wn,
                                        c->G <= 64 ? (mshard ? c->d_first_g.p : c->d_first.p) + row_base : nullptr));
-        c->nz_floor = 0.0f;
+        c->nz_floor = floor;
         c->post_gathered = false;
-    }
+        c->nz_rebuilds++;
+        return 0;
+    };
+    // before the codes travel: the E-step assumed a squaring M-step - the exact `!= 0` rule (whatever the form: live_floor_fixed is
+    // live_floor_float64 for such a power)
+    if (!a.square && c->nz_floor != 0.0f) DMX_TRY(rebuild_codes(0.0f));
     DMX_TRY(gather_posteriors(c));
     c->add_is_zero = false;
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
-    mplan::Facts f{};
-    f.mstep_tiles = c->mstep_tiles;
-    f.mstep_incremental = c->mstep_incremental;
-    f.exact_additions = c->exact_additions;
-    f.G = c->G;
-    f.has_calls = c->n_csc > 0;
-    f.power = power;
-    f.attached = c->attached();  // also with one rank: keeps the collective path testable on one GPU
-    f.mshard = c->mshard;
-    f.sliced = c->sliced;
-    f.reduce_f64 = c->reduce_dtype == DMX_F64;
-    f.has_call_pairs = c->d_call_pairs.p != nullptr;
-    f.has_item_variant = c->d_item_variant.p != nullptr;
-    f.has_shift_v = c->d_mt_shift_v.p != nullptr;
-    f.has_incr_state = c->d_incr_state.p != nullptr;
-    f.has_slice_rec = c->d_slice_rec.p != nullptr;
-    f.n_mt = c->n_mt;
-    f.mt_tried = c->mt_tried;
-    f.msteps_done = c->msteps_done;
-    f.msteps_ahead = c->msteps_ahead;
-    f.msteps_expected = c->msteps_expected;
-    f.incr_heavy = c->incr_heavy;
-    f.rows_total = c->rows_total;
+    mplan::Facts f = mstep_facts(c, power);
     if (mplan::probe_due(f)) {
         unsigned full_passes = 0;
         HIP_TRY(hipMemcpyAsync(&full_passes, c->d_incr_state.p + 2 * dmx::IS_WORDS + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -692,6 +709,10 @@ int run_mstep(dmx_ctx *c, float power)
     f.has_shift_v = c->d_mt_shift_v.p != nullptr;
     const mplan::Launch plan = mplan::launch(f);
     const mplan::Dest dest = mplan::destination(f);
+    // The form is known: a float64 form (1: the work items' float64 sums, the exact additions) reads the codes for the reference's own sum
+    // and takes none written above its floor; the fixed-point forms take either (the dense regime's k_mstep_dense reads no codes at all).
+    // Only a context that is not attached ever holds such codes (mplan::live_floor_on_grid), so nothing has travelled.
+    if (!mplan::grid_floor_admitted(plan) && c->nz_floor > dmx::live_floor_float64(power)) DMX_TRY(rebuild_codes(dmx::live_floor_float64(power)));
     const bool incremental = plan.incr != mplan::INCR_NONE, sharded = plan.incr == mplan::INCR_SHARDED;
     const long long incr_rows = sharded ? c->rows_total : c->B;
     if (incremental) DMX_TRY(ensure_incremental_state(c, sharded, incr_rows, power));
@@ -1004,13 +1025,13 @@ int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, 
     for (int it = 0; it < n_iterations; it++) {
         const bool kept = it + 1 == n_iterations && keep_last;  // somebody can read this E-step's logits
         DMX_TRY(run_pstep(c, lo, hi, true, !kept && it > 0 && ep::coarse_capable(estep_facts(c, with_doublets, false, kept), lo)));  // (iteration 0: the dictionary form)
-        DMX_TRY(run_estep(c, with_doublets, it == 0 && prior_logits != nullptr, prior_dtype, power, kept));
-        if (it + 1 < n_iterations) {  // the M-step after the last yield is dead
-            c->msteps_ahead = n_iterations - 1 - it;
-            const int rc_m = run_mstep(c, power);
-            c->msteps_ahead = 0;
-            if (rc_m) return rc_m;
-        }
+        // (the E-step asks the plan of the M-step behind it for the codes' floor: msteps_ahead as that M-step will find it - 0 behind the
+        // last E-step, whose M-step, if any, is a later call's)
+        c->msteps_ahead = n_iterations - 1 - it;
+        const int rc_e = run_estep(c, with_doublets, it == 0 && prior_logits != nullptr, prior_dtype, power, kept);
+        const int rc_m = rc_e == 0 && it + 1 < n_iterations ? run_mstep(c, power) : rc_e;  // the M-step after the last yield is dead
+        c->msteps_ahead = 0;
+        if (rc_m) return rc_m;
     }
     const size_t bk = (size_t)c->B * c->K;
     DMX_TRY(copy_out(c, logits_out, c->d_logits.p, bk));
@@ -1064,9 +1085,9 @@ int dmx_run_iterations(dmx_ctx *c, int n_iterations, float lo, float hi, float p
     for (int it = 0; it < n_iterations; it++) {
         const bool kept = it + 1 == n_iterations && c->logits_needed;  // somebody can read this E-step's logits
         DMX_TRY(run_pstep(c, lo, hi, true, !kept && ep::coarse_capable(estep_facts(c, with_doublets, false, kept), lo)));
-        DMX_TRY(run_estep(c, with_doublets, false, DMX_F32, power, kept));
-        c->msteps_ahead = n_iterations - it;
-        const int rc_m = run_mstep(c, power);
+        c->msteps_ahead = n_iterations - it;  // (read by the E-step too: the plan of the M-step behind it, for the codes' floor)
+        const int rc_e = run_estep(c, with_doublets, false, DMX_F32, power, kept);
+        const int rc_m = rc_e == 0 ? run_mstep(c, power) : rc_e;
         c->msteps_ahead = 0;
         if (rc_m) return rc_m;
     }

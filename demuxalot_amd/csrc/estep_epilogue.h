@@ -323,6 +323,7 @@ static __device__ __forceinline__ void estep_epilogue(const EstepArgs &a, long l
     const float tot = reg_row_sum<L, A>(x, K, lane, gbase);
     const int W = (a.G + 63) >> 6;
     unsigned long long mine = 0ull;  // L < 64: the group's bitmap of live singlet posteriors, over all slots
+    unsigned long long mine_stat = 0ull;  // ... of those above the regime statistic's floor (EstepArgs::dense_floor <= nz_floor)
     float post[A];
 #pragma unroll
     for (int s = 0; s < A; s++) {
@@ -334,12 +335,15 @@ static __device__ __forceinline__ void estep_epilogue(const EstepArgs &a, long l
             if (a.post_singlets != nullptr && kk[s] < a.G) a.post_singlets[(size_t)b * a.G + kk[s]] = post[s];
         }
         // non-zero bitmap of the singlet columns (the M-step skips exact zeros: (0*keep)^2 = +0)
-        const unsigned long long bal = __ballot(live && valid[s] && (li + L * s) < a.G && !(post[s] <= a.nz_floor));
+        const bool singlet = live && valid[s] && (li + L * s) < a.G;
+        const unsigned long long bal = __ballot(singlet && !(post[s] <= a.nz_floor));
+        const unsigned long long bal_stat = __ballot(singlet && !(post[s] <= a.dense_floor));
         if (L == 64) {
             if (lane == 0 && s < W) a.nz[(size_t)b * W + s] = bal;
-            if (s == 0) mine = bal;
+            if (s == 0) mine = bal, mine_stat = bal_stat;
         } else if (L * s < 64) {
             mine |= ((bal >> gbase) & group_mask<L>()) << ((L * s) & 63);
+            mine_stat |= ((bal_stat >> gbase) & group_mask<L>()) << ((L * s) & 63);
         }
     }
     if (L < 64 && live && li == 0) a.nz[(size_t)b] = mine;
@@ -383,8 +387,9 @@ static __device__ __forceinline__ void estep_epilogue(const EstepArgs &a, long l
 #pragma unroll
         for (int s = 1; s < A; s++) p0 = (g0 >> log2_lanes<L>()) == s ? post[s] : p0;
         if (live && li == (g0 & (L - 1))) a.first[b] = nz_code(mine, p0);
-        // statistic for the M-step's choice of kernel (G <= 64): calls whose barcode has more than 4 live posteriors
-        if (a.dense_calls && live && !redo && li == 0 && __popcll(mine) > 4)
+        // statistic for the M-step's choice of kernel (G <= 64): calls whose barcode has more than 4 posteriors above dense_floor -
+        // a ballot of its own, so that the choice (and the bits that go with the kernel) is the same at whatever floor the codes are
+        if (a.dense_calls && live && !redo && li == 0 && __popcll(mine_stat) > 4)
             atomicAdd(a.dense_calls + 1 + (b & (DENSE_SLOTS - 1)), (unsigned long long)row_calls);
     }
 }

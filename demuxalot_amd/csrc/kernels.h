@@ -2,9 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "demux_hip.h"
 #include "demux_hip_debug.h"
 #include "estep_plan.h"
+#include "fixed_point.h"
 
 namespace dmx {
 
@@ -64,9 +67,10 @@ struct EstepArgs {
     unsigned long long *nz;     // [B, ceil(G/64)] bit g set <=> !(post[b, g] <= nz_floor) (singlet columns; read by the M-step)
     uint2 *first;               // nullable [B] (G <= 64): {bits of post[b, lowest live genotype], count | first four live
                                 // genotypes} (kernels.hip: nz_code): the M-step's one gather per call
-    float nz_floor;             // 0, or NZ_FLOOR_SQUARE when the M-step squares (see below)
+    float nz_floor;             // the floor of nz and first: what the M-step that follows admits - live_floor_float64(power), or
+                                // live_floor_fixed(power) where that M-step sums on the grid (see below; dmx_steps.cpp: run_estep)
     unsigned long long *dense_calls;  // nullable [1 + DENSE_SLOTS]: slot 1 + (b % DENSE_SLOTS) += (padded) calls of every
-                                      // barcode b with more than 4 live posteriors (G <= 64); slot 0: their sum (launch_sum_dense)
+                                      // barcode b with more than 4 posteriors above dense_floor (G <= 64); slot 0: their sum (launch_sum_dense)
     long long B;
     unsigned prob_bytes;        // V * G * 4 (< 4 GiB): extent of the prob table for buffer addressing
     int G;
@@ -139,6 +143,8 @@ struct EstepArgs {
     long long n_long;
     const float *dict;            // [rows, DICT_CAP]
     const unsigned char *codes;   // [rows, dict_code_pitch(G)] 8 x index of every genotype's value in its row's dictionary
+    float dense_floor;            // the floor of the regime statistic (dense_calls): always live_floor_float64(power), so that dense_regime() -
+                                  // which kernel sums, and with it the bits - does not move with nz_floor
 };
 
 // device state of the guarded mode (dmx_ctx::d_guard_count: GS_WORDS + GUARD_SLOTS x unsigned)
@@ -280,8 +286,11 @@ struct MstepArgs {
 // A posterior p <= 2^-80 contributes (p * keep)^2 = +0 exactly for |keep| <= 32 (|p * keep| <= 2^-75, and a
 // float32 square below 2^-150 rounds to +0), so with contribution_power == 2 the M-step may treat it as absent.
 // exp(-55) is about 2^-80: most barcodes then have ONE live posterior instead of one per genotype within 103
-// logit units of the best.
+// logit units of the best.  (The fixed-point forms admit a higher floor: live_floor_fixed below.)
 constexpr float NZ_FLOOR_SQUARE = 8.271806125530277e-25f;  // 2^-80
+// the floor a FLOAT64 M-step form needs of the codes and the bitmap (form 1, the exact additions; k_mstep_dense reads no codes): the
+// reference's sum itself, so only what adds +0 there may be absent; also the floor of the regime statistic (EstepArgs::dense_floor)
+inline float live_floor_float64(float power) { return power == 2.0f ? NZ_FLOOR_SQUARE : 0.0f; }
 
 // Longest run of one variant's calls handled by one wavefront.  Long items keep hot variants in few pieces (every
 // extra piece makes more sums order-sensitive, see k_mcombine), short items keep the tail of the launch short:
@@ -396,6 +405,19 @@ enum { IS_N = 0,        // changed barcodes of this M-step
 // posteriors below this contribute exactly 0 on every tile's grid (shift <= 50): p^power 2^50 <= 2^-2 for p <= 2^(-52 / power) - 2^-26 for the
 // reference's power of 2; powers for which that is not a normal float32: 0 (every bit counts)
 inline float mincr_floor(float power) { return power * 126.0f > 52.0f ? exp2f(-52.0f / power) : 0.0f; }
+// The live floor of a FIXED-POINT M-step (k_mstep_tiles, k_mstep_calls<..., FIXED>, k_mincr_delta*): the codes and the bitmap may leave
+// out every posterior whose contribution is the INTEGER 0 on every grid, not only those whose float32 contribution is +0.
+//   keep = fl32(1 - p_base_wrong) with 0 <= p_base_wrong <= 1 (repack_device.hip: k_validate refuses anything else, in every pack), so
+//   0 <= keep <= KEEP_MAX = 1.  For 0 <= p <= 2^-26: p keep <= 2^-26, rounding is monotone and 2^-26 is a float32, so fl32(p keep) <=
+//   2^-26; its square is <= 2^-52, again a float32, so c = fl32(fl32(p keep)^2) <= 2^-52.  fixed_of adds rint(c 2^shift), shift <=
+//   FIXED_SHIFT_MAX = 50: c 2^shift <= 2^-2 exactly (a power-of-two scaling in float64), and rint of a value in [0, 1/4] is 0.
+//   (2^-25 fails: c 2^50 = 1.  tests/live_floor_check.cpp runs every float32 around the floor through fixed_of.)
+// The codes call a posterior live when !(p <= floor), the incremental comparison ignores a pair when both are < mincr_floor
+// (kernels.hip: mincr_differs), so the floor is the largest float32 BELOW mincr_floor: live <=> p >= 2^-26 in both, and a barcode with one
+// live posterior and an unchanged code has no pair for mincr_differs whatever floor its codes were written at (k_mincr_changes).
+// Powers other than the reference's 2 keep the float64 forms' floor.  Who writes codes at which floor: mstep_plan.h, live_floor_on_grid.
+constexpr float KEEP_MAX = 1.0f;
+inline float live_floor_fixed(float power) { return power == 2.0f ? nextafterf(mincr_floor(power) / KEEP_MAX, 0.0f) : live_floor_float64(power); }
 // t: the tile-major records of the full pass, or null: the fixed-point work-item form (MstepArgs::fixed_shift_v) is the full pass.  The delta
 // pass follows from x: rec_ptr / changed_map of a variant-sharded rank, else the context's own records
 hipError_t launch_mstep_incremental(hipStream_t st, const MstepArgs &a, const MTileArgs *t, const MIncrArgs &x);

@@ -1628,11 +1628,12 @@ __global__ __launch_bounds__(256) void k_softmax_rows(EstepArgs a)
         }
         if (k0 < G) {
             const unsigned long long bal = __ballot(k < G && !(p <= a.nz_floor));
+            const unsigned long long bal_stat = __ballot(k < G && !(p <= a.dense_floor));  // (the regime statistic's own floor: EstepArgs)
             const int word = (k0 >> 6) + wave;
             if (lane == 0 && word < W) a.nz[(size_t)b * W + word] = bal;
             if (a.first && word == 0 && lane == (bal ? __builtin_ctzll(bal) : 0)) {
                 a.first[b] = nz_code(bal, p);
-                if (a.dense_calls && !redo && __popcll(bal) > 4)
+                if (a.dense_calls && !redo && __popcll(bal_stat) > 4)
                     atomicAdd(a.dense_calls + 1 + (b & (DENSE_SLOTS - 1)), (unsigned long long)(2 * (a.pair_ptr[b + 1] - a.pair_ptr[b])));
             }
         }
@@ -1644,7 +1645,8 @@ __global__ __launch_bounds__(256) void k_softmax_rows(EstepArgs a)
 // wavefront that walks it in CSC (= reference bincount) order with float64 accumulation and leaves
 // one float64 partial per item.  Items are handed out from a length-sorted list.
 // The E-step leaves a per-barcode bitmap of the posteriors that can contribute (kernels.h:
-// NZ_FLOOR_SQUARE); everything else adds exactly +0 and is never loaded.
+// live_floor_float64: NZ_FLOOR_SQUARE when it squares); everything else adds exactly +0 and is never loaded.  (Codes written at the
+// fixed-point forms' higher floor are rebuilt before these float64 sums read them: dmx_steps.cpp, run_mstep.)
 //
 // Genotype-per-lane form (G > 64; A = ceil(G / 64) accumulators per lane): 64 calls per chunk are
 // loaded one per lane, then handled call by call: v_readlane -> SGPRs, the call's bitmap word becomes
@@ -2014,14 +2016,8 @@ static __device__ __forceinline__ bool incr_full(const unsigned *state, const Ms
     return state[IS_VALID] == 0u || 8ull * calls > (a.incr_total ? a.incr_total : a.total_calls) || dense_regime(a);
 }
 
-// c in [0, 1] -> rint(c 2^shift) as an integer (k_mstep_tiles, k_mincr_delta and the fixed-point work-item form add the same
-// integers): adding 1.5 x 2^52 leaves the rounded value (ties to even) in the low bits of the sum's mantissa (c 2^shift < 2^51)
-static __device__ __forceinline__ unsigned long long fixed_of(float c, int shift)
-{
-    constexpr double MAGIC = 6755399441055744.0;
-    const double d = __builtin_ldexp((double)c, shift) + MAGIC;
-    return (unsigned long long)(__double_as_longlong(d) - __double_as_longlong(MAGIC));
-}
+// c in [0, 1] -> rint(c 2^shift) as an integer: fixed_of (fixed_point.h) - k_mstep_tiles, k_mincr_delta and the fixed-point work-item
+// form add the same integers.  A posterior at or below live_floor_fixed (kernels.h) gives the integer 0 at every shift.
 
 // Where the integer sums of work item `item` go (fixed-point work-item form, MstepArgs::fixed_shift_v): a variant of ONE item is
 // finished here - its sums into fixed_acc64, converted once into the addition, as k_mstep_tiles writes them -, the others leave
@@ -2195,8 +2191,8 @@ __global__ __launch_bounds__(256) void k_mstep_calls(MstepArgs a)
             }
         }
     };
-    // Dense calls (more than NZ_S live posteriors; 3.6 % of the calls of the 200k x 100k x 64 workload once it has
-    // converged, i.e. two or three in nine chunks out of ten) are handled one at a time by the whole wavefront, lane
+    // Dense calls (more than NZ_S live posteriors; with the codes at 2^-80 3.6 % of the calls of the 200k x 100k x 64 workload once
+    // it has converged, i.e. two or three in nine chunks out of ten) are handled one at a time by the whole wavefront, lane
     // g taking post[cb, g].  Their rows come from the 51 MB posterior table, i.e. over the fabric: fetched inside
     // the iteration that needs them, that latency was what the kernel ran on.  So the rows of the first DP dense
     // calls of a chunk are requested one iteration ahead, unmasked (a dead posterior is simply not used), and the
@@ -2421,6 +2417,9 @@ __global__ __launch_bounds__(256) void k_mstep_calls(MstepArgs a)
 // Requesting the next round's records before working on this one's: 70 VGPRs, or 64 with spills - 0.40 ms.
 // All loads as raw buffer loads with out-of-range masking (no EXEC regions, no 64-bit address arithmetic: 52 VGPRs, a tenth
 // fewer instructions): 0.34 ms as well (0.32 against 0.30 at 32 genotypes) - PMC: VALU 64 %, address unit 69 %, LDS 49 % busy.
+// All of that with the codes at 2^-80.  With the codes at the grid's live floor (kernels.h: live_floor_fixed; most dense calls and extra
+// posteriors only ever added the integer 0): 0.24 ms, per launch 2.7 M instead of 6.9 M vector memory reads, 61 M instead of 139 M VALU
+// instructions (profiles/live_floor_mstep.txt).
 constexpr int MTILE_THREADS = 1024;
 constexpr int MTILE_QUEUE = 96;  // dense calls a wavefront parks before it takes their rows (64 + the flush threshold)
 
@@ -2444,17 +2443,17 @@ __global__ __launch_bounds__(MTILE_THREADS) void k_mstep_tiles(MstepArgs a, MTil
     unsigned *q_rec = mt_queue[wave][0], *q_keep = mt_queue[wave][1];
     int queued = 0;  // (uniform)
     auto power_of = [&](float c) { return SQUARE ? c * c : powf(c, a.power); };
-    // c in [0, 1] -> rint(c 2^shift) as an integer: adding 1.5 x 2^52 leaves the rounded value (ties to even) in the low bits
-    // of the sum's mantissa (c 2^shift < 2^51)
-    constexpr double MAGIC = 6755399441055744.0;
     auto add = [&](int index, float c) {
-        const double d = __builtin_ldexp((double)c, shift) + MAGIC;
-        const unsigned long long q = (unsigned long long)(__double_as_longlong(d) - __double_as_longlong(MAGIC));
-        __hip_atomic_fetch_add(&mt_acc[index], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&mt_acc[index], fixed_of(c, shift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    // a dense row is mostly dead posteriors, whatever floor made it dense: a lane whose integer is 0 leaves the sum alone
+    auto add_nonzero = [&](int index, float c) {
+        const unsigned long long q = fixed_of(c, shift);
+        if (q != 0ull) __hip_atomic_fetch_add(&mt_acc[index], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     // The parked dense calls, 16 at a time: lane g takes post[row, g] of every one of them (16 row loads in flight: they come
     // from the posterior table, i.e. over the fabric, and one at a time their latency was the whole kernel), then adds.  A
-    // posterior at or below the contribution floor contributes exactly +0 (as in k_mstep_dense): no bitmap is read.
+    // posterior at or below the live floor contributes the integer 0 (k_mstep_dense: exactly +0 below 2^-80): no bitmap is read.
     auto flush = [&]() {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -2469,7 +2468,7 @@ __global__ __launch_bounds__(MTILE_THREADS) void k_mstep_tiles(MstepArgs a, MTil
             }
 #pragma unroll
             for (int i = 0; i < DB; i++)
-                if (q0 + i < queued && lane < G) add((int)(q_rec[q0 + i] >> 24) * G + lane, power_of(p[i] * __uint_as_float(q_keep[q0 + i])));
+                if (q0 + i < queued && lane < G) add_nonzero((int)(q_rec[q0 + i] >> 24) * G + lane, power_of(p[i] * __uint_as_float(q_keep[q0 + i])));
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -2590,11 +2589,7 @@ __global__ __launch_bounds__(256) void k_mincr_delta(MstepArgs a, MIncrArgs x)
     const int lane = threadIdx.x & 63;
     const unsigned n = x.state[IS_N];
     const int G = a.G;
-    constexpr double MAGIC = 6755399441055744.0;  // (k_mstep_tiles: the same conversion)
-    auto quant = [&](float c, int shift) {
-        const double d = __builtin_ldexp((double)(SQUARE ? c * c : powf(c, a.power)), shift) + MAGIC;
-        return (unsigned long long)(__double_as_longlong(d) - __double_as_longlong(MAGIC));
-    };
+    auto quant = [&](float c, int shift) { return fixed_of(SQUARE ? c * c : powf(c, a.power), shift); };  // (k_mstep_tiles: the same conversion)
     // a workgroup per changed barcode (the workgroups stride over the list), its four wavefronts taking the chunks of 64 calls in turn:
     // a launch lasts as long as its longest barcode
     const int wave = threadIdx.x >> 6;
@@ -3474,6 +3469,7 @@ hipError_t launch_mcombine(hipStream_t st, const MstepArgs &a, const long long *
 // What the M-step reads of a barcode with ONE live posterior - or none, a doublet's row - is in its 8-byte code (nz_code); its 256-byte
 // row need not travel: the receivers rebuild it - the code's posterior at the code's genotype, zeros elsewhere; a posterior that is not live contributes
 // exactly +0 to every sum (NZ_FLOOR_SQUARE; with another contribution_power "live" means non-zero), so the additions keep their bits.
+// (An attached context always writes its codes at that floor, never at live_floor_fixed: which M-step form the receivers run is theirs to know.)
 // Rows with several live posteriors (1 - 15 % of the barcodes) travel in a list: block = {rows listed (beyond `cap`: overflow - the
 // caller falls back to the all-gather of the whole table), 3 words of padding, cap entries of (row, G floats)}.
 // (peers, emulated wire only: nobody fills the other ranks' blocks; they list nothing, wherever this exchange's block size puts their

@@ -32,6 +32,7 @@ struct Facts {
     long long msteps_expected;  // still to come as the caller announced (dmx_set_msteps_expected)
     bool incr_heavy;            // full passes keep coming on this problem (heavy_after_probe)
     long long rows_total;       // barcode rows of all ranks
+    bool shift_tried;           // the tile cut for the exponents alone was attempted (plan_mstep_shifts; read by sums_on_grid only)
 };
 
 // The tile form's arithmetic - integer sums of rint(c 2^shift), in any order - is possible: not with the exact additions, which are the
@@ -101,6 +102,21 @@ inline Launch launch(const Facts &f)
     const Incr incr = sharded ? INCR_SHARDED : !own ? INCR_NONE : items ? INCR_WORK_ITEMS : INCR_OWN_RECORDS;
     return {tiles ? 2 : incr == INCR_WORK_ITEMS ? 3 : 1, incr, own && f.sliced};
 }
+// AHEAD of the M-step - what the E-step before it asks (dmx_steps.cpp: run_estep, with the facts as that M-step will find them): will
+// its sums be formed on the fixed-point grid (form 2 or 3)?  Then the codes and the bitmap may be written at the grid's live floor
+// (kernels.h: live_floor_fixed).  Tiles ready, or their build due; or the work items' exponents wanted and at hand or still to be cut.
+// Where neither a build nor a cut is pending the answer IS launch()'s: true <=> form 2 or 3 (tests/live_floor_check.cpp walks the fact
+// space); a build or a cut that leaves nothing ends in form 1, and run_mstep rebuilds the codes once - the next E-step knows.
+inline bool sums_on_grid(const Facts &f)
+{
+    return tiles_ready(f) || build_due(f) || (shifts_wanted(f) && (f.has_shift_v || !f.shift_tried));
+}
+// ... and only where the codes stay on this context: an attached one sends them to other ranks (k_post_compact_build,
+// k_post_reconstruct), whose M-step forms are not this rank's to know.
+inline bool live_floor_on_grid(const Facts &f) { return !f.attached && sums_on_grid(f); }
+// what the codes' floor must not exceed for the form launch() chose: a float64 form (1) reads them for the reference's own sum
+inline bool grid_floor_admitted(const Launch &l) { return l.form != 1; }
+
 // a sharded rank's delta pass, behind the first-use build of its row index (build_slice_row_index): k_mincr_delta on the slice's records
 // by barcode row - or, where the index does not apply, the masked walk of the variant-major records and its byte map
 inline bool sharded_by_row_index(const Facts &f) { return f.has_slice_rec; }

@@ -28,7 +28,8 @@ namespace {
 // range check without atomics in the good case: a wave only touches memory when it saw a bad index
 // bad[0..2] = flags (barcode, variant, p_base_wrong out of range), bad[3] = lowest offending call index.
 // p_base_wrong must be a probability: the E-step's log assumes a finite argument >= 1e-4, which
-// p * (1 - e) + max(e, 1e-4) is exactly when 0 <= e <= 1 (NaN fails both comparisons).
+// p * (1 - e) + max(e, 1e-4) is exactly when 0 <= e <= 1 (NaN fails both comparisons).  Every pack passes here (repack_core), so
+// keep = fl32(1 - e) lies in [0, 1] in every record the M-step forms read: the bound the live floors lean on (kernels.h: KEEP_MAX).
 __global__ __launch_bounds__(256) void k_validate(const int *__restrict__ variant, const int *__restrict__ cb,
                                                   const float *__restrict__ p_wrong, long long N, long long B, long long V,
                                                   unsigned long long *__restrict__ bad)
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void k_build_pairs(const unsigned *__restrict_
     const int h = (int)(j & 1);
     pr.row_off[h] = (unsigned)variant[i] * G * 4u;   // byte offset of the variant's row in prob[V, G]
     call_rows[2 * (pair_ptr[b] + (j >> 1)) + h] = (unsigned)variant[i];  // the row itself, compact (estep_dict.hip)
-    pr.keep[h] = 1.0f - e;                          // float32, numpy's `1 - e`
+    pr.keep[h] = 1.0f - e;                          // float32, numpy's `1 - e`: in [0, 1] (k_validate; kernels.h: KEEP_MAX)
     pr.floor[h] = e > 1e-4f ? e : 1e-4f;            // numpy's `e.clip(1e-4)`
 }
 
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(256) void k_build_csc(const unsigned *__restrict__ 
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= N) return;
     const unsigned i = perm[s];
-    const float keep = 1.0f - p_wrong[i];  // the M-step only ever needs 1 - e
+    const float keep = 1.0f - p_wrong[i];  // the M-step only ever needs 1 - e; in [0, 1] for the 0 <= e <= 1 k_validate admits (kernels.h: KEEP_MAX)
     csc[s] = make_uint2((unsigned)cb[i], __float_as_uint(keep));
 }
 
@@ -766,7 +767,7 @@ bool cut_mstep_tiles(dmx_ctx *c, long long v_lo, long long v_hi, TileCut &t)
         long long longest = 1;
         for (long long v = t.tile_first[(size_t)i]; v < t.tile_first[(size_t)i + 1]; v++)
             longest = std::max(longest, first_call[(size_t)v + 1] - first_call[(size_t)v]);
-        t.tile_shift[(size_t)i] = std::min(50, 62 - (int)bits_of((unsigned long long)longest));
+        t.tile_shift[(size_t)i] = std::min(FIXED_SHIFT_MAX, 62 - (int)bits_of((unsigned long long)longest));
     }
     return true;
 }

@@ -41,7 +41,8 @@ class DeviceContext:
         DEMUXALOT_AMD_ESTEP_PACKED = never | auto | always (dmx_set_estep_packing); DEMUXALOT_AMD_COARSE_PASS = 1 | 0: the guarded
         mode's binary16 pass for E-steps whose logits nobody reads (dmx_set_coarse_pass; default on); DEMUXALOT_AMD_MSTEP_INCREMENTAL
         = 1 | 0: the tile-major M-step keeps its integer sums and adds differences (dmx_set_mstep_incremental; default on);
-        DEMUXALOT_AMD_LEAN = 0 | 1: release the fine pass's copy of the E-step records once the coarse pass's are built (dmx_set_lean_memory)."""
+        DEMUXALOT_AMD_LEAN = 0 | 1: release the fine pass's copy of the E-step records once the coarse pass's are built (dmx_set_lean_memory);
+        DEMUXALOT_AMD_LIVE_FLOOR_GRID = 1 | 0: barcode codes at the fixed-point M-step's live floor (dmx_set_live_floor_on_grid; default on)."""
         mode = os.environ.get('DEMUXALOT_AMD_ESTEP', '') or DEFAULT_ESTEP_MODE
         assert mode in ('exact', 'fast', 'guarded'), f'DEMUXALOT_AMD_ESTEP={mode!r}: exact, fast or guarded'
         self.set_estep_mode(mode)
@@ -55,6 +56,7 @@ class DeviceContext:
         self.set_coarse_pass(os.environ.get('DEMUXALOT_AMD_COARSE_PASS', '1') != '0')
         self.set_mstep_incremental(os.environ.get('DEMUXALOT_AMD_MSTEP_INCREMENTAL', '1') != '0')
         self.set_lean_memory(os.environ.get('DEMUXALOT_AMD_LEAN', '0') not in ('', '0'))
+        self.set_live_floor_on_grid(os.environ.get('DEMUXALOT_AMD_LIVE_FLOOR_GRID', '1') != '0')
         self.set_phase_timers(False)
         self.set_logits_needed(True)
 
@@ -917,6 +919,24 @@ class DeviceContext:
         form = ctypes.c_int32(0)
         check(self._lib.dmx_get_mstep_form(self._h, ctypes.byref(form)))
         return {0: None, 1: 'items', 2: 'tiles', 3: 'items_fixed'}[form.value]
+
+    def set_live_floor_on_grid(self, on_grid):
+        """True (default): an E-step ahead of a fixed-point M-step counts a posterior as live from 2^-26 on - below it the M-step adds
+        the integer 0; False: from 2^-80 on, as the float64 forms need it.  Same additions bit for bit
+        (include/demux_hip_debug.h: dmx_set_live_floor_on_grid)."""
+        check(self._lib.dmx_set_live_floor_on_grid(self._h, int(bool(on_grid))))
+
+    def live_floor(self):
+        """(floor of the barcode codes the last E-step - or a rebuild - left, rebuild launches of M-steps since reset_timings)."""
+        floor, rebuilds = ctypes.c_float(0), ctypes.c_int64(0)
+        check(self._lib.dmx_get_live_floor(self._h, ctypes.byref(floor), ctypes.byref(rebuilds)))
+        return floor.value, rebuilds.value
+
+    def debug_live_counts(self):
+        """[B] int32: live posteriors of every barcode as its code counts them (G <= 64; dmx_debug_get_live_counts)."""
+        out = np.empty(self.B, dtype=np.int32)
+        check(self._lib.dmx_debug_get_live_counts(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def redo_count(self):
         """Sums the last exact-mode M-step redid in the reference's order (include/demux_hip.h: dmx_get_redo_count)."""

@@ -39,6 +39,19 @@ int dmx_get_mstep_tiles_info(dmx_ctx *ctx, int32_t *built, double *build_ms);
 /* form of the last M-step launch: 0 none yet, 1 work items (float64 partial sums), 2 tiles, 3 work items adding the tile-major form's
  * integers under the incremental M-step (the dense regime's kernel may still have taken any of them) */
 int dmx_get_mstep_form(dmx_ctx *ctx, int32_t *form);
+/* The live floor of the barcode codes and the bitmap the E-step leaves for the M-step (csrc/kernels.h: live_floor_fixed).  With
+ * contribution_power == 2 a float64 M-step form needs every posterior above 2^-80 in them (below it the float32 contribution is +0);
+ * the fixed-point forms (dmx_get_mstep_form 2 and 3, the incremental delta pass) add integers rint(c 2^shift), shift <= 50, and a
+ * posterior below 2^-26 adds the integer 0 there.  on_grid = 1 (default): an E-step that a fixed-point M-step will follow - as the
+ * M-step's plan says ahead - on a context without a communicator calls a posterior live from 2^-26 on; far fewer barcodes then count
+ * as dense or carry extra live posteriors, same sums bit for bit.  The M-step's choice between the dense regime's kernel and the others
+ * keeps its own count above 2^-80.  An M-step whose form turns out to be a float64 one rebuilds the codes at 2^-80 first.  on_grid = 0:
+ * always 2^-80 (tests, measurements).
+ * dmx_get_live_floor: the floor of the current codes, and the rebuild launches of M-steps since dmx_reset_timings (0 in steady state).
+ * dmx_debug_get_live_counts: [B] live posteriors of every barcode as its code counts them (G <= 64, after an E-step). */
+int dmx_set_live_floor_on_grid(dmx_ctx *ctx, int on_grid);
+int dmx_get_live_floor(dmx_ctx *ctx, float *floor, int64_t *rebuilds);
+int dmx_debug_get_live_counts(dmx_ctx *ctx, int32_t *counts);
 
 /* Worst case of the guarded mode.  With the fast pass taking F, the exact kernel over every barcode E, and a fraction f of the
  * barcodes queued, a guarded E-step costs F + f E: more than the exact mode's E once f > 1 - F / E, and (F + E) / E on a
