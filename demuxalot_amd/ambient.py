@@ -1,0 +1,104 @@
+"""Per-barcode ambient RNA fractions (Demultiplexer.estimate_ambient).
+
+How much of a droplet's signal is NOT from the option it was assigned to: for every barcode the log-likelihood of its calls when a
+share alpha of its molecules comes from the soup, on a grid of alphas; the estimate is the grid value of the first maximum.  The
+device pass (include/demux_hip_debug.h: dmx_ambient_profile) returns B-length read-outs and, if asked, the [B, A] profile; this
+module resolves the caller's assignments into table columns and composes the frames.  Pure numpy / pandas: imports without a GPU.
+"""
+import numbers
+
+import numpy as np
+import pandas as pd
+
+from . import donor_readout
+
+
+def default_alphas():
+    """The grid of estimate_ambient: 64 values, 0 .. 0.63 in steps of 0.01, one per lane of the device pass."""
+    return np.linspace(0, 0.63, 64, dtype=np.float32)
+
+
+def _is_skip(value):
+    if value is None:
+        return True
+    if isinstance(value, (float, np.floating)) and np.isnan(value):
+        return True
+    return isinstance(value, (numbers.Integral, np.integer)) and not isinstance(value, (bool, np.bool_)) and int(value) == -1
+
+
+def resolve_assignments(option_names, ordered_barcodes, assignments):
+    """int64[B] option columns (-1: skip) from a Series or mapping barcode -> option name | integer option column | None / NaN / -1.
+    option_names: the columns of the posteriors (singlets, then 'A+B'); a name is looked up exactly, never split on '+', so donor
+    names may contain one.  A barcode of the handler that `assignments` does not mention is skipped.  ValueError: a name that is no
+    option, a column outside the options, a barcode that is not the handler's."""
+    column_of = {}
+    for k, name in enumerate(option_names):
+        column_of.setdefault(name, k)  # (the first of equal names, as an exact look-up of the frame's columns would find)
+    row_of = {barcode: b for b, barcode in enumerate(ordered_barcodes)}
+    columns = np.full(len(ordered_barcodes), -1, dtype=np.int64)
+    items = assignments.items() if hasattr(assignments, 'items') else dict(assignments).items()
+    for barcode, value in items:
+        if barcode not in row_of:
+            raise ValueError(f'assignments: barcode {barcode!r} is not one of the barcode handler')
+        if _is_skip(value):
+            continue
+        if isinstance(value, (numbers.Integral, np.integer)) and not isinstance(value, (bool, np.bool_)):
+            if not 0 <= int(value) < len(option_names):
+                raise ValueError(f'assignments: option column {int(value)} of barcode {barcode!r} is outside [0, {len(option_names)})')
+            columns[row_of[barcode]] = int(value)
+        elif value in column_of:
+            columns[row_of[barcode]] = column_of[value]
+        else:
+            raise ValueError(f'assignments: {value!r} of barcode {barcode!r} is not an option')
+    return columns
+
+
+def assigned_donors(n_donors, columns):
+    """(donor1, donor2) int32[B] as the device pass takes them: table columns, (-1, -1) skipped, (d, -1) a singlet, d1 < d2 a pair."""
+    d1, d2 = donor_readout.column_donors(n_donors, columns)
+    return d1.astype(np.int32), d2.astype(np.int32)
+
+
+class AmbientEstimate:
+    """The result of one estimate_ambient call, host-resident.
+
+    alphas float32[A]: the grid; ambient float32[V]: the soup's allele profile that was used; profile: DataFrame [B, A] of the
+    log-likelihoods (columns: the grid values), or None when it was not kept; best int32[B]: the grid point of the first maximum
+    (-1: skipped); ll_best / ll_zero float32[B]: the log-likelihood there and at the first alpha == 0 (NaN: skipped / no 0 on the
+    grid)."""
+
+    def __init__(self, barcodes, option_names, columns, alphas, ambient, best, ll_best, ll_zero, loglik=None, index_name='BARCODE'):
+        self.barcodes = list(barcodes)
+        self.alphas = np.asarray(alphas, dtype=np.float32)
+        self.ambient = np.asarray(ambient, dtype=np.float32)
+        self.best = np.asarray(best, dtype=np.int32)
+        self.ll_best = np.asarray(ll_best, dtype=np.float32)
+        self.ll_zero = np.asarray(ll_zero, dtype=np.float32)
+        self.index_name = index_name
+        self._option_names = list(option_names)
+        self._columns = np.asarray(columns, dtype=np.int64)
+        B = len(self.barcodes)
+        assert self._columns.shape == (B,) and self.best.shape == (B,) and self.ll_best.shape == (B,) and self.ll_zero.shape == (B,)
+        self.profile = None
+        if loglik is not None:
+            loglik = np.asarray(loglik, dtype=np.float32)
+            assert loglik.shape == (B, len(self.alphas))
+            self.profile = pd.DataFrame(loglik, index=self._index(), columns=self.alphas)
+
+    def _index(self):
+        index = pd.Index(self.barcodes)
+        index.name = self.index_name
+        return index
+
+    def summary(self) -> pd.DataFrame:
+        """Per barcode (all of them, handler order): `option`, the name it was assigned (None: skipped); `alpha`, the grid value of
+        the first maximum (NaN: skipped); `log_likelihood_ratio`, float64 ll_best - ll_zero (how much better the estimate explains
+        the calls than no contamination; NaN where the grid has no 0); `at_grid_edge`: the estimate is the largest grid value, so
+        the maximum may lie beyond the grid."""
+        names = np.asarray(self._option_names + [None], dtype=object)
+        found = self.best >= 0
+        alpha = np.where(found, self.alphas[np.where(found, self.best, 0)].astype(np.float64), np.nan)
+        ratio = self.ll_best.astype(np.float64) - self.ll_zero.astype(np.float64)
+        at_edge = found & (alpha == np.float64(self.alphas.max()))
+        return pd.DataFrame({'option': names[self._columns], 'alpha': alpha, 'log_likelihood_ratio': ratio, 'at_grid_edge': at_edge},
+                            index=self._index())

@@ -21,6 +21,7 @@
 #include "dmx_ctx.h"
 #include "dmx_host.h"
 #include "estep_plan.h"
+#include "ambient_profile.h"
 #include "estep_pools.h"
 #include "mstep_plan.h"
 
@@ -993,6 +994,26 @@ int dmx_estep_pools_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, con
     DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
     DMX_TRY(dmx::launch_estep_pools_pass(c, *run, 2.0f));  // (the floor of a squaring M-step; run_mstep rebuilds for another power)
     return dmx::read_back_estep_pools(c, *run);
+}
+
+// Ambient RNA fractions (ambient_profile.hip).  Everything is checked on the host (ambient_plan.h) before anything is uploaded or
+// launched; the resident results of the last E-step are not touched.
+int dmx_ambient_profile(dmx_ctx *c, float lo, float hi, int32_t n_alphas, const float *alphas, const int32_t *donor1, const int32_t *donor2,
+                        const float *ambient, float *loglik, int32_t *best, float *ll_best, float *ll_zero, float *ambient_out)
+{
+    namespace ap = dmx::aplan;
+    static_assert(ap::OK == DMX_OK && ap::INVALID == DMX_ERR_INVALID && ap::UNSUPPORTED == DMX_ERR_UNSUPPORTED, "ambient_plan.h restates the codes");
+    static_assert(sizeof(int) == sizeof(int32_t), "");
+    DMX_TRY(bind(c));
+    const ap::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
+                          c->B,           c->V,          c->G};
+    const ap::Verdict verdict = ap::check(facts, n_alphas, alphas, (const int *)donor1, (const int *)donor2, ambient);
+    if (verdict.status != ap::OK) {
+        if (verdict.at >= 0) return fail(verdict.status, "dmx_ambient_profile: %s (index %lld)", verdict.what, verdict.at);
+        return fail(verdict.status, "dmx_ambient_profile: %s", verdict.what);
+    }
+    const dmx::AmbientPlan plan{lo, hi, (int)n_alphas, alphas, donor1, donor2, ambient, loglik, best, ll_best, ll_zero, ambient_out};
+    return dmx::run_ambient_profile(c, plan);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)

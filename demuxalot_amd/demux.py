@@ -27,6 +27,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, donor_readout
+from .ambient import AmbientEstimate, assigned_donors, default_alphas, resolve_assignments
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
 from .pools import PooledPosteriors, resolve_pools
@@ -815,6 +816,44 @@ class Demultiplexer:
             out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty)
         return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                 out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
+
+    @staticmethod
+    def estimate_ambient(chromosome2compressed_snp_calls,
+                         genotypes,
+                         barcode_handler,
+                         assignments,
+                         alphas=None,
+                         p_genotype_clip=0.01,
+                         ambient=None,
+                         keep_profile=False) -> AmbientEstimate:
+        """(not in the reference) Per-barcode ambient RNA fractions: how much of a droplet's signal is not from the option it was
+        assigned to.  For every assigned barcode and every alpha of the grid, the log-likelihood of its calls when a share alpha of
+        its molecules comes from the soup (allele profile `ambient`) and the rest from its donor(s); the estimate is the grid value
+        of the first maximum (AmbientEstimate.summary()).  At alpha = 0 the likelihood of a singlet is, bit for bit, the donor's
+        column of predict_posteriors' logits.
+        :param assignments: Series or mapping barcode -> option name (as predict_posteriors' columns or DevicePosteriors.best()
+            give it; looked up exactly, so donor names may contain '+'), integer option column, or None / NaN / -1 to skip; a
+            barcode that is not mentioned is skipped
+        :param alphas: the grid, 1 .. 64 values in [0, 1] in any order; None: 0, 0.01 .. 0.63
+        :param ambient: float32[n_variants] allele profile of the soup per variant row, or None: derived from the calls (per SNP
+            the share of every allele among the barcode-level calls, one pseudo-count each, clipped like the genotype table)
+        :param keep_profile: also return the [B, A] log-likelihoods (AmbientEstimate.profile)
+        ValueError: an unknown option name, a column outside the options, a barcode that is not the handler's."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions are estimated on barcode-level calls; aggregate_on_snps has none'
+        names = list(genotypes.genotype_names)
+        option_names = _option_names(names, 1)  # every option a run with doublets can assign; a singlet run's names are its first G
+        columns = resolve_assignments(option_names, barcode_handler.ordered_barcodes, assignments)
+        donor1, donor2 = assigned_donors(len(names), columns)
+        alphas = default_alphas() if alphas is None else np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
+        with shared_context_lock:
+            ctx = get_context()
+            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
+            ctx.set_addition(None)
+            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+            assert np.isfinite(genotype_prob).all()
+            out = ctx.ambient_profile(donor1, donor2, alphas, p_genotype_clip, ambient=ambient, fetch_profile=keep_profile)
+        return AmbientEstimate(barcode_handler.ordered_barcodes, option_names, columns, alphas, out['ambient'], out['best'], out['ll_best'],
+                               out['ll_zero'], loglik=out['loglik'], index_name='BARCODE')
 
     @staticmethod
     def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):

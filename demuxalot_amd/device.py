@@ -723,6 +723,29 @@ class DeviceContext:
         self.K = self.G
         return out
 
+    def ambient_profile(self, donor1, donor2, alphas, p_genotype_clip=0.01, ambient=None, fetch_profile=True):
+        """Ambient RNA fractions (include/demux_hip_debug.h: dmx_ambient_profile): the log-likelihood of every barcode's calls under
+        its assigned option mixed with the soup's allele profile, on the grid `alphas` (float32, 1 .. 64 values in [0, 1]).
+        donor1 / donor2: int32[B] table columns as donor_readout.column_donors gives them ((-1, .) skipped, (d, -1) a singlet, d1 < d2 a
+        pair); ambient: float32[V] or None (derived from the resident calls, clipped as the genotype table is).  Returns a dict:
+        loglik float32[B, A] (None without fetch_profile), best int32[B], ll_best, ll_zero float32[B], ambient float32[V] (the profile
+        that was used).  The resident results of the last E-step are left as they are."""
+        B = self.B
+        alphas = as_c(alphas, np.float32)
+        assert alphas.ndim == 1, 'the grid is one-dimensional'
+        donor1, donor2 = as_c(donor1, np.int32), as_c(donor2, np.int32)
+        assert donor1.shape == (B,) and donor2.shape == (B,), 'one option per barcode'
+        if ambient is not None:
+            ambient = as_c(ambient, np.float32)
+            assert ambient.shape == (self.V,), 'one ambient value per variant'
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        A = len(alphas)
+        out = dict(loglik=np.empty((B, A), np.float32) if fetch_profile else None, best=np.full(B, -1, np.int32),
+                   ll_best=np.full(B, np.nan, np.float32), ll_zero=np.full(B, np.nan, np.float32), ambient=np.empty(self.V, np.float32))
+        check(self._lib.dmx_ambient_profile(self._h, lo, hi, A, ptr(alphas), ptr(donor1), ptr(donor2), ptr(ambient), ptr(out['loglik']),
+                                            ptr(out['best']), ptr(out['ll_best']), ptr(out['ll_zero']), ptr(out['ambient'])))
+        return out
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

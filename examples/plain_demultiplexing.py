@@ -47,3 +47,10 @@ print('Result:')
 print(posterior_probabilities.round(3))
 assigned = posterior_probabilities[posterior_probabilities.max(axis=1) > 0.9].idxmax(axis=1)
 print(assigned.value_counts())
+
+# (not in the reference) how much of every assigned droplet's signal is not from its donor(s): the ambient RNA fraction
+ambient = Demultiplexer.estimate_ambient(snps, learnt_genotypes, barcode_handler, assigned)
+contamination = ambient.summary().loc[assigned.index]
+print('Ambient fraction of the assigned droplets:')
+print(contamination['alpha'].describe().round(3))
+print('kept at alpha <= 0.1:', int((contamination['alpha'] <= 0.1).sum()), 'of', len(contamination))

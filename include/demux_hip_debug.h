@@ -451,6 +451,37 @@ int dmx_em_pools(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_do
                  int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
                  float *addition_out /* nullable, float32[V, G] */);
 
+/* ------------------------------------------------------------------------- *
+ * Ambient RNA fractions (product API; declared here because demux_hip.h is kept to 64 entry points; csrc/ambient_profile.hip;
+ * DESIGN.md 4.6).  How much of a barcode's signal is NOT from the option it was assigned to: the log-likelihood of its calls on a
+ * grid of contamination fractions, in one pass over the resident call records and the resident genotype table (call order: a
+ * problem and dmx_probs_from_betas / dmx_set_probs; single GPU).
+ *   alphas      float32[n_alphas], 1 <= n_alphas <= 64, every value finite and in [0, 1]; any order, duplicates allowed.
+ *   donor1/2    int32[B]: the assigned option of barcode b as table columns.  donor1 == -1: skipped; donor2 == -1: the singlet
+ *               donor1; otherwise the pair 0 <= donor1 < donor2 < G.
+ *   ambient     float32[V], nullable: the soup's allele profile per table row, every value finite and in [0, 1].  NULL: derived
+ *               from the resident calls - with c[v] the barcode-level calls of variant v (padding not counted), the P-step's
+ *               own formula (demux.py:267-274) on the one-column table beta[v] = f32(c[v] + 1), clipped to [lo, hi]: a SNP
+ *               nobody called comes out uniform.  DMX_ERR_UNSUPPORTED where a variant has 2^24 calls or more.
+ *   loglik      for barcode b and grid point j, in float32 without contraction, over the calls of b in stored order:
+ *                 q = prob[v, d1]  or  (prob[v, d1] + prob[v, d2]) * 0.5f
+ *                 m = q * (1.0f - alphas[j]) + ambient[v] * alphas[j]          two products, one sum, each rounded
+ *                 L[b, j] = f32( sum of f64( log_f32(m * keep + floor) ) )     the exact E-step's log, sequential float64 sum
+ *               At alphas[j] == 0, m == q: that column of a singlet is the donor's column of the reference's logits, bit for bit.
+ *   outputs     each nullable: loglik float32[B, n_alphas]; best int32[B], the first maximum over j (ties to the lower index,
+ *               NaN never wins); ll_best, ll_zero float32[B]: L[b, best] and L[b, j0], j0 the first j with alphas[j] == 0 (NaN
+ *               where the grid has no 0); ambient_out float32[V]: the profile that was used.  A skipped barcode gets NaN / -1 /
+ *               NaN / NaN; a barcode without calls +0.0 in every column and best 0.
+ * Checked on the host before anything is uploaded or launched.  DMX_ERR_INVALID: no problem or no table, n_alphas < 1, a grid or
+ * ambient value that is not finite or outside [0, 1], donors that break the rules above.  DMX_ERR_UNSUPPORTED: n_alphas > 64, a
+ * communicator attached.  The resident results of the last dmx_estep / dmx_em are left as they are; the pass is counted in the
+ * DMX_T_ESTEP slot of dmx_get_timings.
+ * ------------------------------------------------------------------------- */
+int dmx_ambient_profile(dmx_ctx *ctx, float lo, float hi, int32_t n_alphas, const float *alphas /* [n_alphas] */,
+                        const int32_t *donor1, const int32_t *donor2 /* [B] */, const float *ambient /* nullable, [V] */,
+                        float *loglik /* nullable, [B, n_alphas] */, int32_t *best, float *ll_best, float *ll_zero /* nullable, [B] */,
+                        float *ambient_out /* nullable, [V] */);
+
 #ifdef __cplusplus
 }
 #endif
