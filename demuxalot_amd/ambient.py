@@ -53,6 +53,38 @@ def resolve_assignments(option_names, ordered_barcodes, assignments):
     return columns
 
 
+def resolve_fractions(ordered_barcodes, ambient_fractions):
+    """float32[B] per-barcode fractions (predict_posteriors_with_ambient) from a Series or mapping barcode -> alpha.  A barcode that
+    is missing, None or NaN gets 0: it is scored as predict_posteriors scores it.  ValueError: a value that is no number or lies
+    outside [0, 1] (as float32, which is what the device pass reads), a barcode that is not the handler's."""
+    row_of = {barcode: b for b, barcode in enumerate(ordered_barcodes)}
+    alpha = np.zeros(len(ordered_barcodes), dtype=np.float32)
+    items = ambient_fractions.items() if hasattr(ambient_fractions, 'items') else dict(ambient_fractions).items()
+    for barcode, value in items:
+        if barcode not in row_of:
+            raise ValueError(f'ambient_fractions: barcode {barcode!r} is not one of the barcode handler')
+        if value is None:
+            continue
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (numbers.Real, np.number)):
+            raise ValueError(f'ambient_fractions: {value!r} of barcode {barcode!r} is not a number')
+        if np.isnan(value):
+            continue
+        as_f32 = np.float32(value)
+        if not (0 <= value <= 1 and np.float32(0) <= as_f32 <= np.float32(1)):
+            raise ValueError(f'ambient_fractions: {value!r} of barcode {barcode!r} is outside [0, 1]')
+        alpha[row_of[barcode]] = as_f32
+    return alpha
+
+
+def best_singlets(logits, n_donors):
+    """int64[B]: every barcode's best singlet - the first maximum over the first n_donors columns of the plain logits (the singlets'
+    penalty is 0: these are the donors' log-likelihoods), whatever the doublet columns say; -1 where every singlet logit is NaN."""
+    singlets = np.asarray(logits)[:, :n_donors]
+    nan = np.isnan(singlets)
+    first = np.where(nan, -np.inf, singlets).argmax(axis=1)
+    return np.where(nan.all(axis=1), -1, first).astype(np.int64)
+
+
 def assigned_donors(n_donors, columns):
     """(donor1, donor2) int32[B] as the device pass takes them: table columns, (-1, -1) skipped, (d, -1) a singlet, d1 < d2 a pair."""
     d1, d2 = donor_readout.column_donors(n_donors, columns)
@@ -89,6 +121,13 @@ class AmbientEstimate:
         index = pd.Index(self.barcodes)
         index.name = self.index_name
         return index
+
+    def fractions(self) -> pd.Series:
+        """barcode -> the estimated alpha (float64: the grid value of the first maximum), NaN where the barcode was skipped; all
+        barcodes, handler order.  What predict_posteriors_with_ambient takes as `ambient_fractions`."""
+        found = self.best >= 0
+        alpha = np.where(found, self.alphas[np.where(found, self.best, 0)].astype(np.float64), np.nan)
+        return pd.Series(alpha, index=self._index(), name='alpha')
 
     def summary(self) -> pd.DataFrame:
         """Per barcode (all of them, handler order): `option`, the name it was assigned (None: skipped); `alpha`, the grid value of

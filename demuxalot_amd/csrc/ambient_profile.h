@@ -47,4 +47,12 @@ struct AmbientPlan {
 // DMX_ERR_UNSUPPORTED where a variant has 2^24 calls or more (the derived profile's counts are float32).
 int run_ambient_profile(dmx_ctx *c, const AmbientPlan &plan);
 
+namespace scratch {
+struct Scratch;
+}
+// The soup's profile on the device, [V + 1] floats of `sc` (one entry past the variants, 0: what a padding record's row may find):
+// the caller's `ambient`, or, for NULL, the one derived from the resident calls as dmx_ambient_profile defines it.  Shared by
+// dmx_ambient_profile and dmx_estep_ambient (estep_ambient.hip); `who` names the entry point in a refusal.
+int soup_profile(dmx_ctx *c, scratch::Scratch &sc, const char *who, const float *ambient, float lo, float hi, float **soup);
+
 }  // namespace dmx

@@ -161,24 +161,22 @@ hipError_t launch_ambient_profile(hipStream_t st, const AmbientArgs &a)
     return hipGetLastError();
 }
 
-int run_ambient_profile(dmx_ctx *c, const AmbientPlan &plan)
+// the soup's profile: the caller's, or the P-step's formula on the call counts (one column: beta[v] = calls of v + 1)
+int soup_profile(dmx_ctx *c, scratch::Scratch &sc, const char *who, const float *ambient, float lo, float hi, float **soup)
 {
     using namespace dmx::scratch;
     using namespace dmx::host;
-    const long long B = c->B, V = c->V;
-    const int A = plan.n_alphas;
+    const long long V = c->V;
     const hipStream_t st = c->stream;
-    Scratch sc(c);
-
-    // the soup's profile: the caller's, or the P-step's formula on the call counts (one column: beta[v] = calls of v + 1)
     float *d_soup = nullptr;
     DMX_TRY(sc.get(&d_soup, (size_t)V + 1));
+    *soup = d_soup;
     HIP_TRY(hipMemsetAsync(d_soup, 0, sizeof(float) * ((size_t)V + 1), st));
-    if (plan.ambient) {
-        if (V) HIP_TRY(hipMemcpyAsync(d_soup, plan.ambient, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, st));
+    if (ambient) {
+        if (V) HIP_TRY(hipMemcpyAsync(d_soup, ambient, sizeof(float) * (size_t)V, hipMemcpyHostToDevice, st));
     } else if (V) {
         if (c->n_csc != c->N || (c->n_items > 0 && (!c->d_item_variant.p || !c->d_item_len.p)))
-            return fail(DMX_ERR_UNSUPPORTED, "dmx_ambient_profile: the resident M-step records are not this problem's calls; supply `ambient`");
+            return fail(DMX_ERR_UNSUPPORTED, "%s: the resident M-step records are not this problem's calls; supply `ambient`", who);
         unsigned *d_count = nullptr;
         float *d_beta = nullptr;
         int *d_flags = nullptr;
@@ -197,10 +195,24 @@ int run_ambient_profile(dmx_ctx *c, const AmbientPlan &plan)
         int flags = 0;
         HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (flags) return fail(DMX_ERR_UNSUPPORTED, "dmx_ambient_profile: a variant has 2^24 calls or more: its count is no float32; supply `ambient`");
+        if (flags) return fail(DMX_ERR_UNSUPPORTED, "%s: a variant has 2^24 calls or more: its count is no float32; supply `ambient`", who);
         HIP_TRY(launch_probs_from_betas(st, d_beta, nullptr, c->d_v2snp.p, c->d_snp_ptr.p, c->d_snp_vars.p, 0LL, V, (long long)c->S, 1, nullptr,
-                                        plan.lo, plan.hi, d_soup));
+                                        lo, hi, d_soup));
     }
+    return 0;
+}
+
+int run_ambient_profile(dmx_ctx *c, const AmbientPlan &plan)
+{
+    using namespace dmx::scratch;
+    using namespace dmx::host;
+    const long long B = c->B, V = c->V;
+    const int A = plan.n_alphas;
+    const hipStream_t st = c->stream;
+    Scratch sc(c);
+
+    float *d_soup = nullptr;
+    DMX_TRY(soup_profile(c, sc, "dmx_ambient_profile", plan.ambient, plan.lo, plan.hi, &d_soup));
 
     AmbientArgs a = {};
     a.pair_ptr = c->d_pair_ptr.p;

@@ -22,6 +22,8 @@
 #include "dmx_host.h"
 #include "estep_plan.h"
 #include "ambient_profile.h"
+#include "ambient_scoring_plan.h"
+#include "estep_ambient.h"
 #include "estep_pools.h"
 #include "mstep_plan.h"
 
@@ -1014,6 +1016,30 @@ int dmx_ambient_profile(dmx_ctx *c, float lo, float hi, int32_t n_alphas, const 
     }
     const dmx::AmbientPlan plan{lo, hi, (int)n_alphas, alphas, donor1, donor2, ambient, loglik, best, ll_best, ll_zero, ambient_out};
     return dmx::run_ambient_profile(c, plan);
+}
+
+// The pooled E-step under per-barcode ambient fractions (estep_ambient.hip).  ambient_scoring_plan.h refuses, on the host, before
+// anything is uploaded or launched; plan_pools then lays out what it has accepted.
+int dmx_estep_ambient(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                      const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out, float *probs_out,
+                      int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi, const float *alpha, const float *ambient,
+                      float *ambient_out)
+{
+    namespace sp = dmx::asplan;
+    DMX_TRY(bind(c));
+    const sp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
+                          c->B,           c->V,          c->G};
+    const sp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    const sp::Verdict verdict = sp::check(facts, pools, alpha, ambient);
+    if (verdict.status != sp::OK) {
+        if (verdict.at >= 0) return fail(verdict.status, "dmx_estep_ambient: %s (index %lld)", verdict.what, verdict.at);
+        return fail(verdict.status, "dmx_estep_ambient: %s", verdict.what);
+    }
+    dmx::PoolsPlan plan;
+    DMX_TRY(plan_pools(c, "dmx_estep_ambient", true, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
+                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+    const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out};
+    return dmx::run_estep_ambient(c, plan, scoring);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)

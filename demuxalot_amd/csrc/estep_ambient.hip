@@ -1,0 +1,271 @@
+// estep_ambient.hip -- the pooled E-step under per-barcode ambient RNA fractions (include/demux_hip_debug.h: dmx_estep_ambient;
+// DESIGN.md 4.7).  Every option k of a barcode's pool is scored as dmx_estep_pools scores it, with one change to a call's term:
+//   m = q (1 - alpha[b]) + ambient[v] alpha[b],   logit[b, k] = f32( f64(pen) + sum over the calls in stored order of f64( log_f32(m keep + floor) ) )
+// q the option's own term (estep_epilogue.h: estep_terms), the mixture dmx_ambient_profile's line (ambient_profile.hip), every
+// operation rounded.  With alpha[b] == 0 the mixture IS q (q * 1 + a * 0), so the row is dmx_estep_pools' row bit for bit; a singlet's
+// logit with penalty 0 is dmx_ambient_profile's L for that donor and that alpha.
+// The walk is k_estep_pools': one wavefront per barcode, lane l / slot s holds option l + 64 s, records by wave-uniform loads, the
+// row offset as the scalar offset of the buffer loads.  What the mixture adds per call is the same for all lanes: the second product
+// ambient[v] alpha[b].  A 4-byte uniform request per call for ambient[v] is what bounded dmx_ambient_profile's first form at 1.7 x
+// the exact E-step, so a prologue (k_soup_terms, a call per lane, vector loads) leaves that product as a stream
+// beside the records, 8 bytes per CallPair, which the walk fetches with the record - contiguously, through the scalar cache.
+#include <hip/hip_runtime.h>
+
+#include "ambient_profile.h"
+#include "ambient_scoring_plan.h"
+#include "device_scratch.h"
+#include "estep_ambient.h"
+#include "estep_epilogue.h"
+
+namespace dmx {
+
+static_assert(asplan::MAX_OPTIONS == POOL_MAX_OPTIONS, "ambient_scoring_plan.h restates the limit");
+
+namespace {
+
+// first maximum, NaN never wins (results.hip: better)
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+constexpr int NO_OPTION = 0x7FFFFFFF;
+
+// One wavefront per barcode of a.order, lane l takes the calls l, l + 64, ... of the padded row: the record's row offset by a vector
+// load, the profile's entry of that row, one product - the contract's second one, rounded once.  A padding record (keep 0, floor 1)
+// points at row 0 and gets ambient[0] alpha[b]: finite, and multiplied by keep = 0 in the walk.
+__global__ __launch_bounds__(256) void k_soup_terms(SoupTermArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long slot = (long long)blockIdx.x * 4 + wave;
+    if (slot >= a.B) return;
+    const int b = __builtin_amdgcn_readfirstlane(a.order[slot]);
+    if (a.pool_of[b] < 0) return;  // (wave-uniform) nobody reads this row's terms
+    const float alpha = a.alpha[b];
+    const long long pbeg = a.pair_ptr[b];
+    const int ncalls = 2 * (int)(a.pair_ptr[b + 1] - pbeg);
+    const unsigned *__restrict__ words = (const unsigned *)(a.pairs + pbeg);  // a record: row_off[2], keep[2], floor[2], reserved[2]
+    float *__restrict__ out = a.soup_term + 2 * pbeg;
+    for (int call = lane; call < ncalls; call += 64) {
+        const unsigned row_off = words[(size_t)(call >> 1) * 8 + (call & 1)];
+        out[call] = a.ambient[aplan::row_of(row_off, a.row_shift, a.row_inverse)] * alpha;
+    }
+}
+
+// estep_terms with the mixture in place of the option's own term: two packed operations per pair of calls more
+template <int A, bool PAIRS, int H>
+__device__ __forceinline__ void estep_terms_mixed(const npm::f32x2 (&p1)[H][A], const npm::f32x2 (&p2)[H][A], const npm::f32x2 (&keep)[H],
+                                                  const npm::f32x2 (&flo)[H], const npm::f32x2 (&soup)[H], float w0, double (&acc)[A], int n_slots)
+{
+#pragma unroll
+    for (int q = 0; q < H; q++) {
+#pragma unroll
+        for (int s = 0; s < A; s++) {
+            if (A > 1 && s >= n_slots) continue;  // wave-uniform: slot entirely past the last option
+            npm::f32x2 p = p1[q][s];
+            if (PAIRS) p = (p + p2[q][s]) * 0.5f;
+            const npm::f32x2 own = p * w0;  // two products, one sum, each rounded (-ffp-contract=off)
+            const npm::f32x2 m = own + soup[q];
+            npm::f32x2 t = m * keep[q];
+            t = t + flo[q];
+            const npm::f32x2 lp = npm::log_f32_hot2(t);
+            acc[s] += (double)lp.x;  // call order preserved: 2q before 2q+1
+            acc[s] += (double)lp.y;
+        }
+    }
+}
+
+// k_estep_pools (estep_pools.hip) without its dense form, with the mixture
+template <int A, bool PAIRS, int U>
+__global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
+{
+    const PoolEstepArgs &a = args.pools;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long slot = (long long)blockIdx.x * 4 + wave;
+    if (slot >= a.n_list) return;
+    const int b = __builtin_amdgcn_readfirstlane(a.list[slot]);
+    const int p = __builtin_amdgcn_readfirstlane(a.pool_of[b]);
+    const long long obeg = a.opt_ptr[p];
+    const int K = (int)(a.opt_ptr[p + 1] - obeg);  // 1 .. 64 A
+    const int n_single = a.pool_size[p];
+    const float pen_pair = a.pair_penalty[p];
+    const float w0 = 1.0f - args.alpha[b];  // wave-uniform for the whole row
+    const unsigned *__restrict__ opts = a.opts + obeg;
+    const int n_slots = (K + 63) >> 6;
+
+    unsigned o1[A], o2[A];  // byte offsets of this lane's column(s) inside a table row
+    int kk[A];
+    bool valid[A];
+#pragma unroll
+    for (int s = 0; s < A; s++) {
+        const int k = lane + 64 * s;
+        valid[s] = k < K;
+        kk[s] = valid[s] ? k : K - 1;  // (a lane without an option repeats the last one: loads stay inside the table)
+        const unsigned pr = opts[kk[s]];
+        o1[s] = (pr & 0xFFFFu) * 4u;
+        o2[s] = (pr >> 16) * 4u;
+    }
+    double acc[A];
+#pragma unroll
+    for (int s = 0; s < A; s++) acc[s] = 0.0;
+
+    const long long pbeg = a.pair_ptr[b];
+    const int npairs = (int)(a.pair_ptr[b + 1] - pbeg);  // a multiple of 4: rows are padded to 8 calls
+    const CallPair *__restrict__ recs = a.pairs + pbeg;
+    const float2 *__restrict__ soup_terms = args.soup_term + pbeg;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.prob, 0, (int)a.prob_bytes, 0x00020000);
+    constexpr int H = U / 2;
+    static_assert(H == 1 || H == 2 || H == 4, "batches tile a row of whole 8-call groups");
+    for (int j0 = 0; j0 < npairs; j0 += H) {
+        RecBatch<A, H, PAIRS> x;
+        load_batch<A, H, PAIRS>(x, recs, j0, rsrc, o1, o2, n_slots);
+        const int j = __builtin_amdgcn_readfirstlane(j0);  // wave-uniform, as in load_batch: the terms come by scalar loads too
+        npm::f32x2 soup[H];
+#pragma unroll
+        for (int q = 0; q < H; q++) {
+            const float2 st = soup_terms[j + q];
+            soup[q] = npm::f32x2{st.x, st.y};
+        }
+        estep_terms_mixed<A, PAIRS, H>(x.p1, x.p2, x.keep, x.flo, soup, w0, acc, n_slots);
+    }
+
+    // ---- epilogue: k_estep_pools' - the logit, the softmax as the exact forms evaluate it, the compact row, the read-outs ----
+    float lg[A], x[A];
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int s = 0; s < A; s++) {
+        const float pen = kk[s] >= n_single ? pen_pair : 0.0f;
+        lg[s] = (float)((double)pen + acc[s]);
+        mx = valid[s] ? fmaxf(mx, lg[s]) : mx;
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+#pragma unroll
+    for (int s = 0; s < A; s++) x[s] = npm::exp_f32(lg[s] - mx);
+    const float tot = reg_row_sum<64, A>(x, K, lane, 0);
+    const long long row = a.row_ptr[b];
+    float post[A];
+    float bv = -__builtin_inff();
+    int bi = NO_OPTION;
+#pragma unroll
+    for (int s = 0; s < A; s++) {
+        post[s] = x[s] / tot;
+        if (valid[s]) {
+            a.logits[row + kk[s]] = lg[s];
+            a.post[row + kk[s]] = post[s];
+            if (better(post[s], kk[s], bv, bi)) {
+                bv = post[s];
+                bi = kk[s];
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (better(ov, oi, bv, bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    // the pair posteriors, widened to float64 and added in ascending option order (the order is the contract): option k sits in
+    // lane k % 64 of slot k / 64 and comes out by v_readlane (k is wave-uniform)
+    double mass = 0.0;
+    if (PAIRS) {
+#pragma unroll
+        for (int s = 0; s < A; s++) {
+            const int lo = max(n_single - 64 * s, 0), hi = min(K - 64 * s, 64);
+            for (int l = lo; l < hi; l++)
+                mass += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, post[s]), l));
+        }
+    }
+    if (lane == 0) {
+        a.best[b] = bi != NO_OPTION ? bi : -1;
+        a.best_prob[b] = bi != NO_OPTION ? bv : __builtin_nanf("");
+        a.pair_mass[b] = mass;
+    }
+}
+
+template <int A, int U>
+void launch_one(hipStream_t st, const AmbientEstepArgs &a, bool pairs)
+{
+    const dim3 grid((unsigned)((a.pools.n_list + 3) / 4)), block(256);
+    if (pairs)
+        hipLaunchKernelGGL((k_estep_ambient<A, true, U>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((k_estep_ambient<A, false, U>), grid, block, 0, st, a);
+}
+
+}  // namespace
+
+hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a)
+{
+    if (a.B == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_soup_terms, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// calls per batch as launch_estep_pools has them
+hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs)
+{
+    if (a.pools.n_list == 0) return hipSuccess;
+    switch (slots) {
+    case 1: launch_one<1, 8>(st, a, pairs); break;
+    case 2: launch_one<2, 4>(st, a, pairs); break;
+    case 4: launch_one<4, 2>(st, a, pairs); break;
+    case 8: launch_one<8, 2>(st, a, pairs); break;
+    case 16: launch_one<16, 2>(st, a, pairs); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring)
+{
+    using namespace dmx::scratch;
+    using namespace dmx::host;
+    const long long B = c->B, V = c->V;
+    const hipStream_t st = c->stream;
+    PoolsRunPtr run;
+    DMX_TRY(prepare_estep_pools(c, plan, false, run));
+    const PoolsLaunchView view = pools_launch_view(*run);
+
+    Scratch sc(c);
+    float *d_soup = nullptr, *d_alpha = nullptr, *d_terms = nullptr;
+    DMX_TRY(soup_profile(c, sc, "dmx_estep_ambient", scoring.ambient, scoring.lo, scoring.hi, &d_soup));
+    DMX_TRY(upload(sc, &d_alpha, scoring.alpha, (size_t)B, st));
+    DMX_TRY(sc.get(&d_terms, 2 * (size_t)c->n_pairs));  // 4 bytes per padded call
+
+    SoupTermArgs t = {};
+    t.pair_ptr = c->d_pair_ptr.p;
+    t.pairs = c->d_call_pairs.p;
+    t.order = c->d_bc_order.p;
+    t.B = B;
+    t.pool_of = view.args.pool_of;
+    t.alpha = d_alpha;
+    t.ambient = d_soup;
+    const aplan::RowDivide rows = aplan::row_divide((unsigned)c->G * 4u);
+    t.row_shift = rows.shift;
+    t.row_inverse = rows.inverse;
+    t.soup_term = d_terms;
+
+    AmbientEstepArgs a = {};
+    a.pools = view.args;
+    a.pools.dense = nullptr;
+    a.alpha = d_alpha;
+    a.soup_term = (const float2 *)d_terms;
+    {
+        TimerSpan ev{nullptr, nullptr};
+        SpanGuard ev_guard{c, &ev};
+        timer_begin(c, DMX_T_ESTEP, &ev);
+        HIP_TRY(launch_soup_terms(st, t));
+        for (int k = 0; k < POOL_BUCKETS; k++) {
+            a.pools.list = view.lists[k];
+            a.pools.n_list = view.n_lists[k];
+            HIP_TRY(launch_estep_ambient(st, a, pool_bucket_slots(k), view.with_doublets));
+        }
+        timer_end(c, DMX_T_ESTEP, ev);
+    }
+    if (scoring.ambient_out && V) HIP_TRY(hipMemcpyAsync(scoring.ambient_out, d_soup, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, st));
+    return read_back_estep_pools(c, *run);  // (synchronises: the uploads read the caller's arrays, the downloads fill them)
+}
+
+}  // namespace dmx

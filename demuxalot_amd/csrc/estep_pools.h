@@ -81,5 +81,14 @@ int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &run, float power);
 int read_back_estep_pools(dmx_ctx *c, PoolsRun &run);
 // the three in a row without the dense form: dmx_estep_pools
 int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan);
+// What another kernel needs to walk a prepared run in place of launch_estep_pools_pass (estep_ambient.hip): the argument block
+// without `list` / `n_list` / `dense`, and the barcodes of every bucket.
+struct PoolsLaunchView {
+    PoolEstepArgs args;
+    const int *lists[POOL_BUCKETS];
+    long long n_lists[POOL_BUCKETS];
+    bool with_doublets;
+};
+PoolsLaunchView pools_launch_view(const PoolsRun &run);
 
 }  // namespace dmx

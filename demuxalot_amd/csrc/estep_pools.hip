@@ -303,6 +303,18 @@ int read_back_estep_pools(dmx_ctx *c, PoolsRun &r)
     return 0;
 }
 
+PoolsLaunchView pools_launch_view(const PoolsRun &run)
+{
+    PoolsLaunchView view = {};
+    view.args = run.a;
+    for (int k = 0; k < POOL_BUCKETS; k++) {
+        view.lists[k] = run.d_lists[k];
+        view.n_lists[k] = run.n_lists[k];
+    }
+    view.with_doublets = run.plan->with_doublets;
+    return view;
+}
+
 int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
 {
     PoolsRunPtr run;

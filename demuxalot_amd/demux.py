@@ -27,7 +27,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, donor_readout
-from .ambient import AmbientEstimate, assigned_donors, default_alphas, resolve_assignments
+from .ambient import AmbientEstimate, assigned_donors, best_singlets, default_alphas, resolve_assignments, resolve_fractions
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
 from .pools import PooledPosteriors, resolve_pools
@@ -854,6 +854,109 @@ class Demultiplexer:
             out = ctx.ambient_profile(donor1, donor2, alphas, p_genotype_clip, ambient=ambient, fetch_profile=keep_profile)
         return AmbientEstimate(barcode_handler.ordered_barcodes, option_names, columns, alphas, out['ambient'], out['best'], out['ll_best'],
                                out['ll_zero'], loglik=out['loglik'], index_name='BARCODE')
+
+    @staticmethod
+    def _one_pool_of_everybody(genotypes, barcode_handler, doublet_prior, who):
+        """The arguments of a pooled pass that scores every barcode against all donors with the reference's penalties:
+        (pool columns, pool_of_barcode, pair_penalty, option names)."""
+        G = genotypes.n_genotypes
+        n_options = G * (G + 1) // 2 if doublet_prior != 0 else G
+        if n_options > 1024:
+            raise ValueError(f'{who}: {G} donors make {n_options} options, more than the 1024 one pool can hold (44 donors with doublets); '
+                             'give every barcode a pool of its own donors with barcode2pool / pool2donors')
+        penalties = Demultiplexer._doublet_penalties(G, doublet_prior)
+        pair_penalty = np.array([penalties[-1] if G > 1 else 0.0], dtype=np.float32)
+        return ([np.arange(G, dtype=np.int64)], np.zeros(barcode_handler.n_barcodes, dtype=np.int32), pair_penalty,
+                _option_names(genotypes.genotype_names, doublet_prior))
+
+    @staticmethod
+    def predict_posteriors_with_ambient(chromosome2compressed_snp_calls,
+                                        genotypes,
+                                        barcode_handler,
+                                        ambient_fractions,
+                                        ambient=None,
+                                        p_genotype_clip=0.01,
+                                        doublet_prior=0.35,
+                                        barcode2pool=None,
+                                        pool2donors=None):
+        """(not in the reference) predict_posteriors with every option scored under the barcode's own ambient fraction: a call's
+        term is q (1 - alpha_b) + ambient[v] alpha_b in place of the option's q, so a contaminated singlet - its donor plus a little
+        of everybody - is not taken for a doublet.  With every fraction 0 the result is predict_posteriors' (exact mode) bit for bit.
+        :param ambient_fractions: Series or mapping barcode -> alpha in [0, 1] (AmbientEstimate.fractions() gives one); a barcode
+            that is missing, None or NaN is scored with 0
+        :param ambient: float32[n_variants] allele profile of the soup, or None: derived from the calls as estimate_ambient does
+        :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
+        Returns (logits_df, probs_df) with predict_posteriors' index, columns and dtypes; with pools a PooledPosteriors.
+        ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        alpha = resolve_fractions(barcode_handler.ordered_barcodes, ambient_fractions)
+        pooled = barcode2pool is not None
+        if pooled:
+            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        else:
+            pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
+                genotypes, barcode_handler, doublet_prior, 'predict_posteriors_with_ambient')
+        with shared_context_lock:
+            ctx = get_context()
+            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
+            ctx.set_addition(None)
+            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+            assert np.isfinite(genotype_prob).all()
+            out = ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip, ambient=ambient)
+        if pooled:
+            return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
+                                    out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
+        shape = (barcode_handler.n_barcodes, len(column_names))
+        logits_df = pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
+        probs_df = pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
+        return logits_df, probs_df
+
+    @staticmethod
+    def predict_posteriors_decontaminated(chromosome2compressed_snp_calls,
+                                          genotypes,
+                                          barcode_handler,
+                                          alphas=None,
+                                          ambient=None,
+                                          p_genotype_clip=0.01,
+                                          doublet_prior=0.35):
+        """(not in the reference) Three passes over one packed, resident problem: (1) plain posteriors, in the exact arithmetic;
+        (2) estimate_ambient with every barcode assigned its best SINGLET - the first maximum over the singlet columns of the plain
+        logits (their penalty is 0: the donors' log-likelihoods), whatever the doublet columns say, since a contaminated singlet is
+        exactly what the plain pass takes for a doublet; (3) predict_posteriors_with_ambient with those fractions and the same soup
+        profile.  Returns (logits_df, probs_df, AmbientEstimate): the re-scored frames and the estimate of pass 2.
+        The fractions are estimated under the singlet hypothesis: part of a true doublet's second donor can be absorbed as
+        contamination.
+        :param alphas, ambient: as estimate_ambient takes them
+        ValueError: more than 1024 options (44 donors with doublets)."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        names = list(genotypes.genotype_names)
+        G = len(names)
+        pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
+            genotypes, barcode_handler, doublet_prior, 'predict_posteriors_decontaminated')
+        alphas = default_alphas() if alphas is None else np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
+        B, with_doublets = barcode_handler.n_barcodes, doublet_prior != 0
+        with shared_context_lock:
+            ctx = get_context()
+            _pack_on_device(chromosome2compressed_snp_calls, genotypes, B, False, fetch_betas=False, ctx=ctx)
+            ctx.set_addition(None)
+            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+            assert np.isfinite(genotype_prob).all()
+            plain = ctx.estep_pools(pool_columns, pool_of_barcode, with_doublets, pair_penalty, fetch_probs=False)
+            columns = best_singlets(plain['logits'].reshape(B, len(column_names)), G)
+            donor1, donor2 = assigned_donors(G, columns)
+            profile = ctx.ambient_profile(donor1, donor2, alphas, p_genotype_clip, ambient=ambient, fetch_profile=False)
+            estimate = AmbientEstimate(barcode_handler.ordered_barcodes, _option_names(names, 1), columns, alphas, profile['ambient'],
+                                       profile['best'], profile['ll_best'], profile['ll_zero'], index_name='BARCODE')
+            alpha = np.nan_to_num(estimate.fractions().values, nan=0.0).astype(np.float32)
+            out = ctx.estep_ambient(pool_columns, pool_of_barcode, with_doublets, pair_penalty, alpha, p_genotype_clip, ambient=profile['ambient'])
+        shape = (B, len(column_names))
+        logits_df = pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
+        probs_df = pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
+        return logits_df, probs_df, estimate
 
     @staticmethod
     def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):

@@ -746,6 +746,25 @@ class DeviceContext:
                                             ptr(out['best']), ptr(out['ll_best']), ptr(out['ll_zero']), ptr(out['ambient'])))
         return out
 
+    def estep_ambient(self, pools, pool_of_barcode, with_doublets, pair_penalty, alpha, p_genotype_clip=0.01, ambient=None,
+                      fetch_logits=True, fetch_probs=True):
+        """The pooled E-step under per-barcode ambient fractions (include/demux_hip_debug.h: dmx_estep_ambient): estep_pools() with
+        every option scored as q (1 - alpha[b]) + ambient[v] alpha[b].  alpha: float32[B] in [0, 1] (not looked at for a barcode in no
+        pool); ambient: float32[V] or None (derived from the resident calls, clipped as the genotype table is).  Returns
+        estep_pools()'s dict with one more key, 'ambient': float32[V], the profile that was used.  The resident results of the last
+        E-step are left as they are."""
+        alpha = as_c(alpha, np.float32)
+        assert alpha.shape == (self.B,), 'one fraction per barcode'
+        if ambient is not None:
+            ambient = as_c(ambient, np.float32)
+            assert ambient.shape == (self.V,), 'one ambient value per variant'
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        out['ambient'] = np.empty(self.V, np.float32)
+        check(self._lib.dmx_estep_ambient(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, ptr(alpha),
+                                          ptr(ambient), ptr(out['ambient'])))
+        return out
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

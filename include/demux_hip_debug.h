@@ -482,6 +482,34 @@ int dmx_ambient_profile(dmx_ctx *ctx, float lo, float hi, int32_t n_alphas, cons
                         float *loglik /* nullable, [B, n_alphas] */, int32_t *best, float *ll_best, float *ll_zero /* nullable, [B] */,
                         float *ambient_out /* nullable, [V] */);
 
+/* ------------------------------------------------------------------------- *
+ * The pooled E-step under per-barcode ambient RNA fractions (product API; csrc/estep_ambient.hip).  dmx_estep_pools
+ * with every option scored under the barcode's own contamination fraction: a contaminated singlet - its donor plus a little of
+ * everybody - is no longer taken for a doublet.  (call order: a problem and dmx_probs_from_betas / dmx_set_probs; single GPU)
+ *   pools, rows, read-outs   the arguments of dmx_estep_pools, with its meaning.
+ *   alpha       float32[B]: the fraction of barcode b, finite and in [0, 1]; not looked at for a barcode in no pool.
+ *   ambient     float32[V], nullable: the soup's allele profile, as dmx_ambient_profile takes it; NULL: derived exactly as
+ *               dmx_ambient_profile derives it, clipped to [lo, hi].  ambient_out (nullable, float32[V]): the profile that was used.
+ *   logit       for barcode b of pool p and option k of that pool, in float32 without contraction, over the calls of b in stored order:
+ *                 q = prob[v, d]  or  (prob[v, d1] + prob[v, d2]) * 0.5f                  as dmx_estep_pools
+ *                 m = q * (1.0f - alpha[b]) + ambient[v] * alpha[b]                       two products, one sum, each rounded
+ *                 logit[b, k] = f32( f64(pen) + sum of f64( log_f32(m * keep + floor) ) )  pen = 0 for a singlet, pair_penalty[p] for a pair
+ *               The softmax, the compact rows and the read-outs are dmx_estep_pools'.
+ * Two identities: with alpha all 0, m == q, and every output equals dmx_estep_pools' on the same arguments bit for bit; with
+ * pair_penalty 0, logit[b, k] equals dmx_ambient_profile's L[b, j] for the option's donors and alphas[j] == alpha[b], bit for bit.
+ * Checked on the host before anything is uploaded or launched (csrc/ambient_scoring_plan.h).  DMX_ERR_INVALID: everything
+ * dmx_estep_pools refuses so, a null alpha with B > 0, an alpha of a pooled barcode or an ambient value that is not finite or outside
+ * [0, 1].  DMX_ERR_UNSUPPORTED: a pool of more than 1024 options, a communicator attached, a genotype table in a padded exchange
+ * layout.  The resident results of the last dmx_estep / dmx_em are left as they are; the pass is counted in the DMX_T_ESTEP slot.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_ambient(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                      const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                      const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                      float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                      int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                      float lo, float hi, const float *alpha /* [B] */, const float *ambient /* nullable, [V] */,
+                      float *ambient_out /* nullable, [V] */);
+
 #ifdef __cplusplus
 }
 #endif
