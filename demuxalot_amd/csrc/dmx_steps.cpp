@@ -26,6 +26,7 @@
 #include "estep_ambient.h"
 #include "estep_pools.h"
 #include "mstep_plan.h"
+#include "pools_plan.h"
 
 using namespace dmx::host;
 
@@ -891,12 +892,39 @@ int dmx_estep(dmx_ctx *c, int with_doublets, const float *penalties, const void 
     return 0;
 }
 
-// The pooled E-step (estep_pools.hip).  Everything is checked here, on the host, before anything is uploaded or launched: one
+// What a plan header refuses (pools_plan.h, ambient_plan.h, ambient_scoring_plan.h), as the entry's error:
+// "<who>: [<value> ]<text>[ (index <at>)]".
+static int refuse(const char *who, int status, const char *what, long long at, long long value = -1)
+{
+    static_assert(dmx::pplan::OK == DMX_OK && dmx::pplan::INVALID == DMX_ERR_INVALID && dmx::pplan::UNSUPPORTED == DMX_ERR_UNSUPPORTED, "pools_plan.h restates the codes");
+    char number[24] = "", index[40] = "";
+    if (value >= 0) snprintf(number, sizeof number, "%lld ", value);
+    if (at >= 0) snprintf(index, sizeof index, " (index %lld)", at);
+    return fail(status, "%s: %s%s%s", who, number, what, index);
+}
+
+// what the device half reads of a call that check() has accepted: the options laid out, the caller's arrays and outputs
+static void fill_pools_plan(const dmx::pplan::Pools &pools, float *logits_out, float *probs_out, int32_t *best_option, float *best_prob,
+                            double *doublet_mass, dmx::PoolsPlan &plan)
+{
+    plan.with_doublets = pools.with_doublets != 0;
+    plan.n_pools = pools.n_pools;
+    dmx::pplan::layout(pools, plan.opt_ptr, plan.opts, plan.pool_size);
+    plan.pair_penalty = pools.pair_penalty;
+    plan.pool_of_barcode = pools.pool_of_barcode;
+    plan.row_ptr = pools.row_ptr;
+    plan.logits_out = logits_out;
+    plan.probs_out = probs_out;
+    plan.best_option = best_option;
+    plan.best_prob = best_prob;
+    plan.doublet_mass = doublet_mass;
+}
+
+// The pooled E-step (estep_pools.hip).  Everything is checked on the host (pools_plan.h) before anything is uploaded or launched: one
 // function for dmx_estep_pools, dmx_estep_pools_resident and dmx_em_pools.  resident: the entry leaves the dense singlet posteriors in
 // the context (single GPU, no communicator).
-static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_betas, int with_doublets, int32_t n_pools, const int64_t *pool_start,
-                      const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
-                      float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, dmx::PoolsPlan &plan)
+static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_betas, const dmx::pplan::Pools &pools, float *logits_out, float *probs_out,
+                      int32_t *best_option, float *best_prob, double *doublet_mass, dmx::PoolsPlan &plan)
 {
     if (need_betas) {
         if (!(c->have_problem && c->have_betas)) return fail(DMX_ERR_INVALID, "call order: dmx_set_problem + dmx_set_betas before %s", who);
@@ -905,58 +933,9 @@ static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_beta
     }
     if (c->nranks > 1) return fail(DMX_ERR_UNSUPPORTED, "%s: single GPU only", who);
     if (resident && c->attached()) return fail(DMX_ERR_UNSUPPORTED, "%s: a context with a communicator attached is not supported", who);
-    if (with_doublets != 0 && with_doublets != 1) return fail(DMX_ERR_INVALID, "%s: with_doublets must be 0 or 1", who);
-    if (n_pools < 0) return fail(DMX_ERR_INVALID, "%s: negative n_pools", who);
-    if (!pool_start || !row_ptr) return fail(DMX_ERR_INVALID, "%s: null pool_start / row_ptr", who);
-    if (n_pools > 0 && (!pool_donors || !pair_penalty)) return fail(DMX_ERR_INVALID, "%s: null pool_donors / pair_penalty", who);
-    if (c->B > 0 && !pool_of_barcode) return fail(DMX_ERR_INVALID, "%s: null pool_of_barcode", who);
-    if (pool_start[0] != 0) return fail(DMX_ERR_INVALID, "%s: pool_start[0] is %lld, not 0", who, (long long)pool_start[0]);
-    const long long B = c->B;
-    const int G = c->G;
-    plan.with_doublets = with_doublets != 0;
-    plan.n_pools = n_pools;
-    plan.opt_ptr.assign(1, 0);
-    for (int p = 0; p < n_pools; p++) {
-        const long long first = pool_start[p], g = pool_start[p + 1] - first;
-        if (g < 0) return fail(DMX_ERR_INVALID, "%s: pool_start decreases at pool %d", who, p);
-        if (g == 0) return fail(DMX_ERR_INVALID, "%s: pool %d is empty", who, p);
-        for (long long i = 0; i < g; i++) {
-            const long long d = pool_donors[first + i];
-            if (d < 0 || d >= G) return fail(DMX_ERR_INVALID, "%s: donor %lld of pool %d is outside [0, %d)", who, d, p, G);
-            if (i > 0 && d <= pool_donors[first + i - 1])
-                return fail(DMX_ERR_INVALID, "%s: the donors of pool %d are not strictly ascending", who, p);
-            if (d >= 65536) return fail(DMX_ERR_UNSUPPORTED, "%s: donor index %lld does not fit the 16 bits of an option's column", who, d);
-        }
-        const long long options = with_doublets ? g * (g + 1) / 2 : g;
-        if (options > dmx::POOL_MAX_OPTIONS)
-            return fail(DMX_ERR_UNSUPPORTED, "%s: pool %d has %lld options, more than %d (44 donors with doublets, 1024 without)", who, p,
-                        options, dmx::POOL_MAX_OPTIONS);
-        // the reference's options for the genotype list (demux.py:175-191): singlets in list order, then the pairs i < j, i-major
-        const int32_t *d = pool_donors + first;
-        for (long long i = 0; i < g; i++) plan.opts.push_back((unsigned)d[i] | (unsigned)d[i] << 16);
-        if (with_doublets)
-            for (long long i = 0; i < g; i++)
-                for (long long j = i + 1; j < g; j++) plan.opts.push_back((unsigned)d[i] | (unsigned)d[j] << 16);
-        plan.pool_size.push_back((int)g);
-        plan.opt_ptr.push_back((long long)plan.opts.size());
-    }
-    if (row_ptr[0] != 0) return fail(DMX_ERR_INVALID, "%s: row_ptr[0] is %lld, not 0", who, (long long)row_ptr[0]);
-    for (long long b = 0; b < B; b++) {
-        const int p = pool_of_barcode[b];
-        if (p < -1 || p >= n_pools) return fail(DMX_ERR_INVALID, "%s: pool_of_barcode[%lld] = %d is outside [-1, %d)", who, b, p, (int)n_pools);
-        const long long options = p < 0 ? 0 : plan.opt_ptr[(size_t)p + 1] - plan.opt_ptr[(size_t)p];
-        if (row_ptr[b + 1] - row_ptr[b] != options)
-            return fail(DMX_ERR_INVALID, "%s: row_ptr gives barcode %lld %lld entries, its pool has %lld options", who, b,
-                        (long long)(row_ptr[b + 1] - row_ptr[b]), options);
-    }
-    plan.pair_penalty = pair_penalty;
-    plan.pool_of_barcode = pool_of_barcode;
-    plan.row_ptr = row_ptr;
-    plan.logits_out = logits_out;
-    plan.probs_out = probs_out;
-    plan.best_option = best_option;
-    plan.best_prob = best_prob;
-    plan.doublet_mass = doublet_mass;
+    const dmx::pplan::Verdict verdict = dmx::pplan::check(c->G, c->B, pools);
+    if (verdict.status != dmx::pplan::OK) return refuse(who, verdict.status, verdict.what, verdict.at, verdict.value);
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
     return 0;
 }
 
@@ -978,7 +957,7 @@ int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_
 {
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
-    DMX_TRY(plan_pools(c, "dmx_estep_pools", false, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
+    DMX_TRY(plan_pools(c, "dmx_estep_pools", false, false, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
                        logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
     return dmx::run_estep_pools(c, plan);
 }
@@ -989,8 +968,8 @@ int dmx_estep_pools_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, con
 {
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
-    DMX_TRY(plan_pools(c, "dmx_estep_pools_resident", true, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode,
-                       row_ptr, logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+    DMX_TRY(plan_pools(c, "dmx_estep_pools_resident", true, false, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
+                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
     DMX_TRY(begin_dense_pools(c));
     dmx::PoolsRunPtr run;
     DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
@@ -1010,16 +989,13 @@ int dmx_ambient_profile(dmx_ctx *c, float lo, float hi, int32_t n_alphas, const 
     const ap::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
                           c->B,           c->V,          c->G};
     const ap::Verdict verdict = ap::check(facts, n_alphas, alphas, (const int *)donor1, (const int *)donor2, ambient);
-    if (verdict.status != ap::OK) {
-        if (verdict.at >= 0) return fail(verdict.status, "dmx_ambient_profile: %s (index %lld)", verdict.what, verdict.at);
-        return fail(verdict.status, "dmx_ambient_profile: %s", verdict.what);
-    }
+    if (verdict.status != ap::OK) return refuse("dmx_ambient_profile", verdict.status, verdict.what, verdict.at);
     const dmx::AmbientPlan plan{lo, hi, (int)n_alphas, alphas, donor1, donor2, ambient, loglik, best, ll_best, ll_zero, ambient_out};
     return dmx::run_ambient_profile(c, plan);
 }
 
 // The pooled E-step under per-barcode ambient fractions (estep_ambient.hip).  ambient_scoring_plan.h refuses, on the host, before
-// anything is uploaded or launched; plan_pools then lays out what it has accepted.
+// anything is uploaded or launched - the pools among the rest, once; what it has accepted is laid out as for dmx_estep_pools.
 int dmx_estep_ambient(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
                       const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out, float *probs_out,
                       int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi, const float *alpha, const float *ambient,
@@ -1031,13 +1007,9 @@ int dmx_estep_ambient(dmx_ctx *c, int with_doublets, int32_t n_pools, const int6
                           c->B,           c->V,          c->G};
     const sp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
     const sp::Verdict verdict = sp::check(facts, pools, alpha, ambient);
-    if (verdict.status != sp::OK) {
-        if (verdict.at >= 0) return fail(verdict.status, "dmx_estep_ambient: %s (index %lld)", verdict.what, verdict.at);
-        return fail(verdict.status, "dmx_estep_ambient: %s", verdict.what);
-    }
+    if (verdict.status != sp::OK) return refuse("dmx_estep_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    DMX_TRY(plan_pools(c, "dmx_estep_ambient", true, false, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
-                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
     const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out};
     return dmx::run_estep_ambient(c, plan, scoring);
 }
@@ -1097,7 +1069,7 @@ int dmx_em_pools(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doub
 {
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
-    DMX_TRY(plan_pools(c, "dmx_em_pools", true, true, with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr,
+    DMX_TRY(plan_pools(c, "dmx_em_pools", true, true, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
                        logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
     if (n_iterations < 1) return fail(DMX_ERR_INVALID, "dmx_em_pools: n_iterations must be >= 1");
     DMX_TRY(begin_dense_pools(c));

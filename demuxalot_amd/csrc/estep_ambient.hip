@@ -4,28 +4,22 @@
 // q the option's own term (estep_epilogue.h: estep_terms), the mixture dmx_ambient_profile's line (ambient_profile.hip), every
 // operation rounded.  With alpha[b] == 0 the mixture IS q (q * 1 + a * 0), so the row is dmx_estep_pools' row bit for bit; a singlet's
 // logit with penalty 0 is dmx_ambient_profile's L for that donor and that alpha.
-// The walk is k_estep_pools': one wavefront per barcode, lane l / slot s holds option l + 64 s, records by wave-uniform loads, the
-// row offset as the scalar offset of the buffer loads.  What the mixture adds per call is the same for all lanes: the second product
-// ambient[v] alpha[b].  A 4-byte uniform request per call for ambient[v] is what bounded dmx_ambient_profile's first form at 1.7 x
-// the exact E-step, so a prologue (k_soup_terms, a call per lane, vector loads) leaves that product as a stream
-// beside the records, 8 bytes per CallPair, which the walk fetches with the record - contiguously, through the scalar cache.
+// The two ends of a row are k_estep_pools' own (estep_pools_row.h), and so is the shape of the walk between them.  What the mixture
+// adds per call is the same for all lanes: the second product ambient[v] alpha[b].  A 4-byte uniform request per call for
+// ambient[v] is what bounded dmx_ambient_profile's first form at 1.7 x the exact E-step, so a prologue
+// (k_soup_terms, a call per lane, vector loads) leaves that product as a stream beside the records, 8 bytes per CallPair, which the
+// walk fetches with the record - contiguously, through the scalar cache.
 #include <hip/hip_runtime.h>
 
 #include "ambient_profile.h"
-#include "ambient_scoring_plan.h"
 #include "device_scratch.h"
 #include "estep_ambient.h"
 #include "estep_epilogue.h"
+#include "estep_pools_row.h"
 
 namespace dmx {
 
-static_assert(asplan::MAX_OPTIONS == POOL_MAX_OPTIONS, "ambient_scoring_plan.h restates the limit");
-
 namespace {
-
-// first maximum, NaN never wins (results.hip: better)
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-constexpr int NO_OPTION = 0x7FFFFFFF;
 
 // One wavefront per barcode of a.order, lane l takes the calls l, l + 64, ... of the padded row: the record's row offset by a vector
 // load, the profile's entry of that row, one product - the contract's second one, rounded once.  A padding record (keep 0, floor 1)
@@ -72,7 +66,7 @@ __device__ __forceinline__ void estep_terms_mixed(const npm::f32x2 (&p1)[H][A], 
     }
 }
 
-// k_estep_pools (estep_pools.hip) without its dense form, with the mixture
+// k_estep_pools (estep_pools.hip) without its dense form, with the mixture: w0 and the stream of the soup's terms beside the records
 template <int A, bool PAIRS, int U>
 __global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
 {
@@ -81,42 +75,21 @@ __global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long slot = (long long)blockIdx.x * 4 + wave;
     if (slot >= a.n_list) return;
-    const int b = __builtin_amdgcn_readfirstlane(a.list[slot]);
-    const int p = __builtin_amdgcn_readfirstlane(a.pool_of[b]);
-    const long long obeg = a.opt_ptr[p];
-    const int K = (int)(a.opt_ptr[p + 1] - obeg);  // 1 .. 64 A
-    const int n_single = a.pool_size[p];
-    const float pen_pair = a.pair_penalty[p];
-    const float w0 = 1.0f - args.alpha[b];  // wave-uniform for the whole row
-    const unsigned *__restrict__ opts = a.opts + obeg;
-    const int n_slots = (K + 63) >> 6;
-
-    unsigned o1[A], o2[A];  // byte offsets of this lane's column(s) inside a table row
-    int kk[A];
-    bool valid[A];
-#pragma unroll
-    for (int s = 0; s < A; s++) {
-        const int k = lane + 64 * s;
-        valid[s] = k < K;
-        kk[s] = valid[s] ? k : K - 1;  // (a lane without an option repeats the last one: loads stay inside the table)
-        const unsigned pr = opts[kk[s]];
-        o1[s] = (pr & 0xFFFFu) * 4u;
-        o2[s] = (pr >> 16) * 4u;
-    }
+    PoolRow<A> row;
+    pool_row_open<A>(a, slot, lane, row);
+    const float w0 = 1.0f - args.alpha[row.b];  // wave-uniform for the whole row
     double acc[A];
 #pragma unroll
     for (int s = 0; s < A; s++) acc[s] = 0.0;
 
-    const long long pbeg = a.pair_ptr[b];
-    const int npairs = (int)(a.pair_ptr[b + 1] - pbeg);  // a multiple of 4: rows are padded to 8 calls
-    const CallPair *__restrict__ recs = a.pairs + pbeg;
-    const float2 *__restrict__ soup_terms = args.soup_term + pbeg;
+    const CallPair *__restrict__ recs = a.pairs + row.pbeg;
+    const float2 *__restrict__ soup_terms = args.soup_term + row.pbeg;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.prob, 0, (int)a.prob_bytes, 0x00020000);
     constexpr int H = U / 2;
     static_assert(H == 1 || H == 2 || H == 4, "batches tile a row of whole 8-call groups");
-    for (int j0 = 0; j0 < npairs; j0 += H) {
+    for (int j0 = 0; j0 < row.npairs; j0 += H) {
         RecBatch<A, H, PAIRS> x;
-        load_batch<A, H, PAIRS>(x, recs, j0, rsrc, o1, o2, n_slots);
+        load_batch<A, H, PAIRS>(x, recs, j0, rsrc, row.o1, row.o2, row.n_slots);
         const int j = __builtin_amdgcn_readfirstlane(j0);  // wave-uniform, as in load_batch: the terms come by scalar loads too
         npm::f32x2 soup[H];
 #pragma unroll
@@ -124,64 +97,14 @@ __global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
             const float2 st = soup_terms[j + q];
             soup[q] = npm::f32x2{st.x, st.y};
         }
-        estep_terms_mixed<A, PAIRS, H>(x.p1, x.p2, x.keep, x.flo, soup, w0, acc, n_slots);
+        estep_terms_mixed<A, PAIRS, H>(x.p1, x.p2, x.keep, x.flo, soup, w0, acc, row.n_slots);
     }
-
-    // ---- epilogue: k_estep_pools' - the logit, the softmax as the exact forms evaluate it, the compact row, the read-outs ----
-    float lg[A], x[A];
-    float mx = -__builtin_inff();
+    // close reads a copy of the sums: handed `acc` itself, the array the walk's functions wrote through, the multi-slot kernels set
+    // their sums up with other moves and k_estep_ambient<4, false, 2> took two registers more
+    double sum[A];
 #pragma unroll
-    for (int s = 0; s < A; s++) {
-        const float pen = kk[s] >= n_single ? pen_pair : 0.0f;
-        lg[s] = (float)((double)pen + acc[s]);
-        mx = valid[s] ? fmaxf(mx, lg[s]) : mx;
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-#pragma unroll
-    for (int s = 0; s < A; s++) x[s] = npm::exp_f32(lg[s] - mx);
-    const float tot = reg_row_sum<64, A>(x, K, lane, 0);
-    const long long row = a.row_ptr[b];
-    float post[A];
-    float bv = -__builtin_inff();
-    int bi = NO_OPTION;
-#pragma unroll
-    for (int s = 0; s < A; s++) {
-        post[s] = x[s] / tot;
-        if (valid[s]) {
-            a.logits[row + kk[s]] = lg[s];
-            a.post[row + kk[s]] = post[s];
-            if (better(post[s], kk[s], bv, bi)) {
-                bv = post[s];
-                bi = kk[s];
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float ov = __shfl_xor(bv, off);
-        const int oi = __shfl_xor(bi, off);
-        if (better(ov, oi, bv, bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    // the pair posteriors, widened to float64 and added in ascending option order (the order is the contract): option k sits in
-    // lane k % 64 of slot k / 64 and comes out by v_readlane (k is wave-uniform)
-    double mass = 0.0;
-    if (PAIRS) {
-#pragma unroll
-        for (int s = 0; s < A; s++) {
-            const int lo = max(n_single - 64 * s, 0), hi = min(K - 64 * s, 64);
-            for (int l = lo; l < hi; l++)
-                mass += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, post[s]), l));
-        }
-    }
-    if (lane == 0) {
-        a.best[b] = bi != NO_OPTION ? bi : -1;
-        a.best_prob[b] = bi != NO_OPTION ? bv : __builtin_nanf("");
-        a.pair_mass[b] = mass;
-    }
+    for (int s = 0; s < A; s++) sum[s] = acc[s];
+    pool_row_close<A, PAIRS, false>(a, lane, row, sum);
 }
 
 template <int A, int U>
@@ -203,19 +126,10 @@ hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a)
     return hipGetLastError();
 }
 
-// calls per batch as launch_estep_pools has them
 hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs)
 {
     if (a.pools.n_list == 0) return hipSuccess;
-    switch (slots) {
-    case 1: launch_one<1, 8>(st, a, pairs); break;
-    case 2: launch_one<2, 4>(st, a, pairs); break;
-    case 4: launch_one<4, 2>(st, a, pairs); break;
-    case 8: launch_one<8, 2>(st, a, pairs); break;
-    case 16: launch_one<16, 2>(st, a, pairs); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a, pairs); });
 }
 
 int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring)

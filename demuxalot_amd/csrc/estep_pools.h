@@ -8,14 +8,16 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "pools_plan.h"
 
 struct dmx_ctx;
 
 namespace dmx {
 
-constexpr int POOL_MAX_OPTIONS = 1024;  // the register-resident row of the exact epilogue (estep_epilogue.h: reg_row_sum)
+constexpr int POOL_MAX_OPTIONS = (int)pplan::MAX_OPTIONS;  // what pools_plan.h lets through: the widest bucket, 16 slots of 64 lanes
 constexpr int POOL_BUCKETS = 5;         // option slots per lane of a launch: 1, 2, 4, 8, 16
 inline int pool_bucket_slots(int bucket) { return 1 << bucket; }
+static_assert(POOL_MAX_OPTIONS == 64 << (POOL_BUCKETS - 1), "the widest bucket holds the largest pool");
 inline int pool_bucket_of(int n_options)  // the narrowest instantiation that holds ceil(n_options / 64) slots
 {
     const int slots = (n_options + 63) / 64;
@@ -49,7 +51,7 @@ struct PoolEstepArgs {
 // dense: the form that also leaves the singlet posteriors in a.dense (learning within pools: the M-step's input)
 hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs, bool dense = false);
 
-// what dmx_estep_pools has validated and laid out on the host
+// what dmx_estep_pools has validated and laid out on the host (pools_plan.h: check, layout)
 struct PoolsPlan {
     bool with_doublets;
     long long n_pools;

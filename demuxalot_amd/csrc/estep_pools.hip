@@ -14,20 +14,13 @@
 #include "device_scratch.h"
 #include "estep_epilogue.h"
 #include "estep_pools.h"
+#include "estep_pools_row.h"
 
 namespace dmx {
 
 namespace {
 
-// first maximum, NaN never wins (results.hip: better)
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-constexpr int NO_OPTION = 0x7FFFFFFF;
-
-// One wavefront per barcode.  Lane l, slot s takes option l + 64 s of the barcode's pool; slots entirely past the pool's last
-// option are skipped wave-uniformly.  Everything about the row and the pool lives in SGPRs: records by scalar loads, a call's row
-// offset as the scalar offset of the buffer loads on the table, the lane's two column offsets fixed for the whole row.
-// DENSE: the lanes that hold the pool's singlet options also store their posterior at the donor's table column of the barcode's row
-// of a.dense ([B, G]: what the M-step reads).  Nothing else of that row is written here - the other columns are the host's zeros.
+// pool_row_open, the walk as k_estep_direct's exact 64-lane path has it (estep_epilogue.h: load_batch, estep_terms), pool_row_close
 template <int A, bool PAIRS, int U, bool DENSE>
 __global__ __launch_bounds__(256) void k_estep_pools(PoolEstepArgs a)
 {
@@ -35,144 +28,50 @@ __global__ __launch_bounds__(256) void k_estep_pools(PoolEstepArgs a)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long slot = (long long)blockIdx.x * 4 + wave;
     if (slot >= a.n_list) return;
-    const int b = __builtin_amdgcn_readfirstlane(a.list[slot]);
-    const int p = __builtin_amdgcn_readfirstlane(a.pool_of[b]);
-    const long long obeg = a.opt_ptr[p];
-    const int K = (int)(a.opt_ptr[p + 1] - obeg);  // 1 .. 64 A
-    const int n_single = a.pool_size[p];
-    const float pen_pair = a.pair_penalty[p];
-    const unsigned *__restrict__ opts = a.opts + obeg;
-    const int n_slots = (K + 63) >> 6;
-
-    unsigned o1[A], o2[A];  // byte offsets of this lane's column(s) inside a table row
-    int kk[A];
-    bool valid[A];
-#pragma unroll
-    for (int s = 0; s < A; s++) {
-        const int k = lane + 64 * s;
-        valid[s] = k < K;
-        kk[s] = valid[s] ? k : K - 1;  // (a lane without an option repeats the last one: loads stay inside the table)
-        const unsigned pr = opts[kk[s]];
-        o1[s] = (pr & 0xFFFFu) * 4u;
-        o2[s] = (pr >> 16) * 4u;
-    }
+    PoolRow<A> row;
+    pool_row_open<A>(a, slot, lane, row);
     double acc[A];
 #pragma unroll
     for (int s = 0; s < A; s++) acc[s] = 0.0;
 
-    const long long pbeg = a.pair_ptr[b];
-    const int npairs = (int)(a.pair_ptr[b + 1] - pbeg);  // a multiple of 4: rows are padded to 8 calls
-    const CallPair *__restrict__ recs = a.pairs + pbeg;
+    const CallPair *__restrict__ recs = a.pairs + row.pbeg;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.prob, 0, (int)a.prob_bytes, 0x00020000);
     constexpr int H = U / 2;
     static_assert(H == 1 || H == 2 || H == 4, "batches tile a row of whole 8-call groups");
-    for (int j0 = 0; j0 < npairs; j0 += H) {
+    for (int j0 = 0; j0 < row.npairs; j0 += H) {
         RecBatch<A, H, PAIRS> x;
-        load_batch<A, H, PAIRS>(x, recs, j0, rsrc, o1, o2, n_slots);
-        estep_terms<A, PAIRS, H>(x.p1, x.p2, x.keep, x.flo, acc, n_slots);
+        load_batch<A, H, PAIRS>(x, recs, j0, rsrc, row.o1, row.o2, row.n_slots);
+        estep_terms<A, PAIRS, H>(x.p1, x.p2, x.keep, x.flo, acc, row.n_slots);
     }
-
-    // ---- epilogue: the logit, the softmax as the exact forms evaluate it, the compact row, the two read-outs ----
-    float lg[A], x[A];
-    float mx = -__builtin_inff();
+    // close reads a copy of the sums: handed `acc` itself, the array the walk's functions wrote through, the multi-slot kernels set
+    // their sums up with other moves and k_estep_ambient<4, false, 2> took two registers more
+    double sum[A];
 #pragma unroll
-    for (int s = 0; s < A; s++) {
-        const float pen = kk[s] >= n_single ? pen_pair : 0.0f;
-        lg[s] = (float)((double)pen + acc[s]);
-        mx = valid[s] ? fmaxf(mx, lg[s]) : mx;
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-#pragma unroll
-    for (int s = 0; s < A; s++) x[s] = npm::exp_f32(lg[s] - mx);
-    const float tot = reg_row_sum<64, A>(x, K, lane, 0);
-    const long long row = a.row_ptr[b];
-    float post[A];
-    float bv = -__builtin_inff();
-    int bi = NO_OPTION;
-#pragma unroll
-    for (int s = 0; s < A; s++) {
-        post[s] = x[s] / tot;
-        if (valid[s]) {
-            a.logits[row + kk[s]] = lg[s];
-            a.post[row + kk[s]] = post[s];
-            if (better(post[s], kk[s], bv, bi)) {
-                bv = post[s];
-                bi = kk[s];
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float ov = __shfl_xor(bv, off);
-        const int oi = __shfl_xor(bi, off);
-        if (better(ov, oi, bv, bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    // the pair posteriors, widened to float64 and added in ascending option order: the order is the contract, so the sum is a
-    // sequential one; option k sits in lane k % 64 of slot k / 64 and comes out by v_readlane (k is wave-uniform)
-    double mass = 0.0;
-    if (PAIRS) {
-#pragma unroll
-        for (int s = 0; s < A; s++) {
-            const int lo = max(n_single - 64 * s, 0), hi = min(K - 64 * s, 64);
-            for (int l = lo; l < hi; l++)
-                mass += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, post[s]), l));
-        }
-    }
-    if (lane == 0) {
-        a.best[b] = bi != NO_OPTION ? bi : -1;
-        a.best_prob[b] = bi != NO_OPTION ? bv : __builtin_nanf("");
-        a.pair_mass[b] = mass;
-    }
-    if (DENSE) {
-        // with pairs a pool has at most 44 donors (POOL_MAX_OPTIONS): its singlets are all in slot 0
-        static_assert(POOL_MAX_OPTIONS < 64 * 65 / 2, "a pool with pairs and 64 donors or more: singlets beyond slot 0");
-        constexpr int SINGLET_SLOTS = PAIRS ? 1 : A;
-        float *__restrict__ out = a.dense + (long long)b * a.G;
-#pragma unroll
-        for (int s = 0; s < SINGLET_SLOTS; s++)
-            if (valid[s] && kk[s] < n_single) out[o1[s] >> 2] = post[s];
-    }
-}
-
-template <int A, int U, bool DENSE>
-void launch_form(hipStream_t st, const PoolEstepArgs &a, bool pairs)
-{
-    const dim3 grid((unsigned)((a.n_list + 3) / 4)), block(256);
-    if (pairs)
-        hipLaunchKernelGGL((k_estep_pools<A, true, U, DENSE>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_estep_pools<A, false, U, DENSE>), grid, block, 0, st, a);
+    for (int s = 0; s < A; s++) sum[s] = acc[s];
+    pool_row_close<A, PAIRS, DENSE>(a, lane, row, sum);
 }
 
 template <int A, int U>
 void launch_one(hipStream_t st, const PoolEstepArgs &a, bool pairs, bool dense)
 {
-    if (dense)
-        launch_form<A, U, true>(st, a, pairs);
+    const dim3 grid((unsigned)((a.n_list + 3) / 4)), block(256);
+    if (pairs && dense)
+        hipLaunchKernelGGL((k_estep_pools<A, true, U, true>), grid, block, 0, st, a);
+    else if (pairs)
+        hipLaunchKernelGGL((k_estep_pools<A, true, U, false>), grid, block, 0, st, a);
+    else if (dense)
+        hipLaunchKernelGGL((k_estep_pools<A, false, U, true>), grid, block, 0, st, a);
     else
-        launch_form<A, U, false>(st, a, pairs);
+        hipLaunchKernelGGL((k_estep_pools<A, false, U, false>), grid, block, 0, st, a);
 }
 
 }  // namespace
 
-// calls per batch as k_estep_direct's exact 64-lane launches have them (kernels.hip: launch_estep)
 hipError_t launch_estep_pools(hipStream_t st, const PoolEstepArgs &a, int slots, bool pairs, bool dense)
 {
     if (a.n_list == 0) return hipSuccess;
     if (dense && (a.dense == nullptr || a.G <= 0)) return hipErrorInvalidValue;
-    switch (slots) {
-    case 1: launch_one<1, 8>(st, a, pairs, dense); break;
-    case 2: launch_one<2, 4>(st, a, pairs, dense); break;
-    case 4: launch_one<4, 2>(st, a, pairs, dense); break;
-    case 8: launch_one<8, 2>(st, a, pairs, dense); break;
-    case 16: launch_one<16, 2>(st, a, pairs, dense); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a, pairs, dense); });
 }
 
 // what a pooled call keeps on the device between its parts (estep_pools.h)

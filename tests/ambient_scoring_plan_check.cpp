@@ -1,7 +1,8 @@
 // ambient_scoring_plan_check.cpp -- walks demuxalot_amd/csrc/ambient_scoring_plan.h on the CPU (tests/test_ambient_scoring_cpu.py
 // builds it with AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a plain program): every refusal of dmx_estep_ambient
-// with its code - everything dmx_estep_pools refuses, the fractions, the profile, the contexts the pass does not run on -, the
-// boundaries of the option limit, the order of the checks, and that nothing is read of a barcode in no pool.
+// with its code - the contexts the pass does not run on, everything dmx_estep_pools refuses (pools_plan.h's check, composed here;
+// tests/pools_plan_check.cpp walks it on its own), the fractions, the profile -, the boundaries of the option limit, the order of
+// the checks, and that nothing is read of a barcode in no pool.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
