@@ -161,6 +161,8 @@ DEBUG_SIGNATURES = {
     'dmx_em_pools': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
     'dmx_ambient_profile': (c_int, [_P, c_float, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'dmx_estep_ambient': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P]),
+    'dmx_estep_ambient_grid': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int32, _P, _P, _P, _P, _P,
+                                       _P]),
 }
 
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings

@@ -3,7 +3,9 @@
 How much of a droplet's signal is NOT from the option it was assigned to: for every barcode the log-likelihood of its calls when a
 share alpha of its molecules comes from the soup, on a grid of alphas; the estimate is the grid value of the first maximum.  The
 device pass (include/demux_hip_debug.h: dmx_ambient_profile) returns B-length read-outs and, if asked, the [B, A] profile; this
-module resolves the caller's assignments into table columns and composes the frames.  Pure numpy / pandas: imports without a GPU.
+module resolves the caller's assignments into table columns and composes the frames.  JointAmbientPosteriors is the result of
+Demultiplexer.predict_posteriors_joint_ambient: every option scored at its own best fraction of the grid.  Pure
+numpy / pandas: imports without a GPU.
 """
 import numbers
 
@@ -89,6 +91,89 @@ def assigned_donors(n_donors, columns):
     """(donor1, donor2) int32[B] as the device pass takes them: table columns, (-1, -1) skipped, (d, -1) a singlet, d1 < d2 a pair."""
     d1, d2 = donor_readout.column_donors(n_donors, columns)
     return d1.astype(np.int32), d2.astype(np.int32)
+
+
+def resolve_grid(alphas):
+    """float32[A] grid of predict_posteriors_joint_ambient: None -> default_alphas(); otherwise the values as float32, one-dimensional.
+    ValueError: an empty grid, more than 64 values, a value that is not finite or lies outside [0, 1] (as float32, which is what
+    the device pass reads)."""
+    if alphas is None:
+        return default_alphas()
+    grid = np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
+    if not 1 <= len(grid) <= 64:
+        raise ValueError(f'alphas: the grid has {len(grid)} values; 1 .. 64 are supported')
+    if not ((grid >= 0) & (grid <= 1)).all():  # (NaN fails both)
+        raise ValueError('alphas: a grid value is not finite or outside [0, 1]')
+    return grid
+
+
+class JointAmbientPosteriors:
+    """The result of one predict_posteriors_joint_ambient call, host-resident: every option - singlets and pairs - scored at its own
+    best ambient fraction of the grid, one softmax over those scores.
+
+    posteriors: (logits_df, probs_df) with predict_posteriors' index and columns, or, for a call with pools, a PooledPosteriors;
+    alphas float32[A]: the grid; ambient float32[V]: the soup's allele profile that was used; row_ptr int64[B + 1]: barcode b owns the
+    entries row_ptr[b] .. row_ptr[b + 1] of the compact per-option arrays; alpha_index int32[row_ptr[B]]: the grid point of every
+    option's first maximum (-1: every value NaN); option_alphas float64[row_ptr[B]]: its grid value, NaN where there is none;
+    best_option, best_prob, doublet_mass, best_alpha_index [B]: the read-outs of the pass (-1 / NaN / NaN / -1 for a barcode in no
+    pool); profile float32[row_ptr[B], A]: every option's logit at every grid point, or None when it was not kept."""
+
+    def __init__(self, barcodes, option_names, pool_of_barcode, row_ptr, alphas, ambient, alpha_index, best_option, best_prob, doublet_mass,
+                 best_alpha_index, posteriors, profile=None, index_name='BARCODE'):
+        self.barcodes = list(barcodes)
+        self._option_names = [list(names) for names in option_names]  # per pool
+        self.pool_of_barcode = np.asarray(pool_of_barcode, dtype=np.int32)
+        self.row_ptr = np.asarray(row_ptr, dtype=np.int64)
+        self.alphas = np.asarray(alphas, dtype=np.float32)
+        self.ambient = np.asarray(ambient, dtype=np.float32)
+        self.alpha_index = np.asarray(alpha_index, dtype=np.int32)
+        self.best_option = np.asarray(best_option, dtype=np.int32)
+        self.best_prob = np.asarray(best_prob, dtype=np.float32)
+        self.doublet_mass = np.asarray(doublet_mass, dtype=np.float64)
+        self.best_alpha_index = np.asarray(best_alpha_index, dtype=np.int32)
+        self.posteriors = posteriors
+        self.index_name = index_name
+        B = len(self.barcodes)
+        n = int(self.row_ptr[-1]) if B else 0
+        assert self.pool_of_barcode.shape == (B,) and self.row_ptr.shape == (B + 1,) and self.alpha_index.shape == (n,)
+        assert self.best_option.shape == (B,) and self.best_prob.shape == (B,) and self.doublet_mass.shape == (B,) and self.best_alpha_index.shape == (B,)
+        widths = np.array([len(names) for names in self._option_names] + [0], dtype=np.int64)  # (-1 -> no entries)
+        assert np.array_equal(np.diff(self.row_ptr), widths[self.pool_of_barcode]), 'row_ptr does not follow the pools'
+        assert ((self.alpha_index >= -1) & (self.alpha_index < len(self.alphas))).all()
+        self.option_alphas = self._grid_values(self.alpha_index)
+        self.profile = None
+        if profile is not None:
+            self.profile = np.asarray(profile, dtype=np.float32)
+            assert self.profile.shape == (n, len(self.alphas))
+
+    def _grid_values(self, index):
+        found = index >= 0
+        return np.where(found, self.alphas[np.where(found, index, 0)].astype(np.float64), np.nan)
+
+    def _index(self):
+        index = pd.Index(self.barcodes)
+        index.name = self.index_name
+        return index
+
+    def alphas_of(self, barcode) -> pd.Series:
+        """option name -> the grid value of that option's maximum, for one barcode (empty for a barcode in no pool)."""
+        b = self.barcodes.index(barcode)
+        p = self.pool_of_barcode[b]
+        names = self._option_names[p] if p >= 0 else []
+        return pd.Series(self.option_alphas[self.row_ptr[b]:self.row_ptr[b + 1]], index=names, name='alpha')
+
+    def summary(self) -> pd.DataFrame:
+        """Per barcode (all of them, handler order): `option`, the name of the most probable option (None: none, or in no pool);
+        `probability`, its posterior; `alpha`, the grid value at which that option was scored (NaN: none); `doublet_probability`,
+        the posterior mass of the pair options (float64); `at_grid_edge`: that alpha is the largest grid value, so the maximum may
+        lie beyond the grid."""
+        option = np.empty(len(self.barcodes), dtype=object)
+        for b, (p, k) in enumerate(zip(self.pool_of_barcode, self.best_option)):
+            option[b] = self._option_names[p][k] if p >= 0 and k >= 0 else None
+        alpha = self._grid_values(self.best_alpha_index)
+        at_edge = (self.best_alpha_index >= 0) & (alpha == np.float64(self.alphas.max()))
+        return pd.DataFrame({'option': option, 'probability': self.best_prob, 'alpha': alpha, 'doublet_probability': self.doublet_mass,
+                             'at_grid_edge': at_edge}, index=self._index())
 
 
 class AmbientEstimate:

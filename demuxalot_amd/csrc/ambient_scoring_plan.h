@@ -19,22 +19,33 @@ using pplan::Pools;
 using pplan::Verdict;
 using pplan::options_of;
 
-// The order is the order of the refusals: the context, the pools as dmx_estep_pools walks them, the fractions, the profile.
-// alpha[b] of a barcode in no pool is not looked at.
-inline Verdict check(const Facts &f, const Pools &p, const float *alpha, const float *ambient)
+// The two ends of check(), which dmx_estep_ambient_grid's check (ambient_grid_plan.h) puts around its own refusals as well:
+// the context and the pools as dmx_estep_pools walks them; the supplied profile.
+inline Verdict check_context_and_pools(const Facts &f, const Pools &p)
 {
     if (!f.have_problem || !f.have_table) return {INVALID, "call order: a problem and genotype probabilities (dmx_probs_from_betas / dmx_set_probs) come first", -1};
     if (f.attached || f.nranks > 1) return {UNSUPPORTED, "a context with a communicator attached is not supported", -1};
     if (!f.dense_table) return {UNSUPPORTED, "the genotype table is in a padded exchange layout", -1};
-    const Verdict pools = pplan::check(f.G, f.B, p);
-    if (pools.status != OK) return pools;
-    if (f.B > 0 && !alpha) return {INVALID, "null alpha", -1};
-    for (long long b = 0; b < f.B; b++)
-        if (p.pool_of_barcode[b] >= 0 && !aplan::unit_range(alpha[b])) return {INVALID, "alpha of a barcode is not finite or outside [0, 1]", b};
+    return pplan::check(f.G, f.B, p);
+}
+inline Verdict check_profile(const Facts &f, const float *ambient)
+{
     if (ambient)
         for (long long v = 0; v < f.V; v++)
             if (!aplan::unit_range(ambient[v])) return {INVALID, "an ambient value is not finite or outside [0, 1]", v};
     return {OK, "", -1};
+}
+
+// The order is the order of the refusals: the context, the pools as dmx_estep_pools walks them, the fractions, the profile.
+// alpha[b] of a barcode in no pool is not looked at.
+inline Verdict check(const Facts &f, const Pools &p, const float *alpha, const float *ambient)
+{
+    const Verdict pools = check_context_and_pools(f, p);
+    if (pools.status != OK) return pools;
+    if (f.B > 0 && !alpha) return {INVALID, "null alpha", -1};
+    for (long long b = 0; b < f.B; b++)
+        if (p.pool_of_barcode[b] >= 0 && !aplan::unit_range(alpha[b])) return {INVALID, "alpha of a barcode is not finite or outside [0, 1]", b};
+    return check_profile(f, ambient);
 }
 
 }  // namespace asplan

@@ -22,8 +22,10 @@
 #include "dmx_host.h"
 #include "estep_plan.h"
 #include "ambient_profile.h"
+#include "ambient_grid_plan.h"
 #include "ambient_scoring_plan.h"
 #include "estep_ambient.h"
+#include "estep_ambient_grid.h"
 #include "estep_pools.h"
 #include "mstep_plan.h"
 #include "pools_plan.h"
@@ -892,7 +894,7 @@ int dmx_estep(dmx_ctx *c, int with_doublets, const float *penalties, const void 
     return 0;
 }
 
-// What a plan header refuses (pools_plan.h, ambient_plan.h, ambient_scoring_plan.h), as the entry's error:
+// What a plan header refuses (pools_plan.h, ambient_plan.h, ambient_scoring_plan.h, ambient_grid_plan.h), as the entry's error:
 // "<who>: [<value> ]<text>[ (index <at>)]".
 static int refuse(const char *who, int status, const char *what, long long at, long long value = -1)
 {
@@ -1012,6 +1014,26 @@ int dmx_estep_ambient(dmx_ctx *c, int with_doublets, int32_t n_pools, const int6
     fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
     const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out};
     return dmx::run_estep_ambient(c, plan, scoring);
+}
+
+// The pooled E-step with every option at its own best fraction of a grid (estep_ambient_grid.hip).  ambient_grid_plan.h refuses, on
+// the host, before anything is uploaded or launched; what it has accepted is laid out as for dmx_estep_pools.
+int dmx_estep_ambient_grid(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                           const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out, float *probs_out,
+                           int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi, int32_t n_alphas, const float *alphas,
+                           const float *ambient, float *ambient_out, int32_t *alpha_index, int32_t *best_alpha_index, float *profile_out)
+{
+    namespace gp = dmx::agplan;
+    DMX_TRY(bind(c));
+    const gp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
+                          c->B,           c->V,          c->G};
+    const gp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    const gp::Verdict verdict = gp::check(facts, pools, n_alphas, alphas, ambient);
+    if (verdict.status != gp::OK) return refuse("dmx_estep_ambient_grid", verdict.status, verdict.what, verdict.at, verdict.value);
+    dmx::PoolsPlan plan;
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, profile_out};
+    return dmx::run_estep_ambient_grid(c, plan, scoring);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)

@@ -1,0 +1,44 @@
+// estep_ambient_grid.h -- the pooled E-step with every option scored at its own best ambient fraction (estep_ambient_grid.hip;
+// dmx_steps.cpp: dmx_estep_ambient_grid): dmx_estep_ambient's term on a grid of fractions, the maximum over the grid
+// per option, one softmax over those maxima.  The walk is k_estep_ambient's with the grid inside it.
+#pragma once
+#include <cstdint>
+
+#include <hip/hip_runtime.h>
+
+#include "estep_pools.h"
+
+struct dmx_ctx;
+
+namespace dmx {
+
+// argument block of k_estep_ambient_grid: k_estep_pools' (its `dense` is not used) and what the grid adds
+struct AmbientGridArgs {
+    PoolEstepArgs pools;
+    const float2 *soup;   // [n_pairs] beside the records: ambient[row] of a record's two calls (k_soup_terms with a fraction of 1)
+    const float *alphas;  // [n_alphas]
+    int n_alphas;         // 1 .. 64
+    int *alpha_index;     // compact like the logits: the grid point of an option's first maximum, -1: every value NaN
+    float *profile;       // the PROFILE form only: [row_ptr[B], n_alphas] every option's logit at every grid point
+};
+// profile: the form that also stores a.profile
+hipError_t launch_estep_ambient_grid(hipStream_t st, const AmbientGridArgs &a, int slots, bool pairs, bool profile);
+// best_alpha_index[b] = alpha_index[row_ptr[b] + best[b]], -1 where best[b] is -1 or the barcode is in no pool: a thread per barcode
+hipError_t launch_best_alpha_index(hipStream_t st, long long B, const int *pool_of, const long long *row_ptr, const int *best, const int *alpha_index,
+                                   int *best_alpha_index);
+
+// what dmx_estep_ambient_grid passes on beside the pools' plan: host pointers
+struct AmbientGridScoring {
+    float lo, hi;               // the clip of a derived profile
+    int n_alphas;
+    const float *alphas;        // [n_alphas]
+    const float *ambient;       // nullable [V]: derived from the resident calls
+    float *ambient_out;         // nullable [V]
+    int32_t *alpha_index;       // nullable [row_ptr[B]]
+    int32_t *best_alpha_index;  // nullable [B]
+    float *profile_out;         // nullable [row_ptr[B], n_alphas]
+};
+// prepare_estep_pools, the profile (given or derived), the kernels (one span of DMX_T_ESTEP), read_back_estep_pools
+int run_estep_ambient_grid(dmx_ctx *c, const PoolsPlan &plan, const AmbientGridScoring &scoring);
+
+}  // namespace dmx

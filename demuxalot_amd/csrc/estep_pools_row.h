@@ -1,6 +1,6 @@
-// estep_pools_row.h -- the two ends of a pooled row, device code: what k_estep_pools (estep_pools.hip) and k_estep_ambient
-// (estep_ambient.hip) do before and after they walk a barcode's call records, and the table of their instantiations.  Included by
-// those two files alone.  One wavefront per barcode.  Lane l, slot s takes option l + 64 s of the barcode's pool; slots entirely past
+// estep_pools_row.h -- the two ends of a pooled row, device code: what k_estep_pools (estep_pools.hip), k_estep_ambient
+// (estep_ambient.hip) and k_estep_ambient_grid (estep_ambient_grid.hip) do before and after they walk a barcode's call records, and
+// the table of their instantiations.  Included by those three files alone.  One wavefront per barcode.  Lane l, slot s takes option l + 64 s of the barcode's pool; slots entirely past
 // the pool's last option are skipped wave-uniformly.  Everything about the row and the pool lives in SGPRs: records by scalar loads,
 // a call's row offset as the scalar offset of the buffer loads on the table, the lane's two column offsets fixed for the whole row.
 // A kernel is: the early return of a wavefront past the list (in the __global__ function itself), pool_row_open, its own walk over

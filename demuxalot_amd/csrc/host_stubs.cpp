@@ -18,6 +18,7 @@
 #include "ambient_profile.h"
 #include "dmx_ctx.h"
 #include "estep_ambient.h"
+#include "estep_ambient_grid.h"
 #include "estep_pools.h"
 
 // ------------------------------------------------------------------------------------
@@ -164,6 +165,7 @@ int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &, float)
 int read_back_estep_pools(dmx_ctx *, PoolsRun &) { return 0; }
 int run_ambient_profile(dmx_ctx *, const AmbientPlan &) { return 0; }  // (validated by dmx_ambient_profile; nothing is written)
 int run_estep_ambient(dmx_ctx *, const PoolsPlan &, const AmbientScoring &) { return 0; }  // (validated by dmx_estep_ambient; nothing is written)
+int run_estep_ambient_grid(dmx_ctx *, const PoolsPlan &, const AmbientGridScoring &) { return 0; }  // (validated by dmx_estep_ambient_grid; nothing is written)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {
     // this one is cheap enough to do for real: it indexes new_rows with what the records hold

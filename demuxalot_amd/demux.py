@@ -27,7 +27,8 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, donor_readout
-from .ambient import AmbientEstimate, assigned_donors, best_singlets, default_alphas, resolve_assignments, resolve_fractions
+from .ambient import (AmbientEstimate, JointAmbientPosteriors, assigned_donors, best_singlets, default_alphas, resolve_assignments,
+                      resolve_fractions, resolve_grid)
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
 from .pools import PooledPosteriors, resolve_pools
@@ -957,6 +958,62 @@ class Demultiplexer:
         logits_df = pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
         probs_df = pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
         return logits_df, probs_df, estimate
+
+    @staticmethod
+    def predict_posteriors_joint_ambient(chromosome2compressed_snp_calls,
+                                         genotypes,
+                                         barcode_handler,
+                                         alphas=None,
+                                         ambient=None,
+                                         p_genotype_clip=0.01,
+                                         doublet_prior=0.35,
+                                         barcode2pool=None,
+                                         pool2donors=None,
+                                         keep_profile=False) -> JointAmbientPosteriors:
+        """(not in the reference) predict_posteriors with every option - singlets and pairs - scored at its own best ambient
+        fraction: a call's term is q (1 - alpha) + ambient[v] alpha, an option's logit the maximum over the grid `alphas` of its
+        log-likelihood (plus the pair penalty), and the posteriors one softmax over those.  The choice between "a contaminated
+        singlet" and "a doublet" is made inside that softmax, in one pass, where predict_posteriors_decontaminated estimates the
+        fraction under the best singlet first and so explains a true doublet's second donor as contamination.
+        With alphas=[0.0] the result is predict_posteriors' (exact mode) bit for bit.
+        :param alphas: the grid, 1 .. 64 values in [0, 1] in any order; None: 0, 0.01 .. 0.63
+        :param ambient: float32[n_variants] allele profile of the soup, or None: derived from the calls as estimate_ambient does
+        :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
+        :param keep_profile: also return every option's logit at every grid point (JointAmbientPosteriors.profile: the grid's
+            length times the logits' memory)
+        Returns a JointAmbientPosteriors: .posteriors is (logits_df, probs_df) with predict_posteriors' index, columns and dtypes,
+        with pools a PooledPosteriors; .option_alphas, .summary().
+        ValueError: a grid value outside [0, 1], an empty grid or more than 64 values, more than 1024 options without pools."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        grid = resolve_grid(alphas)
+        pooled = barcode2pool is not None
+        if pooled:
+            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        else:
+            pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
+                genotypes, barcode_handler, doublet_prior, 'predict_posteriors_joint_ambient')
+            option_names = [column_names]
+        with shared_context_lock:
+            ctx = get_context()
+            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
+            ctx.set_addition(None)
+            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+            assert np.isfinite(genotype_prob).all()
+            out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
+                                         fetch_profile=keep_profile)
+        if pooled:
+            posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
+                                          out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
+        else:
+            shape = (barcode_handler.n_barcodes, len(column_names))
+            posteriors = (pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names),
+                          pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names))
+        return JointAmbientPosteriors(barcode_handler.ordered_barcodes, option_names, pool_of_barcode, out['row_ptr'], grid, out['ambient'],
+                                      out['alpha_index'], out['best_option'], out['best_prob'], out['doublet_mass'], out['best_alpha_index'],
+                                      posteriors, profile=out['profile'], index_name='BARCODE')
 
     @staticmethod
     def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):

@@ -765,6 +765,34 @@ class DeviceContext:
                                           ptr(ambient), ptr(out['ambient'])))
         return out
 
+    def estep_ambient_grid(self, pools, pool_of_barcode, with_doublets, pair_penalty, alphas, p_genotype_clip=0.01, ambient=None,
+                           fetch_logits=True, fetch_probs=True, fetch_alpha_index=True, fetch_profile=False):
+        """The pooled E-step with every option at its own best ambient fraction (include/demux_hip_debug.h: dmx_estep_ambient_grid):
+        estep_ambient() on the grid `alphas` (float32, 1 .. 64 values in [0, 1], any order), every option's logit its first maximum
+        over the grid, one softmax over those.  ambient: float32[V] or None (derived from the resident calls, clipped as the genotype
+        table is).  Returns estep_pools()'s dict with more keys: 'ambient' float32[V], the profile that was used; 'alphas', the grid;
+        'alpha_index' int32[row_ptr[B]], the grid point of every option's maximum (None without fetch_alpha_index);
+        'best_alpha_index' int32[B], that of best_option (-1: none); 'profile' float32[row_ptr[B], A], every option's logit at every
+        grid point (None without fetch_profile: A times the logits' memory).  The resident results of the last E-step are left as
+        they are."""
+        alphas = as_c(alphas, np.float32)
+        assert alphas.ndim == 1, 'the grid is one-dimensional'
+        if ambient is not None:
+            ambient = as_c(ambient, np.float32)
+            assert ambient.shape == (self.V,), 'one ambient value per variant'
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        n, A = int(out['row_ptr'][-1]), len(alphas)
+        out['ambient'] = np.empty(self.V, np.float32)
+        out['alphas'] = alphas
+        out['alpha_index'] = np.full(n, -1, np.int32) if fetch_alpha_index else None
+        out['best_alpha_index'] = np.full(self.B, -1, np.int32)
+        out['profile'] = np.empty((n, A), np.float32) if fetch_profile else None
+        check(self._lib.dmx_estep_ambient_grid(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, A, ptr(alphas),
+                                               ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']), ptr(out['best_alpha_index']),
+                                               ptr(out['profile'])))
+        return out
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

@@ -510,6 +510,48 @@ int dmx_estep_ambient(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const in
                       float lo, float hi, const float *alpha /* [B] */, const float *ambient /* nullable, [V] */,
                       float *ambient_out /* nullable, [V] */);
 
+/* ------------------------------------------------------------------------- *
+ * The pooled E-step with every option scored at its own best ambient fraction (product API; csrc/estep_ambient_grid.hip;
+ * DESIGN.md 4.8).  dmx_estep_ambient needs a fraction per barcode, and a fraction estimated under the best singlet absorbs a true
+ * doublet's second donor as contamination.  Here every option, singlets and pairs, is scored on a grid of fractions and enters the
+ * softmax with its own maximum: the choice between "contaminated singlet" and "doublet" is made inside one softmax, in one pass.
+ * (call order: a problem and dmx_probs_from_betas / dmx_set_probs; single GPU)
+ *   pools, rows, read-outs   the arguments of dmx_estep_pools, with its meaning.
+ *   lo, hi, ambient, ambient_out   as dmx_estep_ambient takes them.
+ *   alphas      float32[n_alphas], the grid under dmx_ambient_profile's rules: 1 <= n_alphas <= 64, every value finite and in
+ *               [0, 1]; any order, duplicates allowed.
+ *   logit       for barcode b of pool p, option k of that pool and grid point j, in float32 without contraction, over the calls of
+ *               b in stored order:
+ *                 q = prob[v, d]  or  (prob[v, d1] + prob[v, d2]) * 0.5f                     as dmx_estep_pools
+ *                 m = q * (1.0f - alphas[j]) + ambient[v] * alphas[j]                        two products, one sum, each rounded
+ *                 lambda[b, k, j] = f32( f64(pen) + sum of f64( log_f32(m * keep + floor) ) )   pen as dmx_estep_pools
+ *                 j*[b, k] = the first maximum of lambda[b, k, .] in float32 (ties to the lower j, NaN never wins; -1 if all NaN)
+ *                 logit[b, k] = lambda[b, k, j*]                                              NaN if j* == -1
+ *               The softmax, the compact rows and the read-outs are dmx_estep_pools' on these logits.  A barcode without calls
+ *               has lambda = pen for every j, hence j* = 0.
+ *   outputs     beside dmx_estep_pools', each nullable: alpha_index int32[row_ptr[B]], j* per option, compact like the logits;
+ *               best_alpha_index int32[B], j* of best_option (-1 where best_option is -1 or the barcode is in no pool);
+ *               profile_out float32[row_ptr[B] * n_alphas], lambda itself, the grid point minor - n_alphas times the logits'
+ *               memory, for small runs and tests.
+ * Three identities, bit for bit: with n_alphas == 1 every shared output is dmx_estep_ambient's with alpha[b] = alphas[0] for all b
+ * (so alphas = {0} gives dmx_estep_pools); column j of profile_out is dmx_estep_ambient's logits_out with alpha = alphas[j]
+ * everywhere; with pair_penalty 0, lambda[b, k, .] is dmx_ambient_profile's L[b, .] for that option's donors and j*[b, k] its best.
+ * Checked on the host before anything is uploaded or launched (csrc/ambient_grid_plan.h).  DMX_ERR_INVALID: everything
+ * dmx_estep_pools refuses so, n_alphas < 1, null alphas, a grid or ambient value that is not finite or outside [0, 1].
+ * DMX_ERR_UNSUPPORTED: n_alphas > 64, a pool of more than 1024 options, a communicator attached, a genotype table in a padded
+ * exchange layout.  The resident results of the last dmx_estep / dmx_em are left as they are; the pass is counted in the
+ * DMX_T_ESTEP slot.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_ambient_grid(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                           const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                           const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                           float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                           int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                           float lo, float hi, int32_t n_alphas, const float *alphas /* [n_alphas] */,
+                           const float *ambient /* nullable, [V] */, float *ambient_out /* nullable, [V] */,
+                           int32_t *alpha_index /* nullable, int32[row_ptr[B]] */, int32_t *best_alpha_index /* nullable, [B] */,
+                           float *profile_out /* nullable, float32[row_ptr[B] * n_alphas] */);
+
 #ifdef __cplusplus
 }
 #endif
