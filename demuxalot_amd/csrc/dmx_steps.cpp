@@ -23,10 +23,12 @@
 #include "estep_plan.h"
 #include "ambient_profile.h"
 #include "ambient_grid_plan.h"
+#include "ambient_learning_plan.h"
 #include "ambient_scoring_plan.h"
 #include "estep_ambient.h"
 #include "estep_ambient_grid.h"
 #include "estep_pools.h"
+#include "mstep_ambient.h"
 #include "mstep_plan.h"
 #include "pools_plan.h"
 
@@ -1114,6 +1116,78 @@ int dmx_em_pools(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doub
     }
     DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
     return dmx::read_back_estep_pools(c, *run);
+}
+
+// Learning under per-barcode ambient fractions (estep_ambient.hip: the dense form; mstep_ambient.hip).  ambient_learning_plan.h refuses,
+// on the host, before anything is uploaded or launched.
+static dmx::alplan::Facts ambient_learning_facts(const dmx_ctx *c, bool have_table)
+{
+    return {c->have_problem, have_table, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr, c->B, c->V, c->G};
+}
+
+int dmx_estep_ambient_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                               const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                               float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi,
+                               const float *alpha, const float *ambient, float *ambient_out)
+{
+    namespace sp = dmx::asplan;
+    DMX_TRY(bind(c));
+    const sp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    const sp::Verdict verdict = sp::check(ambient_learning_facts(c, c->have_probs), pools, alpha, ambient);
+    if (verdict.status != sp::OK) return refuse("dmx_estep_ambient_resident", verdict.status, verdict.what, verdict.at, verdict.value);
+    dmx::PoolsPlan plan;
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out, "dmx_estep_ambient_resident"};
+    DMX_TRY(begin_dense_pools(c));
+    dmx::AmbientRunPtr run;
+    DMX_TRY(dmx::prepare_estep_ambient(c, plan, scoring, true, run));
+    DMX_TRY(dmx::launch_estep_ambient_pass(c, *run, 2.0f));  // (the floor of a squaring M-step; the M-steps rebuild for another power)
+    return dmx::read_back_estep_ambient(c, *run);
+}
+
+int dmx_mstep_ambient(dmx_ctx *c, float power, const float *alpha, const float *ambient, float lo, float hi, float *addition_out)
+{
+    namespace lp = dmx::alplan;
+    DMX_TRY(bind(c));
+    const lp::Verdict verdict = lp::check_mstep(ambient_learning_facts(c, c->have_probs), c->have_post, power, alpha, ambient);
+    if (verdict.status != lp::OK) return refuse("dmx_mstep_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
+    DMX_TRY(dmx::run_mstep_ambient_from_host(c, power, alpha, ambient, lo, hi));
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// dmx_em_pools with the E-step and the M-step under the fractions: P-step, dense ambient E-step, ambient M-step, all on the device; the
+// round trip of the pools, the uploads, the profile and the soup's terms are paid once, the read-back once after the last E-step.
+int dmx_em_ambient(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                   const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float power,
+                   const float *alpha, const float *ambient, float *logits_out, float *probs_out, int32_t *best_option, float *best_prob,
+                   double *doublet_mass, float *addition_out, float *ambient_out)
+{
+    namespace lp = dmx::alplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    const lp::Verdict verdict = lp::check_em(ambient_learning_facts(c, c->have_betas), pools, n_iterations, power, alpha, ambient);
+    if (verdict.status != lp::OK) return refuse("dmx_em_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
+    dmx::PoolsPlan plan;
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out, "dmx_em_ambient"};
+    DMX_TRY(begin_dense_pools(c));
+    const size_t vg = (size_t)c->V * c->G;
+    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));  // demux.py:86
+    c->incr_valid = false;
+    c->add_is_zero = true;
+    c->add_partial = false;
+    dmx::AmbientRunPtr run;
+    DMX_TRY(dmx::prepare_estep_ambient(c, plan, scoring, true, run));
+    for (int it = 0; it < n_iterations; it++) {
+        DMX_TRY(run_pstep(c, lo, hi, true, false));
+        DMX_TRY(dmx::launch_estep_ambient_pass(c, *run, power));
+        if (it + 1 < n_iterations)  // the M-step after the last yield is dead
+            DMX_TRY(dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)));
+    }
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
+    return dmx::read_back_estep_ambient(c, *run);
 }
 
 int dmx_run_iterations(dmx_ctx *c, int n_iterations, float lo, float hi, float power)

@@ -10,7 +10,7 @@ struct dmx_ctx;
 
 namespace dmx {
 
-// argument block of k_estep_ambient: k_estep_pools' (its `dense` is not used) and what the mixture adds
+// argument block of k_estep_ambient: k_estep_pools' (its `dense`: the DENSE form only) and what the mixture adds
 struct AmbientEstepArgs {
     PoolEstepArgs pools;
     const float *alpha;       // [B] the barcode's fraction
@@ -30,7 +30,8 @@ struct SoupTermArgs {
     float *soup_term;           // [2 n_pairs]
 };
 hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a);
-hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs);
+// dense: the form that also leaves the singlet posteriors in a.pools.dense (learning under ambient fractions: the M-step's input)
+hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs, bool dense = false);
 
 // what dmx_estep_ambient passes on beside the pools' plan: host pointers
 struct AmbientScoring {
@@ -38,8 +39,28 @@ struct AmbientScoring {
     const float *alpha;    // [B]
     const float *ambient;  // nullable [V]: derived from the resident calls
     float *ambient_out;    // nullable [V]
+    const char *who = "dmx_estep_ambient";  // the entry point a refusal of the derived profile names
 };
-// prepare_estep_pools, the profile (given or derived), the two kernels (counted in DMX_T_ESTEP), read_back_estep_pools
+// The device half in three parts, as the pooled pass has them (estep_pools.h), so that a call of several E-steps (dmx_em_ambient)
+// pays the pools' round trip, the uploads, the profile and the soup's terms once.
+//   prepare    prepare_estep_pools, the profile (given or derived), the fractions, the stream of the soup's terms; `plan` and the
+//              arrays of `scoring` outlive the run
+//   launch     k_soup_terms in the first pass of a run, then one launch per non-empty bucket (counted in DMX_T_ESTEP).  A dense run
+//              writes the singlet posteriors into the context's d_post as [B, G] and leaves the context as the dense pooled pass does
+//   read back  the profile, then read_back_estep_pools
+// The run holds its temporaries (device_scratch.h) until it is destroyed.
+struct AmbientRun;
+struct AmbientRunDeleter {
+    void operator()(AmbientRun *run) const;
+};
+typedef std::unique_ptr<AmbientRun, AmbientRunDeleter> AmbientRunPtr;
+int prepare_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring, bool dense, AmbientRunPtr &run);
+int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &run, float power);
+int read_back_estep_ambient(dmx_ctx *c, AmbientRun &run);
+// what the M-step under the same fractions reads of a run (mstep_ambient.hip): device pointers, [B] and [V + 1]
+const float *ambient_run_alpha(const AmbientRun &run);
+const float *ambient_run_soup(const AmbientRun &run);
+// the three in a row without the dense form: dmx_estep_ambient
 int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring);
 
 }  // namespace dmx

@@ -66,8 +66,9 @@ __device__ __forceinline__ void estep_terms_mixed(const npm::f32x2 (&p1)[H][A], 
     }
 }
 
-// k_estep_pools (estep_pools.hip) without its dense form, with the mixture: w0 and the stream of the soup's terms beside the records
-template <int A, bool PAIRS, int U>
+// k_estep_pools (estep_pools.hip) with the mixture: w0 and the stream of the soup's terms beside the records.  DENSE: the close also
+// leaves the singlet posteriors in a.dense, as k_estep_pools' dense form does (learning under ambient fractions: DESIGN.md 4.9)
+template <int A, bool PAIRS, int U, bool DENSE>
 __global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
 {
     const PoolEstepArgs &a = args.pools;
@@ -104,17 +105,21 @@ __global__ __launch_bounds__(256) void k_estep_ambient(AmbientEstepArgs args)
     double sum[A];
 #pragma unroll
     for (int s = 0; s < A; s++) sum[s] = acc[s];
-    pool_row_close<A, PAIRS, false>(a, lane, row, sum);
+    pool_row_close<A, PAIRS, DENSE>(a, lane, row, sum);
 }
 
 template <int A, int U>
-void launch_one(hipStream_t st, const AmbientEstepArgs &a, bool pairs)
+void launch_one(hipStream_t st, const AmbientEstepArgs &a, bool pairs, bool dense)
 {
     const dim3 grid((unsigned)((a.pools.n_list + 3) / 4)), block(256);
-    if (pairs)
-        hipLaunchKernelGGL((k_estep_ambient<A, true, U>), grid, block, 0, st, a);
+    if (pairs && dense)
+        hipLaunchKernelGGL((k_estep_ambient<A, true, U, true>), grid, block, 0, st, a);
+    else if (pairs)
+        hipLaunchKernelGGL((k_estep_ambient<A, true, U, false>), grid, block, 0, st, a);
+    else if (dense)
+        hipLaunchKernelGGL((k_estep_ambient<A, false, U, true>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((k_estep_ambient<A, false, U>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((k_estep_ambient<A, false, U, false>), grid, block, 0, st, a);
 }
 
 }  // namespace
@@ -126,60 +131,108 @@ hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a)
     return hipGetLastError();
 }
 
-hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs)
+hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs, bool dense)
 {
     if (a.pools.n_list == 0) return hipSuccess;
-    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a, pairs); });
+    if (dense && (a.pools.dense == nullptr || a.pools.G <= 0)) return hipErrorInvalidValue;
+    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a, pairs, dense); });
 }
 
-int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring)
+// what a call under ambient fractions keeps on the device between its parts (estep_ambient.h)
+struct AmbientRun {
+    scratch::Scratch sc;
+    PoolsRunPtr pools;
+    AmbientScoring scoring;
+    SoupTermArgs t = {};
+    AmbientEstepArgs a = {};
+    float *d_soup = nullptr, *d_alpha = nullptr;
+    bool dense = false;
+    bool terms_done = false;
+    AmbientRun(dmx_ctx *c, const AmbientScoring &s) : sc(c), scoring(s) {}
+};
+
+void AmbientRunDeleter::operator()(AmbientRun *run) const { delete run; }
+
+int prepare_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring, bool dense, AmbientRunPtr &run)
 {
     using namespace dmx::scratch;
     using namespace dmx::host;
-    const long long B = c->B, V = c->V;
+    const long long B = c->B;
     const hipStream_t st = c->stream;
-    PoolsRunPtr run;
-    DMX_TRY(prepare_estep_pools(c, plan, false, run));
-    const PoolsLaunchView view = pools_launch_view(*run);
+    run.reset(new AmbientRun(c, scoring));
+    AmbientRun &r = *run;
+    r.dense = dense;
+    DMX_TRY(prepare_estep_pools(c, plan, dense, r.pools));
+    const PoolsLaunchView view = pools_launch_view(*r.pools);
 
-    Scratch sc(c);
-    float *d_soup = nullptr, *d_alpha = nullptr, *d_terms = nullptr;
-    DMX_TRY(soup_profile(c, sc, "dmx_estep_ambient", scoring.ambient, scoring.lo, scoring.hi, &d_soup));
-    DMX_TRY(upload(sc, &d_alpha, scoring.alpha, (size_t)B, st));
-    DMX_TRY(sc.get(&d_terms, 2 * (size_t)c->n_pairs));  // 4 bytes per padded call
+    float *d_terms = nullptr;
+    DMX_TRY(soup_profile(c, r.sc, scoring.who, scoring.ambient, scoring.lo, scoring.hi, &r.d_soup));
+    DMX_TRY(upload(r.sc, &r.d_alpha, scoring.alpha, (size_t)B, st));
+    DMX_TRY(r.sc.get(&d_terms, 2 * (size_t)c->n_pairs));  // 4 bytes per padded call
 
-    SoupTermArgs t = {};
+    SoupTermArgs &t = r.t;
     t.pair_ptr = c->d_pair_ptr.p;
     t.pairs = c->d_call_pairs.p;
     t.order = c->d_bc_order.p;
     t.B = B;
     t.pool_of = view.args.pool_of;
-    t.alpha = d_alpha;
-    t.ambient = d_soup;
+    t.alpha = r.d_alpha;
+    t.ambient = r.d_soup;
     const aplan::RowDivide rows = aplan::row_divide((unsigned)c->G * 4u);
     t.row_shift = rows.shift;
     t.row_inverse = rows.inverse;
     t.soup_term = d_terms;
 
-    AmbientEstepArgs a = {};
-    a.pools = view.args;
-    a.pools.dense = nullptr;
-    a.alpha = d_alpha;
-    a.soup_term = (const float2 *)d_terms;
-    {
-        TimerSpan ev{nullptr, nullptr};
-        SpanGuard ev_guard{c, &ev};
-        timer_begin(c, DMX_T_ESTEP, &ev);
-        HIP_TRY(launch_soup_terms(st, t));
-        for (int k = 0; k < POOL_BUCKETS; k++) {
-            a.pools.list = view.lists[k];
-            a.pools.n_list = view.n_lists[k];
-            HIP_TRY(launch_estep_ambient(st, a, pool_bucket_slots(k), view.with_doublets));
-        }
-        timer_end(c, DMX_T_ESTEP, ev);
+    r.a.pools = view.args;
+    r.a.pools.dense = nullptr;
+    r.a.alpha = r.d_alpha;
+    r.a.soup_term = (const float2 *)d_terms;
+    return 0;
+}
+
+// The soup's terms depend on the fractions, the profile and the records, not on the table: the first pass of a run builds the stream
+// (inside its span of the DMX_T_ESTEP slot), the later ones of an EM call find it.
+int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &r, float power)
+{
+    using namespace dmx::host;
+    const hipStream_t st = c->stream;
+    const PoolsLaunchView view = pools_launch_view(*r.pools);
+    AmbientEstepArgs a = r.a;
+    a.pools.dense = r.dense ? c->d_post.p : nullptr;  // [B, G]: K = G
+    TimerSpan ev{nullptr, nullptr};
+    SpanGuard ev_guard{c, &ev};
+    timer_begin(c, DMX_T_ESTEP, &ev);
+    if (!r.terms_done) {
+        HIP_TRY(launch_soup_terms(st, r.t));
+        r.terms_done = true;
     }
-    if (scoring.ambient_out && V) HIP_TRY(hipMemcpyAsync(scoring.ambient_out, d_soup, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, st));
-    return read_back_estep_pools(c, *run);  // (synchronises: the uploads read the caller's arrays, the downloads fill them)
+    for (int k = 0; k < POOL_BUCKETS; k++) {
+        a.pools.list = view.lists[k];
+        a.pools.n_list = view.n_lists[k];
+        HIP_TRY(launch_estep_ambient(st, a, pool_bucket_slots(k), view.with_doublets, r.dense));
+    }
+    if (r.dense) DMX_TRY(close_dense_pools_pass(c, power));
+    timer_end(c, DMX_T_ESTEP, ev);
+    return 0;
+}
+
+int read_back_estep_ambient(dmx_ctx *c, AmbientRun &r)
+{
+    const AmbientScoring &scoring = r.scoring;
+    if (scoring.ambient_out && c->V)
+        HIP_TRY(hipMemcpyAsync(scoring.ambient_out, r.d_soup, sizeof(float) * (size_t)c->V, hipMemcpyDeviceToHost, c->stream));
+    return read_back_estep_pools(c, *r.pools);  // (synchronises: the uploads read the caller's arrays, the downloads fill them)
+}
+
+const float *ambient_run_alpha(const AmbientRun &run) { return run.d_alpha; }
+const float *ambient_run_soup(const AmbientRun &run) { return run.d_soup; }
+
+int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring)
+{
+    AmbientRunPtr run;
+    DMX_TRY(prepare_estep_ambient(c, plan, scoring, false, run));
+    DMX_TRY(launch_estep_ambient_pass(c, *run, 2.0f));
+    return read_back_estep_ambient(c, *run);
 }
 
 }  // namespace dmx

@@ -81,6 +81,9 @@ typedef std::unique_ptr<PoolsRun, PoolsRunDeleter> PoolsRunPtr;
 int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunPtr &run);
 int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &run, float power);
 int read_back_estep_pools(dmx_ctx *c, PoolsRun &run);
+// the tail of a dense launch, inside its span of the timer: the rebuild and the context's state.  The dense pass of another kernel
+// on a prepared run (estep_ambient.hip) ends with it too.
+int close_dense_pools_pass(dmx_ctx *c, float power);
 // the three in a row without the dense form: dmx_estep_pools
 int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan);
 // What another kernel needs to walk a prepared run in place of launch_estep_pools_pass (estep_ambient.hip): the argument block

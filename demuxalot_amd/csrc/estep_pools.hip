@@ -150,6 +150,21 @@ int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunP
     return 0;
 }
 
+int close_dense_pools_pass(dmx_ctx *c, float power)
+{
+    // the bitmap and the codes of the M-step from the [B, G] matrix, with the floor a full-table E-step of this power takes
+    // (dmx_steps.cpp: fill_estep_args); the context as run_estep leaves it, without statistics of the dense calls
+    const float floor = power == 2.0f ? NZ_FLOOR_SQUARE : 0.0f;
+    HIP_TRY(launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->G, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
+    c->post_gathered = false;
+    c->dense_stat_valid = false;
+    c->nz_floor = floor;
+    c->guard_ran = false;
+    c->have_post = true;
+    c->logits_readable = false;  // (d_logits holds nothing of this pass)
+    return 0;
+}
+
 int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &r, float power)
 {
     using namespace dmx::host;
@@ -164,18 +179,7 @@ int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &r, float power)
         a.n_list = r.n_lists[k];
         HIP_TRY(launch_estep_pools(st, a, pool_bucket_slots(k), r.plan->with_doublets, r.dense));
     }
-    if (r.dense) {
-        // the bitmap and the codes of the M-step from the [B, G] matrix, with the floor a full-table E-step of this power takes
-        // (dmx_steps.cpp: fill_estep_args); the context as run_estep leaves it, without statistics of the dense calls
-        const float floor = power == 2.0f ? NZ_FLOOR_SQUARE : 0.0f;
-        HIP_TRY(launch_rebuild_nz(st, c->d_post.p, c->B, c->G, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
-        c->post_gathered = false;
-        c->dense_stat_valid = false;
-        c->nz_floor = floor;
-        c->guard_ran = false;
-        c->have_post = true;
-        c->logits_readable = false;  // (d_logits holds nothing of this pass)
-    }
+    if (r.dense) DMX_TRY(close_dense_pools_pass(c, power));
     timer_end(c, DMX_T_ESTEP, ev);
     return 0;
 }

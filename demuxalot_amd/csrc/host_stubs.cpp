@@ -165,6 +165,23 @@ int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &, float)
 int read_back_estep_pools(dmx_ctx *, PoolsRun &) { return 0; }
 int run_ambient_profile(dmx_ctx *, const AmbientPlan &) { return 0; }  // (validated by dmx_ambient_profile; nothing is written)
 int run_estep_ambient(dmx_ctx *, const PoolsPlan &, const AmbientScoring &) { return 0; }  // (validated by dmx_estep_ambient; nothing is written)
+struct AmbientRun {};
+void AmbientRunDeleter::operator()(AmbientRun *run) const { delete run; }
+int prepare_estep_ambient(dmx_ctx *, const PoolsPlan &, const AmbientScoring &, bool, AmbientRunPtr &run)
+{
+    run.reset(new AmbientRun);
+    return 0;
+}
+int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &, float)
+{
+    c->have_post = true;
+    return 0;
+}
+int read_back_estep_ambient(dmx_ctx *, AmbientRun &) { return 0; }
+const float *ambient_run_alpha(const AmbientRun &) { return nullptr; }
+const float *ambient_run_soup(const AmbientRun &) { return nullptr; }
+int run_mstep_ambient(dmx_ctx *, float, const float *, const float *) { return 0; }  // (validated by dmx_mstep_ambient / dmx_em_ambient; nothing is written)
+int run_mstep_ambient_from_host(dmx_ctx *, float, const float *, const float *, float, float) { return 0; }
 int run_estep_ambient_grid(dmx_ctx *, const PoolsPlan &, const AmbientGridScoring &) { return 0; }  // (validated by dmx_estep_ambient_grid; nothing is written)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {

@@ -1099,6 +1099,117 @@ class Demultiplexer:
         else:
             release_private_context(ctx)
 
+    @staticmethod
+    def _ambient_learning_arguments(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, who):
+        """What the two learning entries under ambient fractions share: (alpha float32[B], pooled, pool names or None, per pool its
+        table columns, pool_of_barcode, option names - per pool, or the one list without pools -, pair_penalty)."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        alpha = resolve_fractions(barcode_handler.ordered_barcodes, ambient_fractions)
+        if barcode2pool is not None:
+            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
+                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+            return alpha, True, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty
+        pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
+            genotypes, barcode_handler, doublet_prior, who)
+        return alpha, False, None, pool_columns, pool_of_barcode, column_names, pair_penalty
+
+    @staticmethod
+    def learn_genotypes_with_ambient(chromosome2compressed_snp_calls,
+                                     genotypes,
+                                     barcode_handler,
+                                     ambient_fractions,
+                                     ambient=None,
+                                     n_iterations=5,
+                                     p_genotype_clip=0.01,
+                                     doublet_prior=0.,
+                                     barcode2pool=None,
+                                     pool2donors=None):
+        """(not in the reference) learn_genotypes for contaminated droplets: the loop of learn_genotypes_in_pools with every option
+        scored under the barcode's own ambient fraction (predict_posteriors_with_ambient's E-step) and every call's contribution to
+        the betas weighted by the probability that the call came from the donor and not from the soup,
+        r = own / (own + ambient[v] alpha_b) with own = genotype_prob[v, g] (1 - alpha_b) - at alpha = 0.4 four calls in ten come from
+        the soup and would pull the donor's betas towards the population mean.  With every fraction 0 the result is
+        learn_genotypes_in_pools' (exact mode) bit for bit.  The fractions and the soup's profile are fixed for the call (alternate
+        estimate_ambient and this call to refine them).  The whole loop runs on the GPU (dmx_em_ambient); its sums are float64 in the
+        reference's order whatever DEMUXALOT_AMD_ESTEP says.
+        :param ambient_fractions: Series or mapping barcode -> alpha in [0, 1] (AmbientEstimate.fractions() gives one); a barcode
+            that is missing, None or NaN learns with 0
+        :param ambient: float32[n_variants] allele profile of the soup, or None: derived from the calls as estimate_ambient does
+        :param barcode2pool, pool2donors: as learn_genotypes_in_pools takes them (both or neither); without them every barcode is
+            scored against all donors
+        :return: learnt genotypes (betas = raw betas + the addition used by the last E-step) and the posteriors of the last
+            iteration: probs_df as learn_genotypes returns it, or with pools a PooledPosteriors.
+        ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        alpha, pooled, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._ambient_learning_arguments(
+            genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, 'learn_genotypes_with_ambient')
+        with shared_context_lock:
+            ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
+                                          fetch_betas=False)
+            out = ctx.em_ambient(n_iterations, p_genotype_clip, pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha,
+                                 ambient=ambient, contribution_power=Demultiplexer.contribution_power, fetch_logits=pooled,
+                                 fetch_addition=False)
+            learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
+        learnt_genotypes = genotypes._with_betas(learnt_betas, _take=True)
+        if pooled:
+            return learnt_genotypes, PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode,
+                                                      out['row_ptr'], out['logits'], out['probs'], out['best_option'], out['best_prob'],
+                                                      out['doublet_mass'])
+        probs = out['probs'].reshape(barcode_handler.n_barcodes, len(option_names))
+        return learnt_genotypes, pd.DataFrame(data=probs, index=_barcode_index(barcode_handler), columns=option_names)
+
+    @staticmethod
+    def staged_genotype_learning_with_ambient(chromosome2compressed_snp_calls,
+                                              genotypes,
+                                              barcode_handler,
+                                              ambient_fractions,
+                                              ambient=None,
+                                              n_iterations=5,
+                                              p_genotype_clip=0.01,
+                                              doublet_prior=0.,
+                                              barcode2pool=None,
+                                              pool2donors=None):
+        """Generator over the iterations of learn_genotypes_with_ambient, shaped like staged_genotype_learning_in_pools: yields
+        (posteriors, debug dict with 'genotype_prior', 'genotype_addition', 'ambient'); the posteriors are a PooledPosteriors with
+        pools and probs_df without, the yielded addition is the one the iteration's E-step used, 'ambient' the soup's profile in use
+        (the one of the first iteration is kept for the later ones).  The EM state lives on the GPU between yields, in a device
+        context private to this generator."""
+        alpha, pooled, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._ambient_learning_arguments(
+            genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, 'staged_genotype_learning_with_ambient')
+
+        ctx = acquire_private_context()
+        try:
+            _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
+            genotype_addition = np.zeros_like(prior_betas)
+            ctx.set_addition(None)
+            for _iteration in range(n_iterations):
+                ctx.probs_from_betas(p_genotype_clip, fetch=False)
+                out = ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip,
+                                        ambient=ambient, fetch_logits=pooled, resident=True)
+                ambient = out['ambient']  # (a derived profile depends on the calls only: the same every iteration)
+                if pooled:
+                    posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
+                                                  out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
+                else:
+                    posteriors = pd.DataFrame(data=out['probs'].reshape(barcode_handler.n_barcodes, len(option_names)),
+                                              index=_barcode_index(barcode_handler), columns=option_names)
+                yield posteriors, {
+                    'genotype_prior': prior_betas,
+                    'genotype_addition': genotype_addition,
+                    'ambient': ambient,
+                }
+                genotype_addition = ctx.mstep_ambient(alpha, Demultiplexer.contribution_power, p_genotype_clip, ambient=ambient)
+        except GeneratorExit:  # the consumer stopped early: nothing wrong with the context
+            release_private_context(ctx)
+            raise
+        except BaseException:
+            release_private_context(ctx, failed=True)
+            raise
+        else:
+            release_private_context(ctx)
+
     # ------------------------------------------------------------------------------------
     @staticmethod
     def _doublet_penalties(n_genotypes: int, doublet_prior: float) -> np.ndarray:

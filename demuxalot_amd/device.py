@@ -747,22 +747,61 @@ class DeviceContext:
         return out
 
     def estep_ambient(self, pools, pool_of_barcode, with_doublets, pair_penalty, alpha, p_genotype_clip=0.01, ambient=None,
-                      fetch_logits=True, fetch_probs=True):
+                      fetch_logits=True, fetch_probs=True, resident=False):
         """The pooled E-step under per-barcode ambient fractions (include/demux_hip_debug.h: dmx_estep_ambient): estep_pools() with
         every option scored as q (1 - alpha[b]) + ambient[v] alpha[b].  alpha: float32[B] in [0, 1] (not looked at for a barcode in no
         pool); ambient: float32[V] or None (derived from the resident calls, clipped as the genotype table is).  Returns
         estep_pools()'s dict with one more key, 'ambient': float32[V], the profile that was used.  The resident results of the last
-        E-step are left as they are."""
+        E-step are left as they are - unless resident=True (dmx_estep_ambient_resident): then the singlet posteriors are left in the
+        context as a dense [B, G] matrix, zero outside a barcode's pool, so that mstep_ambient() or mstep() may follow and get_probs()
+        returns it."""
+        alpha, ambient = self._ambient_arguments(alpha, ambient)
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        out['ambient'] = np.empty(self.V, np.float32)
+        entry = self._lib.dmx_estep_ambient_resident if resident else self._lib.dmx_estep_ambient
+        check(entry(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, ptr(alpha), ptr(ambient),
+                    ptr(out['ambient'])))
+        if resident:
+            self.K = self.G
+        return out
+
+    def _ambient_arguments(self, alpha, ambient):
+        """(alpha float32[B], ambient float32[V] or None) as the entries under ambient fractions take them."""
         alpha = as_c(alpha, np.float32)
         assert alpha.shape == (self.B,), 'one fraction per barcode'
         if ambient is not None:
             ambient = as_c(ambient, np.float32)
             assert ambient.shape == (self.V,), 'one ambient value per variant'
+        return alpha, ambient
+
+    def mstep_ambient(self, alpha, contribution_power=2., p_genotype_clip=0.01, ambient=None, fetch=True):
+        """The M-step under per-barcode ambient fractions (include/demux_hip_debug.h: dmx_mstep_ambient): mstep() with every call's
+        contribution weighted by the probability that the call came from the donor and not from the soup,
+        r = own / (own + ambient[v] alpha[b]), own = genotype_prob[v, g] (1 - alpha[b]), on the resident posteriors and the table of
+        the last P-step.  alpha: float32[B] in [0, 1], every barcode's is read; ambient: float32[V] or None (derived from the resident
+        calls, clipped as the genotype table is).  The sums are float64 in the reference's order whatever the E-step mode.  Returns
+        the addition float32[V, G] (None without fetch); it becomes the context's, as after mstep()."""
+        alpha, ambient = self._ambient_arguments(alpha, ambient)
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        addition = np.empty((self.V, self.G), dtype=np.float32) if fetch else None
+        check(self._lib.dmx_mstep_ambient(self._h, float(contribution_power), ptr(alpha), ptr(ambient), lo, hi, ptr(addition)))
+        return addition
+
+    def em_ambient(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, alpha, ambient=None,
+                   contribution_power=2., fetch_logits=True, fetch_probs=True, fetch_addition=True):
+        """n_iterations of P-step, dense E-step under the fractions and weighted M-step on the device (include/demux_hip_debug.h:
+        dmx_em_ambient): em_pools() with estep_ambient() and mstep_ambient() in place of its two steps; the soup's profile is fixed for
+        the call.  Returns em_pools()'s dict with one more key, 'ambient': float32[V], the profile that was used.  get_learnt_betas()
+        and get_probs() (the dense [B, G] singlet posteriors) work afterwards."""
+        alpha, ambient = self._ambient_arguments(alpha, ambient)
         lo, hi = self.clip_bounds(p_genotype_clip)
         pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        out['addition'] = np.empty((self.V, self.G), dtype=np.float32) if fetch_addition else None
         out['ambient'] = np.empty(self.V, np.float32)
-        check(self._lib.dmx_estep_ambient(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, ptr(alpha),
-                                          ptr(ambient), ptr(out['ambient'])))
+        check(self._lib.dmx_em_ambient(self._h, int(n_iterations), lo, hi, int(bool(with_doublets)), *pool_args, float(contribution_power),
+                                       ptr(alpha), ptr(ambient), *self._pools_results(out), ptr(out['addition']), ptr(out['ambient'])))
+        self.K = self.G
         return out
 
     def estep_ambient_grid(self, pools, pool_of_barcode, with_doublets, pair_penalty, alphas, p_genotype_clip=0.01, ambient=None,

@@ -552,6 +552,61 @@ int dmx_estep_ambient_grid(dmx_ctx *ctx, int with_doublets, int32_t n_pools, con
                            int32_t *alpha_index /* nullable, int32[row_ptr[B]] */, int32_t *best_alpha_index /* nullable, [B] */,
                            float *profile_out /* nullable, float32[row_ptr[B] * n_alphas] */);
 
+/* ------------------------------------------------------------------------- *
+ * Learning under per-barcode ambient RNA fractions (product API; csrc/mstep_ambient.hip, csrc/estep_ambient.hip).
+ * dmx_em_pools' loop with two changes per iteration: the pooled row is dmx_estep_ambient's, and every call's contribution to the
+ * M-step is weighted by the probability that the call came from the donor and not from the soup.  For variant v, donor column g and
+ * the calls c of v in stored variant-major order, b = cb_c, in float32 without contraction:
+ *     own = prob[v, g] * (1.0f - alpha[b])
+ *     mix = own + ambient[v] * alpha[b]
+ *     r   = own == 0 ? 0.0f : own / mix                          IEEE float32 division, correctly rounded
+ *     w   = ((dense[b, g] * keep_c) * r) ^ power                 power 2: one float32 product w * w; another power:
+ *                                                                f32(pow(f64(base), f64(power))), where dmx_mstep has powf
+ *     addition[v, g] = f32( sum over c of f64(w) )               one float64 accumulator, in call order
+ * prob is the table the E-step of `dense` read; `dense` as "Learning within pools" defines it.  With alpha[b] == 0, r == 1 for every
+ * table entry other than 0, and w is dmx_mstep's: with every fraction 0 the loop is dmx_em_pools with exact additions, bit for bit (on a
+ * table without zeros: lo > 0; with another power than 2: to float32 accuracy).  alpha[b] == 1 gives r == 0: a droplet that is all
+ * soup teaches nothing.
+ * There is ONE arithmetic: the sums are float64 in the reference's order whatever dmx_set_estep_mode / dmx_set_exact_additions say;
+ * the fixed-point, tile-major and incremental M-step forms do not apply (the weights change with the table).  Only the singlet
+ * columns are learnt from, with_doublets or not.  The soup's profile is fixed for the call: supplied, or derived once from the calls
+ * as dmx_ambient_profile derives it; it does not depend on the betas.
+ *   dmx_estep_ambient_resident   the arguments, the pass and the results of dmx_estep_ambient.  It also leaves `dense` as the
+ *               context's resident posteriors with K = G (and their bitmaps and codes), as dmx_estep_pools_resident does:
+ *               dmx_get_probs, dmx_mstep, dmx_mstep_ambient and dmx_get_learnt_betas work after it.
+ *   dmx_mstep_ambient   stateless: the M-step above of the context's resident posteriors (singlet columns) and the table of the
+ *               last P-step (dmx_probs_from_betas / dmx_set_probs), with alpha float32[B] (EVERY barcode's is read), ambient
+ *               float32[V] or NULL (derived, clipped to [lo, hi]).  The addition becomes the context's (dmx_get_learnt_betas, the
+ *               next P-step) and is copied to addition_out (nullable, float32[V, G]).  DMX_ERR_INVALID without a problem, a
+ *               table or posteriors.
+ *   dmx_em_ambient   n_iterations >= 1 of: genotype_prob from betas + addition clipped to [lo, hi] (the addition starts at 0), the
+ *               dense E-step under the fractions, the M-step above - all on the device, the M-step after the last E-step left out;
+ *               the pools' round trip, the uploads, the profile and the soup's terms are paid once.  Outputs (each nullable): what
+ *               dmx_em_pools returns, and ambient_out float32[V], the profile that was used.  (call order: a problem and
+ *               dmx_set_betas / dmx_set_prior_betas)
+ * Checked on the host before anything is uploaded or launched (csrc/ambient_learning_plan.h).  DMX_ERR_INVALID: n_iterations < 1, a
+ * power that is not finite or not above 0, everything dmx_estep_ambient refuses so.  DMX_ERR_UNSUPPORTED: a communicator attached or
+ * more than one rank, a pool of more than 1024 options, a genotype table in a padded exchange layout.  The E-steps are counted in
+ * the DMX_T_ESTEP slot, the walk of the M-step in DMX_T_MSTEP, its combining pass and the redo in DMX_T_MCOMBINE; dmx_get_redo_count
+ * returns the sums the last M-step redid in call order.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_ambient_resident(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                               const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                               const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                               float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                               int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                               float lo, float hi, const float *alpha /* [B] */, const float *ambient /* nullable, [V] */,
+                               float *ambient_out /* nullable, [V] */);
+int dmx_mstep_ambient(dmx_ctx *ctx, float power, const float *alpha /* [B] */, const float *ambient /* nullable, [V] */, float lo, float hi,
+                      float *addition_out /* nullable, float32[V, G] */);
+int dmx_em_ambient(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools,
+                   const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                   const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */, float power,
+                   const float *alpha /* [B] */, const float *ambient /* nullable, [V] */,
+                   float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                   int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                   float *addition_out /* nullable, float32[V, G] */, float *ambient_out /* nullable, [V] */);
+
 #ifdef __cplusplus
 }
 #endif
