@@ -116,10 +116,13 @@ class JointAmbientPosteriors:
     entries row_ptr[b] .. row_ptr[b + 1] of the compact per-option arrays; alpha_index int32[row_ptr[B]]: the grid point of every
     option's first maximum (-1: every value NaN); option_alphas float64[row_ptr[B]]: its grid value, NaN where there is none;
     best_option, best_prob, doublet_mass, best_alpha_index [B]: the read-outs of the pass (-1 / NaN / NaN / -1 for a barcode in no
-    pool); profile float32[row_ptr[B], A]: every option's logit at every grid point, or None when it was not kept."""
+    pool); profile float32[row_ptr[B], A]: every option's logit at every grid point, or None when it was not kept.
+    over_grid: 'max', or 'marginal' - every option's logit the log of the (weighted) sum over the grid, alpha_index the grid point of
+    the largest term; then option_alpha_means float64[row_ptr[B]] is every option's posterior mean fraction (NaN where there is
+    none) and best_alpha_mean float32[B] that of best_option; under 'max' both are None."""
 
     def __init__(self, barcodes, option_names, pool_of_barcode, row_ptr, alphas, ambient, alpha_index, best_option, best_prob, doublet_mass,
-                 best_alpha_index, posteriors, profile=None, index_name='BARCODE'):
+                 best_alpha_index, posteriors, profile=None, index_name='BARCODE', over_grid='max', alpha_mean=None, best_alpha_mean=None):
         self.barcodes = list(barcodes)
         self._option_names = [list(names) for names in option_names]  # per pool
         self.pool_of_barcode = np.asarray(pool_of_barcode, dtype=np.int32)
@@ -141,6 +144,13 @@ class JointAmbientPosteriors:
         assert np.array_equal(np.diff(self.row_ptr), widths[self.pool_of_barcode]), 'row_ptr does not follow the pools'
         assert ((self.alpha_index >= -1) & (self.alpha_index < len(self.alphas))).all()
         self.option_alphas = self._grid_values(self.alpha_index)
+        assert over_grid in ('max', 'marginal') and (over_grid == 'marginal') == (alpha_mean is not None) == (best_alpha_mean is not None)
+        self.over_grid = over_grid
+        self.option_alpha_means = self.best_alpha_mean = None
+        if over_grid == 'marginal':
+            self.option_alpha_means = np.asarray(alpha_mean, dtype=np.float32).astype(np.float64)
+            self.best_alpha_mean = np.asarray(best_alpha_mean, dtype=np.float32)
+            assert self.option_alpha_means.shape == self.option_alphas.shape and self.best_alpha_mean.shape == (B,)
         self.profile = None
         if profile is not None:
             self.profile = np.asarray(profile, dtype=np.float32)
@@ -166,14 +176,18 @@ class JointAmbientPosteriors:
         """Per barcode (all of them, handler order): `option`, the name of the most probable option (None: none, or in no pool);
         `probability`, its posterior; `alpha`, the grid value at which that option was scored (NaN: none); `doublet_probability`,
         the posterior mass of the pair options (float64); `at_grid_edge`: that alpha is the largest grid value, so the maximum may
-        lie beyond the grid."""
+        lie beyond the grid.  Under over_grid='marginal' `alpha` is the grid value of that option's largest term, and one more
+        column, `alpha_mean`, holds its posterior mean fraction (float64; NaN: none)."""
         option = np.empty(len(self.barcodes), dtype=object)
         for b, (p, k) in enumerate(zip(self.pool_of_barcode, self.best_option)):
             option[b] = self._option_names[p][k] if p >= 0 and k >= 0 else None
         alpha = self._grid_values(self.best_alpha_index)
         at_edge = (self.best_alpha_index >= 0) & (alpha == np.float64(self.alphas.max()))
-        return pd.DataFrame({'option': option, 'probability': self.best_prob, 'alpha': alpha, 'doublet_probability': self.doublet_mass,
-                             'at_grid_edge': at_edge}, index=self._index())
+        frame = pd.DataFrame({'option': option, 'probability': self.best_prob, 'alpha': alpha, 'doublet_probability': self.doublet_mass,
+                              'at_grid_edge': at_edge}, index=self._index())
+        if self.over_grid == 'marginal':
+            frame['alpha_mean'] = self.best_alpha_mean.astype(np.float64)
+        return frame
 
 
 class AmbientEstimate:

@@ -3,7 +3,8 @@
 // restated: they are ambient_scoring_plan.h's two ends (the same pplan::check inside).  What this header adds is the grid, under
 // dmx_ambient_profile's rules: 1 .. 64 values, finite, in [0, 1], any order, duplicates allowed.  Host only: nothing of HIP, nothing
 // of dmx_ctx.  dmx_steps.cpp: dmx_estep_ambient_grid asks check() before anything is uploaded or launched;
-// tests/ambient_grid_plan_check.cpp walks it on the CPU.
+// tests/ambient_grid_plan_check.cpp walks it on the CPU.  check_marginal() is dmx_estep_ambient_grid_marginal's:
+// check() and the rule for its log weights; tests/ambient_marginal_plan_check.cpp walks that.
 #pragma once
 #include "ambient_scoring_plan.h"
 
@@ -30,6 +31,17 @@ inline Verdict check(const Facts &f, const Pools &p, long long n_alphas, const f
     for (long long j = 0; j < n_alphas; j++)
         if (!aplan::unit_range(alphas[j])) return {INVALID, "a grid value is not finite or outside [0, 1]", j};
     return asplan::check_profile(f, ambient);
+}
+
+// dmx_estep_ambient_grid_marginal: check() and the prior over the grid, log_weights - absent (all 0) or n_alphas finite values.  The
+// weights come last: a call that check() refuses is refused with check()'s words.
+inline Verdict check_marginal(const Facts &f, const Pools &p, long long n_alphas, const float *alphas, const float *ambient, const float *log_weights)
+{
+    const Verdict grid = check(f, p, n_alphas, alphas, ambient);
+    if (grid.status != OK || !log_weights) return grid;
+    for (long long j = 0; j < n_alphas; j++)
+        if (!(log_weights[j] - log_weights[j] == 0.0f)) return {INVALID, "a log weight is not finite", j};
+    return grid;
 }
 
 }  // namespace agplan

@@ -1034,7 +1034,30 @@ int dmx_estep_ambient_grid(dmx_ctx *c, int with_doublets, int32_t n_pools, const
     if (verdict.status != gp::OK) return refuse("dmx_estep_ambient_grid", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
     fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
-    const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, profile_out};
+    const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, profile_out,
+                                          false, nullptr, nullptr, nullptr};
+    return dmx::run_estep_ambient_grid(c, plan, scoring);
+}
+
+// The same pass with every option's logit the log of the weighted sum over the grid (estep_ambient_grid.hip: the MARGINAL forms).
+// ambient_grid_plan.h's check_marginal refuses, on the host, before anything is uploaded or launched.
+int dmx_estep_ambient_grid_marginal(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                                    const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                                    float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi,
+                                    int32_t n_alphas, const float *alphas, const float *ambient, float *ambient_out, int32_t *alpha_index,
+                                    int32_t *best_alpha_index, const float *log_weights, float *alpha_mean, float *best_alpha_mean)
+{
+    namespace gp = dmx::agplan;
+    DMX_TRY(bind(c));
+    const gp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
+                          c->B,           c->V,          c->G};
+    const gp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    const gp::Verdict verdict = gp::check_marginal(facts, pools, n_alphas, alphas, ambient, log_weights);
+    if (verdict.status != gp::OK) return refuse("dmx_estep_ambient_grid_marginal", verdict.status, verdict.what, verdict.at, verdict.value);
+    dmx::PoolsPlan plan;
+    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, nullptr,
+                                          true, log_weights, alpha_mean, best_alpha_mean};
     return dmx::run_estep_ambient_grid(c, plan, scoring);
 }
 

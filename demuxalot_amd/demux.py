@@ -969,7 +969,9 @@ class Demultiplexer:
                                          doublet_prior=0.35,
                                          barcode2pool=None,
                                          pool2donors=None,
-                                         keep_profile=False) -> JointAmbientPosteriors:
+                                         keep_profile=False,
+                                         over_grid='max',
+                                         alpha_log_weights=None) -> JointAmbientPosteriors:
         """(not in the reference) predict_posteriors with every option - singlets and pairs - scored at its own best ambient
         fraction: a call's term is q (1 - alpha) + ambient[v] alpha, an option's logit the maximum over the grid `alphas` of its
         log-likelihood (plus the pair penalty), and the posteriors one softmax over those.  The choice between "a contaminated
@@ -981,13 +983,29 @@ class Demultiplexer:
         :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
         :param keep_profile: also return every option's logit at every grid point (JointAmbientPosteriors.profile: the grid's
             length times the logits' memory)
+        :param over_grid: 'max' (the default, as above) or 'marginal': an option's logit is the log of the sum over the grid of
+            exp(log-likelihood + alpha_log_weights) - an option that fits over a wide range of fractions is credited for it, which
+            finds more of the true doublets among droplets with few calls.  With alphas=[0.0] both are
+            predict_posteriors'.  'marginal' keeps no profile: with keep_profile it raises.
+        :param alpha_log_weights: ('marginal' only) the log of a prior over the grid, one finite value per grid value; None: flat
         Returns a JointAmbientPosteriors: .posteriors is (logits_df, probs_df) with predict_posteriors' index, columns and dtypes,
-        with pools a PooledPosteriors; .option_alphas, .summary().
-        ValueError: a grid value outside [0, 1], an empty grid or more than 64 values, more than 1024 options without pools."""
+        with pools a PooledPosteriors; .option_alphas, .summary(); under 'marginal' also .option_alpha_means.
+        ValueError: a grid value outside [0, 1], an empty grid or more than 64 values, more than 1024 options without pools,
+        over_grid='marginal' with keep_profile, alpha_log_weights with over_grid='max'."""
+        if over_grid not in ('max', 'marginal'):
+            raise ValueError(f"over_grid is 'max' or 'marginal', not {over_grid!r}")
+        if over_grid == 'marginal' and keep_profile:
+            raise ValueError("keep_profile needs over_grid='max': the marginal pass keeps no profile")
+        if alpha_log_weights is not None and over_grid != 'marginal':
+            raise ValueError("alpha_log_weights are the prior of over_grid='marginal'; the maximum takes none")
         assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
         assert 0 <= doublet_prior < 1
         assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
         grid = resolve_grid(alphas)
+        if alpha_log_weights is not None:
+            alpha_log_weights = np.ascontiguousarray(alpha_log_weights, dtype=np.float32).reshape(-1)
+            if alpha_log_weights.shape != grid.shape or not np.isfinite(alpha_log_weights).all():
+                raise ValueError('alpha_log_weights: one finite value per grid value')
         pooled = barcode2pool is not None
         if pooled:
             pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
@@ -1002,8 +1020,12 @@ class Demultiplexer:
             ctx.set_addition(None)
             genotype_prob = ctx.probs_from_betas(p_genotype_clip)
             assert np.isfinite(genotype_prob).all()
-            out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
-                                         fetch_profile=keep_profile)
+            if over_grid == 'marginal':
+                out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
+                                             over_grid='marginal', log_weights=alpha_log_weights)
+            else:
+                out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
+                                             fetch_profile=keep_profile)
         if pooled:
             posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                           out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
@@ -1013,7 +1035,8 @@ class Demultiplexer:
                           pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names))
         return JointAmbientPosteriors(barcode_handler.ordered_barcodes, option_names, pool_of_barcode, out['row_ptr'], grid, out['ambient'],
                                       out['alpha_index'], out['best_option'], out['best_prob'], out['doublet_mass'], out['best_alpha_index'],
-                                      posteriors, profile=out['profile'], index_name='BARCODE')
+                                      posteriors, profile=out['profile'], index_name='BARCODE', over_grid=over_grid,
+                                      alpha_mean=out.get('alpha_mean'), best_alpha_mean=out.get('best_alpha_mean'))
 
     @staticmethod
     def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):

@@ -805,7 +805,8 @@ class DeviceContext:
         return out
 
     def estep_ambient_grid(self, pools, pool_of_barcode, with_doublets, pair_penalty, alphas, p_genotype_clip=0.01, ambient=None,
-                           fetch_logits=True, fetch_probs=True, fetch_alpha_index=True, fetch_profile=False):
+                           fetch_logits=True, fetch_probs=True, fetch_alpha_index=True, fetch_profile=False, over_grid='max', log_weights=None,
+                           fetch_alpha_mean=True):
         """The pooled E-step with every option at its own best ambient fraction (include/demux_hip_debug.h: dmx_estep_ambient_grid):
         estep_ambient() on the grid `alphas` (float32, 1 .. 64 values in [0, 1], any order), every option's logit its first maximum
         over the grid, one softmax over those.  ambient: float32[V] or None (derived from the resident calls, clipped as the genotype
@@ -813,9 +814,24 @@ class DeviceContext:
         'alpha_index' int32[row_ptr[B]], the grid point of every option's maximum (None without fetch_alpha_index);
         'best_alpha_index' int32[B], that of best_option (-1: none); 'profile' float32[row_ptr[B], A], every option's logit at every
         grid point (None without fetch_profile: A times the logits' memory).  The resident results of the last E-step are left as
-        they are."""
+        they are.
+        over_grid='marginal' (dmx_estep_ambient_grid_marginal): every option's logit is the log of the sum over the grid of
+        exp(its logit there + log_weights) instead of the maximum; log_weights: float32[A], the log of a prior over the grid, or None
+        (all 0).  'alpha_index' is then the first maximum of logit + log_weights, and there are two more keys: 'alpha_mean'
+        float32[row_ptr[B]], every option's posterior mean fraction (None without fetch_alpha_mean), 'best_alpha_mean' float32[B],
+        that of best_option (NaN: none).  The profile is the max mode's: fetch_profile with 'marginal' raises."""
+        if over_grid not in ('max', 'marginal'):
+            raise ValueError(f"over_grid is 'max' or 'marginal', not {over_grid!r}")
+        marginal = over_grid == 'marginal'
+        if marginal and fetch_profile:
+            raise ValueError("the profile is not kept with over_grid='marginal': ask for it with over_grid='max'")
+        if log_weights is not None and not marginal:
+            raise ValueError("log_weights are the prior of over_grid='marginal'; the maximum takes none")
         alphas = as_c(alphas, np.float32)
         assert alphas.ndim == 1, 'the grid is one-dimensional'
+        if log_weights is not None:
+            log_weights = as_c(log_weights, np.float32)
+            assert log_weights.shape == alphas.shape, 'one log weight per grid value'
         if ambient is not None:
             ambient = as_c(ambient, np.float32)
             assert ambient.shape == (self.V,), 'one ambient value per variant'
@@ -827,6 +843,14 @@ class DeviceContext:
         out['alpha_index'] = np.full(n, -1, np.int32) if fetch_alpha_index else None
         out['best_alpha_index'] = np.full(self.B, -1, np.int32)
         out['profile'] = np.empty((n, A), np.float32) if fetch_profile else None
+        if marginal:
+            out['alpha_mean'] = np.full(n, np.nan, np.float32) if fetch_alpha_mean else None
+            out['best_alpha_mean'] = np.full(self.B, np.nan, np.float32)
+            check(self._lib.dmx_estep_ambient_grid_marginal(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, A,
+                                                            ptr(alphas), ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']),
+                                                            ptr(out['best_alpha_index']), ptr(log_weights), ptr(out['alpha_mean']),
+                                                            ptr(out['best_alpha_mean'])))
+            return out
         check(self._lib.dmx_estep_ambient_grid(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, A, ptr(alphas),
                                                ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']), ptr(out['best_alpha_index']),
                                                ptr(out['profile'])))

@@ -553,6 +553,45 @@ int dmx_estep_ambient_grid(dmx_ctx *ctx, int with_doublets, int32_t n_pools, con
                            float *profile_out /* nullable, float32[row_ptr[B] * n_alphas] */);
 
 /* ------------------------------------------------------------------------- *
+ * The same pass with the grid summed instead of searched (product API; csrc/estep_ambient_grid.hip: the MARGINAL forms;
+ * DESIGN.md 4.10).  The maximum gives an option no credit for fitting over a wide range of fractions; here an option's logit is the
+ * log of the sum over the grid of exp(lambda + log_weights), in a defined order.  The arguments are dmx_estep_ambient_grid's without
+ * profile_out, and:
+ *   log_weights      float32[n_alphas], nullable (NULL: all 0): the log of a prior over the grid; every value finite.
+ *   alpha_mean       float32[row_ptr[B]], nullable, compact like the logits; best_alpha_mean float32[B], nullable.
+ * lambda[b, k, j], pen and the float64 sum S[b, k, j] of the log terms are dmx_estep_ambient_grid's: lambda = f32(f64(pen) + S).  Per
+ * option, j ascending, in float32, every operation rounded, no contraction (exp and log are the E-step's own float32 kernels):
+ *     t = lambda[j] + log_weights[j]                                  a NaN is skipped
+ *     first t:    jm = j; m = t; s = 1; u = alphas[j]
+ *     t >  m:     r = exp(m - t); s = s * r + 1; u = u * r + alphas[j]; m = t; jm = j
+ *     t == m:     s = s + 1; u = u + alphas[j]                        (-inf == -inf among them)
+ *     t <  m:     x = exp(t - m); s = s + x; u = u + alphas[j] * x
+ *   after the grid:
+ *     logit[b, k]      = f32( f64(pen) + ( S[b, k, jm] + f64( f32(log_weights[jm] + log(s)) ) ) )     NaN if no t was a number
+ *     alpha_index      = jm (-1 if none): the first maximum of lambda + log_weights
+ *     alpha_mean[b, k] = u / s                                        IEEE float32 division; NaN if none
+ * The softmax, the compact rows and the read-outs are dmx_estep_pools' on these logits; best_alpha_index[b] and best_alpha_mean[b]
+ * are best_option's entries (-1 / NaN where there is none).
+ * Identities, bit for bit: with n_alphas == 1 and log_weights NULL or {0} every shared output is dmx_estep_ambient_grid's (and so
+ * dmx_estep_ambient's; with alphas = {0} dmx_estep_pools'), and alpha_mean is alphas[0] wherever the logit is no NaN; with
+ * log_weights NULL alpha_index and best_alpha_index are dmx_estep_ambient_grid's and every logit is >= its logit; with the grid
+ * {a, a} the logit is f32(f64(pen) + (S + f64(log(2.0f)))); log_weights of all zeros is log_weights NULL.
+ * Checked on the host before anything is uploaded or launched (csrc/ambient_grid_plan.h: check_marginal): everything
+ * dmx_estep_ambient_grid refuses, with its codes, and DMX_ERR_INVALID for a log weight that is not finite.  The resident results of
+ * the last dmx_estep / dmx_em are left as they are; the pass is counted in the DMX_T_ESTEP slot.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_ambient_grid_marginal(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                                    const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                                    const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                                    float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                                    int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                                    float lo, float hi, int32_t n_alphas, const float *alphas /* [n_alphas] */,
+                                    const float *ambient /* nullable, [V] */, float *ambient_out /* nullable, [V] */,
+                                    int32_t *alpha_index /* nullable, int32[row_ptr[B]] */, int32_t *best_alpha_index /* nullable, [B] */,
+                                    const float *log_weights /* nullable, [n_alphas] */,
+                                    float *alpha_mean /* nullable, float32[row_ptr[B]] */, float *best_alpha_mean /* nullable, [B] */);
+
+/* ------------------------------------------------------------------------- *
  * Learning under per-barcode ambient RNA fractions (product API; csrc/mstep_ambient.hip, csrc/estep_ambient.hip).
  * dmx_em_pools' loop with two changes per iteration: the pooled row is dmx_estep_ambient's, and every call's contribution to the
  * M-step is weighted by the probability that the call came from the donor and not from the soup.  For variant v, donor column g and
