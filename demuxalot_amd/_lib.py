@@ -169,8 +169,20 @@ DEBUG_SIGNATURES = {
     'dmx_mstep_ambient': (c_int, [_P, c_float, _P, _P, c_float, c_float, _P]),
     'dmx_em_ambient': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P,
                                _P]),
+    'dmx_set_keep_pooled': (c_int, [_P, c_int]),
+    'dmx_pooled_upload': (c_int, [_P, c_int64, c_int32, c_int, c_int32, _P, _P, _P, _P, _P, _P]),
+    'dmx_pooled_info': (c_int, [_P, POINTER(c_int64)]),
+    'dmx_pooled_release': (c_int, [_P]),
+    'dmx_pooled_get': (c_int, [_P, c_int, c_int64, c_int64, _P]),
+    'dmx_pooled_get_pool': (c_int, [_P, c_int, c_int32, _P]),
+    'dmx_pooled_readout': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'dmx_pooled_top_options': (c_int, [_P, c_int32, _P, _P]),
+    'dmx_pooled_option_sums': (c_int, [_P, _P, _P]),
+    'dmx_pooled_allowed_mass': (c_int, [_P, _P, _P, _P, _P]),
 }
 
+POOLED_INFO = ('present', 'B', 'n_pools', 'n_values', 'with_doublets', 'has_logits', 'has_alpha_index', 'has_alpha_mean')  # dmx_pooled_info
+POOLED_WHAT = {'logits': (0, 'float32'), 'probs': (1, 'float32'), 'alpha_index': (2, 'int32'), 'alpha_mean': (3, 'float32')}  # dmx_pooled_get
 COVERAGE_STAGES = ('upload', 'walk', 'window', 'accumulate', 'filter', 'top_n')  # dmx_get_coverage_timings
 COVERAGE_ATOMIC, COVERAGE_TILED = 0, 1  # dmx_set_coverage_form
 CALLS_INFO = ('n_molecules', 'n_snp_calls', 'nbytes', 'sealed')  # dmx_calls_info

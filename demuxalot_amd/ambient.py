@@ -190,6 +190,68 @@ class JointAmbientPosteriors:
         return frame
 
 
+class DeviceJointAmbientPosteriors:
+    """The result of one predict_posteriors_joint_ambient call with on_device=True: the compact rows - logits, posteriors, every
+    option's grid point and, under 'marginal', its posterior mean fraction - stay on the GPU; what is held here is
+    B-sized.  posteriors: the DevicePooledPosteriors of the call (without pools: one pool, 'all'); alphas, ambient, over_grid,
+    best_alpha_index and best_alpha_mean as JointAmbientPosteriors holds them.  close() closes the posteriors."""
+
+    def __init__(self, posteriors, alphas, ambient, best_alpha_index, over_grid='max', best_alpha_mean=None):
+        self.posteriors = posteriors
+        self.barcodes = posteriors.barcodes
+        self.alphas = np.asarray(alphas, dtype=np.float32)
+        self.ambient = np.asarray(ambient, dtype=np.float32)
+        self.best_alpha_index = np.asarray(best_alpha_index, dtype=np.int32)
+        assert over_grid in ('max', 'marginal') and (over_grid == 'marginal') == (best_alpha_mean is not None)
+        self.over_grid = over_grid
+        self.best_alpha_mean = None if best_alpha_mean is None else np.asarray(best_alpha_mean, dtype=np.float32)
+        assert self.best_alpha_index.shape == (len(self.barcodes),)
+
+    def _grid_values(self, index):
+        found = index >= 0
+        return np.where(found, self.alphas[np.where(found, index, 0)].astype(np.float64), np.nan)
+
+    def _row(self, barcode, what):
+        post = self.posteriors
+        b = post.barcodes.index(barcode)
+        p = post.pool_of_barcode[b]
+        names = post.columns_of(post.pools[p]) if p >= 0 else []
+        return post._ctx.pooled_get(what, b, b + 1, len(names)), names
+
+    def alphas_of(self, barcode) -> pd.Series:
+        """option name -> the grid value of that option's maximum, for one barcode (empty for a barcode in no pool): one row of
+        the resident alpha_index."""
+        index, names = self._row(barcode, 'alpha_index')
+        return pd.Series(self._grid_values(index), index=names, name='alpha')
+
+    def alpha_means_of(self, barcode) -> pd.Series:
+        """('marginal' only) option name -> that option's posterior mean fraction, for one barcode."""
+        if self.over_grid != 'marginal':
+            raise ValueError("posterior mean fractions come with over_grid='marginal'")
+        mean, names = self._row(barcode, 'alpha_mean')
+        return pd.Series(mean.astype(np.float64), index=names, name='alpha_mean')
+
+    def summary(self) -> pd.DataFrame:
+        """JointAmbientPosteriors.summary(), from the B-sized read-outs alone."""
+        post = self.posteriors
+        alpha = self._grid_values(self.best_alpha_index)
+        at_edge = (self.best_alpha_index >= 0) & (alpha == np.float64(self.alphas.max()))
+        frame = pd.DataFrame({'option': post._option_labels(post.best_option), 'probability': post.best_prob, 'alpha': alpha,
+                              'doublet_probability': post.doublet_mass, 'at_grid_edge': at_edge}, index=post._index())
+        if self.over_grid == 'marginal':
+            frame['alpha_mean'] = self.best_alpha_mean.astype(np.float64)
+        return frame
+
+    def close(self):
+        self.posteriors.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class AmbientEstimate:
     """The result of one estimate_ambient call, host-resident.
 

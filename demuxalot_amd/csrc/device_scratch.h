@@ -40,6 +40,17 @@ struct Scratch {
         *out = (T *)p;
         return 0;
     }
+    // Hand-over: the block leaves this call's temporaries and stays allocated; the caller owns it from here (ctx_free when done).
+    // False when the block is not one of this call's.
+    bool hand_over(const void *p)
+    {
+        for (size_t i = 0; i < ptrs.size(); i++)
+            if (ptrs[i] == p) {
+                ptrs.erase(ptrs.begin() + (long)i);
+                return true;
+            }
+        return false;
+    }
 };
 
 inline unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }

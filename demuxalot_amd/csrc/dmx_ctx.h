@@ -113,6 +113,31 @@ struct ResidentCalls {
     bool sealed = false;
 };
 
+// The resident compact result of a pooled pass (include/demux_hip_debug.h "Pooled results kept resident"; csrc/pooled_readout.hip;
+// DESIGN.md 4.11): the pool layout, the compact rows and every pool's barcode list in blocks of the context's cache, beside host
+// copies of what the entries validate against.  Independent of have_post / d_post; its blocks are NOT counted in dmx_ctx::bytes
+// (dmx_pooled_info reports them).
+struct PooledSlot {
+    bool present = false;
+    bool with_doublets = false;
+    long long B = 0, n_pools = 0, n_values = 0;
+    long long *opt_ptr = nullptr;        // [n_pools + 1] first option of every pool in `opts`
+    unsigned *opts = nullptr;            // d1 | d2 << 16 (PoolEstepArgs::opts)
+    int *pool_size = nullptr;            // [n_pools]
+    int *pool_of = nullptr;              // [B]
+    long long *row_ptr = nullptr;        // [B + 1]
+    float *post = nullptr, *logits = nullptr;  // compact rows (logits may be absent)
+    int *alpha_index = nullptr;          // compact, from the grid passes
+    float *alpha_mean = nullptr;         // compact, from the marginal pass
+    long long *marg_ptr = nullptr;       // [B + 1] first donor marginal of every barcode (g_p entries each)
+    long long *pool_list_ptr = nullptr;  // [n_pools + 1]
+    int *pool_list = nullptr;            // every pool's barcodes, ascending
+    std::vector<int64_t> h_opt_ptr, h_row_ptr, h_pool_list_ptr, h_marg_ptr;
+    std::vector<int> h_pool_size;
+    std::vector<int32_t> h_pool_of;
+    int64_t bytes = 0;                   // device bytes held
+};
+
 struct dmx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -299,6 +324,9 @@ struct dmx_ctx {
     // resident call sets (resident_calls.hip): the caller's, by handle, with the life cycle of the resident read sets
     std::map<int64_t, ResidentCalls> resident_calls;
     int64_t calls_transfer_bytes[2] = {0, 0};  // call records copied host to device / device to host so far (dmx_get_calls_transfer_bytes)
+    // the pooled slot (pooled_readout.hip): dmx_release_problem and dmx_destroy drop it; nothing of the dense path reads or writes it
+    PooledSlot pooled;
+    int keep_pooled = 0;  // dmx_set_keep_pooled: dmx_estep_pools, dmx_estep_ambient and the two grid passes leave their compact result there
 
     // ---- multi-GPU (dmx_api.cpp: "exchange") ----
     // The [V, G] tables that cross ranks live in a PADDED row layout: the variants are cut into nranks slices at

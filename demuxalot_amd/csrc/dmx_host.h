@@ -26,6 +26,8 @@ void release_count_reads(dmx_ctx *c);    // the records of dmx_count_reads / dmx
 void release_count_reads_carry(dmx_ctx *c);   // the carry of a read-counting stream
 void release_count_reads_stream(dmx_ctx *c);  // the whole stream: carry, positions, table, state
 void release_coverage(dmx_ctx *c);       // the window and the candidates of dmx_coverage_* (coverage.hip)
+void release_pooled_slot(dmx_ctx *c);     // the resident compact result of a pooled pass (pooled_readout.hip)
+void free_pooled_slot(dmx_ctx *c, PooledSlot &slot);  // ... and one that is not (yet, or any more) the context's
 void release_resident_reads(dmx_ctx *c, ResidentReads &set);  // the buffers of one resident read set (resident_reads.hip)
 // the set behind a handle of dmx_reads_upload on this context; a stale or foreign handle: DMX_ERR_INVALID
 int find_resident_reads(dmx_ctx *c, int64_t handle, const char *who, ResidentReads **set);

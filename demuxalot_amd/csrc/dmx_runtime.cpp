@@ -608,6 +608,18 @@ void release_coverage(dmx_ctx *c)
     c->cov_start = 0;
 }
 
+// every block of a pooled slot back to the cache (a slot that was never filled holds none)
+void free_pooled_slot(dmx_ctx *c, PooledSlot &slot)
+{
+    void *const blocks[] = {slot.opt_ptr, slot.opts, slot.pool_size, slot.pool_of, slot.row_ptr, slot.post, slot.logits, slot.alpha_index,
+                            slot.alpha_mean, slot.marg_ptr, slot.pool_list_ptr, slot.pool_list};
+    for (void *p : blocks)
+        if (p) ctx_free(c, p);
+    slot = PooledSlot();
+}
+
+void release_pooled_slot(dmx_ctx *c) { free_pooled_slot(c, c->pooled); }
+
 void release_resident_reads(dmx_ctx *c, ResidentReads &set)
 {
     free_read_columns(c, set.columns);
@@ -723,6 +735,7 @@ int dmx_destroy(dmx_ctx *c)
     release_count_reads(c);
     release_count_reads_stream(c);
     release_coverage(c);
+    release_pooled_slot(c);
     for (auto &entry : c->resident_reads) release_resident_reads(c, entry.second);
     c->resident_reads.clear();
     for (auto &entry : c->resident_calls) release_resident_calls(c, entry.second);
@@ -758,6 +771,7 @@ int dmx_release_problem(dmx_ctx *c)
     release_count_reads(c);
     release_count_reads_stream(c);
     release_coverage(c);
+    release_pooled_slot(c);
     dmx::release_staged_calls(c);
     return 0;
 }

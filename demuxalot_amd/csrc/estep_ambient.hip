@@ -232,7 +232,8 @@ int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &s
     AmbientRunPtr run;
     DMX_TRY(prepare_estep_ambient(c, plan, scoring, false, run));
     DMX_TRY(launch_estep_ambient_pass(c, *run, 2.0f));
-    return read_back_estep_ambient(c, *run);
+    DMX_TRY(read_back_estep_ambient(c, *run));
+    return keep_pools_run(c, *run->pools);
 }
 
 }  // namespace dmx

@@ -413,7 +413,8 @@ int run_estep_ambient_grid(dmx_ctx *c, const PoolsPlan &plan, const AmbientGridS
     if (marginal && scoring.best_alpha_mean && B) HIP_TRY(hipMemcpyAsync(scoring.best_alpha_mean, d_best_mean, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (with_profile && n_values)
         HIP_TRY(hipMemcpyAsync(scoring.profile_out, d_profile, sizeof(float) * n_values * (size_t)scoring.n_alphas, hipMemcpyDeviceToHost, st));
-    return read_back_estep_pools(c, *run);  // (synchronises: the uploads read the caller's arrays, the downloads fill them)
+    DMX_TRY(read_back_estep_pools(c, *run));  // (synchronises: the uploads read the caller's arrays, the downloads fill them)
+    return keep_pools_run(c, *run, &sc, d_alpha_index, d_alpha_mean);
 }
 
 }  // namespace dmx

@@ -96,4 +96,16 @@ struct PoolsLaunchView {
 };
 PoolsLaunchView pools_launch_view(const PoolsRun &run);
 
+// dmx_set_keep_pooled: after a successful read-back the pass's compact result becomes the context's pooled slot.
+// keep_pooled_result (pooled_readout.hip) hands the layout arrays and the rows over from the temporaries they were allocated in;
+// keep_pools_run does so for a prepared run when the switch is on (and nothing when it is off), with the compact alpha_index /
+// alpha_mean of a grid pass out of that pass's own temporaries.  dmx_estep_pools_resident, dmx_estep_ambient_resident, dmx_em_pools
+// and dmx_em_ambient never call it: the slot is none of theirs.
+namespace scratch {
+struct Scratch;
+}
+int keep_pooled_result(dmx_ctx *c, const PoolsPlan &plan, const PoolEstepArgs &a, scratch::Scratch &rows, scratch::Scratch *grid,
+                       const int *alpha_index, const float *alpha_mean);
+int keep_pools_run(dmx_ctx *c, PoolsRun &run, scratch::Scratch *grid = nullptr, const int *alpha_index = nullptr, const float *alpha_mean = nullptr);
+
 }  // namespace dmx

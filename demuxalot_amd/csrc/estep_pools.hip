@@ -218,12 +218,19 @@ PoolsLaunchView pools_launch_view(const PoolsRun &run)
     return view;
 }
 
+int keep_pools_run(dmx_ctx *c, PoolsRun &r, scratch::Scratch *grid, const int *alpha_index, const float *alpha_mean)
+{
+    if (!c->keep_pooled) return 0;
+    return keep_pooled_result(c, *r.plan, r.a, r.sc, grid, alpha_index, alpha_mean);
+}
+
 int run_estep_pools(dmx_ctx *c, const PoolsPlan &plan)
 {
     PoolsRunPtr run;
     DMX_TRY(prepare_estep_pools(c, plan, false, run));
     DMX_TRY(launch_estep_pools_pass(c, *run, 2.0f));
-    return read_back_estep_pools(c, *run);
+    DMX_TRY(read_back_estep_pools(c, *run));
+    return keep_pools_run(c, *run);
 }
 
 }  // namespace dmx

@@ -27,11 +27,11 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, donor_readout
-from .ambient import (AmbientEstimate, JointAmbientPosteriors, assigned_donors, best_singlets, default_alphas, resolve_assignments,
+from .ambient import (AmbientEstimate, DeviceJointAmbientPosteriors, JointAmbientPosteriors, assigned_donors, best_singlets, default_alphas, resolve_assignments,
                       resolve_fractions, resolve_grid)
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
-from .pools import PooledPosteriors, resolve_pools
+from .pools import DevicePooledPosteriors, PooledPosteriors, resolve_pools
 
 _MOLECULE_CALL_DTYPE = [('variant_id', 'int32'), ('snp_id', 'int32'), ('compressed_cb', 'int32'),
                         ('molecule_id', 'int32'), ('p_base_wrong', 'float32'), ('p_molecule_aligned_wrong', 'float32')]
@@ -484,6 +484,29 @@ def _option_names(genotype_names, doublet_prior):
     return names
 
 
+def _release_pooled_context(ctx):
+    """close() of a DevicePooledPosteriors: the private context goes back to its pool as it came (the switch off, the slot dropped
+    with the problem)."""
+    ctx.set_keep_pooled(False)
+    release_private_context(ctx)
+
+
+def _pooled_on_device(run, barcodes, pool_names, option_names, pool_columns, pool_of_barcode):
+    """run(ctx) - pack, table and one pooled pass with nothing of the rows fetched - on a private context with the keep switch on:
+    (the pass's dict, the DevicePooledPosteriors over the slot it left)."""
+    ctx = acquire_private_context()
+    try:
+        ctx.set_keep_pooled(True)
+        out = run(ctx)
+        posteriors = DevicePooledPosteriors(ctx, barcodes, pool_names, option_names, [len(c) for c in pool_columns], pool_of_barcode,
+                                            out['row_ptr'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE',
+                                            release=_release_pooled_context)
+    except BaseException:
+        ctx.close()
+        raise
+    return out, posteriors
+
+
 class DevicePosteriors:
     """Posteriors (and logits) of one predict_posteriors / learn_genotypes call, kept on the GPU
     (`on_device=True`), with the reductions users of the reference apply to the DataFrame done there:
@@ -795,7 +818,8 @@ class Demultiplexer:
                                     barcode2pool,
                                     pool2donors,
                                     p_genotype_clip=0.01,
-                                    doublet_prior=0.35) -> PooledPosteriors:
+                                    doublet_prior=0.35,
+                                    on_device: bool = False) -> PooledPosteriors:
         """(not in the reference) predict_posteriors with every barcode scored against the donors of its own pool only - a
         lane, hashtag group or sub-experiment that holds a known subset of the donors -, all pools in one pass over one packed
         problem and one genotype table.  The frames of a pool (PooledPosteriors.to_dataframes) are, bit for bit, the rows of the
@@ -803,18 +827,26 @@ class Demultiplexer:
         :param barcode2pool: barcode -> pool name, or None for "in no pool"; every barcode of the handler has an entry
         :param pool2donors: pool name -> donor names, in any order (sorted into genotype order); at most 44 donors per pool
             with doublets, 1024 without
+        :param on_device: keep the compact logits and posteriors on the GPU and return a DevicePooledPosteriors (best options,
+            droplet calls, donor marginals and summaries, option sums and qualities are then computed there)
         ValueError: a duplicate or unknown donor, an empty pool, a barcode without an entry, an unknown pool."""
         assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
         assert 0 <= doublet_prior < 1
         pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
             genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
-        with shared_context_lock:
-            ctx = get_context()
+
+        def run(ctx, fetch=True):
             _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
             ctx.set_addition(None)
             genotype_prob = ctx.probs_from_betas(p_genotype_clip)
             assert np.isfinite(genotype_prob).all()
-            out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty)
+            return ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, fetch_logits=fetch, fetch_probs=fetch)
+
+        if on_device:
+            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, pool_names, option_names, pool_columns,
+                                     pool_of_barcode)[1]
+        with shared_context_lock:
+            out = run(get_context())
         return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                 out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
 
@@ -879,7 +911,8 @@ class Demultiplexer:
                                         p_genotype_clip=0.01,
                                         doublet_prior=0.35,
                                         barcode2pool=None,
-                                        pool2donors=None):
+                                        pool2donors=None,
+                                        on_device: bool = False):
         """(not in the reference) predict_posteriors with every option scored under the barcode's own ambient fraction: a call's
         term is q (1 - alpha_b) + ambient[v] alpha_b in place of the option's q, so a contaminated singlet - its donor plus a little
         of everybody - is not taken for a doublet.  With every fraction 0 the result is predict_posteriors' (exact mode) bit for bit.
@@ -887,6 +920,8 @@ class Demultiplexer:
             that is missing, None or NaN is scored with 0
         :param ambient: float32[n_variants] allele profile of the soup, or None: derived from the calls as estimate_ambient does
         :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
+        :param on_device: keep the compact rows on the GPU and return a DevicePooledPosteriors (without pools it holds the one
+            all-donor pool, named 'all')
         Returns (logits_df, probs_df) with predict_posteriors' index, columns and dtypes; with pools a PooledPosteriors.
         ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
         assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
@@ -900,13 +935,20 @@ class Demultiplexer:
         else:
             pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
                 genotypes, barcode_handler, doublet_prior, 'predict_posteriors_with_ambient')
-        with shared_context_lock:
-            ctx = get_context()
+
+        def run(ctx, fetch=True):
             _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
             ctx.set_addition(None)
             genotype_prob = ctx.probs_from_betas(p_genotype_clip)
             assert np.isfinite(genotype_prob).all()
-            out = ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip, ambient=ambient)
+            return ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip, ambient=ambient,
+                                     fetch_logits=fetch, fetch_probs=fetch)
+
+        if on_device:
+            names, columns = (pool_names, option_names) if pooled else (['all'], [column_names])
+            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, names, columns, pool_columns, pool_of_barcode)[1]
+        with shared_context_lock:
+            out = run(get_context())
         if pooled:
             return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                     out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
@@ -971,7 +1013,8 @@ class Demultiplexer:
                                          pool2donors=None,
                                          keep_profile=False,
                                          over_grid='max',
-                                         alpha_log_weights=None) -> JointAmbientPosteriors:
+                                         alpha_log_weights=None,
+                                         on_device: bool = False) -> JointAmbientPosteriors:
         """(not in the reference) predict_posteriors with every option - singlets and pairs - scored at its own best ambient
         fraction: a call's term is q (1 - alpha) + ambient[v] alpha, an option's logit the maximum over the grid `alphas` of its
         log-likelihood (plus the pair penalty), and the posteriors one softmax over those.  The choice between "a contaminated
@@ -988,6 +1031,9 @@ class Demultiplexer:
             finds more of the true doublets among droplets with few calls.  With alphas=[0.0] both are
             predict_posteriors'.  'marginal' keeps no profile: with keep_profile it raises.
         :param alpha_log_weights: ('marginal' only) the log of a prior over the grid, one finite value per grid value; None: flat
+        :param on_device: keep the compact rows - logits, posteriors, every option's grid point and mean fraction - on the GPU and
+            return a DeviceJointAmbientPosteriors, whose .posteriors is a DevicePooledPosteriors (without pools: one pool, 'all');
+            with keep_profile it raises
         Returns a JointAmbientPosteriors: .posteriors is (logits_df, probs_df) with predict_posteriors' index, columns and dtypes,
         with pools a PooledPosteriors; .option_alphas, .summary(); under 'marginal' also .option_alpha_means.
         ValueError: a grid value outside [0, 1], an empty grid or more than 64 values, more than 1024 options without pools,
@@ -998,6 +1044,8 @@ class Demultiplexer:
             raise ValueError("keep_profile needs over_grid='max': the marginal pass keeps no profile")
         if alpha_log_weights is not None and over_grid != 'marginal':
             raise ValueError("alpha_log_weights are the prior of over_grid='marginal'; the maximum takes none")
+        if on_device and keep_profile:
+            raise ValueError('keep_profile with on_device: the profile is not kept on the device; ask for it with on_device=False')
         assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
         assert 0 <= doublet_prior < 1
         assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
@@ -1014,18 +1062,26 @@ class Demultiplexer:
             pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
                 genotypes, barcode_handler, doublet_prior, 'predict_posteriors_joint_ambient')
             option_names = [column_names]
-        with shared_context_lock:
-            ctx = get_context()
+
+        def run(ctx, fetch=True):
             _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
             ctx.set_addition(None)
             genotype_prob = ctx.probs_from_betas(p_genotype_clip)
             assert np.isfinite(genotype_prob).all()
             if over_grid == 'marginal':
-                out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
-                                             over_grid='marginal', log_weights=alpha_log_weights)
-            else:
-                out = ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
-                                             fetch_profile=keep_profile)
+                return ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
+                                              over_grid='marginal', log_weights=alpha_log_weights, fetch_logits=fetch, fetch_probs=fetch,
+                                              fetch_alpha_index=fetch, fetch_alpha_mean=fetch)
+            return ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
+                                          fetch_profile=keep_profile, fetch_logits=fetch, fetch_probs=fetch, fetch_alpha_index=fetch)
+
+        if on_device:
+            out, posteriors = _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, pool_names if pooled else ['all'],
+                                                option_names, pool_columns, pool_of_barcode)
+            return DeviceJointAmbientPosteriors(posteriors, grid, out['ambient'], out['best_alpha_index'], over_grid=over_grid,
+                                                best_alpha_mean=out.get('best_alpha_mean'))
+        with shared_context_lock:
+            out = run(get_context())
         if pooled:
             posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
                                           out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')

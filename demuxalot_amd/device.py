@@ -856,6 +856,112 @@ class DeviceContext:
                                                ptr(out['profile'])))
         return out
 
+    # ---- pooled results kept resident (include/demux_hip_debug.h "Pooled results kept resident"; csrc/pooled_readout.hip) ----
+    def set_keep_pooled(self, keep):
+        """With True, estep_pools(), estep_ambient() and estep_ambient_grid() (not their resident / EM siblings) leave their compact
+        result in the context's pooled slot (dmx_set_keep_pooled)."""
+        check(self._lib.dmx_set_keep_pooled(self._h, int(bool(keep))))
+
+    def pooled_upload(self, n_donors, pools, pool_of_barcode, with_doublets, probs, logits=None):
+        """Fills the pooled slot from host arrays (dmx_pooled_upload): pools as estep_pools() takes them (columns below n_donors),
+        pool_of_barcode int32[B], compact float32 probs (and logits, or None).  Returns row_ptr int64[B + 1]."""
+        sizes = np.array([len(d) for d in pools], dtype=np.int64)
+        pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        donors = as_c(np.concatenate([np.asarray(d, dtype=np.int64).reshape(-1) for d in pools]) if len(pools) else [], np.int32)
+        pool_of_barcode = as_c(pool_of_barcode, np.int32)
+        n_options = sizes * (sizes + 1) // 2 if with_doublets else sizes
+        in_pool = (pool_of_barcode >= 0) & (pool_of_barcode < len(pools))  # (ids outside: the library's error)
+        row_len = np.zeros(len(pool_of_barcode), dtype=np.int64)
+        row_len[in_pool] = n_options[pool_of_barcode[in_pool]]
+        row_ptr = np.concatenate([[0], np.cumsum(row_len)]).astype(np.int64)
+        probs = as_c(probs, np.float32)
+        assert probs.shape == (int(row_ptr[-1]),), 'compact probs: row_ptr[B] values'
+        if logits is not None:
+            logits = as_c(logits, np.float32)
+            assert logits.shape == probs.shape, 'compact logits: row_ptr[B] values'
+        check(self._lib.dmx_pooled_upload(self._h, len(pool_of_barcode), int(n_donors), int(bool(with_doublets)), len(pools), ptr(pool_start),
+                                          ptr(donors), ptr(pool_of_barcode), ptr(row_ptr), ptr(logits), ptr(probs)))
+        return row_ptr
+
+    def pooled_info(self):
+        """dict of _lib.POOLED_INFO (dmx_pooled_info): present, B, n_pools, n_values, with_doublets, has_logits, has_alpha_index,
+        has_alpha_mean."""
+        info = (ctypes.c_int64 * len(_lib.POOLED_INFO))()
+        check(self._lib.dmx_pooled_info(self._h, info))
+        return dict(zip(_lib.POOLED_INFO, (int(v) for v in info)))
+
+    def pooled_release(self):
+        check(self._lib.dmx_pooled_release(self._h))
+
+    def pooled_get(self, what, b0, b1, n_values):
+        """The compact entries of barcodes [b0, b1) of 'logits' | 'probs' | 'alpha_index' | 'alpha_mean' (dmx_pooled_get); n_values:
+        row_ptr[b1] - row_ptr[b0], which the caller knows."""
+        code, dtype = _lib.POOLED_WHAT[what]
+        out = np.empty(int(n_values), dtype=dtype)
+        check(self._lib.dmx_pooled_get(self._h, code, int(b0), int(b1), ptr(out)))
+        return out
+
+    def pooled_get_pool(self, what, pool, n_barcodes, n_options):
+        """[n_barcodes, n_options] rows of one pool's barcodes, ascending (dmx_pooled_get_pool)."""
+        code, dtype = _lib.POOLED_WHAT[what]
+        out = np.empty((int(n_barcodes), int(n_options)), dtype=dtype)
+        check(self._lib.dmx_pooled_get_pool(self._h, code, int(pool), ptr(out)))
+        return out
+
+    def _pooled_staging(self, name, shape, dtype):
+        """A download target of the pooled read-outs that outlives the call.  The runtime pins the pages of a pageable download's
+        target; giving fresh arrays back to the allocator after every call made the next calls wait 10 - 30 ms each at 200 000
+        barcodes (scripts/pooled_readout_timing.py), where the same call into arrays that stay takes 0.7 ms.  The read-outs
+        therefore land here and the caller gets copies."""
+        buffers = self.__dict__.setdefault('_pooled_buffers', {})
+        held = buffers.get(name)
+        if held is None or held.shape != tuple(np.atleast_1d(shape)) or held.dtype != np.dtype(dtype):
+            held = buffers[name] = np.zeros(shape, dtype)
+        return held
+
+    def pooled_readout(self, marginals=False, masses=True):
+        """One pass over the slot's posteriors (dmx_pooled_readout): dict of singlet_mass, doublet_mass (float64[B]; None without
+        masses), best_option, best_singlet, best_pair (int32[B], pool-local, -1: none) with best_prob, best_singlet_prob,
+        best_pair_prob (float32[B]) and, with marginals=True, marg_ptr (int64[B + 1]) and donor_marginals (compact float32)."""
+        B = self.pooled_info()['B']
+        kinds = dict(singlet_mass=np.float64, doublet_mass=np.float64, best_option=np.int32, best_prob=np.float32, best_singlet=np.int32,
+                     best_singlet_prob=np.float32, best_pair=np.int32, best_pair_prob=np.float32)
+        stage = {name: None if not masses and name.endswith('_mass') else self._pooled_staging(name, B, kind) for name, kind in kinds.items()}
+        marg_ptr = marg = None
+        if marginals:
+            marg_ptr = np.empty(B + 1, np.int64)
+            check(self._lib.dmx_pooled_readout(self._h, *([None] * len(kinds)), ptr(marg_ptr), None))  # (sizes only: nothing is launched for them)
+            marg = self._pooled_staging('donor_marginals', int(marg_ptr[-1]), np.float32)
+        check(self._lib.dmx_pooled_readout(self._h, *(ptr(stage[name]) for name in kinds), None, ptr(marg)))
+        out = {name: None if held is None else held.copy() for name, held in stage.items()}
+        if marginals:
+            out['marg_ptr'], out['donor_marginals'] = marg_ptr, marg.copy()
+        return out
+
+    def pooled_top_options(self, k):
+        """(int32[B, k] pool-local options, float32[B, k]), best first (dmx_pooled_top_options)."""
+        B = self.pooled_info()['B']
+        options, probs = self._pooled_staging('top_options', (B, int(k)), np.int32), self._pooled_staging('top_probs', (B, int(k)), np.float32)
+        check(self._lib.dmx_pooled_top_options(self._h, int(k), ptr(options), ptr(probs)))
+        return options.copy(), probs.copy()
+
+    def pooled_option_sums(self, n_options_total):
+        """(float64[n_options_total] option sums, pool after pool; int64[n_pools] barcodes per pool) - dmx_pooled_option_sums."""
+        sums = np.zeros(int(n_options_total), np.float64)
+        counts = np.zeros(self.pooled_info()['n_pools'], np.int64)
+        check(self._lib.dmx_pooled_option_sums(self._h, ptr(sums), ptr(counts)))
+        return sums, counts
+
+    def pooled_allowed_mass(self, start, options):
+        """get_allowed_mass() on the slot, with pool-local options (dmx_pooled_allowed_mass)."""
+        B = self.pooled_info()['B']
+        start, options = as_c(start, np.int64), as_c(options, np.int32)
+        assert start.shape == (B + 1,), 'one start per barcode and the end'
+        assert options.ndim == 1 and len(options) >= (start[-1] if len(start) else 0), 'allowed options shorter than start[-1]'
+        mass, hit = self._pooled_staging('allowed_mass', B, np.float64), self._pooled_staging('allowed_hit', B, np.int32)
+        check(self._lib.dmx_pooled_allowed_mass(self._h, ptr(start), ptr(options), ptr(mass), ptr(hit)))
+        return mass.copy(), hit.copy()
+
     def synchronize(self):
         check(self._lib.dmx_synchronize(self._h))
 

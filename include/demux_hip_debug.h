@@ -592,6 +592,69 @@ int dmx_estep_ambient_grid_marginal(dmx_ctx *ctx, int with_doublets, int32_t n_p
                                     float *alpha_mean /* nullable, float32[row_ptr[B]] */, float *best_alpha_mean /* nullable, [B] */);
 
 /* ------------------------------------------------------------------------- *
+ * Pooled results kept resident (product API; declared here because demux_hip.h is kept to 64 entry points;
+ * csrc/pooled_readout.hip).  The context owns one "pooled slot": the compact result of a pooled pass - the pool
+ * layout, pool_of_barcode, row_ptr, the compact posteriors, the compact logits (may be absent), from the grid passes the compact
+ * alpha_index and from the marginal pass also alpha_mean, and every pool's barcodes in ascending order - on the device.  The slot is
+ * independent of the resident results of dmx_estep / dmx_em: neither touches the other, and the dense read-outs do not see it.
+ * dmx_destroy and dmx_release_problem drop it.
+ *   dmx_set_keep_pooled   keep = 1: dmx_estep_pools, dmx_estep_ambient, dmx_estep_ambient_grid and dmx_estep_ambient_grid_marginal
+ *                         leave their compact result in the slot on a successful return (default 0: nothing is kept, nothing
+ *                         changes).  The buffers are handed over from the pass's temporaries, not copied.  Every output pointer of
+ *                         those entries keeps its meaning; with NULL for logits_out / probs_out nothing of size row_ptr[B] is
+ *                         downloaded.  A kept result replaces the previous one; a failed call leaves the previous one in place.
+ *                         dmx_estep_pools_resident, dmx_estep_ambient_resident, dmx_em_pools and dmx_em_ambient never touch the slot.
+ *   dmx_pooled_upload     fills the slot from host arrays (a result saved earlier; tests).  Needs no problem on the context.  The
+ *                         pool arguments are dmx_estep_pools' (without penalties) and are refused as it refuses them, G being
+ *                         the number of table columns the donors index; probs must not be NULL when row_ptr[B] > 0.
+ *   dmx_pooled_info       info[8] = present, B, n_pools, n_values (= row_ptr[B]), with_doublets, has_logits, has_alpha_index,
+ *                         has_alpha_mean.
+ *   dmx_pooled_release    drops the slot (nothing to drop: no error).
+ *   dmx_pooled_get        entries row_ptr[b0] .. row_ptr[b1] of matrix `what` (0 logits, 1 probs: float32; 2 alpha_index: int32;
+ *                         3 alpha_mean: float32) - the rows of barcodes b0 <= b < b1, contiguous.
+ *   dmx_pooled_get_pool   the rows of one pool's barcodes, in ascending barcode order, as a dense [n_p, K_p] block of `what`
+ *                         (gathered on the device, one download).
+ * Read-outs of the slot's posteriors.  Option indices are POOL-LOCAL: for a pool of g donors option i < g is singlet i, pair
+ * (i < j) is at g + i (2g - i - 1) / 2 + (j - i - 1); K_p = g or g (g + 1) / 2 <= 1024.  The order of additions is the contract.
+ *   dmx_pooled_readout    one pass; every output nullable and B long but donor_marginals:
+ *                         singlet_mass / doublet_mass   float64: the row's singlet / pair entries widened and added sequentially
+ *                             in ascending option order - dmx_estep_pools' own doublet_mass, bit for bit (0 without doublets);
+ *                         best_option / best_singlet / best_pair with their posteriors: the first maximum over the whole row /
+ *                             its singlets / its pairs (ties to the lower index, NaN never wins); -1 and NaN where there is none;
+ *                         donor_marginals   compact float32: barcode b owns entries marg_ptr[b] .. marg_ptr[b + 1), g_p of them
+ *                             (marg_ptr_out int64[B + 1], nullable); entry i is singlet i, then pairs (0, i) .. (i-1, i), then
+ *                             (i, i+1) .. (i, g-1), widened to float64, added in that order and rounded once.  NULL: neither
+ *                             computed nor allocated.
+ *                         A barcode in no pool gets -1 / NaN everywhere (masses included) and no marginal entries.
+ *   dmx_pooled_top_options  the k (1..4) best options per barcode, best first, as dmx_get_top_options: int32 / float32 [B, k],
+ *                         -1 / NaN where the row is shorter than k or the barcode is in no pool.
+ *   dmx_pooled_option_sums  sums float64[opt_ptr[P]] (pool after pool, K_p entries each), n_barcodes int64[P]; either nullable.
+ *                         Per pool and option the float64 sum over the pool's n_p barcodes in ascending order, in a fixed order:
+ *                         per = ceil(n_p / 512); slab j = list positions [j per, min((j + 1) per, n_p)) added sequentially; then
+ *                         the 512 slab sums in slab order (dmx_get_option_sums' rule).  An empty pool gives zeros.
+ *   dmx_pooled_allowed_mass  dmx_get_allowed_mass with pool-local options.  DMX_ERR_INVALID before anything is launched:
+ *                         allowed_start[0] != 0, a decreasing start, an option outside [0, K_p(b)), a non-empty list for a barcode
+ *                         in no pool - which gets mass NaN and best_is_allowed 0.
+ * Every entry but dmx_set_keep_pooled, dmx_pooled_upload, dmx_pooled_info and dmx_pooled_release returns DMX_ERR_INVALID with a
+ * call-order message while the slot is empty.
+ * ------------------------------------------------------------------------- */
+int dmx_set_keep_pooled(dmx_ctx *ctx, int keep);
+int dmx_pooled_upload(dmx_ctx *ctx, int64_t B, int32_t G, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                      const int32_t *pool_donors, const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                      const float *logits /* nullable */, const float *probs /* float32[row_ptr[B]] */);
+int dmx_pooled_info(dmx_ctx *ctx, int64_t info[8]);
+int dmx_pooled_release(dmx_ctx *ctx);
+int dmx_pooled_get(dmx_ctx *ctx, int what, int64_t b0, int64_t b1, void *out);
+int dmx_pooled_get_pool(dmx_ctx *ctx, int what, int32_t pool, void *out /* [n_p, K_p] */);
+int dmx_pooled_readout(dmx_ctx *ctx, double *singlet_mass, double *doublet_mass, int32_t *best_option, float *best_prob,
+                       int32_t *best_singlet, float *best_singlet_prob, int32_t *best_pair, float *best_pair_prob,
+                       int64_t *marg_ptr_out /* [B+1] */, float *donor_marginals /* float32[marg_ptr[B]] */);
+int dmx_pooled_top_options(dmx_ctx *ctx, int32_t k, int32_t *options, float *probs);
+int dmx_pooled_option_sums(dmx_ctx *ctx, double *sums /* [opt_ptr[P]] */, int64_t *n_barcodes /* [P] */);
+int dmx_pooled_allowed_mass(dmx_ctx *ctx, const int64_t *allowed_start, const int32_t *allowed_options, double *mass,
+                            int32_t *best_is_allowed);
+
+/* ------------------------------------------------------------------------- *
  * Learning under per-barcode ambient RNA fractions (product API; csrc/mstep_ambient.hip, csrc/estep_ambient.hip).
  * dmx_em_pools' loop with two changes per iteration: the pooled row is dmx_estep_ambient's, and every call's contribution to the
  * M-step is weighted by the probability that the call came from the donor and not from the soup.  For variant v, donor column g and
