@@ -907,28 +907,40 @@ static int refuse(const char *who, int status, const char *what, long long at, l
     return fail(status, "%s: %s%s%s", who, number, what, index);
 }
 
-// what the device half reads of a call that check() has accepted: the options laid out, the caller's arrays and outputs
-static void fill_pools_plan(const dmx::pplan::Pools &pools, float *logits_out, float *probs_out, int32_t *best_option, float *best_prob,
-                            double *doublet_mass, dmx::PoolsPlan &plan)
+// the caller's result arrays of a pooled entry, in the order every entry of the family takes them (PoolsPlan says which are nullable)
+struct PoolsOutputs {
+    float *logits, *probs;
+    int32_t *best_option;
+    float *best_prob;
+    double *doublet_mass;
+};
+
+// What every pooled entry does with the verdict of its plan header (pools_plan.h, ambient_scoring_plan.h, ambient_grid_plan.h,
+// ambient_learning_plan.h): a refusal becomes the entry's error; what was accepted is laid out for the device half - the options,
+// the caller's arrays and outputs.
+static int accept_pools(const char *who, const dmx::pplan::Verdict &verdict, const dmx::pplan::Pools &pools, const PoolsOutputs &out,
+                        dmx::PoolsPlan &plan)
 {
+    if (verdict.status != dmx::pplan::OK) return refuse(who, verdict.status, verdict.what, verdict.at, verdict.value);
     plan.with_doublets = pools.with_doublets != 0;
     plan.n_pools = pools.n_pools;
     dmx::pplan::layout(pools, plan.opt_ptr, plan.opts, plan.pool_size);
     plan.pair_penalty = pools.pair_penalty;
     plan.pool_of_barcode = pools.pool_of_barcode;
     plan.row_ptr = pools.row_ptr;
-    plan.logits_out = logits_out;
-    plan.probs_out = probs_out;
-    plan.best_option = best_option;
-    plan.best_prob = best_prob;
-    plan.doublet_mass = doublet_mass;
+    plan.logits_out = out.logits;
+    plan.probs_out = out.probs;
+    plan.best_option = out.best_option;
+    plan.best_prob = out.best_prob;
+    plan.doublet_mass = out.doublet_mass;
+    return 0;
 }
 
 // The pooled E-step (estep_pools.hip).  Everything is checked on the host (pools_plan.h) before anything is uploaded or launched: one
 // function for dmx_estep_pools, dmx_estep_pools_resident and dmx_em_pools.  resident: the entry leaves the dense singlet posteriors in
 // the context (single GPU, no communicator).
-static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_betas, const dmx::pplan::Pools &pools, float *logits_out, float *probs_out,
-                      int32_t *best_option, float *best_prob, double *doublet_mass, dmx::PoolsPlan &plan)
+static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_betas, const dmx::pplan::Pools &pools, const PoolsOutputs &out,
+                      dmx::PoolsPlan &plan)
 {
     if (need_betas) {
         if (!(c->have_problem && c->have_betas)) return fail(DMX_ERR_INVALID, "call order: dmx_set_problem + dmx_set_betas before %s", who);
@@ -937,10 +949,14 @@ static int plan_pools(dmx_ctx *c, const char *who, bool resident, bool need_beta
     }
     if (c->nranks > 1) return fail(DMX_ERR_UNSUPPORTED, "%s: single GPU only", who);
     if (resident && c->attached()) return fail(DMX_ERR_UNSUPPORTED, "%s: a context with a communicator attached is not supported", who);
-    const dmx::pplan::Verdict verdict = dmx::pplan::check(c->G, c->B, pools);
-    if (verdict.status != dmx::pplan::OK) return refuse(who, verdict.status, verdict.what, verdict.at, verdict.value);
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
-    return 0;
+    return accept_pools(who, dmx::pplan::check(c->G, c->B, pools), pools, out, plan);
+}
+
+// what the plan headers of the entries under ambient fractions read of the context (ambient_plan.h: Facts).  have_table: what the
+// entry computes from - the genotype probabilities, or for dmx_em_ambient, whose P-step forms them, the betas
+static dmx::aplan::Facts ambient_facts(const dmx_ctx *c, bool have_table)
+{
+    return {c->have_problem, have_table, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr, c->B, c->V, c->G};
 }
 
 // what a dense pooled E-step writes into: the context's own result arrays with K = G, the [B, G] posteriors zeroed once - the kernel
@@ -962,7 +978,7 @@ int dmx_estep_pools(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
     DMX_TRY(plan_pools(c, "dmx_estep_pools", false, false, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
-                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+                       {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     return dmx::run_estep_pools(c, plan);
 }
 
@@ -973,7 +989,7 @@ int dmx_estep_pools_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, con
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
     DMX_TRY(plan_pools(c, "dmx_estep_pools_resident", true, false, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
-                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+                       {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     DMX_TRY(begin_dense_pools(c));
     dmx::PoolsRunPtr run;
     DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
@@ -990,9 +1006,7 @@ int dmx_ambient_profile(dmx_ctx *c, float lo, float hi, int32_t n_alphas, const 
     static_assert(ap::OK == DMX_OK && ap::INVALID == DMX_ERR_INVALID && ap::UNSUPPORTED == DMX_ERR_UNSUPPORTED, "ambient_plan.h restates the codes");
     static_assert(sizeof(int) == sizeof(int32_t), "");
     DMX_TRY(bind(c));
-    const ap::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
-                          c->B,           c->V,          c->G};
-    const ap::Verdict verdict = ap::check(facts, n_alphas, alphas, (const int *)donor1, (const int *)donor2, ambient);
+    const ap::Verdict verdict = ap::check(ambient_facts(c, c->have_probs), n_alphas, alphas, (const int *)donor1, (const int *)donor2, ambient);
     if (verdict.status != ap::OK) return refuse("dmx_ambient_profile", verdict.status, verdict.what, verdict.at);
     const dmx::AmbientPlan plan{lo, hi, (int)n_alphas, alphas, donor1, donor2, ambient, loglik, best, ll_best, ll_zero, ambient_out};
     return dmx::run_ambient_profile(c, plan);
@@ -1007,13 +1021,10 @@ int dmx_estep_ambient(dmx_ctx *c, int with_doublets, int32_t n_pools, const int6
 {
     namespace sp = dmx::asplan;
     DMX_TRY(bind(c));
-    const sp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
-                          c->B,           c->V,          c->G};
     const sp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
-    const sp::Verdict verdict = sp::check(facts, pools, alpha, ambient);
-    if (verdict.status != sp::OK) return refuse("dmx_estep_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    DMX_TRY(accept_pools("dmx_estep_ambient", sp::check(ambient_facts(c, c->have_probs), pools, alpha, ambient), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out};
     return dmx::run_estep_ambient(c, plan, scoring);
 }
@@ -1027,13 +1038,10 @@ int dmx_estep_ambient_grid(dmx_ctx *c, int with_doublets, int32_t n_pools, const
 {
     namespace gp = dmx::agplan;
     DMX_TRY(bind(c));
-    const gp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
-                          c->B,           c->V,          c->G};
     const gp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
-    const gp::Verdict verdict = gp::check(facts, pools, n_alphas, alphas, ambient);
-    if (verdict.status != gp::OK) return refuse("dmx_estep_ambient_grid", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    DMX_TRY(accept_pools("dmx_estep_ambient_grid", gp::check(ambient_facts(c, c->have_probs), pools, n_alphas, alphas, ambient), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, profile_out,
                                           false, nullptr, nullptr, nullptr};
     return dmx::run_estep_ambient_grid(c, plan, scoring);
@@ -1049,13 +1057,11 @@ int dmx_estep_ambient_grid_marginal(dmx_ctx *c, int with_doublets, int32_t n_poo
 {
     namespace gp = dmx::agplan;
     DMX_TRY(bind(c));
-    const gp::Facts facts{c->have_problem, c->have_probs, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr,
-                          c->B,           c->V,          c->G};
     const gp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
-    const gp::Verdict verdict = gp::check_marginal(facts, pools, n_alphas, alphas, ambient, log_weights);
-    if (verdict.status != gp::OK) return refuse("dmx_estep_ambient_grid_marginal", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    DMX_TRY(accept_pools("dmx_estep_ambient_grid_marginal",
+                         gp::check_marginal(ambient_facts(c, c->have_probs), pools, n_alphas, alphas, ambient, log_weights), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, nullptr,
                                           true, log_weights, alpha_mean, best_alpha_mean};
     return dmx::run_estep_ambient_grid(c, plan, scoring);
@@ -1072,6 +1078,17 @@ int dmx_mstep(dmx_ctx *c, float power, float *addition_out)
     return 0;
 }
 
+// demux.py:86: an EM call starts from a zero addition, which no kept state of an earlier M-step describes
+static int begin_em_additions(dmx_ctx *c)
+{
+    const size_t vg = (size_t)c->V * c->G;
+    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));
+    c->incr_valid = false;
+    c->add_is_zero = true;
+    c->add_partial = false;
+    return 0;
+}
+
 int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, const float *penalties,
            const void *prior_logits, int prior_dtype, float power, float *logits_out, float *probs_out,
            float *addition_out)
@@ -1082,11 +1099,7 @@ int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, 
     if (!penalties) return fail(DMX_ERR_INVALID, "null penalties");
     DMX_TRY(ensure_options(c, with_doublets, penalties));
     DMX_TRY(upload_prior_logits(c, prior_logits, prior_dtype));
-    const size_t vg = (size_t)c->V * c->G;
-    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));  // demux.py:86
-    c->incr_valid = false;
-    c->add_is_zero = true;
-    c->add_partial = false;
+    DMX_TRY(begin_em_additions(c));
     const bool keep_last = c->logits_needed || logits_out != nullptr;  // (dmx_set_logits_needed)
     for (int it = 0; it < n_iterations; it++) {
         const bool kept = it + 1 == n_iterations && keep_last;  // somebody can read this E-step's logits
@@ -1103,9 +1116,23 @@ int dmx_em(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, 
     DMX_TRY(copy_out(c, logits_out, c->d_logits.p, bk));
     DMX_TRY(copy_out(c, probs_out, c->d_post.p, bk));
     DMX_TRY(ensure_full_addition(c));  // (collective when sliced) the slices of the last M-step, on every rank
-    DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// The loop of an EM call whose E-step is a dense pooled pass (dmx_em_pools, dmx_em_ambient): P-step, estep_pass(), and between two
+// iterations mstep(M-steps the call still has to do, this one included) - the M-step after the last yield is dead; then the addition
+// the last E-step used goes to the caller.  The caller has begun the dense pass and the additions and prepared its run.
+static int run_dense_em(dmx_ctx *c, int n_iterations, float lo, float hi, float *addition_out, const std::function<int()> &estep_pass,
+                        const std::function<int(int)> &mstep)
+{
+    for (int it = 0; it < n_iterations; it++) {
+        DMX_TRY(run_pstep(c, lo, hi, true, false));
+        DMX_TRY(estep_pass());
+        if (it + 1 < n_iterations) DMX_TRY(mstep(n_iterations - 1 - it));
+    }
+    return copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G);
 }
 
 // dmx_em with the pooled E-step in place of the full-table one: P-step, dense pooled E-step, M-step, all on the device; the host
@@ -1117,37 +1144,25 @@ int dmx_em_pools(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doub
     DMX_TRY(bind(c));
     dmx::PoolsPlan plan;
     DMX_TRY(plan_pools(c, "dmx_em_pools", true, true, {with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr},
-                       logits_out, probs_out, best_option, best_prob, doublet_mass, plan));
+                       {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     if (n_iterations < 1) return fail(DMX_ERR_INVALID, "dmx_em_pools: n_iterations must be >= 1");
     DMX_TRY(begin_dense_pools(c));
-    const size_t vg = (size_t)c->V * c->G;
-    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));  // demux.py:86
-    c->incr_valid = false;
-    c->add_is_zero = true;
-    c->add_partial = false;
+    DMX_TRY(begin_em_additions(c));
     dmx::PoolsRunPtr run;
     DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
-    for (int it = 0; it < n_iterations; it++) {
-        DMX_TRY(run_pstep(c, lo, hi, true, false));
-        DMX_TRY(dmx::launch_estep_pools_pass(c, *run, power));
-        if (it + 1 < n_iterations) {  // the M-step after the last yield is dead
-            c->msteps_ahead = n_iterations - 1 - it;
+    DMX_TRY(run_dense_em(
+        c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_pools_pass(c, *run, power); },
+        [&](int msteps_ahead) {  // run_mstep's plan (mstep_plan.h) weighs the M-steps still to come when it chooses a form that pays back
+            c->msteps_ahead = msteps_ahead;
             const int rc_m = run_mstep(c, power);
             c->msteps_ahead = 0;
-            if (rc_m) return rc_m;
-        }
-    }
-    DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
+            return rc_m;
+        }));
     return dmx::read_back_estep_pools(c, *run);
 }
 
-// Learning under per-barcode ambient fractions (estep_ambient.hip: the dense form; mstep_ambient.hip).  ambient_learning_plan.h refuses,
-// on the host, before anything is uploaded or launched.
-static dmx::alplan::Facts ambient_learning_facts(const dmx_ctx *c, bool have_table)
-{
-    return {c->have_problem, have_table, c->attached(), c->nranks, !c->sliced && c->prob_rows == c->V && c->d_prow.p == nullptr, c->B, c->V, c->G};
-}
-
+// Learning under per-barcode ambient fractions (estep_ambient.hip: the dense form; mstep_ambient.hip).  ambient_scoring_plan.h and
+// ambient_learning_plan.h refuse, on the host, before anything is uploaded or launched.
 int dmx_estep_ambient_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
                                const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
                                float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, float lo, float hi,
@@ -1156,10 +1171,9 @@ int dmx_estep_ambient_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, c
     namespace sp = dmx::asplan;
     DMX_TRY(bind(c));
     const sp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
-    const sp::Verdict verdict = sp::check(ambient_learning_facts(c, c->have_probs), pools, alpha, ambient);
-    if (verdict.status != sp::OK) return refuse("dmx_estep_ambient_resident", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    DMX_TRY(accept_pools("dmx_estep_ambient_resident", sp::check(ambient_facts(c, c->have_probs), pools, alpha, ambient), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out, "dmx_estep_ambient_resident"};
     DMX_TRY(begin_dense_pools(c));
     dmx::AmbientRunPtr run;
@@ -1172,7 +1186,7 @@ int dmx_mstep_ambient(dmx_ctx *c, float power, const float *alpha, const float *
 {
     namespace lp = dmx::alplan;
     DMX_TRY(bind(c));
-    const lp::Verdict verdict = lp::check_mstep(ambient_learning_facts(c, c->have_probs), c->have_post, power, alpha, ambient);
+    const lp::Verdict verdict = lp::check_mstep(ambient_facts(c, c->have_probs), c->have_post, power, alpha, ambient);
     if (verdict.status != lp::OK) return refuse("dmx_mstep_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
     DMX_TRY(dmx::run_mstep_ambient_from_host(c, power, alpha, ambient, lo, hi));
     DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
@@ -1190,26 +1204,19 @@ int dmx_em_ambient(dmx_ctx *c, int n_iterations, float lo, float hi, int with_do
     namespace lp = dmx::alplan;
     DMX_TRY(bind(c));
     const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
-    const lp::Verdict verdict = lp::check_em(ambient_learning_facts(c, c->have_betas), pools, n_iterations, power, alpha, ambient);
-    if (verdict.status != lp::OK) return refuse("dmx_em_ambient", verdict.status, verdict.what, verdict.at, verdict.value);
     dmx::PoolsPlan plan;
-    fill_pools_plan(pools, logits_out, probs_out, best_option, best_prob, doublet_mass, plan);
+    DMX_TRY(accept_pools("dmx_em_ambient", lp::check_em(ambient_facts(c, c->have_betas), pools, n_iterations, power, alpha, ambient), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
     const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out, "dmx_em_ambient"};
     DMX_TRY(begin_dense_pools(c));
-    const size_t vg = (size_t)c->V * c->G;
-    HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));  // demux.py:86
-    c->incr_valid = false;
-    c->add_is_zero = true;
-    c->add_partial = false;
+    DMX_TRY(begin_em_additions(c));
     dmx::AmbientRunPtr run;
     DMX_TRY(dmx::prepare_estep_ambient(c, plan, scoring, true, run));
-    for (int it = 0; it < n_iterations; it++) {
-        DMX_TRY(run_pstep(c, lo, hi, true, false));
-        DMX_TRY(dmx::launch_estep_ambient_pass(c, *run, power));
-        if (it + 1 < n_iterations)  // the M-step after the last yield is dead
-            DMX_TRY(dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)));
-    }
-    DMX_TRY(copy_out(c, addition_out, c->d_add.p, vg));
+    // msteps_ahead is not set around this M-step: run_mstep_ambient (mstep_ambient.hip) has one form, the float64 sums, asks no plan of
+    // mstep_plan.h and never consults it
+    DMX_TRY(run_dense_em(
+        c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_ambient_pass(c, *run, power); },
+        [&](int) { return dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)); }));
     return dmx::read_back_estep_ambient(c, *run);
 }
 

@@ -30,6 +30,8 @@ struct SoupTermArgs {
     float *soup_term;           // [2 n_pairs]
 };
 hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a);
+// the block over the context's records and the pools of `view`; device pointers: the fractions [B], the profile [V + 1], the stream
+SoupTermArgs soup_term_args(const dmx_ctx *c, const PoolsLaunchView &view, const float *d_alpha, const float *d_soup, float *d_terms);
 // dense: the form that also leaves the singlet posteriors in a.pools.dense (learning under ambient fractions: the M-step's input)
 hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs, bool dense = false);
 

@@ -131,6 +131,23 @@ hipError_t launch_soup_terms(hipStream_t st, const SoupTermArgs &a)
     return hipGetLastError();
 }
 
+SoupTermArgs soup_term_args(const dmx_ctx *c, const PoolsLaunchView &view, const float *d_alpha, const float *d_soup, float *d_terms)
+{
+    SoupTermArgs t = {};
+    t.pair_ptr = c->d_pair_ptr.p;
+    t.pairs = c->d_call_pairs.p;
+    t.order = c->d_bc_order.p;
+    t.B = c->B;
+    t.pool_of = view.args.pool_of;
+    t.alpha = d_alpha;
+    t.ambient = d_soup;
+    const aplan::RowDivide rows = aplan::row_divide((unsigned)c->G * 4u);
+    t.row_shift = rows.shift;
+    t.row_inverse = rows.inverse;
+    t.soup_term = d_terms;
+    return t;
+}
+
 hipError_t launch_estep_ambient(hipStream_t st, const AmbientEstepArgs &a, int slots, bool pairs, bool dense)
 {
     if (a.pools.n_list == 0) return hipSuccess;
@@ -170,18 +187,7 @@ int prepare_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScorin
     DMX_TRY(upload(r.sc, &r.d_alpha, scoring.alpha, (size_t)B, st));
     DMX_TRY(r.sc.get(&d_terms, 2 * (size_t)c->n_pairs));  // 4 bytes per padded call
 
-    SoupTermArgs &t = r.t;
-    t.pair_ptr = c->d_pair_ptr.p;
-    t.pairs = c->d_call_pairs.p;
-    t.order = c->d_bc_order.p;
-    t.B = B;
-    t.pool_of = view.args.pool_of;
-    t.alpha = r.d_alpha;
-    t.ambient = r.d_soup;
-    const aplan::RowDivide rows = aplan::row_divide((unsigned)c->G * 4u);
-    t.row_shift = rows.shift;
-    t.row_inverse = rows.inverse;
-    t.soup_term = d_terms;
+    r.t = soup_term_args(c, view, r.d_alpha, r.d_soup, d_terms);
 
     r.a.pools = view.args;
     r.a.pools.dense = nullptr;

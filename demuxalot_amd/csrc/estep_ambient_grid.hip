@@ -367,18 +367,7 @@ int run_estep_ambient_grid(dmx_ctx *c, const PoolsPlan &plan, const AmbientGridS
     }
 
     // the stream of ambient[v] beside the records: dmx_estep_ambient's prologue with a fraction of exactly 1
-    SoupTermArgs t = {};
-    t.pair_ptr = c->d_pair_ptr.p;
-    t.pairs = c->d_call_pairs.p;
-    t.order = c->d_bc_order.p;
-    t.B = B;
-    t.pool_of = view.args.pool_of;
-    t.alpha = d_ones;
-    t.ambient = d_soup;
-    const aplan::RowDivide rows = aplan::row_divide((unsigned)c->G * 4u);
-    t.row_shift = rows.shift;
-    t.row_inverse = rows.inverse;
-    t.soup_term = d_terms;
+    const SoupTermArgs t = soup_term_args(c, view, d_ones, d_soup, d_terms);
 
     AmbientGridArgs a = {};
     a.pools = view.args;

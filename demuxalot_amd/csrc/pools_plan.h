@@ -1,7 +1,7 @@
 // pools_plan.h -- what the pooled entries (dmx_estep_pools, dmx_estep_pools_resident, dmx_em_pools, dmx_estep_ambient)
 // refuse of their pool arguments and how they lay a pool's options out, as pure functions of plain values.  Host only: nothing of
-// HIP, nothing of dmx_ctx.  dmx_steps.cpp: plan_pools asks check() before anything is uploaded or launched and layout() for what it
-// has accepted; ambient_scoring_plan.h puts its own refusals around the same check(); tests/pools_plan_check.cpp walks both on the CPU.
+// HIP, nothing of dmx_ctx.  dmx_steps.cpp: plan_pools asks check() before anything is uploaded or launched, accept_pools layout() for
+// what was accepted; ambient_scoring_plan.h puts its own refusals around the same check(); tests/pools_plan_check.cpp walks both on the CPU.
 #pragma once
 #include <cstdint>
 #include <vector>

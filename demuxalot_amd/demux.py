@@ -20,8 +20,9 @@ What runs where
               calls and the float64 M-step that follows it                   -> demux.py:204-244
 There is no CPU fallback for the GPU steps.
 """
+import contextlib
 import os
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Tuple
 
 import numpy as np
 import pandas as pd
@@ -491,19 +492,97 @@ def _release_pooled_context(ctx):
     release_private_context(ctx)
 
 
-def _pooled_on_device(run, barcodes, pool_names, option_names, pool_columns, pool_of_barcode):
-    """run(ctx) - pack, table and one pooled pass with nothing of the rows fetched - on a private context with the keep switch on:
-    (the pass's dict, the DevicePooledPosteriors over the slot it left)."""
+@contextlib.contextmanager
+def _generator_context():
+    """The private context of a staged generator, for the generator's life: it goes back to its pool when the generator ends or
+    its consumer stops early (GeneratorExit: nothing wrong with the context), and as failed on any other exception."""
     ctx = acquire_private_context()
     try:
-        ctx.set_keep_pooled(True)
-        out = run(ctx)
-        posteriors = DevicePooledPosteriors(ctx, barcodes, pool_names, option_names, [len(c) for c in pool_columns], pool_of_barcode,
-                                            out['row_ptr'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE',
-                                            release=_release_pooled_context)
+        yield ctx
+    except BaseException as error:
+        release_private_context(ctx, failed=not isinstance(error, GeneratorExit))
+        raise
+    release_private_context(ctx)
+
+
+@contextlib.contextmanager
+def _handed_over_context():
+    """A private context that the result of the call keeps (on_device=True): closed when the call fails, left open when it succeeds -
+    the result object gives it back."""
+    ctx = acquire_private_context()
+    try:
+        yield ctx
     except BaseException:
         ctx.close()
         raise
+
+
+class _PoolSetup(NamedTuple):
+    """What a pooled pass and the framing of its result need to know of the pools: one description for "pools given" and for the one
+    pool of everybody that stands in without them."""
+    pooled: bool                  # the caller gave pools: the result is a PooledPosteriors; False: frames over the one pool
+    pool_names: list              # ['all'] without pools
+    pool_columns: list            # per pool the ascending table columns of its donors
+    pool_of_barcode: np.ndarray   # int32[B], -1: in no pool
+    option_names: list            # per pool the names of its options
+    pair_penalty: np.ndarray      # float32[n_pools]: the reference's bonus for the pool's genotype list (demux.py:164-169: the prior
+                                  # doublet share is doublet_prior inside every pool), 0.0 for a pool of one donor
+
+
+def _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, who):
+    """The _PoolSetup of an entry point.  With barcode2pool / pool2donors: the pools as resolve_pools reads them (its ValueErrors).
+    Without them: one pool that scores every barcode against all donors with the reference's penalties; `who` names the entry in the
+    ValueError for more options than one pool holds.  who=None: an entry that takes pools only."""
+    names = list(genotypes.genotype_names)
+    pooled = who is None or barcode2pool is not None
+    if pooled:
+        pool_names, pool_columns, pool_of_barcode = resolve_pools(names, barcode_handler.ordered_barcodes, barcode2pool, pool2donors)
+    else:
+        G = genotypes.n_genotypes
+        n_options = G * (G + 1) // 2 if doublet_prior != 0 else G
+        if n_options > 1024:
+            raise ValueError(f'{who}: {G} donors make {n_options} options, more than the 1024 one pool can hold (44 donors with doublets); '
+                             'give every barcode a pool of its own donors with barcode2pool / pool2donors')
+        pool_names, pool_columns = ['all'], [np.arange(G, dtype=np.int64)]
+        pool_of_barcode = np.zeros(barcode_handler.n_barcodes, dtype=np.int32)
+    option_names = [_option_names([names[g] for g in columns], doublet_prior) for columns in pool_columns]
+    pair_penalty = np.array([Demultiplexer._doublet_penalties(len(columns), doublet_prior)[-1] if len(columns) > 1 else 0.0
+                             for columns in pool_columns], dtype=np.float32)
+    return _PoolSetup(pooled, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty)
+
+
+def _framed_posteriors(setup, barcode_handler, out, index_name):
+    """The result of a pooled pass (its dict `out`) as the entry points return it: with pools a PooledPosteriors; without, the frames
+    of the one pool with predict_posteriors' index and columns - (logits_df, probs_df), or probs_df alone when the logits were not
+    fetched.  index_name: the frames' (a PooledPosteriors names its own 'BARCODE')."""
+    if setup.pooled:
+        return PooledPosteriors(barcode_handler.ordered_barcodes, setup.pool_names, setup.option_names, setup.pool_of_barcode, out['row_ptr'],
+                                out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
+    columns = setup.option_names[0]
+    shape = (barcode_handler.n_barcodes, len(columns))
+    frames = tuple(pd.DataFrame(data=out[what].reshape(shape), index=_barcode_index(barcode_handler, index_name), columns=columns)
+                   for what in ('logits', 'probs') if out[what] is not None)
+    return frames if len(frames) == 2 else frames[0]
+
+
+def _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, n_barcodes, p_genotype_clip):
+    """What every one-pass entry does before its pass: the calls packed on the context (prior betas without the data term), no
+    addition, the genotype table of the P-step - which must be finite."""
+    _pack_on_device(chromosome2compressed_snp_calls, genotypes, n_barcodes, False, fetch_betas=False, ctx=ctx)
+    ctx.set_addition(None)
+    genotype_prob = ctx.probs_from_betas(p_genotype_clip)
+    assert np.isfinite(genotype_prob).all()
+
+
+def _pooled_on_device(run, barcode_handler, setup):
+    """run(ctx) - pack, table and one pooled pass with nothing of the rows fetched - on a private context with the keep switch on:
+    (the pass's dict, the DevicePooledPosteriors over the slot it left)."""
+    with _handed_over_context() as ctx:
+        ctx.set_keep_pooled(True)
+        out = run(ctx)
+        posteriors = DevicePooledPosteriors(ctx, barcode_handler.ordered_barcodes, setup.pool_names, setup.option_names,
+                                            [len(c) for c in setup.pool_columns], setup.pool_of_barcode, out['row_ptr'], out['best_option'],
+                                            out['best_prob'], out['doublet_mass'], index_name='BARCODE', release=_release_pooled_context)
     return out, posteriors
 
 
@@ -675,17 +754,13 @@ class Demultiplexer:
                 p_genotype_clip=p_genotype_clip, doublet_prior=doublet_prior, barcode_prior_logits=barcode_prior_logits)
             return genotypes._with_betas(genotypes.get_betas() + last['genotype_addition']), probs_df
         if on_device:
-            ctx = acquire_private_context()
-            try:
+            with _handed_over_context() as ctx:
                 _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
                                 fetch_betas=False, ctx=ctx)
                 ctx.em(n_iterations, p_genotype_clip, penalties, with_doublets=doublet_prior != 0,
                        prior_logits=barcode_prior_logits, contribution_power=Demultiplexer.contribution_power,
                        fetch_logits=False, fetch_probs=False, fetch_addition=False)
                 learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
-            except BaseException:
-                ctx.close()
-                raise
             learnt_genotypes = genotypes._with_betas(learnt_betas, _take=True)
             return learnt_genotypes, DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names, n_donors=n_genotypes)
         with shared_context_lock:
@@ -725,8 +800,7 @@ class Demultiplexer:
             assert barcode_prior_logits.shape == (barcode_handler.n_barcodes, len(penalties)), 'wrong shape of priors'
         aggregate = bool(Demultiplexer.aggregate_on_snps)  # read once, like the other class-level knobs of a run
 
-        ctx = acquire_private_context()
-        try:
+        with _generator_context() as ctx:
             ctx.set_keep_molecule_calls(aggregate)
             _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes,
                                                 True, ctx=ctx)
@@ -756,14 +830,6 @@ class Demultiplexer:
                     'genotype_addition': genotype_addition,
                 }
                 genotype_addition = ctx.mstep(Demultiplexer.contribution_power)
-        except GeneratorExit:  # the consumer stopped early: nothing wrong with the context
-            release_private_context(ctx)
-            raise
-        except BaseException:
-            release_private_context(ctx, failed=True)
-            raise
-        else:
-            release_private_context(ctx)
 
     @staticmethod
     def predict_posteriors(chromosome2compressed_snp_calls,
@@ -782,26 +848,18 @@ class Demultiplexer:
         assert not (aggregate and on_device), 'on_device results are float32; aggregate_on_snps yields float64 posteriors'
 
         def run(ctx, fetch):
-            ctx.set_keep_molecule_calls(aggregate)
+            ctx.set_keep_molecule_calls(aggregate)  # (read by the pack alone)
             try:
-                _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False,
-                                fetch_betas=False, ctx=ctx)
+                _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
             finally:
                 ctx.set_keep_molecule_calls(False)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
             if aggregate:  # demux.py:204-244
                 return ctx.estep_snp(doublet_prior != 0, Demultiplexer.compensation_during_computing_barcode_logits)
             return ctx.estep(penalties, with_doublets=doublet_prior != 0, fetch_logits=fetch, fetch_probs=fetch)
 
         if on_device:
-            ctx = acquire_private_context()
-            try:
+            with _handed_over_context() as ctx:
                 run(ctx, False)
-            except BaseException:
-                ctx.close()
-                raise
             return DevicePosteriors(ctx, barcode_handler.ordered_barcodes, column_names, index_name='BARCODE',
                                     n_donors=genotypes.n_genotypes)
         with shared_context_lock:
@@ -832,23 +890,18 @@ class Demultiplexer:
         ValueError: a duplicate or unknown donor, an empty pool, a barcode without an entry, an unknown pool."""
         assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
         assert 0 <= doublet_prior < 1
-        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, None)
 
         def run(ctx, fetch=True):
-            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
-            return ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, fetch_logits=fetch, fetch_probs=fetch)
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
+            return ctx.estep_pools(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, fetch_logits=fetch,
+                                   fetch_probs=fetch)
 
         if on_device:
-            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, pool_names, option_names, pool_columns,
-                                     pool_of_barcode)[1]
+            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler, setup)[1]
         with shared_context_lock:
             out = run(get_context())
-        return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
-                                out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
+        return _framed_posteriors(setup, barcode_handler, out, 'BARCODE')
 
     @staticmethod
     def estimate_ambient(chromosome2compressed_snp_calls,
@@ -880,27 +933,19 @@ class Demultiplexer:
         alphas = default_alphas() if alphas is None else np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
         with shared_context_lock:
             ctx = get_context()
-            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
             out = ctx.ambient_profile(donor1, donor2, alphas, p_genotype_clip, ambient=ambient, fetch_profile=keep_profile)
         return AmbientEstimate(barcode_handler.ordered_barcodes, option_names, columns, alphas, out['ambient'], out['best'], out['ll_best'],
                                out['ll_zero'], loglik=out['loglik'], index_name='BARCODE')
 
     @staticmethod
-    def _one_pool_of_everybody(genotypes, barcode_handler, doublet_prior, who):
-        """The arguments of a pooled pass that scores every barcode against all donors with the reference's penalties:
-        (pool columns, pool_of_barcode, pair_penalty, option names)."""
-        G = genotypes.n_genotypes
-        n_options = G * (G + 1) // 2 if doublet_prior != 0 else G
-        if n_options > 1024:
-            raise ValueError(f'{who}: {G} donors make {n_options} options, more than the 1024 one pool can hold (44 donors with doublets); '
-                             'give every barcode a pool of its own donors with barcode2pool / pool2donors')
-        penalties = Demultiplexer._doublet_penalties(G, doublet_prior)
-        pair_penalty = np.array([penalties[-1] if G > 1 else 0.0], dtype=np.float32)
-        return ([np.arange(G, dtype=np.int64)], np.zeros(barcode_handler.n_barcodes, dtype=np.int32), pair_penalty,
-                _option_names(genotypes.genotype_names, doublet_prior))
+    def _ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, who):
+        """What the entries under per-barcode ambient fractions refuse and resolve, in this order: (alpha float32[B], the _PoolSetup)."""
+        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        alpha = resolve_fractions(barcode_handler.ordered_barcodes, ambient_fractions)
+        return alpha, _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, who)
 
     @staticmethod
     def predict_posteriors_with_ambient(chromosome2compressed_snp_calls,
@@ -924,38 +969,19 @@ class Demultiplexer:
             all-donor pool, named 'all')
         Returns (logits_df, probs_df) with predict_posteriors' index, columns and dtypes; with pools a PooledPosteriors.
         ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
-        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
-        assert 0 <= doublet_prior < 1
-        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
-        alpha = resolve_fractions(barcode_handler.ordered_barcodes, ambient_fractions)
-        pooled = barcode2pool is not None
-        if pooled:
-            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
-        else:
-            pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
-                genotypes, barcode_handler, doublet_prior, 'predict_posteriors_with_ambient')
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'predict_posteriors_with_ambient')
 
         def run(ctx, fetch=True):
-            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
-            return ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip, ambient=ambient,
-                                     fetch_logits=fetch, fetch_probs=fetch)
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
+            return ctx.estep_ambient(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, alpha, p_genotype_clip,
+                                     ambient=ambient, fetch_logits=fetch, fetch_probs=fetch)
 
         if on_device:
-            names, columns = (pool_names, option_names) if pooled else (['all'], [column_names])
-            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, names, columns, pool_columns, pool_of_barcode)[1]
+            return _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler, setup)[1]
         with shared_context_lock:
             out = run(get_context())
-        if pooled:
-            return PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
-                                    out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
-        shape = (barcode_handler.n_barcodes, len(column_names))
-        logits_df = pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
-        probs_df = pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
-        return logits_df, probs_df
+        return _framed_posteriors(setup, barcode_handler, out, 'BARCODE')
 
     @staticmethod
     def predict_posteriors_decontaminated(chromosome2compressed_snp_calls,
@@ -978,28 +1004,22 @@ class Demultiplexer:
         assert 0 <= doublet_prior < 1
         names = list(genotypes.genotype_names)
         G = len(names)
-        pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
-            genotypes, barcode_handler, doublet_prior, 'predict_posteriors_decontaminated')
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, None, None, 'predict_posteriors_decontaminated')
         alphas = default_alphas() if alphas is None else np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
         B, with_doublets = barcode_handler.n_barcodes, doublet_prior != 0
         with shared_context_lock:
             ctx = get_context()
-            _pack_on_device(chromosome2compressed_snp_calls, genotypes, B, False, fetch_betas=False, ctx=ctx)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
-            plain = ctx.estep_pools(pool_columns, pool_of_barcode, with_doublets, pair_penalty, fetch_probs=False)
-            columns = best_singlets(plain['logits'].reshape(B, len(column_names)), G)
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, B, p_genotype_clip)
+            plain = ctx.estep_pools(setup.pool_columns, setup.pool_of_barcode, with_doublets, setup.pair_penalty, fetch_probs=False)
+            columns = best_singlets(plain['logits'].reshape(B, len(setup.option_names[0])), G)
             donor1, donor2 = assigned_donors(G, columns)
             profile = ctx.ambient_profile(donor1, donor2, alphas, p_genotype_clip, ambient=ambient, fetch_profile=False)
             estimate = AmbientEstimate(barcode_handler.ordered_barcodes, _option_names(names, 1), columns, alphas, profile['ambient'],
                                        profile['best'], profile['ll_best'], profile['ll_zero'], index_name='BARCODE')
             alpha = np.nan_to_num(estimate.fractions().values, nan=0.0).astype(np.float32)
-            out = ctx.estep_ambient(pool_columns, pool_of_barcode, with_doublets, pair_penalty, alpha, p_genotype_clip, ambient=profile['ambient'])
-        shape = (B, len(column_names))
-        logits_df = pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
-        probs_df = pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names)
-        return logits_df, probs_df, estimate
+            out = ctx.estep_ambient(setup.pool_columns, setup.pool_of_barcode, with_doublets, setup.pair_penalty, alpha, p_genotype_clip,
+                                    ambient=profile['ambient'])
+        return (*_framed_posteriors(setup, barcode_handler, out, 'BARCODE'), estimate)
 
     @staticmethod
     def predict_posteriors_joint_ambient(chromosome2compressed_snp_calls,
@@ -1054,57 +1074,27 @@ class Demultiplexer:
             alpha_log_weights = np.ascontiguousarray(alpha_log_weights, dtype=np.float32).reshape(-1)
             if alpha_log_weights.shape != grid.shape or not np.isfinite(alpha_log_weights).all():
                 raise ValueError('alpha_log_weights: one finite value per grid value')
-        pooled = barcode2pool is not None
-        if pooled:
-            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
-        else:
-            pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
-                genotypes, barcode_handler, doublet_prior, 'predict_posteriors_joint_ambient')
-            option_names = [column_names]
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, 'predict_posteriors_joint_ambient')
 
         def run(ctx, fetch=True):
-            _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, False, fetch_betas=False, ctx=ctx)
-            ctx.set_addition(None)
-            genotype_prob = ctx.probs_from_betas(p_genotype_clip)
-            assert np.isfinite(genotype_prob).all()
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
+            pools = (setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty)
             if over_grid == 'marginal':
-                return ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
-                                              over_grid='marginal', log_weights=alpha_log_weights, fetch_logits=fetch, fetch_probs=fetch,
-                                              fetch_alpha_index=fetch, fetch_alpha_mean=fetch)
-            return ctx.estep_ambient_grid(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, grid, p_genotype_clip, ambient=ambient,
-                                          fetch_profile=keep_profile, fetch_logits=fetch, fetch_probs=fetch, fetch_alpha_index=fetch)
+                return ctx.estep_ambient_grid(*pools, grid, p_genotype_clip, ambient=ambient, over_grid='marginal', log_weights=alpha_log_weights,
+                                              fetch_logits=fetch, fetch_probs=fetch, fetch_alpha_index=fetch, fetch_alpha_mean=fetch)
+            return ctx.estep_ambient_grid(*pools, grid, p_genotype_clip, ambient=ambient, fetch_profile=keep_profile, fetch_logits=fetch,
+                                          fetch_probs=fetch, fetch_alpha_index=fetch)
 
         if on_device:
-            out, posteriors = _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler.ordered_barcodes, pool_names if pooled else ['all'],
-                                                option_names, pool_columns, pool_of_barcode)
+            out, posteriors = _pooled_on_device(lambda ctx: run(ctx, False), barcode_handler, setup)
             return DeviceJointAmbientPosteriors(posteriors, grid, out['ambient'], out['best_alpha_index'], over_grid=over_grid,
                                                 best_alpha_mean=out.get('best_alpha_mean'))
         with shared_context_lock:
             out = run(get_context())
-        if pooled:
-            posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'], out['logits'],
-                                          out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'], index_name='BARCODE')
-        else:
-            shape = (barcode_handler.n_barcodes, len(column_names))
-            posteriors = (pd.DataFrame(data=out['logits'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names),
-                          pd.DataFrame(data=out['probs'].reshape(shape), index=_barcode_index(barcode_handler, 'BARCODE'), columns=column_names))
-        return JointAmbientPosteriors(barcode_handler.ordered_barcodes, option_names, pool_of_barcode, out['row_ptr'], grid, out['ambient'],
+        return JointAmbientPosteriors(barcode_handler.ordered_barcodes, setup.option_names, setup.pool_of_barcode, out['row_ptr'], grid, out['ambient'],
                                       out['alpha_index'], out['best_option'], out['best_prob'], out['doublet_mass'], out['best_alpha_index'],
-                                      posteriors, profile=out['profile'], index_name='BARCODE', over_grid=over_grid,
+                                      _framed_posteriors(setup, barcode_handler, out, 'BARCODE'), profile=out['profile'], index_name='BARCODE', over_grid=over_grid,
                                       alpha_mean=out.get('alpha_mean'), best_alpha_mean=out.get('best_alpha_mean'))
-
-    @staticmethod
-    def _resolved_pools(genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior):
-        """What the pooled entry points share: (pool names, per pool its table columns, pool_of_barcode, per pool its option names,
-        per pool the reference's bonus for its genotype list - demux.py:164-169: the prior doublet share is doublet_prior inside
-        every pool)."""
-        names = list(genotypes.genotype_names)
-        pool_names, pool_columns, pool_of_barcode = resolve_pools(names, barcode_handler.ordered_barcodes, barcode2pool, pool2donors)
-        option_names = [_option_names([names[g] for g in columns], doublet_prior) for columns in pool_columns]
-        pair_penalty = np.array([Demultiplexer._doublet_penalties(len(columns), doublet_prior)[-1] if len(columns) > 1 else 0.0
-                                 for columns in pool_columns], dtype=np.float32)
-        return pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty
 
     @staticmethod
     def learn_genotypes_in_pools(chromosome2compressed_snp_calls,
@@ -1125,17 +1115,14 @@ class Demultiplexer:
         assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
         assert 0 <= doublet_prior < 1
         assert n_iterations >= 1, 'n_iterations should be positive'
-        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, None)
         with shared_context_lock:
             ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
                                           fetch_betas=False)
-            out = ctx.em_pools(n_iterations, p_genotype_clip, pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty,
+            out = ctx.em_pools(n_iterations, p_genotype_clip, setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty,
                                contribution_power=Demultiplexer.contribution_power, fetch_addition=False)
             learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
-        pooled = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
-                                  out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
-        return genotypes._with_betas(learnt_betas, _take=True), pooled
+        return genotypes._with_betas(learnt_betas, _take=True), _framed_posteriors(setup, barcode_handler, out, None)
 
     @staticmethod
     def staged_genotype_learning_in_pools(chromosome2compressed_snp_calls,
@@ -1151,48 +1138,20 @@ class Demultiplexer:
         iteration's E-step used.  The EM state lives on the GPU between yields, in a device context private to this generator."""
         assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
         assert 0 <= doublet_prior < 1
-        pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-            genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, None)
 
-        ctx = acquire_private_context()
-        try:
+        with _generator_context() as ctx:
             _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
             genotype_addition = np.zeros_like(prior_betas)
             ctx.set_addition(None)
             for _iteration in range(n_iterations):
                 ctx.probs_from_betas(p_genotype_clip, fetch=False)
-                out = ctx.estep_pools(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, resident=True)
-                pooled = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
-                                          out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
-                yield pooled, {
+                out = ctx.estep_pools(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, resident=True)
+                yield _framed_posteriors(setup, barcode_handler, out, None), {
                     'genotype_prior': prior_betas,
                     'genotype_addition': genotype_addition,
                 }
                 genotype_addition = ctx.mstep(Demultiplexer.contribution_power)
-        except GeneratorExit:  # the consumer stopped early: nothing wrong with the context
-            release_private_context(ctx)
-            raise
-        except BaseException:
-            release_private_context(ctx, failed=True)
-            raise
-        else:
-            release_private_context(ctx)
-
-    @staticmethod
-    def _ambient_learning_arguments(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, who):
-        """What the two learning entries under ambient fractions share: (alpha float32[B], pooled, pool names or None, per pool its
-        table columns, pool_of_barcode, option names - per pool, or the one list without pools -, pair_penalty)."""
-        assert not Demultiplexer.aggregate_on_snps, 'ambient fractions act on barcode-level calls; aggregate_on_snps has none'
-        assert 0 <= doublet_prior < 1
-        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
-        alpha = resolve_fractions(barcode_handler.ordered_barcodes, ambient_fractions)
-        if barcode2pool is not None:
-            pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._resolved_pools(
-                genotypes, barcode_handler, barcode2pool, pool2donors, doublet_prior)
-            return alpha, True, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty
-        pool_columns, pool_of_barcode, pair_penalty, column_names = Demultiplexer._one_pool_of_everybody(
-            genotypes, barcode_handler, doublet_prior, who)
-        return alpha, False, None, pool_columns, pool_of_barcode, column_names, pair_penalty
 
     @staticmethod
     def learn_genotypes_with_ambient(chromosome2compressed_snp_calls,
@@ -1222,22 +1181,16 @@ class Demultiplexer:
             iteration: probs_df as learn_genotypes returns it, or with pools a PooledPosteriors.
         ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
         assert n_iterations >= 1, 'n_iterations should be positive'
-        alpha, pooled, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._ambient_learning_arguments(
-            genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, 'learn_genotypes_with_ambient')
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'learn_genotypes_with_ambient')
         with shared_context_lock:
             ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
                                           fetch_betas=False)
-            out = ctx.em_ambient(n_iterations, p_genotype_clip, pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha,
-                                 ambient=ambient, contribution_power=Demultiplexer.contribution_power, fetch_logits=pooled,
+            out = ctx.em_ambient(n_iterations, p_genotype_clip, setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty,
+                                 alpha, ambient=ambient, contribution_power=Demultiplexer.contribution_power, fetch_logits=setup.pooled,
                                  fetch_addition=False)
             learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
-        learnt_genotypes = genotypes._with_betas(learnt_betas, _take=True)
-        if pooled:
-            return learnt_genotypes, PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode,
-                                                      out['row_ptr'], out['logits'], out['probs'], out['best_option'], out['best_prob'],
-                                                      out['doublet_mass'])
-        probs = out['probs'].reshape(barcode_handler.n_barcodes, len(option_names))
-        return learnt_genotypes, pd.DataFrame(data=probs, index=_barcode_index(barcode_handler), columns=option_names)
+        return genotypes._with_betas(learnt_betas, _take=True), _framed_posteriors(setup, barcode_handler, out, None)
 
     @staticmethod
     def staged_genotype_learning_with_ambient(chromosome2compressed_snp_calls,
@@ -1255,39 +1208,24 @@ class Demultiplexer:
         pools and probs_df without, the yielded addition is the one the iteration's E-step used, 'ambient' the soup's profile in use
         (the one of the first iteration is kept for the later ones).  The EM state lives on the GPU between yields, in a device
         context private to this generator."""
-        alpha, pooled, pool_names, pool_columns, pool_of_barcode, option_names, pair_penalty = Demultiplexer._ambient_learning_arguments(
-            genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors, 'staged_genotype_learning_with_ambient')
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'staged_genotype_learning_with_ambient')
 
-        ctx = acquire_private_context()
-        try:
+        with _generator_context() as ctx:
             _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
             genotype_addition = np.zeros_like(prior_betas)
             ctx.set_addition(None)
             for _iteration in range(n_iterations):
                 ctx.probs_from_betas(p_genotype_clip, fetch=False)
-                out = ctx.estep_ambient(pool_columns, pool_of_barcode, doublet_prior != 0, pair_penalty, alpha, p_genotype_clip,
-                                        ambient=ambient, fetch_logits=pooled, resident=True)
+                out = ctx.estep_ambient(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, alpha, p_genotype_clip,
+                                        ambient=ambient, fetch_logits=setup.pooled, resident=True)
                 ambient = out['ambient']  # (a derived profile depends on the calls only: the same every iteration)
-                if pooled:
-                    posteriors = PooledPosteriors(barcode_handler.ordered_barcodes, pool_names, option_names, pool_of_barcode, out['row_ptr'],
-                                                  out['logits'], out['probs'], out['best_option'], out['best_prob'], out['doublet_mass'])
-                else:
-                    posteriors = pd.DataFrame(data=out['probs'].reshape(barcode_handler.n_barcodes, len(option_names)),
-                                              index=_barcode_index(barcode_handler), columns=option_names)
-                yield posteriors, {
+                yield _framed_posteriors(setup, barcode_handler, out, None), {
                     'genotype_prior': prior_betas,
                     'genotype_addition': genotype_addition,
                     'ambient': ambient,
                 }
                 genotype_addition = ctx.mstep_ambient(alpha, Demultiplexer.contribution_power, p_genotype_clip, ambient=ambient)
-        except GeneratorExit:  # the consumer stopped early: nothing wrong with the context
-            release_private_context(ctx)
-            raise
-        except BaseException:
-            release_private_context(ctx, failed=True)
-            raise
-        else:
-            release_private_context(ctx)
 
     # ------------------------------------------------------------------------------------
     @staticmethod

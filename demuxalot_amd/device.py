@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DMX_F32, DMX_F64, as_c, check, ptr
+from .pools import pooled_layout
 
 
 # E-step arithmetic of a new context (include/demux_hip.h: dmx_set_estep_mode); DEMUXALOT_AMD_ESTEP overrides.
@@ -671,18 +672,11 @@ class DeviceContext:
     def _pools_arguments(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs):
         """(the pool arguments of the dmx_estep_pools family as ctypes pointers, the arrays behind them, the result dict)."""
         B = self.B
-        sizes = np.array([len(d) for d in pools], dtype=np.int64)
-        pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        donors = as_c(np.concatenate([np.asarray(d, dtype=np.int64).reshape(-1) for d in pools]) if len(pools) else [], np.int32)
         pool_of_barcode = as_c(pool_of_barcode, np.int32)
         assert pool_of_barcode.shape == (B,), 'one pool id per barcode'
         pair_penalty = as_c(pair_penalty, np.float32)
         assert pair_penalty.shape == (len(pools),), 'one pair penalty per pool'
-        n_options = sizes * (sizes + 1) // 2 if with_doublets else sizes
-        in_pool = (pool_of_barcode >= 0) & (pool_of_barcode < len(pools))  # (ids outside: the library's error)
-        row_len = np.zeros(B, dtype=np.int64)
-        row_len[in_pool] = n_options[pool_of_barcode[in_pool]]
-        row_ptr = np.concatenate([[0], np.cumsum(row_len)]).astype(np.int64)
+        pool_start, donors, row_ptr = pooled_layout(pools, pool_of_barcode, with_doublets)
         n = int(row_ptr[-1])
         out = dict(row_ptr=row_ptr, logits=np.empty(n, np.float32) if fetch_logits else None,
                    probs=np.empty(n, np.float32) if fetch_probs else None, best_option=np.full(B, -1, np.int32),
@@ -695,6 +689,24 @@ class DeviceContext:
     def _pools_results(out):
         return (ptr(out['logits']), ptr(out['probs']), ptr(out['best_option']), ptr(out['best_prob']), ptr(out['doublet_mass']))
 
+    def _pooled_call(self, entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, head=(), middle=(),
+                     tail=lambda out: (), fetch_addition=None, ambient=False, more=None, dense=False):
+        """One call of the dmx_estep_pools family: entry(handle, *head, with_doublets, the pool arguments, *middle, the result
+        pointers, *tail(out)) and its result dict.  fetch_addition (not None: an EM entry): the key 'addition', float32[V, G] or None;
+        ambient: the key 'ambient', float32[V]; more(n values of a compact matrix): further keys; all there before tail(out) is
+        asked.  dense: the entry leaves the dense [B, G] singlet posteriors resident, so K becomes G."""
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
+        if fetch_addition is not None:
+            out['addition'] = np.empty((self.V, self.G), dtype=np.float32) if fetch_addition else None
+        if ambient:
+            out['ambient'] = np.empty(self.V, np.float32)
+        if more is not None:
+            out.update(more(int(out['row_ptr'][-1])))
+        check(entry(self._h, *head, int(bool(with_doublets)), *pool_args, *middle, *self._pools_results(out), *tail(out)))
+        if dense:
+            self.K = self.G
+        return out
+
     def estep_pools(self, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits=True, fetch_probs=True, resident=False):
         """The pooled E-step (include/demux_hip_debug.h: dmx_estep_pools): every barcode against the donors of its own pool.
         pools: one strictly ascending list of table columns per pool; pool_of_barcode int32[B], -1: in no pool;
@@ -702,12 +714,8 @@ class DeviceContext:
         None), best_option int32[B], best_prob float32[B], doublet_mass float64[B].  The resident results of the last
         E-step are left as they are - unless resident=True (dmx_estep_pools_resident): then the singlet posteriors are left in
         the context as a dense [B, G] matrix, zero outside a barcode's pool, so that mstep() may follow and get_probs() returns it."""
-        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
         entry = self._lib.dmx_estep_pools_resident if resident else self._lib.dmx_estep_pools
-        check(entry(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out)))
-        if resident:
-            self.K = self.G
-        return out
+        return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, dense=resident)
 
     def em_pools(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, contribution_power=2.,
                  fetch_logits=True, fetch_probs=True, fetch_addition=True):
@@ -715,13 +723,9 @@ class DeviceContext:
         barcode scored against the donors of its own pool, and posterior 0 for the others.  Returns estep_pools()'s dict of the last
         iteration with one more key, 'addition': float32[V, G], the addition its E-step used (None without fetch_addition).
         get_learnt_betas() and get_probs() (the dense [B, G] singlet posteriors) work afterwards."""
-        lo, hi = self.clip_bounds(p_genotype_clip)
-        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
-        out['addition'] = np.empty((self.V, self.G), dtype=np.float32) if fetch_addition else None
-        check(self._lib.dmx_em_pools(self._h, int(n_iterations), lo, hi, int(bool(with_doublets)), *pool_args, float(contribution_power),
-                                     *self._pools_results(out), ptr(out['addition'])))
-        self.K = self.G
-        return out
+        return self._pooled_call(self._lib.dmx_em_pools, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 head=(int(n_iterations), *self.clip_bounds(p_genotype_clip)), middle=(float(contribution_power),),
+                                 tail=lambda out: (ptr(out['addition']),), fetch_addition=bool(fetch_addition), dense=True)
 
     def ambient_profile(self, donor1, donor2, alphas, p_genotype_clip=0.01, ambient=None, fetch_profile=True):
         """Ambient RNA fractions (include/demux_hip_debug.h: dmx_ambient_profile): the log-likelihood of every barcode's calls under
@@ -735,9 +739,7 @@ class DeviceContext:
         assert alphas.ndim == 1, 'the grid is one-dimensional'
         donor1, donor2 = as_c(donor1, np.int32), as_c(donor2, np.int32)
         assert donor1.shape == (B,) and donor2.shape == (B,), 'one option per barcode'
-        if ambient is not None:
-            ambient = as_c(ambient, np.float32)
-            assert ambient.shape == (self.V,), 'one ambient value per variant'
+        ambient = self._ambient_argument(ambient)
         lo, hi = self.clip_bounds(p_genotype_clip)
         A = len(alphas)
         out = dict(loglik=np.empty((B, A), np.float32) if fetch_profile else None, best=np.full(B, -1, np.int32),
@@ -757,23 +759,22 @@ class DeviceContext:
         returns it."""
         alpha, ambient = self._ambient_arguments(alpha, ambient)
         lo, hi = self.clip_bounds(p_genotype_clip)
-        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
-        out['ambient'] = np.empty(self.V, np.float32)
         entry = self._lib.dmx_estep_ambient_resident if resident else self._lib.dmx_estep_ambient
-        check(entry(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, ptr(alpha), ptr(ambient),
-                    ptr(out['ambient'])))
-        if resident:
-            self.K = self.G
-        return out
+        return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, ambient=True,
+                                 tail=lambda out: (lo, hi, ptr(alpha), ptr(ambient), ptr(out['ambient'])), dense=resident)
 
-    def _ambient_arguments(self, alpha, ambient):
-        """(alpha float32[B], ambient float32[V] or None) as the entries under ambient fractions take them."""
-        alpha = as_c(alpha, np.float32)
-        assert alpha.shape == (self.B,), 'one fraction per barcode'
+    def _ambient_argument(self, ambient):
+        """The soup's profile as every entry under ambient fractions takes it: float32[V], or None (derived from the resident calls)."""
         if ambient is not None:
             ambient = as_c(ambient, np.float32)
             assert ambient.shape == (self.V,), 'one ambient value per variant'
-        return alpha, ambient
+        return ambient
+
+    def _ambient_arguments(self, alpha, ambient):
+        """(alpha float32[B], ambient float32[V] or None) as the entries under per-barcode fractions take them."""
+        alpha = as_c(alpha, np.float32)
+        assert alpha.shape == (self.B,), 'one fraction per barcode'
+        return alpha, self._ambient_argument(ambient)
 
     def mstep_ambient(self, alpha, contribution_power=2., p_genotype_clip=0.01, ambient=None, fetch=True):
         """The M-step under per-barcode ambient fractions (include/demux_hip_debug.h: dmx_mstep_ambient): mstep() with every call's
@@ -795,14 +796,11 @@ class DeviceContext:
         the call.  Returns em_pools()'s dict with one more key, 'ambient': float32[V], the profile that was used.  get_learnt_betas()
         and get_probs() (the dense [B, G] singlet posteriors) work afterwards."""
         alpha, ambient = self._ambient_arguments(alpha, ambient)
-        lo, hi = self.clip_bounds(p_genotype_clip)
-        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
-        out['addition'] = np.empty((self.V, self.G), dtype=np.float32) if fetch_addition else None
-        out['ambient'] = np.empty(self.V, np.float32)
-        check(self._lib.dmx_em_ambient(self._h, int(n_iterations), lo, hi, int(bool(with_doublets)), *pool_args, float(contribution_power),
-                                       ptr(alpha), ptr(ambient), *self._pools_results(out), ptr(out['addition']), ptr(out['ambient'])))
-        self.K = self.G
-        return out
+        return self._pooled_call(self._lib.dmx_em_ambient, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 head=(int(n_iterations), *self.clip_bounds(p_genotype_clip)),
+                                 middle=(float(contribution_power), ptr(alpha), ptr(ambient)),
+                                 tail=lambda out: (ptr(out['addition']), ptr(out['ambient'])), fetch_addition=bool(fetch_addition),
+                                 ambient=True, dense=True)
 
     def estep_ambient_grid(self, pools, pool_of_barcode, with_doublets, pair_penalty, alphas, p_genotype_clip=0.01, ambient=None,
                            fetch_logits=True, fetch_probs=True, fetch_alpha_index=True, fetch_profile=False, over_grid='max', log_weights=None,
@@ -832,29 +830,27 @@ class DeviceContext:
         if log_weights is not None:
             log_weights = as_c(log_weights, np.float32)
             assert log_weights.shape == alphas.shape, 'one log weight per grid value'
-        if ambient is not None:
-            ambient = as_c(ambient, np.float32)
-            assert ambient.shape == (self.V,), 'one ambient value per variant'
+        ambient = self._ambient_argument(ambient)
         lo, hi = self.clip_bounds(p_genotype_clip)
-        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs)
-        n, A = int(out['row_ptr'][-1]), len(alphas)
-        out['ambient'] = np.empty(self.V, np.float32)
-        out['alphas'] = alphas
-        out['alpha_index'] = np.full(n, -1, np.int32) if fetch_alpha_index else None
-        out['best_alpha_index'] = np.full(self.B, -1, np.int32)
-        out['profile'] = np.empty((n, A), np.float32) if fetch_profile else None
-        if marginal:
-            out['alpha_mean'] = np.full(n, np.nan, np.float32) if fetch_alpha_mean else None
-            out['best_alpha_mean'] = np.full(self.B, np.nan, np.float32)
-            check(self._lib.dmx_estep_ambient_grid_marginal(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, A,
-                                                            ptr(alphas), ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']),
-                                                            ptr(out['best_alpha_index']), ptr(log_weights), ptr(out['alpha_mean']),
-                                                            ptr(out['best_alpha_mean'])))
-            return out
-        check(self._lib.dmx_estep_ambient_grid(self._h, int(bool(with_doublets)), *pool_args, *self._pools_results(out), lo, hi, A, ptr(alphas),
-                                               ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']), ptr(out['best_alpha_index']),
-                                               ptr(out['profile'])))
-        return out
+        A = len(alphas)
+
+        def more(n):
+            keys = dict(alphas=alphas, alpha_index=np.full(n, -1, np.int32) if fetch_alpha_index else None,
+                        best_alpha_index=np.full(self.B, -1, np.int32), profile=np.empty((n, A), np.float32) if fetch_profile else None)
+            if marginal:
+                keys.update(alpha_mean=np.full(n, np.nan, np.float32) if fetch_alpha_mean else None,
+                            best_alpha_mean=np.full(self.B, np.nan, np.float32))
+            return keys
+
+        def tail(out):
+            grid = (lo, hi, A, ptr(alphas), ptr(ambient), ptr(out['ambient']), ptr(out['alpha_index']), ptr(out['best_alpha_index']))
+            if marginal:
+                return (*grid, ptr(log_weights), ptr(out['alpha_mean']), ptr(out['best_alpha_mean']))
+            return (*grid, ptr(out['profile']))
+
+        entry = self._lib.dmx_estep_ambient_grid_marginal if marginal else self._lib.dmx_estep_ambient_grid
+        return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, ambient=True, more=more,
+                                 tail=tail)
 
     # ---- pooled results kept resident (include/demux_hip_debug.h "Pooled results kept resident"; csrc/pooled_readout.hip) ----
     def set_keep_pooled(self, keep):
@@ -865,15 +861,8 @@ class DeviceContext:
     def pooled_upload(self, n_donors, pools, pool_of_barcode, with_doublets, probs, logits=None):
         """Fills the pooled slot from host arrays (dmx_pooled_upload): pools as estep_pools() takes them (columns below n_donors),
         pool_of_barcode int32[B], compact float32 probs (and logits, or None).  Returns row_ptr int64[B + 1]."""
-        sizes = np.array([len(d) for d in pools], dtype=np.int64)
-        pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        donors = as_c(np.concatenate([np.asarray(d, dtype=np.int64).reshape(-1) for d in pools]) if len(pools) else [], np.int32)
         pool_of_barcode = as_c(pool_of_barcode, np.int32)
-        n_options = sizes * (sizes + 1) // 2 if with_doublets else sizes
-        in_pool = (pool_of_barcode >= 0) & (pool_of_barcode < len(pools))  # (ids outside: the library's error)
-        row_len = np.zeros(len(pool_of_barcode), dtype=np.int64)
-        row_len[in_pool] = n_options[pool_of_barcode[in_pool]]
-        row_ptr = np.concatenate([[0], np.cumsum(row_len)]).astype(np.int64)
+        pool_start, donors, row_ptr = pooled_layout(pools, pool_of_barcode, with_doublets)
         probs = as_c(probs, np.float32)
         assert probs.shape == (int(row_ptr[-1]),), 'compact probs: row_ptr[B] values'
         if logits is not None:

@@ -45,6 +45,23 @@ def resolve_pools(genotype_names, ordered_barcodes, barcode2pool, pool2donors):
     return pool_names, pool_columns, pool_of_barcode
 
 
+def pooled_layout(pools, pool_of_barcode, with_doublets):
+    """The host layout of a pooled call (include/demux_hip_debug.h: dmx_estep_pools) from one list of table columns per pool and
+    pool_of_barcode: (pool_start int64[n_pools + 1], the lists flat as int32, row_ptr int64[B + 1]).  A barcode's row has the options
+    of its pool; an id that is no pool's - -1, in no pool, or any other, which the library refuses - has a row of length 0."""
+    sizes = np.array([len(d) for d in pools], dtype=np.int64)
+    pool_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    donors = np.ascontiguousarray(np.concatenate([np.asarray(d, dtype=np.int64).reshape(-1) for d in pools]) if len(pools) else [],
+                                  dtype=np.int32)
+    pool_of_barcode = np.asarray(pool_of_barcode, dtype=np.int32)
+    n_options = sizes * (sizes + 1) // 2 if with_doublets else sizes
+    in_pool = (pool_of_barcode >= 0) & (pool_of_barcode < len(pools))
+    row_len = np.zeros(len(pool_of_barcode), dtype=np.int64)
+    row_len[in_pool] = n_options[pool_of_barcode[in_pool]]
+    row_ptr = np.concatenate([[0], np.cumsum(row_len)]).astype(np.int64)
+    return pool_start, donors, row_ptr
+
+
 class PooledPosteriors:
     """Logits and posteriors of one predict_posteriors_in_pools call, compact and host-resident.
 
