@@ -11,9 +11,10 @@ from .genotypes import ProbabilisticGenotypes
 from .demux import Demultiplexer, DevicePosteriors, invalidate_resident
 from .pools import DevicePooledPosteriors, PooledPosteriors
 from .ambient import AmbientEstimate, DeviceJointAmbientPosteriors, JointAmbientPosteriors
+from .doublet_shares import DoubletSharePosteriors, default_shares
 from .snp_detection import (coverage_from_reads, detect_snps_positions_from_calls, detect_snps_positions_from_reads,
                             find_candidate_positions, select_snps_from_calls)
 
-__all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'PooledPosteriors', 'DevicePooledPosteriors', 'AmbientEstimate', 'JointAmbientPosteriors', 'DeviceJointAmbientPosteriors', 'invalidate_resident',
+__all__ = ['BarcodeHandler', 'CompressedSNPCalls', 'ProbabilisticGenotypes', 'Demultiplexer', 'DevicePosteriors', 'PooledPosteriors', 'DevicePooledPosteriors', 'AmbientEstimate', 'JointAmbientPosteriors', 'DeviceJointAmbientPosteriors', 'DoubletSharePosteriors', 'default_shares', 'invalidate_resident',
            'detect_snps_positions_from_calls', 'select_snps_from_calls', 'DecodedReads', 'ResidentReads', 'ResidentCalls', 'calls_per_barcode', 'summarize_counted_SNPs', 'count_snps_from_reads', 'count_snps_from_read_chunks', 'ReadCounter', 'coverage_from_reads',
            'find_candidate_positions', 'detect_snps_positions_from_reads']

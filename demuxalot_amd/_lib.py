@@ -165,6 +165,7 @@ DEBUG_SIGNATURES = {
                                        _P]),
     'dmx_estep_ambient_grid_marginal': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int32, _P, _P, _P,
                                                 _P, _P, _P, _P, _P]),
+    'dmx_estep_pair_shares': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     'dmx_estep_ambient_resident': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P]),
     'dmx_mstep_ambient': (c_int, [_P, c_float, _P, _P, c_float, c_float, _P]),
     'dmx_em_ambient': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P,

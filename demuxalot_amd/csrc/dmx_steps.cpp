@@ -27,9 +27,11 @@
 #include "ambient_scoring_plan.h"
 #include "estep_ambient.h"
 #include "estep_ambient_grid.h"
+#include "estep_pair_shares.h"
 #include "estep_pools.h"
 #include "mstep_ambient.h"
 #include "mstep_plan.h"
+#include "pair_shares_plan.h"
 #include "pools_plan.h"
 
 using namespace dmx::host;
@@ -1065,6 +1067,23 @@ int dmx_estep_ambient_grid_marginal(dmx_ctx *c, int with_doublets, int32_t n_poo
     const dmx::AmbientGridScoring scoring{lo, hi, (int)n_alphas, alphas, ambient, ambient_out, alpha_index, best_alpha_index, nullptr,
                                           true, log_weights, alpha_mean, best_alpha_mean};
     return dmx::run_estep_ambient_grid(c, plan, scoring);
+}
+
+// The pooled E-step with every pair option summed over a grid of mixing shares (estep_pair_shares.hip).  pair_shares_plan.h refuses,
+// on the host, before anything is uploaded or launched; what it has accepted is laid out as for dmx_estep_pools.
+int dmx_estep_pair_shares(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                          const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out, float *probs_out,
+                          int32_t *best_option, float *best_prob, double *doublet_mass, int32_t n_shares, const float *shares,
+                          const float *log_weights, int32_t *share_index, float *share_mean, int32_t *best_share_index, float *best_share_mean)
+{
+    namespace ps = dmx::psplan;
+    DMX_TRY(bind(c));
+    const ps::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_estep_pair_shares", ps::check(ambient_facts(c, c->have_probs), pools, n_shares, shares, log_weights), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
+    const dmx::PairSharesScoring scoring{(int)n_shares, shares, log_weights, share_index, share_mean, best_share_index, best_share_mean};
+    return dmx::run_estep_pair_shares(c, plan, scoring);
 }
 
 int dmx_mstep(dmx_ctx *c, float power, float *addition_out)

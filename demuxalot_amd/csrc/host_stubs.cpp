@@ -19,6 +19,7 @@
 #include "dmx_ctx.h"
 #include "estep_ambient.h"
 #include "estep_ambient_grid.h"
+#include "estep_pair_shares.h"
 #include "estep_pools.h"
 
 // ------------------------------------------------------------------------------------
@@ -183,6 +184,7 @@ const float *ambient_run_soup(const AmbientRun &) { return nullptr; }
 int run_mstep_ambient(dmx_ctx *, float, const float *, const float *) { return 0; }  // (validated by dmx_mstep_ambient / dmx_em_ambient; nothing is written)
 int run_mstep_ambient_from_host(dmx_ctx *, float, const float *, const float *, float, float) { return 0; }
 int run_estep_ambient_grid(dmx_ctx *, const PoolsPlan &, const AmbientGridScoring &) { return 0; }  // (validated by dmx_estep_ambient_grid / _marginal; nothing is written)
+int run_estep_pair_shares(dmx_ctx *, const PoolsPlan &, const PairSharesScoring &) { return 0; }  // (validated by dmx_estep_pair_shares; nothing is written)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {
     // this one is cheap enough to do for real: it indexes new_rows with what the records hold

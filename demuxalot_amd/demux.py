@@ -32,6 +32,7 @@ from .ambient import (AmbientEstimate, DeviceJointAmbientPosteriors, JointAmbien
                       resolve_fractions, resolve_grid)
 from .device import (DeviceContext, acquire_private_context, default_device, get_context, release_private_context,
                      shared_context_lock)
+from .doublet_shares import DoubletSharePosteriors, resolve_shares
 from .pools import DevicePooledPosteriors, PooledPosteriors, resolve_pools
 
 _MOLECULE_CALL_DTYPE = [('variant_id', 'int32'), ('snp_id', 'int32'), ('compressed_cb', 'int32'),
@@ -1095,6 +1096,45 @@ class Demultiplexer:
                                       out['alpha_index'], out['best_option'], out['best_prob'], out['doublet_mass'], out['best_alpha_index'],
                                       _framed_posteriors(setup, barcode_handler, out, 'BARCODE'), profile=out['profile'], index_name='BARCODE', over_grid=over_grid,
                                       alpha_mean=out.get('alpha_mean'), best_alpha_mean=out.get('best_alpha_mean'))
+
+    @staticmethod
+    def predict_posteriors_with_doublet_shares(chromosome2compressed_snp_calls,
+                                               genotypes,
+                                               barcode_handler,
+                                               shares=None,
+                                               share_log_weights=None,
+                                               p_genotype_clip=0.01,
+                                               doublet_prior=0.35,
+                                               barcode2pool=None,
+                                               pool2donors=None) -> DoubletSharePosteriors:
+        """(not in the reference) predict_posteriors / predict_posteriors_in_pools with every pair option scored as the marginal over
+        a grid of mixing shares: a call's term for the pair 'A+B' is prob[A] w + prob[B] (1 - w) in place of the even
+        (prob[A] + prob[B]) / 2, the pair's logit the log of the sum over the grid of exp(log-likelihood + share_log_weights) plus the
+        pair penalty.  Two cells of different RNA content share a droplet unevenly, and an 80 / 20 doublet scored at 0.5 looks like
+        its major donor.  Singlet options are predict_posteriors'.  One pass over the resident problem.
+        With shares=[0.5] and share_log_weights=[0.0] the result is predict_posteriors' (exact mode) bit for bit.
+        :param shares: the grid of shares of the first-named donor, 1 .. 64 values in [0, 1] in any order; None: 0.1, 0.2 .. 0.9
+        :param share_log_weights: the log of a prior over the grid, one finite value per share; None: uniform, -log(n) each.  The
+            normalisation matters: singlets do not go through the grid
+        :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
+        Returns a DoubletSharePosteriors: .posteriors is (logits_df, probs_df) with predict_posteriors' index, columns and dtypes,
+        with pools a PooledPosteriors; .option_shares, .option_share_index, .summary().
+        ValueError: a share outside [0, 1], an empty grid or more than 64 values, weights that do not fit the grid, more than 1024
+        options without pools (give pools with barcode2pool / pool2donors)."""
+        assert not Demultiplexer.aggregate_on_snps, 'doublet shares act on barcode-level calls; aggregate_on_snps has none'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        grid, log_weights = resolve_shares(shares, share_log_weights)
+        setup = _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, 'predict_posteriors_with_doublet_shares')
+        with shared_context_lock:
+            ctx = get_context()
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
+            out = ctx.estep_pair_shares(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, grid, log_weights)
+        names = list(genotypes.genotype_names)
+        return DoubletSharePosteriors(barcode_handler.ordered_barcodes, setup.option_names, [[names[g] for g in columns] for columns in setup.pool_columns],
+                                      setup.pool_of_barcode, out['row_ptr'], grid, log_weights, out['share_index'], out['share_mean'],
+                                      out['best_option'], out['best_prob'], out['doublet_mass'], out['best_share_index'], out['best_share_mean'],
+                                      _framed_posteriors(setup, barcode_handler, out, 'BARCODE'), index_name='BARCODE')
 
     @staticmethod
     def learn_genotypes_in_pools(chromosome2compressed_snp_calls,

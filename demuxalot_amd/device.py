@@ -852,6 +852,35 @@ class DeviceContext:
         return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, ambient=True, more=more,
                                  tail=tail)
 
+    def estep_pair_shares(self, pools, pool_of_barcode, with_doublets, pair_penalty, shares, log_weights=None, fetch_logits=True,
+                          fetch_probs=True, fetch_share_index=True, fetch_share_mean=True):
+        """The pooled E-step with every pair option summed over a grid of mixing shares (include/demux_hip_debug.h:
+        dmx_estep_pair_shares): estep_pools() with a pair (d1, d2) scored as prob[d1] w + prob[d2] (1 - w) at every w of `shares`
+        (float32, 1 .. 64 values in [0, 1], any order) and its logit the log of the sum over the grid of exp(its logit there +
+        log_weights); singlet options are estep_pools()'s own.  log_weights: float32[n_shares], the log of a prior over the grid, or
+        None (all 0: the log of a plain sum, not of a mean).  Returns estep_pools()'s dict with more keys: 'shares', the grid;
+        'share_index' int32[row_ptr[B]], the grid point of every pair's largest term (-1: a singlet; None without fetch_share_index);
+        'share_mean' float32[row_ptr[B]], every pair's posterior mean share of its first donor (NaN: a singlet; None without
+        fetch_share_mean); 'best_share_index' int32[B] and 'best_share_mean' float32[B], those of best_option (-1 / NaN: a singlet
+        or none).  The resident results of the last E-step are left as they are."""
+        shares = as_c(shares, np.float32)
+        assert shares.ndim == 1, 'the grid is one-dimensional'
+        if log_weights is not None:
+            log_weights = as_c(log_weights, np.float32)
+            assert log_weights.shape == shares.shape, 'one log weight per share'
+
+        def more(n):
+            return dict(shares=shares, share_index=np.full(n, -1, np.int32) if fetch_share_index else None,
+                        share_mean=np.full(n, np.nan, np.float32) if fetch_share_mean else None,
+                        best_share_index=np.full(self.B, -1, np.int32), best_share_mean=np.full(self.B, np.nan, np.float32))
+
+        def tail(out):
+            return (len(shares), ptr(shares), ptr(log_weights), ptr(out['share_index']), ptr(out['share_mean']), ptr(out['best_share_index']),
+                    ptr(out['best_share_mean']))
+
+        return self._pooled_call(self._lib.dmx_estep_pair_shares, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 more=more, tail=tail)
+
     # ---- pooled results kept resident (include/demux_hip_debug.h "Pooled results kept resident"; csrc/pooled_readout.hip) ----
     def set_keep_pooled(self, keep):
         """With True, estep_pools(), estep_ambient() and estep_ambient_grid() (not their resident / EM siblings) leave their compact

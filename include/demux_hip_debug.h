@@ -592,6 +592,54 @@ int dmx_estep_ambient_grid_marginal(dmx_ctx *ctx, int with_doublets, int32_t n_p
                                     float *alpha_mean /* nullable, float32[row_ptr[B]] */, float *best_alpha_mean /* nullable, [B] */);
 
 /* ------------------------------------------------------------------------- *
+ * The pooled E-step with every pair option summed over a grid of mixing shares (product API; csrc/estep_pair_shares.hip;
+ * DESIGN.md 4.12).  dmx_estep_pools scores a pair as the even mixture (p1 + p2) * 0.5; two cells of different RNA content share a
+ * droplet unevenly, and an uneven doublet scored at 0.5 looks like its major donor.  Here a pair's logit is the log of the weighted sum
+ * over a grid of shares of its first donor.  Pools, rows, read-outs, the no-pool and no-call conventions and the option order are
+ * dmx_estep_pools'; singlet options are untouched.  Beyond its arguments:
+ *   shares           float32[n_shares], 1 .. 64 values in [0, 1], any order, duplicates allowed: the share of d1 in a pair (d1, d2),
+ *                    d1 ahead of d2 in the pool's option order.
+ *   log_weights      float32[n_shares], nullable (NULL: all 0): the log of a prior over the grid; every value finite.
+ *   share_index, share_mean            int32 / float32[row_ptr[B]], nullable, compact like the logits
+ *   best_share_index, best_share_mean  int32 / float32[B], nullable
+ * Pair option k = (d1, d2) of barcode b in pool p, grid point j; float32, every operation rounded, no contraction, over the calls of b
+ * in stored order:
+ *     w1 = shares[j];  w2 = 1.0f - shares[j]
+ *     q  = prob[v, d1] * w1 + prob[v, d2] * w2                         two products, one sum
+ *     S[b, k, j] = sum of f64( log_f32(q * keep + floor) )             the exact E-step's log, sequential float64 sum
+ *     lambda[b, k, j] = f32( f64(pen) + S[b, k, j] )                   pen = pair_penalty[p]
+ * Across the grid, j ascending: dmx_estep_ambient_grid_marginal's recurrence above with shares[j] for alphas[j] - its t, m, s, u, jm,
+ * its exp and log, its treatment of equal t, -inf and NaN:
+ *     logit[b, k]       = f32( f64(pen) + ( S[b, k, jm] + f64( f32(log_weights[jm] + log(s)) ) ) )    NaN if no t was a number
+ *     share_index[b, k] = jm (-1 if none);   share_mean[b, k] = u / s  IEEE float32 division; NaN if none
+ * A singlet option's logit is dmx_estep_pools' own, f32(f64(0) + S) with q = prob[v, d]; the grid and the weights do not enter it,
+ * its share_index is -1 and its share_mean NaN.  best_share_index[b] and best_share_mean[b] are best_option's entries: -1 / NaN
+ * where best_option is a singlet, where it is -1, or where the barcode is in no pool.
+ * The normalisation of the weights matters here, unlike in dmx_estep_ambient_grid_marginal: singlets do not go through the grid, so a
+ * constant added to every log weight moves every pair against every singlet.  With log_weights NULL a pair's logit is the log of a
+ * SUM over the grid, not of a mean; the uniform prior is log_weights[j] = -log(n_shares).
+ * Identities, bit for bit: (S1) shares = {0.5}, log_weights NULL or {0}: every shared output is dmx_estep_pools' - halving is exact,
+ * fl(p1 / 2 + p2 / 2) = fl(p1 + p2) / 2, on a table whose non-zero entries are at least 2^-125 (no halved entry is subnormal) - and
+ * share_mean is 0.5 on every pair option; (S2) with_doublets == 0 is dmx_estep_pools, the share outputs are -1 / NaN and no grid
+ * kernel is launched; (S3) shares = {1}, log_weights NULL: a pair's logit is f32(f64(pen) + S) with S the float64 sum of its first
+ * donor's singlet option in the same row (shares = {0}: the second donor's); (S4) the grid {a, a}, log_weights NULL:
+ * logit = f32(f64(pen) + (S + f64(log_f32(2.0f)))); (S5) log_weights of all zeros is log_weights NULL.
+ * Checked on the host before anything is uploaded or launched (csrc/pair_shares_plan.h), in this order: everything dmx_estep_pools
+ * and the pooled entries under ambient fractions refuse of the context and the pools, with their codes and words (a communicator, a
+ * padded table layout, more than 1024 options in a pool among them); DMX_ERR_INVALID for n_shares < 1, null shares, a share that is
+ * not finite or outside [0, 1], a log weight that is not finite; DMX_ERR_UNSUPPORTED for n_shares > 64.  The resident results of the
+ * last dmx_estep / dmx_em and the pooled slot (dmx_set_keep_pooled) are left as they are; the pass is counted in the DMX_T_ESTEP slot.
+ * ------------------------------------------------------------------------- */
+int dmx_estep_pair_shares(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                          const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                          const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                          float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                          int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                          int32_t n_shares, const float *shares /* [n_shares] */, const float *log_weights /* nullable, [n_shares] */,
+                          int32_t *share_index /* nullable, int32[row_ptr[B]] */, float *share_mean /* nullable, float32[row_ptr[B]] */,
+                          int32_t *best_share_index /* nullable, [B] */, float *best_share_mean /* nullable, [B] */);
+
+/* ------------------------------------------------------------------------- *
  * Pooled results kept resident (product API; declared here because demux_hip.h is kept to 64 entry points;
  * csrc/pooled_readout.hip).  The context owns one "pooled slot": the compact result of a pooled pass - the pool
  * layout, pool_of_barcode, row_ptr, the compact posteriors, the compact logits (may be absent), from the grid passes the compact
