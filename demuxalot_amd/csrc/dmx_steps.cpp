@@ -25,11 +25,13 @@
 #include "ambient_grid_plan.h"
 #include "ambient_learning_plan.h"
 #include "ambient_scoring_plan.h"
+#include "doublet_learning_plan.h"
 #include "estep_ambient.h"
 #include "estep_ambient_grid.h"
 #include "estep_pair_shares.h"
 #include "estep_pools.h"
 #include "mstep_ambient.h"
+#include "mstep_doublets.h"
 #include "mstep_plan.h"
 #include "pair_shares_plan.h"
 #include "pools_plan.h"
@@ -1237,6 +1239,50 @@ int dmx_em_ambient(dmx_ctx *c, int n_iterations, float lo, float hi, int with_do
         c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_ambient_pass(c, *run, power); },
         [&](int) { return dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)); }));
     return dmx::read_back_estep_ambient(c, *run);
+}
+
+// Learning from doublet posteriors (mstep_doublets.hip).  doublet_learning_plan.h refuses, on the host, before anything
+// is uploaded or launched.  dmx_em_pools' loop with the live-pair list and the crediting M-step between two iterations; the round trip
+// of the pools and the list's buffers are paid once, the read-back once after the last E-step.
+int dmx_em_doublets(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                    const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float power,
+                    float min_pair_posterior, float *logits_out, float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass,
+                    float *addition_out)
+{
+    namespace lp = dmx::dlplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_em_doublets", lp::check_em(ambient_facts(c, c->have_betas), pools, n_iterations, power, min_pair_posterior), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
+    DMX_TRY(begin_dense_pools(c));
+    DMX_TRY(begin_em_additions(c));
+    dmx::PoolsRunPtr run;
+    DMX_TRY(dmx::prepare_estep_pools(c, plan, true, run));
+    dmx::DoubletRunPtr credited;
+    DMX_TRY(dmx::prepare_doublet_run(c, *run, lp::pair_options(c->B, pools), credited));
+    // (msteps_ahead is not set around this M-step: run_mstep_doublets has one form, the float64 sums, and asks no plan of mstep_plan.h)
+    DMX_TRY(run_dense_em(
+        c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_pools_pass(c, *run, power); },
+        [&](int) { return dmx::run_mstep_doublets(c, power, min_pair_posterior, *credited); }));
+    return dmx::read_back_estep_pools(c, *run);
+}
+
+int dmx_mstep_doublets(dmx_ctx *c, float power, float min_pair_posterior, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                       const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr,
+                       const float *post_rows, int64_t n_rows, float *addition_out)
+{
+    namespace lp = dmx::dlplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_mstep_doublets",
+                         lp::check_mstep(ambient_facts(c, c->have_probs), c->have_post, pools, power, min_pair_posterior, n_rows, post_rows), pools,
+                         {nullptr, nullptr, nullptr, nullptr, nullptr}, plan));
+    DMX_TRY(dmx::run_mstep_doublets_from_host(c, power, min_pair_posterior, plan, post_rows, lp::pair_options(c->B, pools)));
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int dmx_run_iterations(dmx_ctx *c, int n_iterations, float lo, float hi, float power)

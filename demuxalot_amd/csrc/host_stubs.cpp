@@ -21,6 +21,7 @@
 #include "estep_ambient_grid.h"
 #include "estep_pair_shares.h"
 #include "estep_pools.h"
+#include "mstep_doublets.h"
 
 // ------------------------------------------------------------------------------------
 // HIP runtime
@@ -183,6 +184,15 @@ const float *ambient_run_alpha(const AmbientRun &) { return nullptr; }
 const float *ambient_run_soup(const AmbientRun &) { return nullptr; }
 int run_mstep_ambient(dmx_ctx *, float, const float *, const float *) { return 0; }  // (validated by dmx_mstep_ambient / dmx_em_ambient; nothing is written)
 int run_mstep_ambient_from_host(dmx_ctx *, float, const float *, const float *, float, float) { return 0; }
+struct DoubletRun {};
+void DoubletRunDeleter::operator()(DoubletRun *run) const { delete run; }
+int prepare_doublet_run(dmx_ctx *, const PoolsRun &, long long, DoubletRunPtr &run)
+{
+    run.reset(new DoubletRun);
+    return 0;
+}
+int run_mstep_doublets(dmx_ctx *, float, float, DoubletRun &) { return 0; }  // (validated by dmx_em_doublets; nothing is written)
+int run_mstep_doublets_from_host(dmx_ctx *, float, float, const PoolsPlan &, const float *, long long) { return 0; }  // (validated by dmx_mstep_doublets)
 int run_estep_ambient_grid(dmx_ctx *, const PoolsPlan &, const AmbientGridScoring &) { return 0; }  // (validated by dmx_estep_ambient_grid / _marginal; nothing is written)
 int run_estep_pair_shares(dmx_ctx *, const PoolsPlan &, const PairSharesScoring &) { return 0; }  // (validated by dmx_estep_pair_shares; nothing is written)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)

@@ -1267,6 +1267,84 @@ class Demultiplexer:
                 }
                 genotype_addition = ctx.mstep_ambient(alpha, Demultiplexer.contribution_power, p_genotype_clip, ambient=ambient)
 
+    @staticmethod
+    def _doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors, who):
+        """What the entries that learn from doublets refuse and resolve: the _PoolSetup."""
+        assert not Demultiplexer.aggregate_on_snps, 'pooled posteriors are float32; aggregate_on_snps yields float64 posteriors'
+        assert 0 <= doublet_prior < 1
+        assert (barcode2pool is None) == (pool2donors is None), 'barcode2pool and pool2donors come together'
+        if not (np.isfinite(min_pair_posterior) and min_pair_posterior > 0):
+            raise ValueError(f'{who}: min_pair_posterior must be finite and above 0, not {min_pair_posterior!r}')
+        return _pool_setup(genotypes, barcode_handler, doublet_prior, barcode2pool, pool2donors, who)
+
+    @staticmethod
+    def learn_genotypes_from_doublets(chromosome2compressed_snp_calls,
+                                      genotypes,
+                                      barcode_handler,
+                                      n_iterations=5,
+                                      p_genotype_clip=0.01,
+                                      doublet_prior=0.35,
+                                      min_pair_posterior=1e-3,
+                                      barcode2pool=None,
+                                      pool2donors=None):
+        """(not in the reference) learn_genotypes that also learns from the droplets it recognises as doublets: the loop of
+        learn_genotypes_in_pools whose M-step credits each donor of a pair option 'A+B' with its share of every call of the
+        barcode, r = genotype_prob[v, A] / (genotype_prob[v, A] + genotype_prob[v, B]) - the donor's responsibility for the call in
+        the even mixture the pair is scored with -, weighted by the pair's posterior.  The reference learns from the singlet
+        columns only, so with doublet_prior = 0.35 a third of a loaded lane teaches nothing.  With
+        doublet_prior = 0, or min_pair_posterior above 1, the result is learn_genotypes_in_pools' (exact mode) bit for bit.  The
+        whole loop runs on the GPU (dmx_em_doublets); its sums are float64 in the reference's order whatever DEMUXALOT_AMD_ESTEP
+        says.
+        :param min_pair_posterior: a pair option is credited when its posterior is at least this (finite, above 0); the pairs
+            left out at the default would have added at most 1e-6 to a weight
+        :param barcode2pool, pool2donors: as learn_genotypes_in_pools takes them (both or neither); without them every barcode is
+            scored against all donors
+        :return: learnt genotypes (betas = raw betas + the addition used by the last E-step) and the posteriors of the last
+            iteration: probs_df as learn_genotypes returns it, or with pools a PooledPosteriors.
+        ValueError: a threshold that is not finite or not above 0, more than 1024 options without pools."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        setup = Demultiplexer._doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors,
+                                                      'learn_genotypes_from_doublets')
+        with shared_context_lock:
+            ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
+                                          fetch_betas=False)
+            out = ctx.em_doublets(n_iterations, p_genotype_clip, setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty,
+                                  min_pair_posterior, contribution_power=Demultiplexer.contribution_power, fetch_logits=setup.pooled,
+                                  fetch_addition=False)
+            learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
+        return genotypes._with_betas(learnt_betas, _take=True), _framed_posteriors(setup, barcode_handler, out, None)
+
+    @staticmethod
+    def staged_genotype_learning_from_doublets(chromosome2compressed_snp_calls,
+                                               genotypes,
+                                               barcode_handler,
+                                               n_iterations=5,
+                                               p_genotype_clip=0.01,
+                                               doublet_prior=0.35,
+                                               min_pair_posterior=1e-3,
+                                               barcode2pool=None,
+                                               pool2donors=None):
+        """Generator over the iterations of learn_genotypes_from_doublets, shaped like staged_genotype_learning_in_pools: yields
+        (posteriors, debug dict with 'genotype_prior', 'genotype_addition'); the posteriors are a PooledPosteriors with pools and
+        probs_df without, the yielded addition is the one the iteration's E-step used.  The EM state lives on the GPU between
+        yields, in a device context private to this generator."""
+        setup = Demultiplexer._doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors,
+                                                      'staged_genotype_learning_from_doublets')
+        pools = (setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty)
+
+        with _generator_context() as ctx:
+            _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
+            genotype_addition = np.zeros_like(prior_betas)
+            ctx.set_addition(None)
+            for _iteration in range(n_iterations):
+                ctx.probs_from_betas(p_genotype_clip, fetch=False)
+                out = ctx.estep_pools(*pools, fetch_logits=setup.pooled, resident=True)
+                yield _framed_posteriors(setup, barcode_handler, out, None), {
+                    'genotype_prior': prior_betas,
+                    'genotype_addition': genotype_addition,
+                }
+                genotype_addition = ctx.mstep_doublets(*pools, out['probs'], min_pair_posterior, Demultiplexer.contribution_power)
+
     # ------------------------------------------------------------------------------------
     @staticmethod
     def _doublet_penalties(n_genotypes: int, doublet_prior: float) -> np.ndarray:

@@ -802,6 +802,31 @@ class DeviceContext:
                                  tail=lambda out: (ptr(out['addition']), ptr(out['ambient'])), fetch_addition=bool(fetch_addition),
                                  ambient=True, dense=True)
 
+    def em_doublets(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, min_pair_posterior=1e-3,
+                    contribution_power=2., fetch_logits=True, fetch_probs=True, fetch_addition=True):
+        """n_iterations of P-step, dense pooled E-step and the M-step that also learns from doublet posteriors, on the device
+        (include/demux_hip_debug.h: dmx_em_doublets): em_pools() whose M-step credits each donor of a pair option at or above
+        min_pair_posterior with its share of every call, r = own / (own + other), weighted by the pair's posterior.  The sums are
+        float64 in the reference's order whatever the E-step mode.  Returns em_pools()'s dict.  get_learnt_betas() and get_probs()
+        (the dense [B, G] singlet posteriors) work afterwards."""
+        return self._pooled_call(self._lib.dmx_em_doublets, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 head=(int(n_iterations), *self.clip_bounds(p_genotype_clip)),
+                                 middle=(float(contribution_power), float(min_pair_posterior)),
+                                 tail=lambda out: (ptr(out['addition']),), fetch_addition=bool(fetch_addition), dense=True)
+
+    def mstep_doublets(self, pools, pool_of_barcode, with_doublets, pair_penalty, post_rows, min_pair_posterior=1e-3, contribution_power=2.,
+                       fetch=True):
+        """The M-step that also learns from doublet posteriors (include/demux_hip_debug.h: dmx_mstep_doublets) on the resident dense
+        posteriors and the table of the last P-step: post_rows is the compact 'probs' estep_pools(..., resident=True) returned for
+        the same pools.  Returns the addition float32[V, G] (None without fetch); it becomes the context's, as after mstep()."""
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, False, False)
+        post_rows = as_c(post_rows, np.float32)
+        assert post_rows.ndim == 1, 'the compact rows are one-dimensional'
+        addition = np.empty((self.V, self.G), dtype=np.float32) if fetch else None
+        check(self._lib.dmx_mstep_doublets(self._h, float(contribution_power), float(min_pair_posterior), int(bool(with_doublets)), *pool_args,
+                                           ptr(post_rows), len(post_rows), ptr(addition)))
+        return addition
+
     def estep_ambient_grid(self, pools, pool_of_barcode, with_doublets, pair_penalty, alphas, p_genotype_clip=0.01, ambient=None,
                            fetch_logits=True, fetch_probs=True, fetch_alpha_index=True, fetch_profile=False, over_grid='max', log_weights=None,
                            fetch_alpha_mean=True):

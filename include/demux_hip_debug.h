@@ -757,6 +757,53 @@ int dmx_em_ambient(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_
                    int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
                    float *addition_out /* nullable, float32[V, G] */, float *ambient_out /* nullable, [V] */);
 
+/* ------------------------------------------------------------------------- *
+ * Learning from doublet posteriors (product API; csrc/mstep_doublets.hip).  dmx_em_pools' loop with one change per
+ * iteration: the M-step credits each donor of a pair option of the barcode's row with its share of every call.  The E-step is
+ * dmx_em_pools' dense pooled pass; it leaves the compact rows post[row_ptr[b] ...] in pool-local option order (singlets, then the
+ * pairs i < j, i-major) and the dense singlets dense[B, G].  For variant v, donor column g and the calls c of v in stored
+ * variant-major order, b = cb_c, in float32 without contraction:
+ *     credit = dense[b, g] when it is live (above 2^-80 at power 2, not 0 at another power), else +0
+ *     for every pair option k of b's row with post[k] >= min_pair_posterior that contains g, in the row's option order, h its other donor:
+ *         own = prob[v, g];  other = prob[v, h]
+ *         r   = own == 0 ? 0.0f : own / (own + other)             IEEE float32 division, correctly rounded
+ *         credit = credit + post[k] * r
+ *     w   = (credit * keep_c) ^ power                             power 2: one float32 product w * w; another power:
+ *                                                                f32(pow(f64(base), f64(power)))
+ *     addition[v, g] = f32( sum over c of f64(w) )               one float64 accumulator, in call order
+ * prob is the table the E-step read; r is the donor's responsibility for the call in the even mixture (p_g + p_h) / 2 the pair was
+ * scored with.  A pair below min_pair_posterior is not credited: that is part of the contract.  min_pair_posterior is finite and
+ * above 0; above 1 it credits no pair, and then, as with with_doublets == 0, the loop is dmx_em_pools with exact additions bit for
+ * bit (another power than 2: to float32 accuracy).  A barcode in no pool contributes nothing.
+ * There is ONE arithmetic: the sums are float64 in the reference's order whatever dmx_set_estep_mode / dmx_set_exact_additions say;
+ * the fixed-point, tile-major and incremental M-step forms do not apply (the weights change with the table).
+ *   dmx_em_doublets   n_iterations >= 1 of: genotype_prob from betas + addition clipped to [lo, hi] (the addition starts at 0), the
+ *               dense pooled E-step, the list of the live pairs, the M-step above - all on the device, the M-step after the last
+ *               E-step left out; the pools' round trip is paid once.  Outputs (each nullable): what dmx_em_pools returns.  (call
+ *               order: a problem and dmx_set_betas / dmx_set_prior_betas)
+ *   dmx_mstep_doublets   stateless: the M-step above of the context's resident dense posteriors (dmx_estep_pools_resident), the table
+ *               of the last P-step and the compact rows post_rows float32[n_rows] that E-step returned, with the pools it was called
+ *               with (n_rows == row_ptr[B]).  The addition becomes the context's and is copied to addition_out (nullable,
+ *               float32[V, G]).  DMX_ERR_INVALID without a problem, a table or posteriors.
+ * Checked on the host before anything is uploaded or launched (csrc/doublet_learning_plan.h).  DMX_ERR_INVALID: n_iterations < 1, a
+ * power or a threshold that is not finite or not above 0, rows of another length than row_ptr[B], a row value that is not finite or
+ * outside [0, 1], everything dmx_estep_pools refuses so.  DMX_ERR_UNSUPPORTED: a communicator attached or more than one rank, a pool
+ * of more than 1024 options, a genotype table in a padded exchange layout.  The E-steps and the list's build are counted in the
+ * DMX_T_ESTEP slot (a span each), the walk of the M-step in DMX_T_MSTEP, its combining pass and the redo in DMX_T_MCOMBINE;
+ * dmx_get_redo_count returns the sums the last M-step redid in call order.
+ * ------------------------------------------------------------------------- */
+int dmx_em_doublets(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools,
+                    const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                    const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */, float power,
+                    float min_pair_posterior,
+                    float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                    int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                    float *addition_out /* nullable, float32[V, G] */);
+int dmx_mstep_doublets(dmx_ctx *ctx, float power, float min_pair_posterior, int with_doublets, int32_t n_pools,
+                       const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                       const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                       const float *post_rows /* [n_rows] */, int64_t n_rows, float *addition_out /* nullable, float32[V, G] */);
+
 #ifdef __cplusplus
 }
 #endif
