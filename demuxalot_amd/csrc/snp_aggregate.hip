@@ -35,7 +35,9 @@ namespace {
 using dmx::fail;
 using namespace dmx::scratch;
 
-constexpr int SNP_MAX_OPTIONS = 256 * 33;  // doublets of 128 genotypes: 8256 options, about 100 KB of LDS per barcode
+// doublets of 128 genotypes: 8256 options, about 100 KB of LDS per barcode.  (The widest form, 33 options per thread, has room
+// for 8448; the limit is the widest table that is tested, and one more genotype with doublets is refused.)
+constexpr int SNP_MAX_OPTIONS = 128 * 129 / 2;
 
 // ---- layout -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pair_keys(const unsigned long long *__restrict__ vb_keys, const int *__restrict__ v2snp,
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(256) void k_estep_snp(SnpArgs a)
     }
 }
 
-// More than 1024 options (doublets of 45+ genotypes): one WORKGROUP walks one barcode, thread t holds options
+// More than 1024 options (doublets of 45+ genotypes, singlets of 1025+): one WORKGROUP walks one barcode, thread t holds options
 // t + 256 s.  Same arithmetic as k_estep_snp; the row maxima go through LDS, the numpy-ordered sums are done by
 // wavefront 0 over the LDS row.  LDS: K float64 + K float32.
 template <int A>
@@ -450,7 +452,9 @@ __global__ __launch_bounds__(256) void k_estep_snp_block(SnpArgs a)
 }
 
 // ---- M-step on float64 posteriors -----------------------------------------------------------------------------
-// one wavefront per variant walks all its calls in order (items in order = CSC order), lane g (+64 s) = genotype
+// one wavefront per (variant, group of 64 A columns) walks all the variant's calls in order (items in order = CSC order),
+// lane g (+64 s) = genotype column inside the group (blockIdx.y).  G <= 1024 is one group; beyond that A = 16 and every
+// group of 1024 columns has wavefronts of its own - a column's additions and their order do not depend on the grouping.
 template <int A, bool SQUARE>
 __global__ __launch_bounds__(256) void k_mstep_f64(const long long *__restrict__ item_ptr, const long long *__restrict__ item_start,
                                                    const int *__restrict__ item_len, const uint2 *__restrict__ calls,
@@ -458,6 +462,7 @@ __global__ __launch_bounds__(256) void k_mstep_f64(const long long *__restrict__
                                                    float *__restrict__ add, double *__restrict__ sums)
 {
     const int lane = threadIdx.x & 63;
+    const int g0 = (int)blockIdx.y * (64 * A) + lane;  // first column of this lane
     const long long v = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (v >= V) return;
     double acc[A];
@@ -471,7 +476,7 @@ __global__ __launch_bounds__(256) void k_mstep_f64(const long long *__restrict__
             const double keep = (double)__uint_as_float(d.y);  // float32 (1 - e), promoted as numpy does
 #pragma unroll
             for (int s = 0; s < A; s++) {
-                const int g = lane + 64 * s;
+                const int g = g0 + 64 * s;
                 if (g >= G) continue;
                 double cterm = post[(size_t)d.x * K + g] * keep;
                 cterm = SQUARE ? cterm * cterm : pow(cterm, power);
@@ -481,7 +486,7 @@ __global__ __launch_bounds__(256) void k_mstep_f64(const long long *__restrict__
     }
 #pragma unroll
     for (int s = 0; s < A; s++) {
-        const int g = lane + 64 * s;
+        const int g = g0 + 64 * s;
         if (g < G) {
             add[v * G + g] = (float)acc[s];
             if (sums) sums[v * G + g] = acc[s];  // the unrounded float64 sum (barcode-sharded runs add these over ranks)
@@ -519,7 +524,7 @@ int launch_snp_block(dmx_ctx *c, const SnpArgs &a)
 template <int A>
 void launch_m64(dmx_ctx *c, double power, double *sums)
 {
-    const dim3 grid((unsigned)((c->V + 3) / 4)), block(256);
+    const dim3 grid((unsigned)((c->V + 3) / 4), (unsigned)((c->G + 64 * A - 1) / (64 * A))), block(256);
     if (power == 2.0)
         hipLaunchKernelGGL((k_mstep_f64<A, true>), grid, block, 0, c->stream, c->d_item_ptr.p, c->d_item_start.p, c->d_item_len.p, c->d_csc.p,
                            c->d_post64.p, c->V, c->G, (long long)c->K, power, c->d_add.p, sums);
@@ -672,7 +677,7 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
     else if (K <= 256) rc = launch_snp<4>(c, a, pairs_on);
     else if (K <= 512) rc = launch_snp<8>(c, a, pairs_on);
     else if (K <= 1024) rc = launch_snp<16>(c, a, pairs_on);
-    else if (K <= 256 * 6) rc = launch_snp_block<6>(c, a);  // K > 1024 is always the doublet table
+    else if (K <= 256 * 6) rc = launch_snp_block<6>(c, a);  // (doublets of 45+ genotypes, or singlets of 1025+: the block form reads g1 == g2)
     else if (K <= 256 * 9) rc = launch_snp_block<9>(c, a);
     else if (K <= 256 * 12) rc = launch_snp_block<12>(c, a);
     else if (K <= 256 * 17) rc = launch_snp_block<17>(c, a);
@@ -696,6 +701,8 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
         return fail(DMX_ERR_UNSUPPORTED, "the float64 M-step of aggregate_on_snps runs on a context without a communicator (its sums are added "
                                          "over the ranks by the caller: dmx_mstep_f64_sums)");
     HIP_TRY(hipSetDevice(c->device));
+    if (!(contribution_power > 0.0 && contribution_power <= 1.7976931348623157e308))  // (NaN fails the comparison)
+        return fail(DMX_ERR_INVALID, "the contribution power must be finite and above 0");
     if (!c->have_problem || !c->have_post64) return fail(DMX_ERR_INVALID, "call order: dmx_estep_snp before dmx_mstep_f64");
     if (c->attached()) return fail(DMX_ERR_UNSUPPORTED, "the float64 M-step does not run the device-side exchange: barcode-sharded "
                                                        "aggregate_on_snps runs add dmx_mstep_f64_sums over ranks on the host");
@@ -705,7 +712,7 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
     else if (G <= 128) launch_m64<2>(c, contribution_power, sums);
     else if (G <= 256) launch_m64<4>(c, contribution_power, sums);
     else if (G <= 512) launch_m64<8>(c, contribution_power, sums);
-    else launch_m64<16>(c, contribution_power, sums);
+    else launch_m64<16>(c, contribution_power, sums);  // (G > 1024: one column group of 1024 per blockIdx.y)
     HIP_TRY(hipGetLastError());
     c->add_partial = false;
     c->add_is_zero = false;

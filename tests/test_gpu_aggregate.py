@@ -142,6 +142,9 @@ def test_float32_and_float64_e_steps_with_different_option_counts_on_one_context
             ctx.mstep(2.)
         add64 = ctx.mstep_f64(2.)
         assert add64.shape == (p.n_variants, G) and np.isfinite(add64).all()
+        from tests.aggregate_problems import mstep_f64_restated  # the M-step is deterministic given the device's own posteriors
+        fio.assert_bitwise(add64, mstep_f64_restated(np.asarray(p.variant_id), np.asarray(p.compressed_cb), np.asarray(p.p_base_wrong, dtype=np.float32),
+                                                     probs64, p.n_variants, G, 2.), 'float64 M-step after E-steps of two option counts')
         logits32b, probs32b = ctx.estep(Demultiplexer._doublet_penalties(G, 0.), with_doublets=False)  # K = 5 again
         fio.assert_bitwise(probs32b, probs32, 'float32 E-step repeated after the aggregate one')
         with pytest.raises(DemuxHipError):  # the float64 posteriors belong to K = 15
