@@ -154,7 +154,7 @@ int close_dense_pools_pass(dmx_ctx *c, float power)
 {
     // the bitmap and the codes of the M-step from the [B, G] matrix, with the floor a full-table E-step of this power takes
     // (dmx_steps.cpp: fill_estep_args); the context as run_estep leaves it, without statistics of the dense calls
-    const float floor = power == 2.0f ? NZ_FLOOR_SQUARE : 0.0f;
+    const float floor = live_floor_float64(power);
     HIP_TRY(launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->G, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
     c->post_gathered = false;
     c->dense_stat_valid = false;

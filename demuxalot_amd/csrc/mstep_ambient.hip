@@ -6,43 +6,34 @@
 // (power 2: one float32 product; another power: the float64 pow of the float32 base, rounded to float32 once)
 // r is the probability that the call came from the donor and not from the soup; with alpha[b] == 0 it is 1 exactly (own != 0) and w is
 // the plain M-step's.  The weight depends on the table of the iteration, so nothing of the fixed-point, tile-major or incremental
-// forms applies: there is one arithmetic, the float64 sum in the reference's order.
+// forms applies: there is one arithmetic, the float64 sum in the reference's order, in the frame of mstep_weighted.h.  This file holds
+//   ambient_weight      the contract's line for one (call, column)
 //   k_mstep_ambient     a wavefront per (work item, 64-column word) walks the item's records in order and leaves the float64 sum of
-//                       every column of its word: in the addition when the variant has this item only, else in the item's partial row
-//   k_mcombine_ambient  the variants of several items: the partial sums added in item order, accepted when no float32 rounding
-//                       boundary lies within 4 n u S of the total (the rule of kernels.hip: k_mcombine), else queued
-//   k_mredo_ambient     a wavefront per queued (variant, column): all calls of the variant, in order, into ONE accumulator
+//                       every column of its word
+//   k_mredo_ambient     the frame's redo of the queued sums with this weight
 // Per-call data - the record, alpha[cb], the bitmap word, and for a call with one live posterior in the word (nearly all of them)
 // the posterior, the table entry and the whole weight - are fetched and computed a call per lane and broadcast by v_readlane; a
 // 4-byte uniform request per call is what bounded dmx_ambient_profile's first form.  All stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "ambient_profile.h"
 #include "device_scratch.h"
 #include "mstep_ambient.h"
+#include "mstep_weighted_device.h"
 
 namespace dmx {
 
 namespace {
 
-// the contract's line for one (call, column): three roundings, one correctly rounded division, the product, the power.  The
-// reference's power of 2 is one float32 product.  Another power is f32(pow(f64(c), f64(power))): a float32 `**` is libm's powf or a
-// vector library's in numpy, whichever the host has, and the device's powf is a third (tests/test_gpu_parity.py compares
-// dmx_mstep's other powers to float32 accuracy for that reason) - the float64 pow rounded once is what all of them approximate, and
-// what the restatement can state.
+// the contract's line for one (call, column): three roundings, one correctly rounded division, the product, the power
 template <bool SQUARE>
 __device__ __forceinline__ float ambient_weight(float post, float keep, float q, float soup, float alpha, float power)
 {
     const float own = q * (1.0f - alpha);
     const float mix = own + soup * alpha;
     const float r = own == 0.0f ? 0.0f : own / mix;  // alpha == 1 (and ambient == 0: 0 / 0): a droplet that is all soup teaches nothing
-    const float c = (post * keep) * r;
-    return SQUARE ? c * c : (float)pow((double)c, (double)power);
+    return power_weight<SQUARE>((post * keep) * r, power);
 }
-
-__device__ __forceinline__ float lane_value(float x, int i) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), i)); }
 
 // One wavefront per (item of a.m.order, word w of the G columns): lane l owns the float64 accumulator of column 64 w + l.  A chunk
 // of 64 records is loaded a call per lane; a call whose bitmap word has ONE bit set has its whole contribution computed by its own
@@ -53,31 +44,23 @@ __device__ __forceinline__ float lane_value(float x, int i) { return __builtin_b
 template <bool SQUARE>
 __global__ __launch_bounds__(256) void k_mstep_ambient(AmbientMstepArgs x)
 {
-    const MstepArgs &a = x.m;
+    const MstepArgs &a = x.w.m;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int G = a.G;
-    const int W = (G + 63) >> 6;
-    const long long slot = (long long)blockIdx.x * 4 + wave;
-    if (slot >= a.n_items * W) return;
-    const long long islot = slot / W;
-    const int w = (int)(slot - islot * W);
-    const long long item = a.order[islot];
-    const int n = a.item_len[item];
-    const long long v = a.item_variant[item];
-    const uint2 *__restrict__ calls = a.calls + a.item_start[item];
-    const int g = lane + 64 * w;
-    const float *__restrict__ prob_row = x.prob + (size_t)v * G;
-    const float q_mine = g < G ? prob_row[g] : 0.0f;
-    const float soup = x.ambient[v];
+    const int W = (a.G + 63) >> 6;
+    const long long slot = wave_slot();
+    if (slot >= walk_slots(x.w)) return;
+    const WalkSlot s = walk_slot(x.w, slot);
+    const int w = s.w, g = s.g;
+    const float q_mine = g < a.G ? s.prob_row[g] : 0.0f;
+    const float soup = x.ambient[s.v];
     double acc = 0.0;
-    for (int c0 = 0; c0 < n; c0 += 64) {
+    for (int c0 = 0; c0 < s.n; c0 += 64) {
         const int ci = c0 + lane;
         uint2 d = make_uint2(0u, 0u);
         float alpha = 0.0f;
         unsigned long long m = 0ull;
-        if (ci < n) {
-            d = calls[ci];
+        if (ci < s.n) {
+            d = s.calls[ci];
             alpha = x.alpha[d.x];
             m = a.nz[(size_t)d.x * W + w];
         }
@@ -86,7 +69,7 @@ __global__ __launch_bounds__(256) void k_mstep_ambient(AmbientMstepArgs x)
         const int col = one ? __builtin_ctzll(m) : 0;  // inside the word
         float contribution = 0.0f;
         if (one)
-            contribution = ambient_weight<SQUARE>(a.post[(size_t)d.x * a.K + 64 * w + col], keep, prob_row[64 * w + col], soup, alpha, a.power);
+            contribution = ambient_weight<SQUARE>(a.post[(size_t)d.x * a.K + 64 * w + col], keep, s.prob_row[64 * w + col], soup, alpha, a.power);
         unsigned long long pending = __ballot(m != 0ull);
         const unsigned long long single = __ballot(one);
         while (pending) {
@@ -98,168 +81,46 @@ __global__ __launch_bounds__(256) void k_mstep_ambient(AmbientMstepArgs x)
                 if (lane == owner) acc += (double)c;
             } else {
                 const unsigned cb = (unsigned)__builtin_amdgcn_readlane((int)d.x, i);
-                const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, i);
-                const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), i);
-                const unsigned long long bits = ((unsigned long long)hi << 32) | lo;
+                const unsigned long long bits = lane_value(m, i);
                 if ((bits >> lane) & 1ull)
                     acc += (double)ambient_weight<SQUARE>(a.post[(size_t)cb * a.K + g], lane_value(keep, i), q_mine, soup, lane_value(alpha, i), a.power);
             }
         }
     }
-    if (g >= G) return;
-    if (a.item_ptr[v + 1] - a.item_ptr[v] == 1) a.out32[(size_t)v * G + g] = (float)acc;  // (what the combining pass would form: 0.0 + acc)
-    else a.partial[(size_t)item * G + g] = acc;
+    walk_store(x.w, s, acc);
 }
 
-// k_mcombine (kernels.hip) for the float64 partials of k_mstep_ambient, always with the redo queue: a thread per (variant, column)
-__global__ __launch_bounds__(256) void k_mcombine_ambient(AmbientMstepArgs x)
-{
-    const MstepArgs &a = x.m;
-    const long long total = x.V * a.G;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long v = i / a.G;
-        const int g = (int)(i - v * a.G);
-        const long long it0 = a.item_ptr[v], it1 = a.item_ptr[v + 1];
-        if (it1 - it0 == 1) continue;  // written by the item's own wavefront
-        double s = 0.0;
-        for (long long it = it0; it < it1; it++) s += a.partial[(size_t)it * a.G + g];
-        a.out32[i] = (float)s;  // (a variant without calls: +0; a NaN stands: no order of the additions removes it)
-        if (it1 - it0 > 1 && s > 0.0) {
-            const long long n = a.item_start[it1 - 1] + a.item_len[it1 - 1] - a.item_start[it0];
-            const double bound = 4.0 * (double)n * 1.1102230246251565e-16 * s;
-            const float f = (float)s;
-            const double lo = 0.5 * ((double)f + (double)nextafterf(f, 0.0f));  // rounding boundary towards zero
-            const double hi = 0.5 * ((double)f + (double)nextafterf(f, __builtin_inff()));
-            if (!(s - bound > lo && s + bound < hi)) {
-                const unsigned at = atomicAdd(&x.n_redo[0], 1u);
-                if (at < a.redo_cap) x.redo[at] = ((unsigned long long)v << 16) | (unsigned long long)g;
-            }
-        }
+// the weight object of a queued (variant, column): the table entry and the soup's profile are the sum's, the fraction the call's
+struct AmbientRedoWeight {
+    const AmbientMstepArgs &x;
+    int g;
+    float q, soup;
+    template <bool SQUARE>
+    __device__ __forceinline__ bool call(uint2 d, bool bit, float &c) const
+    {
+        const MstepArgs &a = x.w.m;
+        if (bit) c = ambient_weight<SQUARE>(a.post[(size_t)d.x * a.K + g], __uint_as_float(d.y), q, soup, x.alpha[d.x], a.power);
+        return bit;
     }
-}
+};
 
-// The queued sums as the reference forms them.  A wavefront per (variant, column): 64 calls at a time, a call per lane - record,
-// bitmap word, posterior, fraction, weight -, then the live contributions added in call order into one accumulator that every lane
-// carries.
 template <bool SQUARE>
 __global__ __launch_bounds__(256) void k_mredo_ambient(AmbientMstepArgs x)
 {
-    const MstepArgs &a = x.m;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int W = (a.G + 63) >> 6;
-    const unsigned long long queued = x.n_redo[0];
-    const unsigned long long count = queued < a.redo_cap ? queued : a.redo_cap;
-    for (unsigned long long e = (unsigned long long)blockIdx.x * 4 + wave; e < count; e += (unsigned long long)gridDim.x * 4) {
-        const unsigned long long entry = x.redo[e];
-        const long long v = (long long)(entry >> 16);
-        const int g = (int)(entry & 0xFFFFull);
-        const long long it0 = a.item_ptr[v], it1 = a.item_ptr[v + 1];
-        const long long first = a.item_start[it0];
-        const long long n = a.item_start[it1 - 1] + a.item_len[it1 - 1] - first;
-        const uint2 *__restrict__ calls = a.calls + first;
-        const float q = x.prob[(size_t)v * a.G + g];
-        const float soup = x.ambient[v];
-        double acc = 0.0;
-        for (long long c0 = 0; c0 < n; c0 += 64) {
-            float c = 0.0f;
-            bool live = false;
-            if (c0 + lane < n) {
-                const uint2 d = calls[c0 + lane];
-                live = (a.nz[(size_t)d.x * W + (g >> 6)] >> (g & 63)) & 1ull;
-                if (live) c = ambient_weight<SQUARE>(a.post[(size_t)d.x * a.K + g], __uint_as_float(d.y), q, soup, x.alpha[d.x], a.power);
-            }
-            unsigned long long pending = __ballot(live);
-            while (pending) {
-                const int i = __builtin_ctzll(pending);
-                pending &= pending - 1ull;
-                acc += (double)lane_value(c, i);
-            }
-        }
-        if (lane == 0) a.out32[(size_t)v * a.G + g] = (float)acc;
-    }
+    mredo_weighted<SQUARE>(x.w, [&x](long long v, int g) { return AmbientRedoWeight{x, g, x.w.prob[(size_t)v * x.w.m.G + g], x.ambient[v]}; });
 }
 
 }  // namespace
 
-hipError_t launch_mstep_ambient(hipStream_t st, const AmbientMstepArgs &a)
-{
-    const long long W = (a.m.G + 63) / 64;
-    const long long slots = a.m.n_items * W;
-    if (slots == 0) return hipSuccess;
-    if (slots > 4ll * 0x7FFFFFFF) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((slots + 3) / 4)), block(256);
-    if (a.m.square)
-        hipLaunchKernelGGL((k_mstep_ambient<true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_mstep_ambient<false>), grid, block, 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_mcombine_ambient(hipStream_t st, const AmbientMstepArgs &a)
-{
-    const long long total = a.V * a.m.G;
-    if (total <= 0) return hipSuccess;
-    const hipError_t e = hipMemsetAsync(a.n_redo, 0, 2 * sizeof(unsigned), st);
-    if (e != hipSuccess) return e;
-    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 1 << 20);
-    hipLaunchKernelGGL(k_mcombine_ambient, dim3(grid), dim3(256), 0, st, a);
-    if (a.m.square)
-        hipLaunchKernelGGL((k_mredo_ambient<true>), dim3(512), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_mredo_ambient<false>), dim3(512), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
 int run_mstep_ambient(dmx_ctx *c, float power, const float *d_alpha, const float *d_soup)
 {
-    using namespace dmx::host;
-    const hipStream_t st = c->stream;
-    // the codes and the bitmap at the floor of a float64 sum (a fixed-point M-step may have asked the E-step for a higher one)
-    const float floor = live_floor_float64(power);
-    if (c->nz_floor > floor) {
-        HIP_TRY(launch_rebuild_nz(st, c->d_post.p, c->B, c->K, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
-        c->nz_floor = floor;
-        c->post_gathered = false;
-        c->nz_rebuilds++;
-    }
     AmbientMstepArgs a = {};
-    a.m.order = c->d_item_order.p;
-    a.m.item_start = c->d_item_start.p;
-    a.m.item_len = c->d_item_len.p;
-    a.m.calls = c->d_csc.p;
-    a.m.post = c->d_post.p;
-    a.m.nz = c->d_nz.p;
-    a.m.K = c->K;
-    a.m.post_bytes = (unsigned long long)c->B * (unsigned long long)c->K * 4ull;
-    a.m.partial = c->d_partial.p;
-    a.m.item_variant = c->d_item_variant.p;
-    a.m.item_ptr = c->d_item_ptr.p;
-    a.m.out32 = c->d_add.p;
-    a.m.n_items = c->n_items;
-    a.m.G = c->G;
-    a.m.square = (power == 2.0f);
-    a.m.power = power;
-    a.m.redo_cap = c->d_redo.n;
-    a.prob = c->d_prob.p;
+    DMX_TRY(begin_weighted_mstep(c, power, a.w));
     a.ambient = d_soup;
     a.alpha = d_alpha;
-    a.V = c->V;
-    a.redo = c->d_redo.p;
-    a.n_redo = c->d_n_redo.p;
-    c->add_is_zero = false;
-    c->add_partial = false;
-    c->incr_valid = false;  // (another form writes the addition: the kept fixed-point sums no longer describe it)
-    TimerSpan ev{nullptr, nullptr};
-    SpanGuard ev_guard{c, &ev};
-    timer_begin(c, DMX_T_MSTEP, &ev);
-    HIP_TRY(launch_mstep_ambient(st, a));
-    c->mstep_form = 1;
-    timer_end(c, DMX_T_MSTEP, ev);
-    timer_begin(c, DMX_T_MCOMBINE, &ev);
-    HIP_TRY(launch_mcombine_ambient(st, a));
-    timer_end(c, DMX_T_MCOMBINE, ev);
-    return 0;
+    return run_weighted_mstep(
+        c, a.w, [&a](hipStream_t st) { return launch_walk(st, k_mstep_ambient<true>, k_mstep_ambient<false>, a); },
+        [&a](hipStream_t st) { return launch_by_power(st, dim3(512), k_mredo_ambient<true>, k_mredo_ambient<false>, a); });
 }
 
 int run_mstep_ambient_from_host(dmx_ctx *c, float power, const float *alpha, const float *ambient, float lo, float hi)

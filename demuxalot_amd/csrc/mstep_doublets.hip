@@ -5,25 +5,23 @@
 //   for every pair option k of b's row with post[k] >= min_pair_posterior that contains g, in the row's option order, h its other donor:
 //       r = prob[v, g] == 0 ? 0 : prob[v, g] / (prob[v, g] + prob[v, h]);   credit = credit + post[k] r      (IEEE division)
 //   w = (credit keep_c) ^ power;   addition[v, g] = f32( sum over c of f64(w) )                    one accumulator, in call order
-// (power 2: one float32 product; another power: the float64 pow of the float32 base, rounded to float32 once - mstep_ambient.hip)
+// (power 2: one float32 product; another power: the float64 pow of the float32 base, rounded to float32 once - power_weight)
 // r is the donor's responsibility for the call in the even mixture (p_g + p_h) / 2 the pair was scored with.  The weight depends on the
 // table of the iteration, so nothing of the fixed-point, tile-major or incremental forms applies: one arithmetic, the float64 sum in
-// the reference's order.
+// the reference's order, in the frame of mstep_weighted.h.  This file holds
 //   k_live_pairs          a wavefront per barcode compacts the pair part of its row by ballot: <false> counts the options at or above
 //                         the threshold, <true> writes them as (g | h << 16, posterior bits) behind the scanned counts, in option order
-//   k_mstep_doublets      a wavefront per (work item, 64-column word), lane l owning the float64 sum of column 64 w + l - the structure
-//                         of k_mstep_ambient.  A call of a barcode without live pairs goes its way; a call of one with live pairs is
-//                         handled by the whole wavefront at its place in call order
-//   k_mcombine_doublets   the variants of several items: k_mcombine_ambient (the 4 n u S rule of kernels.hip: k_mcombine), by copy
-//   k_mredo_doublets      a wavefront per queued (variant, column): all calls of the variant, in order, into ONE accumulator
-// Per-call data - the record, the bitmap word, the two ends of the barcode's list - are fetched a call per lane and broadcast by
-// v_readlane (no uniform 4-byte request per call: DESIGN.md 4.6).  All stores are plain vector stores.
+//   k_mstep_doublets      a wavefront per (work item, 64-column word), lane l owning the float64 sum of column 64 w + l.  A call of a
+//                         barcode without live pairs goes k_mstep_ambient's way; a call of one with live pairs is handled by the whole
+//                         wavefront at its place in call order
+//   k_mredo_doublets      the frame's redo of the queued sums with this weight
+// and the list's buffers of a call (DoubletRun).  Per-call data - the record, the bitmap word, the two ends of the barcode's list - are
+// fetched a call per lane and broadcast by v_readlane (no uniform 4-byte request per call: DESIGN.md 4.6).  All stores are plain vector stores.
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "device_scratch.h"
 #include "mstep_doublets.h"
+#include "mstep_weighted_device.h"
 
 namespace dmx {
 
@@ -34,8 +32,7 @@ typedef unsigned long long ull;
 template <bool SQUARE>
 __device__ __forceinline__ float credit_weight(float credit, float keep, float power)
 {
-    const float c = credit * keep;
-    return SQUARE ? c * c : (float)pow((double)c, (double)power);
+    return power_weight<SQUARE>(credit * keep, power);
 }
 
 // the donor's share of a call in the even mixture of the pair (own + other: float32 addition commutes, so both donors of a pair divide
@@ -54,14 +51,6 @@ __device__ __forceinline__ void pair_terms(uint2 entry, const float *__restrict_
     term_h = posterior * responsibility(ph, pg);
     g = dg;
     h = dh;
-}
-
-__device__ __forceinline__ float lane_value(float x, int i) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), i)); }
-__device__ __forceinline__ ull lane_value(ull x, int i)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, i);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), i);
-    return ((ull)hi << 32) | lo;
 }
 
 // One wavefront per barcode: the pair options of its row, 64 per trip, a lane each; the options at or above the threshold keep their
@@ -110,29 +99,22 @@ constexpr int AHEAD = 4;  // list entries a call's own lane fetches with the rec
 template <bool SQUARE>
 __global__ __launch_bounds__(256) void k_mstep_doublets(DoubletMstepArgs x)
 {
-    const MstepArgs &a = x.m;
+    const MstepArgs &a = x.w.m;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int G = a.G;
-    const int W = (G + 63) >> 6;
-    const long long slot = (long long)blockIdx.x * 4 + wave;
-    if (slot >= a.n_items * W) return;
-    const long long islot = slot / W;
-    const int w = (int)(slot - islot * W);
-    const long long item = a.order[islot];
-    const int n = a.item_len[item];
-    const long long v = a.item_variant[item];
-    const uint2 *__restrict__ calls = a.calls + a.item_start[item];
-    const int g = lane + 64 * w;
-    const float *__restrict__ prob_row = x.prob + (size_t)v * G;
+    const int W = (a.G + 63) >> 6;
+    const long long slot = wave_slot();
+    if (slot >= walk_slots(x.w)) return;
+    const WalkSlot s = walk_slot(x.w, slot);
+    const int w = s.w, g = s.g;
+    const float *__restrict__ prob_row = s.prob_row;
     double acc = 0.0;
-    for (int c0 = 0; c0 < n; c0 += 64) {
+    for (int c0 = 0; c0 < s.n; c0 += 64) {
         const int ci = c0 + lane;
         uint2 d = make_uint2(0u, 0u);
         ull m = 0ull, first = 0ull;
         int n_live = 0;
-        if (ci < n) {
-            d = calls[ci];
+        if (ci < s.n) {
+            d = s.calls[ci];
             m = a.nz[(size_t)d.x * W + w];
             first = x.live_ptr[d.x];
             n_live = (int)(x.live_ptr[d.x + 1] - first);
@@ -210,86 +192,38 @@ __global__ __launch_bounds__(256) void k_mstep_doublets(DoubletMstepArgs x)
             if (credit != 0.0f) acc += (double)credit_weight<SQUARE>(credit, lane_value(keep, i), a.power);  // (+0 adds nothing)
         }
     }
-    if (g >= G) return;
-    if (a.item_ptr[v + 1] - a.item_ptr[v] == 1) a.out32[(size_t)v * G + g] = (float)acc;  // (what the combining pass would form: 0.0 + acc)
-    else a.partial[(size_t)item * G + g] = acc;
+    walk_store(x.w, s, acc);
 }
 
-// k_mcombine_ambient (mstep_ambient.hip) for this argument block: a thread per (variant, column), always with the redo queue
-__global__ __launch_bounds__(256) void k_mcombine_doublets(DoubletMstepArgs x)
-{
-    const MstepArgs &a = x.m;
-    const long long total = x.V * a.G;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long v = i / a.G;
-        const int g = (int)(i - v * a.G);
-        const long long it0 = a.item_ptr[v], it1 = a.item_ptr[v + 1];
-        if (it1 - it0 == 1) continue;  // written by the item's own wavefront
-        double s = 0.0;
-        for (long long it = it0; it < it1; it++) s += a.partial[(size_t)it * a.G + g];
-        a.out32[i] = (float)s;  // (a variant without calls: +0; a NaN stands: no order of the additions removes it)
-        if (it1 - it0 > 1 && s > 0.0) {
-            const long long n = a.item_start[it1 - 1] + a.item_len[it1 - 1] - a.item_start[it0];
-            const double bound = 4.0 * (double)n * 1.1102230246251565e-16 * s;
-            const float f = (float)s;
-            const double lo = 0.5 * ((double)f + (double)nextafterf(f, 0.0f));  // rounding boundary towards zero
-            const double hi = 0.5 * ((double)f + (double)nextafterf(f, __builtin_inff()));
-            if (!(s - bound > lo && s + bound < hi)) {
-                const unsigned at = atomicAdd(&x.n_redo[0], 1u);
-                if (at < a.redo_cap) x.redo[at] = ((unsigned long long)v << 16) | (unsigned long long)g;
-            }
+// the weight object of a queued (variant, column): the live singlet's posterior, then the barcode's list walked by the call's lane in
+// list order; a call whose credit stays +0 adds nothing
+struct DoubletRedoWeight {
+    const DoubletMstepArgs &x;
+    int g;
+    const float *__restrict__ prob_row;
+    template <bool SQUARE>
+    __device__ __forceinline__ bool call(uint2 d, bool bit, float &c) const
+    {
+        const MstepArgs &a = x.w.m;
+        float credit = 0.0f;
+        if (bit) credit = a.post[(size_t)d.x * a.K + g];
+        const ull l1 = x.live_ptr[d.x + 1];
+        for (ull t = x.live_ptr[d.x]; t < l1; t++) {
+            const uint2 pair = x.entries[t];
+            const int dg = (int)(pair.x & 0xFFFFu), dh = (int)(pair.x >> 16);
+            if (dg == g) credit = credit + __uint_as_float(pair.y) * responsibility(prob_row[dg], prob_row[dh]);
+            else if (dh == g) credit = credit + __uint_as_float(pair.y) * responsibility(prob_row[dh], prob_row[dg]);
         }
+        const bool live = credit != 0.0f;
+        if (live) c = credit_weight<SQUARE>(credit, __uint_as_float(d.y), a.power);
+        return live;
     }
-}
+};
 
-// The queued sums as the contract forms them.  A wavefront per (variant, column): 64 calls at a time, a call per lane - record, bitmap
-// bit, posterior, the barcode's list walked by the lane itself in list order, weight -, then the contributions added in call order
-// into one accumulator that every lane carries.
 template <bool SQUARE>
 __global__ __launch_bounds__(256) void k_mredo_doublets(DoubletMstepArgs x)
 {
-    const MstepArgs &a = x.m;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int W = (a.G + 63) >> 6;
-    const ull queued = x.n_redo[0];
-    const ull count = queued < a.redo_cap ? queued : a.redo_cap;
-    for (ull e = (ull)blockIdx.x * 4 + wave; e < count; e += (ull)gridDim.x * 4) {
-        const ull entry = x.redo[e];
-        const long long v = (long long)(entry >> 16);
-        const int g = (int)(entry & 0xFFFFull);
-        const long long it0 = a.item_ptr[v], it1 = a.item_ptr[v + 1];
-        const long long first = a.item_start[it0];
-        const long long n = a.item_start[it1 - 1] + a.item_len[it1 - 1] - first;
-        const uint2 *__restrict__ calls = a.calls + first;
-        const float *__restrict__ prob_row = x.prob + (size_t)v * a.G;
-        double acc = 0.0;
-        for (long long c0 = 0; c0 < n; c0 += 64) {
-            float c = 0.0f;
-            bool live = false;
-            if (c0 + lane < n) {
-                const uint2 d = calls[c0 + lane];
-                float credit = 0.0f;
-                if ((a.nz[(size_t)d.x * W + (g >> 6)] >> (g & 63)) & 1ull) credit = a.post[(size_t)d.x * a.K + g];
-                const ull l1 = x.live_ptr[d.x + 1];
-                for (ull t = x.live_ptr[d.x]; t < l1; t++) {
-                    const uint2 pair = x.entries[t];
-                    const int dg = (int)(pair.x & 0xFFFFu), dh = (int)(pair.x >> 16);
-                    if (dg == g) credit = credit + __uint_as_float(pair.y) * responsibility(prob_row[dg], prob_row[dh]);
-                    else if (dh == g) credit = credit + __uint_as_float(pair.y) * responsibility(prob_row[dh], prob_row[dg]);
-                }
-                live = credit != 0.0f;
-                if (live) c = credit_weight<SQUARE>(credit, __uint_as_float(d.y), a.power);
-            }
-            ull pending = __ballot(live);
-            while (pending) {
-                const int i = __builtin_ctzll(pending);
-                pending &= pending - 1ull;
-                acc += (double)lane_value(c, i);
-            }
-        }
-        if (lane == 0) a.out32[(size_t)v * a.G + g] = (float)acc;
-    }
+    mredo_weighted<SQUARE>(x.w, [&x](long long v, int g) { return DoubletRedoWeight{x, g, x.w.prob + (size_t)v * x.w.m.G}; });
 }
 
 }  // namespace
@@ -307,35 +241,6 @@ hipError_t launch_live_fill(hipStream_t st, const DoubletRows &rows, long long B
     if (B <= 0) return hipSuccess;
     if (B > 4ll * 0x7FFFFFFF) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_live_pairs<true>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rows, B, min_pair_posterior, nullptr, list.live_ptr, list.entries);
-    return hipGetLastError();
-}
-
-hipError_t launch_mstep_doublets(hipStream_t st, const DoubletMstepArgs &a)
-{
-    const long long W = (a.m.G + 63) / 64;
-    const long long slots = a.m.n_items * W;
-    if (slots == 0) return hipSuccess;
-    if (slots > 4ll * 0x7FFFFFFF) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((slots + 3) / 4)), block(256);
-    if (a.m.square)
-        hipLaunchKernelGGL((k_mstep_doublets<true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((k_mstep_doublets<false>), grid, block, 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_mcombine_doublets(hipStream_t st, const DoubletMstepArgs &a)
-{
-    const long long total = a.V * a.m.G;
-    if (total <= 0) return hipSuccess;
-    const hipError_t e = hipMemsetAsync(a.n_redo, 0, 2 * sizeof(unsigned), st);
-    if (e != hipSuccess) return e;
-    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 1 << 20);
-    hipLaunchKernelGGL(k_mcombine_doublets, dim3(grid), dim3(256), 0, st, a);
-    if (a.m.square)
-        hipLaunchKernelGGL((k_mredo_doublets<true>), dim3(512), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_mredo_doublets<false>), dim3(512), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
@@ -373,41 +278,10 @@ int run_mstep_doublets(dmx_ctx *c, float power, float min_pair_posterior, Double
 {
     using namespace dmx::host;
     const hipStream_t st = c->stream;
-    // the codes and the bitmap at the floor of a float64 sum (a fixed-point M-step may have asked the E-step for a higher one)
-    const float floor = live_floor_float64(power);
-    if (c->nz_floor > floor) {
-        HIP_TRY(launch_rebuild_nz(st, c->d_post.p, c->B, c->K, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
-        c->nz_floor = floor;
-        c->post_gathered = false;
-        c->nz_rebuilds++;
-    }
     DoubletMstepArgs a = {};
-    a.m.order = c->d_item_order.p;
-    a.m.item_start = c->d_item_start.p;
-    a.m.item_len = c->d_item_len.p;
-    a.m.calls = c->d_csc.p;
-    a.m.post = c->d_post.p;
-    a.m.nz = c->d_nz.p;
-    a.m.K = c->K;
-    a.m.post_bytes = (unsigned long long)c->B * (unsigned long long)c->K * 4ull;
-    a.m.partial = c->d_partial.p;
-    a.m.item_variant = c->d_item_variant.p;
-    a.m.item_ptr = c->d_item_ptr.p;
-    a.m.out32 = c->d_add.p;
-    a.m.n_items = c->n_items;
-    a.m.G = c->G;
-    a.m.square = (power == 2.0f);
-    a.m.power = power;
-    a.m.redo_cap = c->d_redo.n;
-    a.prob = c->d_prob.p;
+    DMX_TRY(begin_weighted_mstep(c, power, a.w));
     a.live_ptr = r.list.live_ptr;
     a.entries = r.list.entries;
-    a.V = c->V;
-    a.redo = c->d_redo.p;
-    a.n_redo = c->d_n_redo.p;
-    c->add_is_zero = false;
-    c->add_partial = false;
-    c->incr_valid = false;  // (another form writes the addition: the kept fixed-point sums no longer describe it)
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
     timer_begin(c, DMX_T_ESTEP, &ev);  // the list: a pass over the E-step's rows
@@ -415,14 +289,9 @@ int run_mstep_doublets(dmx_ctx *c, float power, float min_pair_posterior, Double
     DMX_TRY(scratch::exclusive_scan(r.sc, r.list.count, r.list.live_ptr, 0ull, (size_t)c->B + 1, rocprim::plus<unsigned long long>(), st));
     HIP_TRY(launch_live_fill(st, r.rows, c->B, min_pair_posterior, r.list));
     timer_end(c, DMX_T_ESTEP, ev);
-    timer_begin(c, DMX_T_MSTEP, &ev);
-    HIP_TRY(launch_mstep_doublets(st, a));
-    c->mstep_form = 1;
-    timer_end(c, DMX_T_MSTEP, ev);
-    timer_begin(c, DMX_T_MCOMBINE, &ev);
-    HIP_TRY(launch_mcombine_doublets(st, a));
-    timer_end(c, DMX_T_MCOMBINE, ev);
-    return 0;
+    return run_weighted_mstep(
+        c, a.w, [&a](hipStream_t s) { return launch_walk(s, k_mstep_doublets<true>, k_mstep_doublets<false>, a); },
+        [&a](hipStream_t s) { return launch_by_power(s, dim3(512), k_mredo_doublets<true>, k_mredo_doublets<false>, a); });
 }
 
 int run_mstep_doublets_from_host(dmx_ctx *c, float power, float min_pair_posterior, const PoolsPlan &plan, const float *rows, long long pair_options)

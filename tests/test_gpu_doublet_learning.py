@@ -225,6 +225,25 @@ def test_variants_of_several_work_items_are_summed_in_call_order():
     assert ctx.redo_count() >= len(differ), 'the sums at a rounding boundary were redone in call order'
 
 
+def test_both_weighted_forms_agree_where_their_weights_do():
+    """With no live pair the crediting M-step, and at fraction 0 the M-step under ambient fractions (the table has no zero entry: r is
+    exactly 1), are the plain float64 M-step of the dense posteriors: one combining rule (csrc/mstep_weighted.hip), so the same sums
+    queued and the same bits from both."""
+    p, rows, dense, _in_order, _of_partials = restated_tie()
+    assert (p['prob'] != 0).all(), 'a zero table entry would make r of the ambient form 0'
+    without = learning.doublet_addition(p['v'], p['cb'], p['e'], dense, rows, p['pools'], p['pool_of'], True, p['prob'], threshold=2.0)
+    ctx, got, _addition = tie_on_device()
+    penalty = pair_penalty(p['pools'], 0.35)
+    uncredited = ctx.mstep_doublets(p['pools'], p['pool_of'], True, penalty, got['probs'], min_pair_posterior=2.0)
+    redone = ctx.redo_count()
+    fio.assert_bitwise(uncredited, without, 'the crediting M-step without a live pair')
+    at_zero = ctx.mstep_ambient(np.zeros(p['B'], np.float32))
+    fio.assert_bitwise(at_zero, without, 'the M-step under ambient fractions at fraction 0')
+    print(f'sums redone in call order: {redone} and {ctx.redo_count()}')
+    assert ctx.redo_count() == redone, 'both forms queue the same sums'
+    ctx.mstep_doublets(p['pools'], p['pool_of'], True, penalty, got['probs'], TIE_THRESHOLD, fetch=False)  # (the shared context as tie_on_device left it)
+
+
 # ---- 5. the fused loop is the step-wise one; the context survives ------------------------------------------------
 def test_fused_equals_stepwise_and_the_context_survives():
     from demuxalot_amd.device import DeviceContext

@@ -163,6 +163,34 @@ def test_a_float64_form_rebuilds_grid_codes_once():
     assert np.array_equal(_bits(out[False][0]), _bits(out[True][0])), 'the exact additions behind rebuilt codes'
 
 
+def test_a_weighted_mstep_rebuilds_grid_codes_once():
+    """The M-step under ambient fractions behind an E-step that expected a fixed-point M-step (csrc/mstep_weighted.hip:
+    begin_weighted_mstep): the codes are rebuilt at 2^-80, one launch.  At fraction 0 and a table clipped at 0.01 the weight's r is
+    exactly 1, so the sums are the exact additions of the same posteriors - those of codes written at 2^-80 in the first place."""
+    p, G, doublets, pen, _betas = _problem('G64')
+    out = {}
+    for grid in (False, True):
+        ctx = _context('G64', grid, tiles='always')
+        try:
+            ctx.reset_timings()
+            ctx.probs_from_betas(0.01, fetch=False)
+            _logits, post = ctx.estep(pen, with_doublets=doublets, fetch_logits=False)
+            assert ctx.live_floor() == ((FLOOR_GRID if grid else FLOOR_F64), 0)
+            out[grid] = ctx.mstep_ambient(np.zeros(p.n_barcodes, np.float32)), ctx.live_floor()
+            if not grid:
+                _assert_not_vacuous('G64', post)  # (posteriors between the two floors: a skipped rebuild changes bits)
+                ctx.set_exact_additions(True)
+                exact = ctx.mstep()
+                assert ctx.mstep_form() == 'items' and ctx.live_floor() == (FLOOR_F64, 0)
+        finally:
+            ctx.close()
+    assert out[True][1] == (FLOOR_F64, 1) and out[False][1] == (FLOOR_F64, 0), (out[True][1], out[False][1])
+    assert np.isfinite(exact).all() and exact.max() > 0
+    assert np.array_equal(_bits(out[False][0]), _bits(out[True][0])), 'the weighted additions behind rebuilt codes'
+    assert np.array_equal(_bits(out[False][0]), _bits(exact)), 'at fraction 0 the weighted M-step is the exact plain one'
+    assert np.array_equal(_bits(out[True][0]), _bits(exact)), 'behind rebuilt codes too'
+
+
 def test_an_attached_context_keeps_the_float64_floor():
     """One rank with a communicator attached: its codes travel to ranks whose M-step forms are theirs to know."""
     from demuxalot_amd import distributed
