@@ -267,7 +267,7 @@ int dmx_set_mstep_incremental(dmx_ctx *c, int incremental)
 {
     if (!c) return fail(DMX_ERR_INVALID, "null context");
     if (incremental < 0 || incremental > 2) return fail(DMX_ERR_INVALID, "incremental M-step: 0 off, 1 on, 2 on with the first sums built by the delta pass");
-    if (incremental != c->mstep_incremental) c->incr_valid = false;
+    if (incremental != c->mstep_incremental) c->kept_sums_dropped();
     c->mstep_incremental = incremental;
     return 0;
 }

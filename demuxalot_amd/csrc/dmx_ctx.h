@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "ctx_state.h"
 #include "dmx_internal.h"
 #include "kernels.h"
 
@@ -138,12 +139,13 @@ struct PooledSlot {
     int64_t bytes = 0;                   // device bytes held
 };
 
-struct dmx_ctx {
+// (which derived device data is current: the flags and every write of them are CtxState's, ctx_state.h)
+struct dmx_ctx : dmx::CtxState {
     int device = 0;
     hipStream_t stream = nullptr;
     long long B = 0, V = 0, N = 0, S = 0;
     int G = 0, K = 0;
-    bool have_problem = false, have_betas = false, have_probs = false, have_post = false;
+    bool have_problem = false, have_betas = false;
 
     DevBuf<long long> d_pair_ptr;
     DevBuf<dmx::CallPair> d_call_pairs;
@@ -172,12 +174,9 @@ struct dmx_ctx {
     DevBuf<long long> d_coarse_bin_ptr;    //   admissible E-step of a problem from the tile-major stream; [n_bins + 1]
     DevBuf<double> d_log2_keep;            // [B]
     bool coarse_ready = false;
-    bool prob16_valid = false;           // ... and it holds the current d_prob
     int coarse_pass = 1;                 // dmx_set_coarse_pass
     int lean_memory = 0;                 // dmx_set_lean_memory: the tile-major E-step stream goes once the coarse pass's records are built from it
     bool logits_needed = true;           // dmx_set_logits_needed: the last E-step of a dmx_em / dmx_run_iterations call keeps its logits readable
-    bool logits_readable = true;         // the last E-step's logits are the fine pass's / the exact kernel's (dmx_get_logits, dmx_get_block)
-    float p_clip_lo = 0.0f;              // lower clip of the P-step that produced d_prob (0: a caller's table, dmx_set_probs)
     DevBuf<double> d_add64, d_partial;
     DevBuf<float> d_logits, d_post;
     DevBuf<unsigned long long> d_nz;
@@ -199,8 +198,6 @@ struct dmx_ctx {
     DevBuf<unsigned char> d_incr_touched;  // [V]
     DevBuf<unsigned> d_incr_state;       // [2 x IS_WORDS] the state words of this and of the next M-step, alternating
     int incr_parity = 0;
-    bool incr_valid = false;                // the device state may be trusted (else the state words are zeroed: a full pass)
-    float incr_power = 0.0f;                // contribution power of the sums in d_acc64
     int mstep_incremental = 1;              // dmx_set_mstep_incremental
     long long mstep_incr_launches = 0;      // M-steps that went through the incremental launch sequence
     long long n_mt = 0;
@@ -235,13 +232,10 @@ struct dmx_ctx {
     DevBuf<int> d_guard_sub;         // [GUARD_QUEUES x guard_sub_cap] EstepArgs::guard_sub
     unsigned guard_sub_cap = 0;
     long long guard_rows_total = 0;     // barcode rows the guarded kernels have walked since the last reset
-    bool guard_ran = false;             // the last E-step evaluated the guard
     int tiled_estep = 1;               // dmx_set_estep_schedule: 0 never, 1 when it pays, 2 whenever the repack built one
     // dictionary form of the E-step (estep_dict.hip): tried when the genotype table was computed without a beta
     // addition (or supplied by the caller), used when every row has few distinct values
     int dict_mode = 1;            // dmx_set_estep_dictionary: 0 never, 1 when the table is a candidate, 2 try always
-    bool add_is_zero = true;      // d_add holds zeros (no M-step / dmx_set_addition since the last reset)
-    bool dict_candidate = false;  // the current d_prob was computed without an addition, or set by the caller
     int estep_form = 0;           // form of the last E-step: DMX_FORM_*
     int estep_packing = 1;        // dmx_set_estep_packing: 0 never, 1 where it pays, 2 wherever the shape exists
     long long max_row_calls = 0;  // calls of the longest barcode row (device repack)
@@ -258,12 +252,9 @@ struct dmx_ctx {
     DevBuf<int> d_split_first;
     DevBuf<double> d_seg_sums;
     long long n_segs = 0, n_split = 0;
-    float nz_floor = 0.0f;     // threshold the current d_nz / d_first were built with
     int live_floor_grid = 1;   // dmx_set_live_floor_on_grid: an E-step ahead of a fixed-point M-step writes them at live_floor_fixed (kernels.h)
-    long long nz_rebuilds = 0; // launches of k_rebuild_nz by run_mstep since dmx_reset_timings (the codes' floor did not fit the M-step's form)
     DevBuf<uint2> d_first;  // [B] {posterior of the lowest live singlet column, count | first live columns} (G <= 64): EstepArgs::first
     DevBuf<unsigned long long> d_dense_calls;  // [1] E-step statistic read by the M-step kernels (kernels.h)
-    bool dense_stat_valid = false;
     DevBuf<float> d_pen;
     DevBuf<unsigned> d_pairs;
     DevBuf<unsigned> d_pair_blocks;  // EstepArgs::pair_blocks (doublet runs whose options go to the workgroup-per-barcode forms)
@@ -284,7 +275,6 @@ struct dmx_ctx {
     DevBuf<long long> d_mc_start;      // [B + 1] first call of every barcode
     unsigned mc_max_count = 0;            // most molecule calls in one (barcode, SNP) pair
     DevBuf<double> d_logits64, d_post64;  // float64 results of dmx_estep_snp
-    bool have_post64 = false;
     DevBuf<unsigned char> d_scratch;  // self tests
     // SNP detection (snp_detect.hip): read and written by the dmx_snp_* entry points only; sd_P < 0: no counts
     DevBuf<unsigned long long> d_sd_pos;  // [sd_P] chrom << 32 | (position ^ 0x80000000), ascending (the canonical order)
@@ -345,12 +335,10 @@ struct dmx_ctx {
     double emu_link_gbps = 50.0, emu_latency_us = 10.0;
     bool in_group = false, group_paid = false;  // coll_group_begin .. coll_group_end: several collectives, one launch
     double group_ns = 0.0;                       // emulated wire: the group's modelled time, held by ONE delay at its end
-    bool emu_table_filled = false;            // the other ranks' slices of genotype_prob hold the table without addition
     double emu_ticks_per_ns = 0.1;            // wall-clock ticks of the delay kernel per nanosecond
     bool attached() const { return comm != nullptr || host_coll != nullptr || emulated; }
     int rank = 0, nranks = 1, reduce_dtype = DMX_F64;
     bool sliced = false;            // reduce-scatter + sliced P-step + all-gather (else: all-reduce + replicated P-step)
-    bool add_partial = false;       // only this rank's slice of d_add is current (sliced mode, after an M-step)
     long long slice_rows = 0;       // rows per slice of the padded tables
     long long prob_rows = 0;        // rows of d_prob (= nranks * slice_rows when sliced, else V)
     std::vector<long long> cut;     // [nranks + 1] first variant of every slice
@@ -365,7 +353,6 @@ struct dmx_ctx {
     DevBuf<uint2> d_first_g;              // [rows_total] EstepArgs::first of every barcode
     DevBuf<unsigned long long> d_nz_g;    // [rows_total, ceil(G / 64)]
     DevBuf<float> d_post_g;               // [rows_total, G] singlet posteriors
-    bool post_gathered = false;              // the tables hold the last E-step of every rank
     bool emu_post_filled = false;            // emulated wire: the other ranks' blocks were filled once
     // compact exchange of the posterior rows (gather_posteriors; G <= 64): per rank a block of {rows listed, 3 pad, cap x (row, G floats)}
     DevBuf<unsigned> d_post_compact;      // [nranks * post_compact_words]
@@ -384,7 +371,6 @@ struct dmx_ctx {
     size_t prob_list_words = 0;              // (0: the whole slices travel)
     unsigned prob_list_cap = 0;
     unsigned prob_cap_now = 0;               // (as post_cap_now)
-    bool prob_prev_valid = false;            // d_prob_prev is what every rank holds of this slice
     unsigned *h_prob_counts = nullptr;       // pinned, [nranks + 1]
     long long prob_compact_taken = 0, prob_compact_overflows = 0;
     DevBuf<unsigned char> d_exch;         // padded send buffer of the reduce-scatter (float64 or float32 partial sums; the incremental

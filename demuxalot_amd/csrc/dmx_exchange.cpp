@@ -405,7 +405,7 @@ int shard_mstep_by_variant(dmx_ctx *c, bool force)
         std::memset(c->h_post_counts, 0, sizeof(unsigned) * (size_t)(n + 1));
     }
     c->mshard = true;
-    c->post_gathered = false;
+    c->gathered_tables_reset();
     c->emu_post_filled = false;
     return 0;
 }
@@ -440,8 +440,7 @@ int layout_exchange(dmx_ctx *c)
         c->prob_rows = new_rows;
         DMX_TRY(dev_alloc(c, c->d_prob, (size_t)new_rows * G));
     }
-    c->have_probs = false;
-    c->emu_table_filled = false;
+    c->table_layout_changed();
     HIP_TRY(hipMemsetAsync(c->d_prob.p, 0, sizeof(float) * (size_t)(new_rows ? new_rows * G : 1), st));
     if (c->sliced) {
         std::vector<int> prow((size_t)V);
@@ -469,7 +468,7 @@ int layout_exchange(dmx_ctx *c)
             const long long asked = compact ? atoll(compact) : -1;
             c->prob_list_words = 0;
             c->prob_list_cap = 0;
-            c->prob_prev_valid = false;
+            c->sent_slice_forgotten();
             if (asked != 0 && n > 1 && rows > 0) {
                 c->prob_list_cap = (unsigned)(asked > 0 ? std::min<long long>(asked, rows) : std::max<long long>(64, rows / 4));
                 c->prob_list_words = 4 + (size_t)c->prob_list_cap * (size_t)(1 + G);
@@ -491,7 +490,7 @@ int layout_exchange(dmx_ctx *c)
         // (forced, it also runs with ONE rank: its collectives through a real one-rank RCCL communicator on a one-GPU test box)
         if ((n > 1 && !by_sums) || by_variant) DMX_TRY(shard_mstep_by_variant(c, by_variant));
     }
-    c->add_partial = false;
+    c->exchange_laid_out();
     return 0;
 }
 
@@ -561,7 +560,7 @@ int gather_posteriors(dmx_ctx *c)
     }
     timer_end(c, DMX_T_ALLREDUCE, ev);
     if (rc) return rc;
-    c->post_gathered = true;
+    c->posteriors_gathered();
     return 0;
 }
 

@@ -398,7 +398,7 @@ void release_incremental(dmx_ctx *c)
     c->incr_rows = 0;
     dev_free(c, c->d_incr_touched);
     dev_free(c, c->d_incr_state);
-    c->incr_valid = false;
+    c->kept_sums_dropped();
 }
 
 // the coarse pass's records and constants (run_estep builds them at the problem's first admissible E-step)
@@ -458,8 +458,7 @@ static void release_dictionary(dmx_ctx *c)
     dev_free(c, c->d_codes);
     dev_free(c, c->d_dtab);
     dev_free(c, c->d_dict_stat);
-    c->dict_candidate = false;
-    c->add_is_zero = true;
+    c->dictionary_released();
     c->dict_distinct = 0;
 }
 
@@ -471,7 +470,7 @@ static void release_guard(dmx_ctx *c)
     dev_free(c, c->d_guard_sub);
     c->guard_sub_cap = 0;
     c->guard_rows_total = 0;
-    c->guard_ran = false;
+    c->guard_released();
     dev_free(c, c->d_segs);
     dev_free(c, c->d_split_first);
     dev_free(c, c->d_seg_sums);
@@ -490,7 +489,6 @@ static void release_exchange(dmx_ctx *c)
     dev_free(c, c->d_prob_prev);
     c->prob_list_words = 0;
     c->prob_list_cap = 0;
-    c->prob_prev_valid = false;
     if (c->h_prob_counts) (void)hipHostFree(c->h_prob_counts);
     c->h_prob_counts = nullptr;
     dev_free(c, c->d_first_g);
@@ -504,9 +502,10 @@ static void release_exchange(dmx_ctx *c)
     c->h_post_counts = nullptr;
     c->post_compact_words = 0;
     c->post_compact_cap = 0;
-    c->mshard = c->post_gathered = c->emu_post_filled = false;
+    c->mshard = c->emu_post_filled = false;
     c->rows_pad = c->rows_total = 0;
-    c->sliced = c->add_partial = false;
+    c->sliced = false;
+    c->exchange_released();
     c->slice_rows = c->prob_rows = 0;
     c->cut.clear();
     c->h_v2snp.clear();
@@ -521,7 +520,7 @@ static void release_snp_groups(dmx_ctx *c)
     c->mc_max_count = 0;
     dev_free(c, c->d_logits64);
     dev_free(c, c->d_post64);
-    c->have_post64 = false;
+    c->float64_posteriors_dropped();
 }
 
 // what the device pack leaves behind: the unique calls (dmx_get_packed_calls) and the molecule calls per variant
@@ -562,9 +561,9 @@ void release_problem(dmx_ctx *c)
     dev_free(c, c->d_dense_calls);
     dev_free(c, c->d_best);
     dev_free(c, c->d_bestp);
-    c->have_raw = c->prob16_valid = c->dense_stat_valid = false;
+    c->problem_released();
     c->estep_form = DMX_FORM_NONE;
-    c->have_problem = c->have_betas = c->have_probs = c->have_post = false;
+    c->have_problem = c->have_betas = c->have_raw = false;
     c->B = c->V = c->N = c->S = 0;
     c->G = c->K = 0;
 }
@@ -830,7 +829,7 @@ int dmx_reset_timings(dmx_ctx *c)
     if (c->d_guard_count.p) HIP_TRY(hipMemsetAsync(c->d_guard_count.p + dmx::GS_COARSE_STEPS, 0, 2 * sizeof(unsigned), c->stream));  // + GS_PROBES
     if (c->d_incr_state.p) HIP_TRY(hipMemsetAsync(c->d_incr_state.p + 2 * dmx::IS_WORDS, 0, sizeof(unsigned) * 3, c->stream));  // (word 3: full passes since the install, kept)
     c->guard_rows_total = 0;
-    c->nz_rebuilds = 0;
+    c->rebuild_count_reset();
     for (int s = 0; s < DMX_T_COUNT; s++) {
         timer_flush(c, s);
         c->timers[s].ms = 0.0;

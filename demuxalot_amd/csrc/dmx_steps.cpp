@@ -124,7 +124,7 @@ int ensure_options(dmx_ctx *c, int with_doublets, const float *penalties)
     DMX_TRY(dmx::ensure_sum_plan(c, K));
     DMX_TRY(dev_grow(c, c->d_seg_sums, (size_t)c->n_segs * (size_t)K));
     HIP_TRY(hipStreamSynchronize(c->stream));  // `pairs` is a local
-    if ((int)K != c->K) c->have_post64 = false;  // the float64 results of dmx_estep_snp were laid out for another K
+    if ((int)K != c->K) c->float64_posteriors_dropped();  // (those of dmx_estep_snp)
     c->K = (int)K;
     return 0;
 }
@@ -158,7 +158,7 @@ int copy_prob_out(dmx_ctx *c, float *dst)
 int copy_prob_in(dmx_ctx *c, const float *src)
 {
     const int G = c->G;
-    c->prob_prev_valid = false;  // (the table is the caller's now: what the ranks hold of each other's slices is no longer what they sent)
+    c->sent_slice_forgotten();  // (the table is the caller's now)
     if (!c->sliced) {
         HIP_TRY(hipMemcpyAsync(c->d_prob.p, src, sizeof(float) * c->V * G, hipMemcpyHostToDevice, c->stream));
         return 0;
@@ -186,7 +186,7 @@ int ensure_full_addition(dmx_ctx *c)
         const long long rows = c->cut[k + 1] - c->cut[k];
         if (rows && k != c->rank) HIP_TRY(hipMemcpyAsync(c->d_add.p + c->cut[k] * G, stage + k * block, sizeof(float) * rows * G, hipMemcpyDeviceToDevice, c->stream));
     }
-    c->add_partial = false;
+    c->addition_gathered();
     return 0;
 }
 
@@ -196,7 +196,7 @@ int ensure_prob16(dmx_ctx *c)
     const size_t need16 = ((size_t)c->prob_rows + 1) * c->G * 2;
     if (need16 > c->d_prob16.n) {
         DMX_TRY(dev_grow(c, c->d_prob16, need16));
-        c->prob16_valid = false;
+        c->half_table_reallocated();
         HIP_TRY(hipMemsetAsync(c->d_prob16.p, 0, need16 * sizeof(unsigned short), c->stream));
     }
     return 0;
@@ -212,7 +212,7 @@ int run_pstep(dmx_ctx *c, float lo, float hi, bool with_addition, bool with_half
     const bool half_rows = with_half && c->sliced && c->prob_list_words != 0 && c->prob_prev_valid && c->prob16_valid && c->d_prob16.p != nullptr;
     with_half = with_half && !c->sliced;
     if (with_half) DMX_TRY(ensure_prob16(c));
-    c->prob16_valid = false;
+    c->pstep_begins();
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
     timer_begin(c, DMX_T_PSTEP, &ev);
@@ -224,12 +224,12 @@ int run_pstep(dmx_ctx *c, float lo, float hi, bool with_addition, bool with_half
             if (r != c->rank)
                 HIP_TRY(dmx::launch_probs_from_betas(c->stream, c->d_prior.p, nullptr, c->d_v2snp.p, c->d_snp_ptr.p, c->d_snp_vars.p, c->cut[r],
                                                      c->cut[r + 1] - c->cut[r], -1LL, c->G, c->d_prow.p, lo, hi, c->d_prob.p));
-        c->emu_table_filled = true;
+        c->emulated_slices_filled();
     }
     HIP_TRY(dmx::launch_probs_from_betas(c->stream, c->d_prior.p, with_addition ? c->d_add.p : nullptr, c->d_v2snp.p,
                                          c->d_snp_ptr.p, c->d_snp_vars.p, v0, v1 - v0, c->sliced ? -1LL : (long long)c->S, c->G, c->d_prow.p, lo, hi,
                                          c->d_prob.p, (with_half || half_rows) ? c->d_prob16.p : nullptr));
-    c->prob16_valid = with_half;
+    c->pstep_launched(with_half);
     timer_end(c, DMX_T_PSTEP, ev);
     if (c->sliced) {  // everybody gets everybody's slice of genotype_prob
         timer_begin(c, DMX_T_ALLREDUCE, &ev);
@@ -262,22 +262,20 @@ int run_pstep(dmx_ctx *c, float lo, float hi, bool with_addition, bool with_half
                 c->prob_cap_now = whole ? c->prob_list_cap : (unsigned)std::min<unsigned long long>(c->prob_list_cap, 4ull * longest + 512ull);
                 if (!whole) {
                     c->prob_compact_taken++;
-                    c->prob16_valid = half_rows;
+                    c->changed_rows_applied(half_rows);
                 } else {
                     c->prob_compact_overflows++;
                 }
             }
         } else if (c->prob_list_words != 0) {  // the first table of a layout (or behind a table somebody else wrote): what is sent now is what the others hold
             HIP_TRY(hipMemcpyAsync(c->d_prob_prev.p, mine, sizeof(float) * block, hipMemcpyDeviceToDevice, c->stream));
-            c->prob_prev_valid = true;
+            c->sent_slice_recorded();
         }
         if (rc == 0 && whole) rc = coll_all_gather(c, c->d_prob.p, block, "genotype_prob");
         timer_end(c, DMX_T_ALLREDUCE, ev);
         if (rc) return rc;
     }
-    c->have_probs = true;
-    c->p_clip_lo = lo;
-    c->dict_candidate = !with_addition || c->add_is_zero;
+    c->table_written_by_pstep(lo, with_addition);
     return 0;
 }
 
@@ -526,7 +524,7 @@ static int guarded_estep(dmx_ctx *c, ep::Facts &f, dmx::EstepArgs &a)
         if (ep::prob16_conversion_due(f)) {
             const bool kept = ep::prob16_stays_valid(f);
             HIP_TRY(dmx::launch_prob_to_half(c->stream, c->d_prob.p, c->prob_rows, c->G, c->d_prob16.p, kept ? nullptr : c->d_guard_count.p + dmx::GS_SKIP_COARSE));
-            c->prob16_valid = kept;
+            c->half_table_converted(kept);
         }
         dmx::EstepArgs coarse = a;
         set_walk(c, coarse, ep::WALK_COARSE_RECORDS, true);
@@ -554,7 +552,7 @@ static int guarded_estep(dmx_ctx *c, ep::Facts &f, dmx::EstepArgs &a)
     redo.order_count = c->d_guard_count.p + dmx::GS_COUNT;
     HIP_TRY(dmx::launch_estep(c->stream, redo, f.with_doublets));
     c->guard_rows_total += c->B;
-    c->guard_ran = true;
+    c->guard_evaluated();
     return 0;
 }
 
@@ -565,11 +563,8 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
 {
     dmx::EstepArgs a;
     fill_estep_args(c, a, with_doublets, with_prior, prior_dtype, power);
-    c->post_gathered = false;
-    // (the slots are zero: set at the install, left so by k_sum_dense at the end of every E-step that used them)
-    c->dense_stat_valid = a.dense_calls != nullptr;
-    c->nz_floor = a.nz_floor;
-    c->guard_ran = false;
+    // (the statistic's slots are zero: set at the install, left so by k_sum_dense at the end of every E-step that used them)
+    c->estep_begins(a.dense_calls != nullptr, a.nz_floor);
     ep::Facts f = estep_facts(c, with_doublets, with_prior, logits_kept);
     if (ep::unused_stream_release_due(f)) {
         dev_free(c, c->d_tile_stream);
@@ -610,8 +605,7 @@ int run_estep(dmx_ctx *c, int with_doublets, bool with_prior, int prior_dtype, f
     if (a.dense_calls) HIP_TRY(dmx::launch_sum_dense(c->stream, c->d_dense_calls.p, c->guard_ran ? c->d_guard_count.p : nullptr));
     else if (c->guard_ran) HIP_TRY(dmx::launch_guard_stamp(c->stream, c->d_guard_count.p, dmx::GS_T_END));
     timer_end(c, DMX_T_ESTEP, ev);
-    c->have_post = true;
-    c->logits_readable = logits_kept;  // (an E-step nobody was to read the logits of may have taken the coarse pass: the device's choice)
+    c->estep_done(logits_kept);
     return 0;
 }
 
@@ -635,7 +629,7 @@ static int ensure_incremental_state(dmx_ctx *c, bool sharded, long long incr_row
         DMX_TRY(dev_alloc(c, c->d_incr_state, (size_t)(3 * dmx::IS_WORDS)));  // two alternating sets + the counters
         HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 3 * dmx::IS_WORDS, c->stream));
         HIP_TRY(hipMemsetAsync(c->d_incr_touched.p, 0, (size_t)c->V, c->stream));
-        c->incr_valid = false;
+        c->kept_sums_dropped();
     }
     if (!c->incr_valid || c->incr_power != power) {  // (nothing to build on: zeroed state words ask for the full pass)
         HIP_TRY(hipMemsetAsync(c->d_incr_state.p, 0, sizeof(unsigned) * 2 * dmx::IS_WORDS, c->stream));
@@ -650,8 +644,7 @@ static int ensure_incremental_state(dmx_ctx *c, bool sharded, long long incr_row
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
         c->incr_parity = 0;
-        c->incr_valid = true;
-        c->incr_power = power;
+        c->kept_sums_started(power);
     }
     return 0;
 }
@@ -688,16 +681,14 @@ int run_mstep(dmx_ctx *c, float power)
     auto rebuild_codes = [&](float floor) -> int {
         HIP_TRY(dmx::launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->K, c->G, floor, (mshard ? c->d_nz_g.p : c->d_nz.p) + row_base * Wn,
                                        c->G <= 64 ? (mshard ? c->d_first_g.p : c->d_first.p) + row_base : nullptr));
-        c->nz_floor = floor;
-        c->post_gathered = false;
-        c->nz_rebuilds++;
+        c->codes_rebuilt(floor);
         return 0;
     };
     // before the codes travel: the E-step assumed a squaring M-step - the exact `!= 0` rule (whatever the form: live_floor_fixed is
     // live_floor_float64 for such a power)
     if (!a.square && c->nz_floor != 0.0f) DMX_TRY(rebuild_codes(0.0f));
     DMX_TRY(gather_posteriors(c));
-    c->add_is_zero = false;
+    c->mstep_begins();
     TimerSpan ev{nullptr, nullptr};
     SpanGuard ev_guard{c, &ev};
     mplan::Facts f = mstep_facts(c, power);
@@ -728,7 +719,7 @@ int run_mstep(dmx_ctx *c, float power)
     const bool incremental = plan.incr != mplan::INCR_NONE, sharded = plan.incr == mplan::INCR_SHARDED;
     const long long incr_rows = sharded ? c->rows_total : c->B;
     if (incremental) DMX_TRY(ensure_incremental_state(c, sharded, incr_rows, power));
-    else c->incr_valid = false;  // (another form writes the addition: the kept sums no longer describe it)
+    else c->kept_sums_dropped();  // (another form writes the addition)
     f.has_slice_rec = c->d_slice_rec.p != nullptr;
     const bool by_rows = sharded && mplan::sharded_by_row_index(f);
     // where k_mcombine writes: the variants of one work item are written there by the M-step kernels themselves
@@ -801,7 +792,7 @@ int run_mstep(dmx_ctx *c, float power)
         if (rc == 0 && dest.f64) HIP_TRY(dmx::launch_f64_to_f32(c->stream, c->d_add64.p, c->d_add.p, (long long)c->V * c->G));
     }
     if (dest.then != mplan::EXCH_NONE) timer_end(c, DMX_T_ALLREDUCE, ev);
-    if (rc == 0 && dest.slice_only) c->add_partial = c->nranks > 1;
+    if (rc == 0) c->addition_written_by_mstep(dest.slice_only, c->nranks);
     return rc;
 }
 
@@ -815,15 +806,14 @@ int dmx_set_addition(dmx_ctx *c, const float *addition)
     DMX_TRY(bind(c));
     DMX_TRY(need(c, c->have_problem, "dmx_set_problem before dmx_set_addition"));
     const size_t vg = (size_t)c->V * c->G;
-    c->incr_valid = false;  // (the addition is no longer the last M-step's: the incremental M-step starts over)
+    c->kept_sums_dropped();  // (the addition is no longer the last M-step's: the incremental M-step starts over)
     if (addition) {
         HIP_TRY(hipMemcpyAsync(c->d_add.p, addition, sizeof(float) * vg, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     } else {
         HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));
     }
-    c->add_is_zero = addition == nullptr;
-    c->add_partial = false;
+    c->addition_set_by_caller(addition == nullptr);
     return 0;
 }
 
@@ -851,10 +841,7 @@ int dmx_set_probs(dmx_ctx *c, const float *prob)
     HIP_TRY(hipMemcpyAsync(&flag, c->d_best.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (flag) return fail(DMX_ERR_INVALID, "genotype_prob has entries outside [0, 1] (or NaN)");
-    c->have_probs = true;
-    c->p_clip_lo = 0.0f;  // (a caller's table: entries may lie below binary16's normal range - no coarse pass)
-    c->prob16_valid = false;
-    c->dict_candidate = true;
+    c->table_written_by_caller();
     return 0;
 }
 
@@ -867,9 +854,10 @@ int dmx_probs_from_betas_f64(dmx_ctx *c, const double *betas, float lo, float hi
     double *d_b = nullptr;
     HIP_TRY(hipMalloc((void **)&d_b, (vg ? vg : 1) * sizeof(double)));
     hipError_t e = vg ? hipMemcpyAsync(d_b, betas, vg * sizeof(double), hipMemcpyHostToDevice, c->stream) : hipSuccess;
-    if (e == hipSuccess)
-        c->prob_prev_valid = false;  // (every rank computes the whole table here)
+    if (e == hipSuccess) {  // (a failed upload launches nothing, and its error is the one reported)
+        c->sent_slice_forgotten();  // (every rank computes the whole table here)
         e = dmx::launch_probs_from_betas_f64(c->stream, d_b, c->d_v2snp.p, c->d_snp_ptr.p, c->d_snp_vars.p, c->V, c->S, c->G, c->d_prow.p, lo, hi, c->d_prob.p);
+    }
     int rc_copy = 0;
     if (e == hipSuccess && vg) rc_copy = copy_prob_out(c, prob_out);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -877,10 +865,7 @@ int dmx_probs_from_betas_f64(dmx_ctx *c, const double *betas, float lo, float hi
     (void)hipFree(d_b);
     if (e != hipSuccess) return fail(DMX_ERR_HIP, "P-step from float64 betas: %s", hipGetErrorString(e));
     if (rc_copy) return rc_copy;
-    c->have_probs = true;
-    c->p_clip_lo = lo;
-    c->prob16_valid = false;
-    c->dict_candidate = true;
+    c->table_written_from_f64_betas(lo);
     return 0;
 }
 
@@ -971,7 +956,7 @@ static int begin_dense_pools(dmx_ctx *c)
     DMX_TRY(ensure_options(c, 0, zeros.data()));
     const size_t bg = (size_t)c->B * c->G;
     HIP_TRY(hipMemsetAsync(c->d_post.p, 0, sizeof(float) * (bg ? bg : 1), c->stream));
-    c->have_post = false;  // (until the first dense E-step has run)
+    c->posteriors_dropped();  // (until the first dense E-step has run)
     return 0;
 }
 
@@ -1104,9 +1089,7 @@ static int begin_em_additions(dmx_ctx *c)
 {
     const size_t vg = (size_t)c->V * c->G;
     HIP_TRY(hipMemsetAsync(c->d_add.p, 0, sizeof(float) * (vg ? vg : 1), c->stream));
-    c->incr_valid = false;
-    c->add_is_zero = true;
-    c->add_partial = false;
+    c->addition_zeroed();
     return 0;
 }
 

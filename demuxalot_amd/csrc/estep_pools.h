@@ -70,7 +70,7 @@ struct PoolsPlan {
 //   prepare    the download of the context's `order`, the bucket lists, every upload, the compact result buffers; `plan` outlives the run
 //   launch     one launch per non-empty bucket.  A dense run writes the singlet posteriors into the context's own d_post as [B, G]
 //              (the caller has set K = G and zeroed it: dmx_steps.cpp, begin_dense_pools), rebuilds d_nz / d_first with the floor of
-//              `power` and leaves the context as run_estep leaves it for run_mstep
+//              `power`; the context's flags: ctx_state.h dense_pass_done
 //   read back  the compact rows and read-outs; -1 / NaN for the barcodes of no pool
 // The run holds its temporaries (device_scratch.h) until it is destroyed.
 struct PoolsRun;
@@ -81,7 +81,7 @@ typedef std::unique_ptr<PoolsRun, PoolsRunDeleter> PoolsRunPtr;
 int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunPtr &run);
 int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &run, float power);
 int read_back_estep_pools(dmx_ctx *c, PoolsRun &run);
-// the tail of a dense launch, inside its span of the timer: the rebuild and the context's state.  The dense pass of another kernel
+// the tail of a dense launch, inside its span of the timer: the rebuild and the context's flags.  The dense pass of another kernel
 // on a prepared run (estep_ambient.hip) ends with it too.
 int close_dense_pools_pass(dmx_ctx *c, float power);
 // the three in a row without the dense form: dmx_estep_pools

@@ -153,15 +153,10 @@ int prepare_estep_pools(dmx_ctx *c, const PoolsPlan &plan, bool dense, PoolsRunP
 int close_dense_pools_pass(dmx_ctx *c, float power)
 {
     // the bitmap and the codes of the M-step from the [B, G] matrix, with the floor a full-table E-step of this power takes
-    // (dmx_steps.cpp: fill_estep_args); the context as run_estep leaves it, without statistics of the dense calls
+    // (dmx_steps.cpp: fill_estep_args); the flags: DESIGN.md 4.15
     const float floor = live_floor_float64(power);
     HIP_TRY(launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->G, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
-    c->post_gathered = false;
-    c->dense_stat_valid = false;
-    c->nz_floor = floor;
-    c->guard_ran = false;
-    c->have_post = true;
-    c->logits_readable = false;  // (d_logits holds nothing of this pass)
+    c->dense_pass_done(floor);
     return 0;
 }
 

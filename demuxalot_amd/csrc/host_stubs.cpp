@@ -159,9 +159,9 @@ int prepare_estep_pools(dmx_ctx *, const PoolsPlan &, bool, PoolsRunPtr &run)
     run.reset(new PoolsRun);
     return 0;
 }
-int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &, float)
+int launch_estep_pools_pass(dmx_ctx *c, PoolsRun &, float power)
 {
-    c->have_post = true;
+    c->dense_pass_done(live_floor_float64(power));  // (what close_dense_pools_pass leaves: the only runs that get here are dense)
     return 0;
 }
 int read_back_estep_pools(dmx_ctx *, PoolsRun &) { return 0; }
@@ -174,9 +174,9 @@ int prepare_estep_ambient(dmx_ctx *, const PoolsPlan &, const AmbientScoring &, 
     run.reset(new AmbientRun);
     return 0;
 }
-int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &, float)
+int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &, float power)
 {
-    c->have_post = true;
+    c->dense_pass_done(live_floor_float64(power));
     return 0;
 }
 int read_back_estep_ambient(dmx_ctx *, AmbientRun &) { return 0; }

@@ -24,8 +24,8 @@ struct WeightedMstepArgs {
 
 // The context's half of such an M-step: the codes are rebuilt first when they were written above live_floor_float64(power) (a
 // fixed-point M-step may have asked the E-step for a higher floor), then `a` is filled from the context's posteriors (d_post, singlet
-// columns; d_nz), records, work items and table (d_prob), with d_add as the result, and the context is marked as run_mstep's
-// float64 form leaves it.
+// columns; d_nz), records, work items and table (d_prob), with d_add as the result; the context's flags:
+// ctx_state.h addition_written_by_other_form.
 int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a);
 
 // k_mcombine_weighted over [V, G] behind the zeroing of the two counters; the form's redo over the queue follows it

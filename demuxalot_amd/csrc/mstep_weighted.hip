@@ -59,9 +59,7 @@ int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a)
     const float floor = live_floor_float64(power);
     if (c->nz_floor > floor) {
         HIP_TRY(launch_rebuild_nz(c->stream, c->d_post.p, c->B, c->K, c->G, floor, c->d_nz.p, c->G <= 64 ? c->d_first.p : nullptr));
-        c->nz_floor = floor;
-        c->post_gathered = false;
-        c->nz_rebuilds++;
+        c->codes_rebuilt(floor);
     }
     a = {};
     a.m.order = c->d_item_order.p;
@@ -85,9 +83,7 @@ int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a)
     a.V = c->V;
     a.redo = c->d_redo.p;
     a.n_redo = c->d_n_redo.p;
-    c->add_is_zero = false;
-    c->add_partial = false;
-    c->incr_valid = false;  // (another form writes the addition: the kept fixed-point sums no longer describe it)
+    c->addition_written_by_other_form();
     return 0;
 }
 

@@ -694,7 +694,7 @@ void release_mstep_tiles(dmx_ctx *c)
     dev_free(c, c->d_mt_order);
     dev_free(c, c->d_mt_shift);
     dev_free(c, c->d_mt_shift_v);
-    c->incr_valid = false;
+    c->kept_sums_dropped();
     c->n_mt = 0;
     c->mt_tv = 0;
     c->mt_tried = false;

@@ -688,9 +688,8 @@ int dmx_estep_snp(dmx_ctx *c, int with_doublets, const double *count_pow, int64_
     if (probs_out && bk) HIP_TRY(hipMemcpyAsync(probs_out, c->d_post64.p, sizeof(double) * bk, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // the float32 logits / posteriors of dmx_estep (and the M-step's bitmaps) were laid out for the previous K
-    if ((int)K != c->K) c->have_post = false;
+    c->float64_posteriors_written((int)K != c->K);
     c->K = (int)K;
-    c->have_post64 = true;
     return 0;
 }
 
@@ -714,9 +713,7 @@ static int mstep_f64(dmx_ctx *c, double contribution_power, float *addition_out,
     else if (G <= 512) launch_m64<8>(c, contribution_power, sums);
     else launch_m64<16>(c, contribution_power, sums);  // (G > 1024: one column group of 1024 per blockIdx.y)
     HIP_TRY(hipGetLastError());
-    c->add_partial = false;
-    c->add_is_zero = false;
-    c->incr_valid = false;  // (the addition is no longer the sums the incremental M-step keeps: its next M-step is a full pass)
+    c->addition_written_by_other_form();  // (the incremental M-step's next M-step is a full pass)
     const size_t vg = (size_t)c->V * G;
     if (addition_out && vg) HIP_TRY(hipMemcpyAsync(addition_out, c->d_add.p, sizeof(float) * vg, hipMemcpyDeviceToHost, c->stream));
     if (sums_out && vg) HIP_TRY(hipMemcpyAsync(sums_out, c->d_add64.p, sizeof(double) * vg, hipMemcpyDeviceToHost, c->stream));

@@ -262,3 +262,67 @@ def test_call_sequence_on_the_emulated_wire(monkeypatch):
     print('emulated rank 0 of 4: (full, delta) passes per step', [s[5] for s in got[0][2]])
     _against_control(got, want)
     _assert_delta_passes(got)
+
+
+def _foreign_writer_sequence(p, pen, incremental):
+    """em(4), two staged iterations, a dense pooled E-step + mstep_ambient at fraction 0, two staged iterations, a dense pooled E-step +
+    mstep_doublets on its rows, two staged iterations: [(step, posteriors, addition, (full, delta) passes of the step)]."""
+    from demuxalot_amd.device import DeviceContext
+    pools, pool_of, no_penalty = [list(range(p.n_genotypes))], np.zeros(p.n_barcodes, np.int32), np.zeros(1, np.float32)
+    out = []
+    with DeviceContext(0) as ctx:
+        ctx.set_problem(p.n_barcodes, p.n_variants, p.n_genotypes, p.variant_id, p.compressed_cb, p.p_base_wrong, p.v2snp)
+        _prepare(ctx, p, incremental, False, True)
+        ctx.reset_timings()
+        seen = [(0, 0)]
+
+        def passes():
+            full, delta, _last = ctx.mstep_incremental()
+            took = (full - seen[0][0], delta - seen[0][1])
+            seen[0] = (full, delta)
+            return took
+
+        def two_staged(behind):
+            for i in range(2):
+                probs, addition = _staged(ctx, pen, False, True)
+                out.append((f'staged iteration {i} behind {behind}', probs, addition, passes()))
+
+        def dense_pooled_estep():
+            ctx.probs_from_betas(CLIP, fetch=False)
+            return ctx.estep_pools(pools, pool_of, False, no_penalty, fetch_logits=False, resident=True)
+
+        _l, probs, addition = ctx.em(4, CLIP, pen, False, fetch_logits=False)
+        out.append(('em(4)', probs, addition, passes()))
+        two_staged('em(4)')
+        dense_pooled_estep()
+        addition = ctx.mstep_ambient(np.zeros(p.n_barcodes, np.float32), POWER, CLIP)
+        out.append(('mstep_ambient', ctx.get_probs(), addition, passes()))
+        two_staged('mstep_ambient')
+        rows = dense_pooled_estep()['probs']
+        addition = ctx.mstep_doublets(pools, pool_of, False, no_penalty, rows, contribution_power=POWER)
+        out.append(('mstep_doublets', ctx.get_probs(), addition, passes()))
+        two_staged('mstep_doublets')
+    return out
+
+
+def test_foreign_writers_of_the_addition_between_incremental_msteps(monkeypatch):
+    """The table-weighted M-steps write the whole addition and keep no sums (ctx_state.h: addition_written_by_other_form): one
+    context without a communicator, incremental on against the incremental-off control.  Every posterior table and every addition
+    equal the control's bit for bit, and by dmx_get_mstep_incremental the first mstep() behind each of the two writers is a full pass,
+    the one after it a delta pass.  The pooled calls score singlets over one pool of all donors, as the workload's E-steps do."""
+    monkeypatch.setenv('DEMUXALOT_AMD_ESTEP', 'exact')
+    monkeypatch.setenv('DEMUXALOT_AMD_EXACT_ADDITIONS', '0')
+    monkeypatch.delenv('DEMUXALOT_AMD_EXCHANGE', raising=False)
+    p, pen = _workload(False)
+    got = _foreign_writer_sequence(p, pen, True)
+    want = _foreign_writer_sequence(p, pen, False)
+    print('(full, delta) passes per step', [(step, took) for step, _p, _a, took in got])
+    assert [s[0] for s in got] == [s[0] for s in want] and len(got) == 9
+    for (step, probs, addition, _took), (_s, probs_c, addition_c, _t) in zip(got, want):
+        fio.assert_bitwise(probs, probs_c, f'{step}: posteriors against the control')
+        fio.assert_bitwise(addition, addition_c, f'{step}: addition against the control')
+    took = {step: passes for step, _p, _a, passes in got}
+    for writer in ('mstep_ambient', 'mstep_doublets'):
+        assert took[writer] == (0, 0), (writer, took)  # (no pass of the incremental M-step's)
+        assert took[f'staged iteration 0 behind {writer}'] == (1, 0), (writer, took)
+        assert took[f'staged iteration 1 behind {writer}'] == (0, 1), (writer, took)
