@@ -39,9 +39,8 @@ inline Verdict check_marginal(const Facts &f, const Pools &p, long long n_alphas
 {
     const Verdict grid = check(f, p, n_alphas, alphas, ambient);
     if (grid.status != OK || !log_weights) return grid;
-    for (long long j = 0; j < n_alphas; j++)
-        if (!(log_weights[j] - log_weights[j] == 0.0f)) return {INVALID, "a log weight is not finite", j};
-    return grid;
+    const long long j = asplan::first_log_weight_not_finite(log_weights, n_alphas);
+    return j < 0 ? grid : Verdict{INVALID, "a log weight is not finite", j};
 }
 
 }  // namespace agplan

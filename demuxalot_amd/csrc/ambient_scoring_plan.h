@@ -36,6 +36,14 @@ inline Verdict check_profile(const Facts &f, const float *ambient)
     return {OK, "", -1};
 }
 
+// The first of n log weights of a prior over a grid that is not finite, -1: none (ambient_grid_plan.h: check_marginal; pair_shares_plan.h)
+inline long long first_log_weight_not_finite(const float *log_weights, long long n)
+{
+    for (long long j = 0; j < n; j++)
+        if (!(log_weights[j] - log_weights[j] == 0.0f)) return j;
+    return -1;
+}
+
 // The order is the order of the refusals: the context, the pools as dmx_estep_pools walks them, the fractions, the profile.
 // alpha[b] of a barcode in no pool is not looked at.
 inline Verdict check(const Facts &f, const Pools &p, const float *alpha, const float *ambient)

@@ -27,12 +27,6 @@ struct AmbientGridArgs {
 // profile: the form that also stores a.profile; marginal (never with profile): the grid summed, a.alpha_index its
 // first maximum of lambda + log_weights
 hipError_t launch_estep_ambient_grid(hipStream_t st, const AmbientGridArgs &a, int slots, bool pairs, bool profile, bool marginal);
-// best_alpha_index[b] = alpha_index[row_ptr[b] + best[b]], -1 where best[b] is -1 or the barcode is in no pool: a thread per barcode
-hipError_t launch_best_alpha_index(hipStream_t st, long long B, const int *pool_of, const long long *row_ptr, const int *best, const int *alpha_index,
-                                   int *best_alpha_index);
-// the same, and best_alpha_mean[b] = alpha_mean[row_ptr[b] + best[b]] (NaN where there is none), for the marginal mode
-hipError_t launch_best_alpha_mean(hipStream_t st, long long B, const int *pool_of, const long long *row_ptr, const int *best, const int *alpha_index,
-                                  const float *alpha_mean, int *best_alpha_index, float *best_alpha_mean);
 
 // what dmx_estep_ambient_grid passes on beside the pools' plan: host pointers
 struct AmbientGridScoring {
@@ -49,7 +43,7 @@ struct AmbientGridScoring {
     float *alpha_mean;          // marginal: nullable [row_ptr[B]]
     float *best_alpha_mean;     // marginal: nullable [B]
 };
-// prepare_estep_pools, the profile (given or derived), the kernels (one span of DMX_T_ESTEP), read_back_estep_pools
+// prepare_estep_pools, the profile (given or derived), the kernels (estep_grid.h: run_grid_estep), read_back_estep_pools
 int run_estep_ambient_grid(dmx_ctx *c, const PoolsPlan &plan, const AmbientGridScoring &scoring);
 
 }  // namespace dmx

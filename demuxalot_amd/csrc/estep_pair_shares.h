@@ -35,7 +35,7 @@ struct PairSharesScoring {
     int32_t *best_share_index;  // nullable [B]
     float *best_share_mean;     // nullable [B]
 };
-// prepare_estep_pools, the kernels (one span of DMX_T_ESTEP), read_back_estep_pools.  Without doublets: the pooled pass itself, the
+// prepare_estep_pools, the kernels (estep_grid.h: run_grid_estep), read_back_estep_pools.  Without doublets: the pooled pass itself, the
 // share outputs filled with -1 / NaN on the host, no grid kernel.  The context's pooled slot (dmx_set_keep_pooled) is left alone.
 int run_estep_pair_shares(dmx_ctx *c, const PoolsPlan &plan, const PairSharesScoring &scoring);
 

@@ -31,9 +31,8 @@ inline Verdict check(const Facts &f, const Pools &p, long long n_shares, const f
     if (!shares) return {INVALID, "null shares", -1};
     for (long long j = 0; j < n_shares; j++)
         if (!aplan::unit_range(shares[j])) return {INVALID, "a share is not finite or outside [0, 1]", j};
-    if (log_weights)
-        for (long long j = 0; j < n_shares; j++)
-            if (!(log_weights[j] - log_weights[j] == 0.0f)) return {INVALID, "a log weight is not finite", j};
+    const long long j = log_weights ? asplan::first_log_weight_not_finite(log_weights, n_shares) : -1;
+    if (j >= 0) return {INVALID, "a log weight is not finite", j};
     static_assert(MAX_SHARES == 64, "the text below spells the limit out");
     if (n_shares > MAX_SHARES) return {UNSUPPORTED, "the grid of shares has more than 64 values", n_shares};
     return {OK, "", -1};

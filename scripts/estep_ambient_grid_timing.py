@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 WARM_UP = 2
 B, S, G = 20_000, 20_000, 64
 GRIDS = (8, 64)
-POINTS_PER_WALK = {'singlets': 4, 'doublets': 1}  # csrc/estep_ambient_grid.hip: GridPoints of the form each shape runs
+POINTS_PER_WALK = {'singlets': 4, 'doublets': 1}  # csrc/estep_grid_device.h: GridPoints of the form each shape runs
 
 
 def run_steps(repeats):

@@ -26,7 +26,7 @@ WARM_UP = 2
 B, S, G = 20_000, 20_000, 64
 GRIDS = (8, 64)
 SHAPES = ('singlets', 'doublets')
-POINTS_PER_WALK = {'singlets': 4, 'doublets': 1}  # csrc/estep_ambient_grid.hip: GridPoints of the form each shape runs
+POINTS_PER_WALK = {'singlets': 4, 'doublets': 1}  # csrc/estep_grid_device.h: GridPoints of the form each shape runs
 PARENT_MAX_MS = {('singlets', 8): 2.005, ('singlets', 64): 15.148, ('doublets', 8): 28.286, ('doublets', 64): 223.020}  # DESIGN.md 4.8's table
 
 

@@ -7,12 +7,14 @@ One invocation measures one variant (shape, grid length); every variant runs in 
 and nothing more is started after one that did not end well:
 
     timeout -k 10 300 python scripts/estep_pair_shares_timing.py one_slot 9 &&
+    timeout -k 10 300 python scripts/estep_pair_shares_timing.py two_slot 9 &&
     timeout -k 10 300 python scripts/estep_pair_shares_timing.py wide 9 &&
     timeout -k 10 300 python scripts/estep_pair_shares_timing.py wide 64
 
 Input and protocol are DESIGN.md 4.8's: synth.generate(20_000, 20_000, 64, doublets=True); 'one_slot': 8 pools of 8 donors with
-doublets (36 options: the one-slot form, 4 grid points per walk), 'wide': 2 pools of 32 donors with doublets (528 options: the 16-slot
-form, 1 grid point per walk); shares 0.1 .. 0.9 in equal steps under the uniform prior; nothing of size row_ptr[B] downloaded; two
+doublets (36 options: the one-slot form, 4 grid points per walk), 'two_slot': 5 pools of 11 of the donors with doublets (66 options: the
+two-slot form, 2 grid points per walk), 'wide': 2 pools of 32 donors with doublets (528 options: the 16-slot form, 1 grid point per
+walk); shares 0.1 .. 0.9 in equal steps under the uniform prior; nothing of size row_ptr[B] downloaded; two
 warm-up repeats, then --repeats repeats, the passes taking turns; of each the library's own phase timer of the E-step slot
 (dmx_get_timings, DMX_T_ESTEP: events around the launches) and the host clock around the call; medians of both."""
 import argparse
@@ -27,7 +29,7 @@ sys.path.insert(0, ROOT)
 
 WARM_UP = 2
 B, S, G = 20_000, 20_000, 64
-SHAPES = {'one_slot': (8, 8, 36, 4), 'wide': (2, 32, 528, 1)}  # pools, donors per pool, options, grid points per walk
+SHAPES = {'one_slot': (8, 8, 36, 4), 'two_slot': (5, 11, 66, 2), 'wide': (2, 32, 528, 1)}  # pools, donors per pool, options, grid points per walk
 
 
 def run_variant(shape, n_shares, repeats):
@@ -35,7 +37,7 @@ def run_variant(shape, n_shares, repeats):
     from demuxalot_amd import synth
     from demuxalot_amd.device import DeviceContext
     n_pools, per_pool, options, points_per_walk = SHAPES[shape]
-    assert per_pool * (per_pool + 1) // 2 == options and n_pools * per_pool == G
+    assert per_pool * (per_pool + 1) // 2 == options and n_pools * per_pool <= G
     p = synth.generate(B, S, G, doublets=True)
     ctx = DeviceContext(0)
     try:

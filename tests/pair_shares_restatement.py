@@ -128,6 +128,49 @@ def restate_all_donors(v, cb, e, prob, B, doublet_prior, shares, log_weights=Non
     return out['logits'].reshape(B, -1), out['probs'].reshape(B, -1), out
 
 
+DESIGNED_LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17, 31, 33, 40, 5]  # calls of a barcode: none, either side of the 8-call padding
+
+
+@functools.lru_cache(maxsize=None)
+def designed_problem():
+    """(v, cb, e, prob, B, lengths, v2snp): 48 barcodes, barcode i with DESIGNED_LENGTHS[i % 12] calls (barcode 0 has none), on 1024
+    donors and 24 biallelic SNPs (48 variants); error probabilities at both ends of their range and table entries of exactly 0 and 1
+    among them.  The problem of tests/test_gpu_pair_shares.py's designed tests, without a device."""
+    rng = np.random.default_rng(29)
+    V, G, B = 48, 1024, 48
+    lengths = [DESIGNED_LENGTHS[i % len(DESIGNED_LENGTHS)] for i in range(B)]
+    v2snp = np.repeat(np.arange(V // 2, dtype=np.int32), 2)
+    v = np.concatenate([np.sort(rng.choice(V, size=n, replace=False)) for n in lengths]).astype(np.int32)
+    cb = np.repeat(np.arange(B), lengths).astype(np.int32)
+    e = rng.choice(np.array([0.0, 1e-5, 1e-4, 0.01, 0.3, 1.0], dtype=np.float32), size=len(v))
+    order = np.lexsort((cb, v))
+    v, cb, e = v[order], cb[order], e[order]
+    prob = rng.uniform(0.01, 0.99, size=(V, G)).astype(np.float32)
+    prob[rng.random(size=prob.shape) < 0.05] = 0.0  # entries of exactly 0 ...
+    prob[rng.random(size=prob.shape) < 0.02] = 1.0  # ... and of exactly 1
+    prob[0, :3] = [0.0, 1.0, 0.5]                   # (row 0 is what the padding calls point at)
+    assert np.bincount(cb, minlength=B).tolist() == lengths and lengths[0] == 0
+    return v, cb, e, prob, B, np.asarray(lengths), v2snp
+
+
+def half_shares_against_no_ambient(sizes, n, seed=12):
+    """The two grid-summed passes where they are one computation: n shares of 0.5 against n ambient fractions of 0,
+    under the same steep, unsorted log weights, on designed pools of `sizes` donors with doublets (the first pool's pair penalty -inf).
+    p1 0.5 + p2 0.5 and (p1 + p2) 0.5 round alike for normal float32 and q 1 + a 0 is q, so every grid point has the same lambda and
+    the two folds see the same t.  (pools, pool_of, penalty, shares, alphas, ambient, log_weights)."""
+    v, cb, e, prob, B, _lengths, _v2snp = designed_problem()
+    rng = np.random.default_rng(seed)
+    pools = [sorted(int(d) for d in rng.choice(prob.shape[1], size=g, replace=False)) for g in sizes]
+    pool_of = (np.arange(B) % (len(pools) + 1)).astype(np.int32)
+    pool_of[pool_of == len(pools)] = -1
+    penalty = np.linspace(-2, 1.5, len(pools)).astype(np.float32)
+    penalty[0] = -np.inf
+    weights = rng.uniform(-30, 2, size=n).astype(np.float32)
+    weights[n // 2] = -60.0
+    ambient = rng.uniform(0, 1, size=prob.shape[0]).astype(np.float32)
+    return pools, pool_of, penalty, np.full(n, 0.5, np.float32), np.zeros(n, np.float32), ambient, weights
+
+
 SHARED = ('row_ptr', 'logits', 'probs', 'best_option', 'best_prob', 'doublet_mass')
 OWN = ('share_index', 'share_mean', 'best_share_index', 'best_share_mean')
 

@@ -25,7 +25,7 @@ DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
 F1, F2, SMALL = 'f1_synthetic_default.npz', 'f2_synthetic_g4.npz', 'f3_small_2.npz'  # G = 20, 4, 5
 GRID = np.array([0.0, 1.0, 0.01, 0.37, 0.63], dtype=np.float32)
 SHARED = ('row_ptr', 'logits', 'probs', 'best_option', 'best_prob', 'doublet_mass')
-POINTS_PER_WALK = (4, 2, 1)  # csrc/estep_ambient_grid.hip: GridPoints - by option slots 1, 2, 4 and more
+POINTS_PER_WALK = (4, 2, 1)  # csrc/estep_grid_device.h: GridPoints - by option slots 1, 2, 4 and more
 
 
 @functools.lru_cache(maxsize=None)

@@ -70,7 +70,7 @@ def test_s1_s2_the_one_share_of_a_half_is_the_pooled_pass(name, doublet_prior):
 
 
 # ---- 2. the designed problem ------------------------------------------------------------------------------------------------------------
-LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17, 31, 33, 40, 5]  # calls of a barcode: none, either side of the 8-call padding
+LENGTHS = restated.DESIGNED_LENGTHS  # calls of a barcode: none, either side of the 8-call padding
 ONE_SLOT, TWO_SLOTS, WIDE = [2, 10], [11, 15], [16, 22, 23, 31, 32, 44]
 
 
@@ -79,24 +79,11 @@ def designed():
     """48 barcodes, barcode i with LENGTHS[i % 12] calls (barcode 0 has none), on 1024 donors and 24 biallelic SNPs (48 variants);
     error probabilities at both ends of their range and table entries of exactly 0 and 1 among them."""
     from demuxalot_amd.device import DeviceContext
-    rng = np.random.default_rng(29)
-    V, G, B = 48, 1024, 48
-    lengths = [LENGTHS[i % len(LENGTHS)] for i in range(B)]
-    v2snp = np.repeat(np.arange(V // 2, dtype=np.int32), 2)
-    v = np.concatenate([np.sort(rng.choice(V, size=n, replace=False)) for n in lengths]).astype(np.int32)
-    cb = np.repeat(np.arange(B), lengths).astype(np.int32)
-    e = rng.choice(np.array([0.0, 1e-5, 1e-4, 0.01, 0.3, 1.0], dtype=np.float32), size=len(v))
-    order = np.lexsort((cb, v))
-    v, cb, e = v[order], cb[order], e[order]
-    prob = rng.uniform(0.01, 0.99, size=(V, G)).astype(np.float32)
-    prob[rng.random(size=prob.shape) < 0.05] = 0.0  # entries of exactly 0 ...
-    prob[rng.random(size=prob.shape) < 0.02] = 1.0  # ... and of exactly 1
-    prob[0, :3] = [0.0, 1.0, 0.5]                   # (row 0 is what the padding calls point at)
+    v, cb, e, prob, B, lengths, v2snp = restated.designed_problem()  # (the CPU tests walk the same problem)
     ctx = DeviceContext(0)
-    ctx.set_problem(B, V, G, v, cb, e, v2snp)
+    ctx.set_problem(B, prob.shape[0], prob.shape[1], v, cb, e, v2snp)
     ctx.set_probs(prob)
-    assert np.bincount(cb, minlength=B).tolist() == lengths and lengths[0] == 0
-    return ctx, v, cb, e, prob, B, np.asarray(lengths)
+    return ctx, v, cb, e, prob, B, lengths
 
 
 def spread_columns(rng, n, G=1024):
@@ -215,6 +202,26 @@ def test_s3_s4_and_pair_penalties_without_end():
     means = endless['share_mean'][endless['row_ptr'][b]:endless['row_ptr'][b + 1]]
     fio.assert_bitwise(means[16:], np.full(120, np.float32(0.75) / np.float32(3), np.float32), '-inf == -inf: every grid point counts once')
     assert np.isnan(means[:16]).all()
+
+
+@pytest.mark.parametrize('n', [1, 3, 5])
+def test_shares_of_a_half_are_the_ambient_marginal_without_ambient(n):
+    """The one fold and finish of the two grid-summed passes (csrc/estep_grid_device.h), on the device: n shares of 0.5
+    and n ambient fractions of 0 under the same steep log weights give every pair option the same logit and the same grid point, bit
+    for bit, on pools of the 1-, 2-, 4-, 8- and 16-slot forms and grids on either side of 2 and 4 points per walk; one pool's pair
+    penalty is -inf.  (tests/test_pair_shares_cpu.py holds the restatements to the same.)"""
+    ctx, v, cb, e, prob, B, lengths = designed()
+    sizes = [2, 11, 16, 23, 44]
+    assert [g * (g + 1) // 2 for g in sizes] == [3, 66, 136, 276, 990]
+    pools, pool_of, penalty, shares, alphas, ambient, weights = restated.half_shares_against_no_ambient(sizes, n)
+    shared = ctx.estep_pair_shares(pools, pool_of, True, penalty, shares, log_weights=weights)
+    summed = ctx.estep_ambient_grid(pools, pool_of, True, penalty, alphas, ambient=ambient, over_grid='marginal', log_weights=weights)
+    assert np.array_equal(shared['row_ptr'], summed['row_ptr'])
+    pairs = ~np.isnan(shared['share_mean'])  # (a singlet's mean is NaN, a pair's 0.5)
+    assert int(pairs.sum()) == sum((g * (g - 1) // 2) * int((pool_of == p).sum()) for p, g in enumerate(sizes))
+    fio.assert_bitwise(shared['logits'][pairs], summed['logits'][pairs], f'{n} grid points: the logits of the pair options')
+    assert np.array_equal(shared['share_index'][pairs], summed['alpha_index'][pairs]), f'{n} grid points: the grid point of the largest term'
+    assert (shared['logits'][pairs] == -np.inf).any() and np.isfinite(shared['logits'][pairs]).any()
 
 
 def test_null_outputs_are_honoured():

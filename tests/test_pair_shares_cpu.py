@@ -129,6 +129,32 @@ def test_s4_s5_and_a_pair_penalty_without_end(name):
         assert not endless['share_index'][pairs].any() and not (endless['probs'][pairs] != 0).any()
 
 
+@pytest.mark.parametrize('n', [1, 3, 5])
+def test_shares_of_a_half_are_the_ambient_marginal_without_ambient(n):
+    """What the two grid-summed passes have in one home (csrc/estep_grid_device.h), pinned on the restatements: with
+    n shares of 0.5 and n ambient fractions of 0 every grid point has the same lambda - p1 0.5 + p2 0.5 and (p1 + p2) 0.5 round alike,
+    q 1 + a 0 is q - so under the same log weights the two folds see the same t: the pair options' logits agree bit for bit and the
+    share index is the alpha index.  (tests/test_gpu_pair_shares.py asserts the same of the device.)"""
+    from tests import ambient_marginal_restatement as marginal
+    v, cb, e, prob, B, _lengths, _v2snp = restated.designed_problem()
+    f = np.float32
+    assert prob[prob != 0].min() >= 2.0 ** -125, 'no halved table entry is subnormal'
+    a, b = prob[:, :512], prob[:, 512:]
+    restated.same_bits(a * f(0.5) + b * f(0.5), (a + b) * f(0.5), 'the two halvings')
+    restated.same_bits(a * (f(1) - f(0)) + b[:, :1] * f(0), a, 'q 1 + a 0 is q')
+    pools, pool_of, penalty, shares, alphas, ambient, weights = restated.half_shares_against_no_ambient([2, 11, 16, 23, 44], n)
+    shared = restated.restate(v, cb, e, prob, B, pools, pool_of, penalty, True, shares, weights)
+    summed = marginal.restate(v, cb, e, prob, B, pools, pool_of, penalty, True, alphas, ambient, weights)
+    assert np.array_equal(shared['row_ptr'], summed['row_ptr'])
+    pairs = ~shared['single']
+    restated.same_bits(shared['S'][pairs], summed['S'][pairs], 'every grid point has the same float64 sum')
+    restated.same_bits(shared['logits'][pairs], summed['logits'][pairs], f'{n} grid points: the logits of the pair options')
+    assert np.array_equal(shared['share_index'][pairs], summed['alpha_index'][pairs])
+    assert (shared['logits'][pairs] == -np.inf).any() and np.isfinite(shared['logits'][pairs]).any()
+    if n > 1:
+        assert len(np.unique(shared['share_index'][pairs])) > 1, 'the weights and the penalty of -inf move the largest term'
+
+
 # ---- 2. the value conditions -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('share', [0.8, 0.5])
 def test_the_value_conditions_hold_on_the_restated_simulation(share):
