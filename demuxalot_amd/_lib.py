@@ -172,6 +172,10 @@ DEBUG_SIGNATURES = {
                                _P]),
     'dmx_em_doublets': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
     'dmx_mstep_doublets': (c_int, [_P, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, _P, c_int64, _P]),
+    'dmx_em_doublet_shares': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_int32, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'dmx_estep_pair_shares_resident': (c_int, [_P, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    'dmx_mstep_doublet_shares': (c_int, [_P, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     'dmx_set_keep_pooled': (c_int, [_P, c_int]),
     'dmx_pooled_upload': (c_int, [_P, c_int64, c_int32, c_int, c_int32, _P, _P, _P, _P, _P, _P]),
     'dmx_pooled_info': (c_int, [_P, POINTER(c_int64)]),

@@ -26,11 +26,13 @@
 #include "ambient_learning_plan.h"
 #include "ambient_scoring_plan.h"
 #include "doublet_learning_plan.h"
+#include "doublet_shares_learning_plan.h"
 #include "estep_ambient.h"
 #include "estep_ambient_grid.h"
 #include "estep_pair_shares.h"
 #include "estep_pools.h"
 #include "mstep_ambient.h"
+#include "mstep_doublet_shares.h"
 #include "mstep_doublets.h"
 #include "mstep_plan.h"
 #include "pair_shares_plan.h"
@@ -1263,6 +1265,73 @@ int dmx_mstep_doublets(dmx_ctx *c, float power, float min_pair_posterior, int wi
                          lp::check_mstep(ambient_facts(c, c->have_probs), c->have_post, pools, power, min_pair_posterior, n_rows, post_rows), pools,
                          {nullptr, nullptr, nullptr, nullptr, nullptr}, plan));
     DMX_TRY(dmx::run_mstep_doublets_from_host(c, power, min_pair_posterior, plan, post_rows, lp::pair_options(c->B, pools)));
+    DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Learning from doublets of unequal shares (estep_pair_shares.hip: the dense form; mstep_doublet_shares.hip).
+// doublet_shares_learning_plan.h refuses, on the host, before anything is uploaded or launched.  dmx_em_doublets' loop with the
+// grid-summed dense E-step and the share-weighted crediting M-step; share_mean stays on the device between the two.
+int dmx_em_doublet_shares(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                          const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr,
+                          float power, float min_pair_posterior, int32_t n_shares, const float *shares, const float *log_weights,
+                          float *logits_out, float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, float *addition_out,
+                          int32_t *share_index, float *share_mean, int32_t *best_share_index, float *best_share_mean)
+{
+    namespace lp = dmx::dslplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_em_doublet_shares",
+                         lp::check_em(ambient_facts(c, c->have_betas), pools, n_shares, shares, log_weights, n_iterations, power, min_pair_posterior),
+                         pools, {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
+    const dmx::PairSharesScoring scoring{(int)n_shares, shares, log_weights, share_index, share_mean, best_share_index, best_share_mean};
+    DMX_TRY(begin_dense_pools(c));
+    DMX_TRY(begin_em_additions(c));
+    dmx::PairSharesRunPtr run;
+    DMX_TRY(dmx::prepare_pair_shares_run(c, plan, scoring, run));
+    dmx::DoubletSharesRunPtr credited;
+    DMX_TRY(dmx::prepare_doublet_shares_run(c, *run, lp::pair_options(c->B, pools), credited));
+    // (msteps_ahead is not set around this M-step: run_mstep_doublet_shares has one form, the float64 sums, and asks no plan of mstep_plan.h)
+    DMX_TRY(run_dense_em(
+        c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_pair_shares_pass(c, *run, power); },
+        [&](int) { return dmx::run_mstep_doublet_shares(c, power, min_pair_posterior, *credited); }));
+    return dmx::read_back_pair_shares(c, *run);
+}
+
+int dmx_estep_pair_shares_resident(dmx_ctx *c, int with_doublets, int32_t n_pools, const int64_t *pool_start, const int32_t *pool_donors,
+                                   const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr, float *logits_out,
+                                   float *probs_out, int32_t *best_option, float *best_prob, double *doublet_mass, int32_t n_shares,
+                                   const float *shares, const float *log_weights, int32_t *share_index, float *share_mean,
+                                   int32_t *best_share_index, float *best_share_mean)
+{
+    namespace lp = dmx::dslplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_estep_pair_shares_resident", lp::check_estep(ambient_facts(c, c->have_probs), pools, n_shares, shares, log_weights),
+                         pools, {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
+    const dmx::PairSharesScoring scoring{(int)n_shares, shares, log_weights, share_index, share_mean, best_share_index, best_share_mean};
+    DMX_TRY(begin_dense_pools(c));
+    dmx::PairSharesRunPtr run;
+    DMX_TRY(dmx::prepare_pair_shares_run(c, plan, scoring, run));
+    DMX_TRY(dmx::launch_pair_shares_pass(c, *run, 2.0f));  // (the floor of a squaring M-step; the M-steps rebuild for another power)
+    return dmx::read_back_pair_shares(c, *run);
+}
+
+int dmx_mstep_doublet_shares(dmx_ctx *c, float power, float min_pair_posterior, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                             const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr,
+                             const float *post_rows, const float *share_rows, int64_t n_rows, float *addition_out)
+{
+    namespace lp = dmx::dslplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_mstep_doublet_shares",
+                         lp::check_mstep(ambient_facts(c, c->have_probs), c->have_post, pools, power, min_pair_posterior, n_rows, post_rows, share_rows),
+                         pools, {nullptr, nullptr, nullptr, nullptr, nullptr}, plan));
+    DMX_TRY(dmx::run_mstep_doublet_shares_from_host(c, power, min_pair_posterior, plan, post_rows, share_rows, lp::pair_options(c->B, pools)));
     DMX_TRY(copy_out(c, addition_out, c->d_add.p, (size_t)c->V * c->G));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

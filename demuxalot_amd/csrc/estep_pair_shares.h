@@ -13,7 +13,7 @@ struct dmx_ctx;
 
 namespace dmx {
 
-// argument block of k_estep_pair_shares: k_estep_pools' (its `dense` is not used) and what the grid adds
+// argument block of k_estep_pair_shares: k_estep_pools' (its `dense` is written by the DENSE form alone) and what the grid adds
 struct PairSharesArgs {
     PoolEstepArgs pools;
     const float *shares;       // [n_shares] the share of a pair's first donor
@@ -23,7 +23,8 @@ struct PairSharesArgs {
     float *share_mean;         // compact like the logits: a pair's posterior mean share; NaN: a singlet, or every value NaN
 };
 // the pools of a launch have pair options (with_doublets): there is no form for singlets alone - that is k_estep_pools
-hipError_t launch_estep_pair_shares(hipStream_t st, const PairSharesArgs &a, int slots);
+// dense: the form that also leaves the singlet posteriors in a.pools.dense (learning under shares: the M-step's input)
+hipError_t launch_estep_pair_shares(hipStream_t st, const PairSharesArgs &a, int slots, bool dense = false);
 
 // what dmx_estep_pair_shares passes on beside the pools' plan: host pointers
 struct PairSharesScoring {
@@ -38,5 +39,24 @@ struct PairSharesScoring {
 // prepare_estep_pools, the kernels (estep_grid.h: run_grid_estep), read_back_estep_pools.  Without doublets: the pooled pass itself, the
 // share outputs filled with -1 / NaN on the host, no grid kernel.  The context's pooled slot (dmx_set_keep_pooled) is left alone.
 int run_estep_pair_shares(dmx_ctx *c, const PoolsPlan &plan, const PairSharesScoring &scoring);
+
+// The dense pass in three parts, as estep_ambient.h has its own, so that a call of several E-steps (dmx_em_doublet_shares) pays the host
+// round trip once and share_mean stays on the device for the M-step between two of them (mstep_doublet_shares.h).
+//   prepare    prepare_estep_pools (dense), the grid and the prior uploaded, the four grid outputs; `plan` outlives the run
+//   launch     the DENSE kernels into the context's own d_post as [B, G] (the caller has begun the dense pass: dmx_steps.cpp),
+//              the best option's entries, close_dense_pools_pass with the floor of `power`.  Without doublets: the dense pooled
+//              pass itself, no grid kernel
+//   read back  the share outputs (-1 / NaN on the host without doublets), then read_back_estep_pools
+struct PairSharesRun;
+struct PairSharesRunDeleter {
+    void operator()(PairSharesRun *run) const;
+};
+typedef std::unique_ptr<PairSharesRun, PairSharesRunDeleter> PairSharesRunPtr;
+int prepare_pair_shares_run(dmx_ctx *c, const PoolsPlan &plan, const PairSharesScoring &scoring, PairSharesRunPtr &run);
+int launch_pair_shares_pass(dmx_ctx *c, PairSharesRun &run, float power);
+int read_back_pair_shares(dmx_ctx *c, PairSharesRun &run);
+// the prepared pooled run inside it, and the compact share_mean on the device (null without doublets)
+const PoolsRun &pair_shares_run_pools(const PairSharesRun &run);
+const float *pair_shares_run_mean(const PairSharesRun &run);
 
 }  // namespace dmx

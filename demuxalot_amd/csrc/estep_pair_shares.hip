@@ -12,6 +12,9 @@
 // the pooled pass's; their state is closed from the grid's first point alone with a weight of 0, so s stays 1, log_f32(1) is +0 and the
 // close receives the sum itself.  They are recomputed on every walk: n of n (n + 1) / 2 options.  With pairs a pool has at most 44
 // donors, so every singlet sits in slot 0: the other slots take their two weights from SGPRs.
+// The DENSE form (dmx_estep_pair_shares_resident, dmx_em_doublet_shares) is the same kernel closed with the dense
+// pool_row_close; its host side is the pass in three parts - prepare / launch pass / read back (PairSharesRun) - with share_mean kept
+// on the device for the M-step between two E-steps (mstep_doublet_shares.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,7 +64,9 @@ __device__ __forceinline__ void share_terms(const npm::f32x2 (&p1)[H][A], const 
 
 // The state per (lane, slot), its fold and its finish are the frame's (estep_grid_device.h), with the shares where the
 // marginal pass has its fractions: registers for one and two slots, LDS from four slots on.
-template <int A, int U, int J>
+// DENSE: the close also leaves the barcode's singlet posteriors in a.dense, as k_estep_pools' dense form does (learning under shares:
+// mstep_doublet_shares.hip); everything else is the same kernel.
+template <int A, int U, int J, bool DENSE>
 __global__ __launch_bounds__(256) void k_estep_pair_shares(PairSharesArgs args)
 {
     constexpr bool IN_LDS = A >= 4;
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(256) void k_estep_pair_shares(PairSharesArgs args)
         sums.load(mine, s, st, jm);
         row_sum[s] = grid_finish(st, jm, args.log_weights, s == 0 && single, mean[s], index[s]);
     }
-    pool_row_close<A, true, false>(a, lane, row, row_sum);
+    pool_row_close<A, true, DENSE>(a, lane, row, row_sum);
     const long long out_row = a.row_ptr[row.b];
 #pragma unroll
     for (int s = 0; s < A; s++)
@@ -150,20 +155,97 @@ __global__ __launch_bounds__(256) void k_estep_pair_shares(PairSharesArgs args)
 }
 
 template <int A, int U>
-void launch_one(hipStream_t st, const PairSharesArgs &a)
+void launch_one(hipStream_t st, const PairSharesArgs &a, bool dense)
 {
     const dim3 grid((unsigned)((a.pools.n_list + 3) / 4)), block(256);
-    hipLaunchKernelGGL((k_estep_pair_shares<A, U, GridPoints<A>::J>), grid, block, 0, st, a);
+    if (dense)
+        hipLaunchKernelGGL((k_estep_pair_shares<A, U, GridPoints<A>::J, true>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((k_estep_pair_shares<A, U, GridPoints<A>::J, false>), grid, block, 0, st, a);
 }
 
 }  // namespace
 
-hipError_t launch_estep_pair_shares(hipStream_t st, const PairSharesArgs &a, int slots)
+hipError_t launch_estep_pair_shares(hipStream_t st, const PairSharesArgs &a, int slots, bool dense)
 {
     if (a.pools.n_list == 0) return hipSuccess;
     if (a.n_shares < 1 || a.n_shares > psplan::MAX_SHARES || !a.shares || !a.log_weights || !a.share_index || !a.share_mean) return hipErrorInvalidValue;
-    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a); });
+    if (dense && (a.pools.dense == nullptr || a.pools.G <= 0)) return hipErrorInvalidValue;
+    return launch_pool_form(slots, [&](auto form) { launch_one<decltype(form)::A, decltype(form)::U>(st, a, dense); });
 }
+
+// what a call that learns under shares keeps on the device between its parts (estep_pair_shares.h)
+struct PairSharesRun {
+    scratch::Scratch sc;
+    PoolsRunPtr pools;
+    PairSharesScoring scoring;
+    const PoolsPlan *plan;
+    GridOutputs out;
+    PairSharesArgs a = {};
+    size_t n_values = 0;
+    PairSharesRun(dmx_ctx *c, const PoolsPlan *p, const PairSharesScoring &s) : sc(c), scoring(s), plan(p) {}
+};
+
+void PairSharesRunDeleter::operator()(PairSharesRun *run) const { delete run; }
+
+int prepare_pair_shares_run(dmx_ctx *c, const PoolsPlan &plan, const PairSharesScoring &scoring, PairSharesRunPtr &run)
+{
+    using namespace dmx::scratch;
+    const hipStream_t st = c->stream;
+    run.reset(new PairSharesRun(c, &plan, scoring));
+    PairSharesRun &r = *run;
+    r.n_values = c->B > 0 ? (size_t)plan.row_ptr[c->B] : 0;
+    DMX_TRY(prepare_estep_pools(c, plan, true, r.pools));
+    if (!plan.with_doublets) return 0;  // no pair option anywhere: the dense pooled pass, and nothing to say about shares
+    float *d_shares = nullptr, *d_log_weights = nullptr;
+    DMX_TRY(upload(r.sc, &d_shares, scoring.shares, (size_t)scoring.n_shares, st));
+    DMX_TRY(upload_log_weights(r.sc, &d_log_weights, scoring.log_weights, scoring.n_shares, st));
+    DMX_TRY(r.out.get(r.sc, r.n_values, (size_t)c->B, true));
+    r.a.shares = d_shares;
+    r.a.log_weights = d_log_weights;
+    r.a.n_shares = scoring.n_shares;
+    r.a.share_index = r.out.index;
+    r.a.share_mean = r.out.mean;
+    HIP_TRY(hipStreamSynchronize(st));  // (the uploads read the caller's arrays)
+    return 0;
+}
+
+int launch_pair_shares_pass(dmx_ctx *c, PairSharesRun &r, float power)
+{
+    using namespace dmx::host;
+    if (!r.plan->with_doublets) return launch_estep_pools_pass(c, *r.pools, power);
+    const PoolsLaunchView view = pools_launch_view(*r.pools);
+    PairSharesArgs a = r.a;
+    DMX_TRY(run_grid_estep(c, view, r.out, nullptr, [&](hipStream_t s, const PoolEstepArgs &pools, int slots) {
+        a.pools = pools;
+        a.pools.dense = c->d_post.p;  // [B, G]: K = G
+        return launch_estep_pair_shares(s, a, slots, true);
+    }));
+    TimerSpan ev{nullptr, nullptr};  // the rebuild of the bitmap and the codes: a second span of the same slot
+    SpanGuard ev_guard{c, &ev};
+    timer_begin(c, DMX_T_ESTEP, &ev);
+    DMX_TRY(close_dense_pools_pass(c, power));
+    timer_end(c, DMX_T_ESTEP, ev);
+    return 0;
+}
+
+int read_back_pair_shares(dmx_ctx *c, PairSharesRun &r)
+{
+    const PairSharesScoring &scoring = r.scoring;
+    const size_t B = (size_t)c->B;
+    if (r.plan->with_doublets) {
+        DMX_TRY(r.out.download(c->stream, r.n_values, B, scoring.share_index, scoring.share_mean, scoring.best_share_index, scoring.best_share_mean));
+    } else {
+        if (scoring.share_index) std::fill_n(scoring.share_index, r.n_values, -1);
+        if (scoring.share_mean) std::fill_n(scoring.share_mean, r.n_values, std::numeric_limits<float>::quiet_NaN());
+        if (scoring.best_share_index) std::fill_n(scoring.best_share_index, B, -1);
+        if (scoring.best_share_mean) std::fill_n(scoring.best_share_mean, B, std::numeric_limits<float>::quiet_NaN());
+    }
+    return read_back_estep_pools(c, *r.pools);  // (synchronises)
+}
+
+const PoolsRun &pair_shares_run_pools(const PairSharesRun &run) { return *run.pools; }
+const float *pair_shares_run_mean(const PairSharesRun &run) { return run.out.mean; }
 
 int run_estep_pair_shares(dmx_ctx *c, const PoolsPlan &plan, const PairSharesScoring &scoring)
 {

@@ -21,6 +21,7 @@
 #include "estep_ambient_grid.h"
 #include "estep_pair_shares.h"
 #include "estep_pools.h"
+#include "mstep_doublet_shares.h"
 #include "mstep_doublets.h"
 
 // ------------------------------------------------------------------------------------
@@ -195,6 +196,28 @@ int run_mstep_doublets(dmx_ctx *, float, float, DoubletRun &) { return 0; }  // 
 int run_mstep_doublets_from_host(dmx_ctx *, float, float, const PoolsPlan &, const float *, long long) { return 0; }  // (validated by dmx_mstep_doublets)
 int run_estep_ambient_grid(dmx_ctx *, const PoolsPlan &, const AmbientGridScoring &) { return 0; }  // (validated by dmx_estep_ambient_grid / _marginal; nothing is written)
 int run_estep_pair_shares(dmx_ctx *, const PoolsPlan &, const PairSharesScoring &) { return 0; }  // (validated by dmx_estep_pair_shares; nothing is written)
+struct PairSharesRun {};
+void PairSharesRunDeleter::operator()(PairSharesRun *run) const { delete run; }
+int prepare_pair_shares_run(dmx_ctx *, const PoolsPlan &, const PairSharesScoring &, PairSharesRunPtr &run)
+{
+    run.reset(new PairSharesRun);
+    return 0;
+}
+int launch_pair_shares_pass(dmx_ctx *c, PairSharesRun &, float power)
+{
+    c->dense_pass_done(live_floor_float64(power));
+    return 0;
+}
+int read_back_pair_shares(dmx_ctx *, PairSharesRun &) { return 0; }
+struct DoubletSharesRun {};
+void DoubletSharesRunDeleter::operator()(DoubletSharesRun *run) const { delete run; }
+int prepare_doublet_shares_run(dmx_ctx *, const PairSharesRun &, long long, DoubletSharesRunPtr &run)
+{
+    run.reset(new DoubletSharesRun);
+    return 0;
+}
+int run_mstep_doublet_shares(dmx_ctx *, float, float, DoubletSharesRun &) { return 0; }  // (validated by dmx_em_doublet_shares; nothing is written)
+int run_mstep_doublet_shares_from_host(dmx_ctx *, float, float, const PoolsPlan &, const float *, const float *, long long) { return 0; }  // (validated by dmx_mstep_doublet_shares)
 hipError_t launch_remap_row_offsets(hipStream_t, CallPair *pairs, long long n_pairs, unsigned row_bytes, const int *new_rows, unsigned *call_rows)
 {
     // this one is cheap enough to do for real: it indexes new_rows with what the records hold

@@ -1,5 +1,5 @@
 // mstep_weighted.h -- the frame of the M-steps whose per-call weight reads the table of the iteration (mstep_weighted.hip; the forms:
-// mstep_ambient.h, mstep_doublets.h): the argument block they share, the host steps around their launches, and the
+// mstep_ambient.h, mstep_doublets.h, mstep_doublet_shares.h): the argument block they share, the host steps around their launches, and the
 // combining pass of the variants that span several work items.  What a form's weight reads comes behind this block in the form's own.
 #pragma once
 #include <functional>

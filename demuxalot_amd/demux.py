@@ -1345,6 +1345,87 @@ class Demultiplexer:
                 }
                 genotype_addition = ctx.mstep_doublets(*pools, out['probs'], min_pair_posterior, Demultiplexer.contribution_power)
 
+    @staticmethod
+    def _share_posteriors(setup, genotypes, barcode_handler, grid, log_weights, out):
+        """The DoubletSharePosteriors of a pass over a grid of mixing shares (index name None: the learning entries' frames)."""
+        names = list(genotypes.genotype_names)
+        return DoubletSharePosteriors(barcode_handler.ordered_barcodes, setup.option_names, [[names[g] for g in columns] for columns in setup.pool_columns],
+                                      setup.pool_of_barcode, out['row_ptr'], grid, log_weights, out['share_index'], out['share_mean'],
+                                      out['best_option'], out['best_prob'], out['doublet_mass'], out['best_share_index'], out['best_share_mean'],
+                                      _framed_posteriors(setup, barcode_handler, out, None), index_name=None)
+
+    @staticmethod
+    def learn_genotypes_with_doublet_shares(chromosome2compressed_snp_calls,
+                                            genotypes,
+                                            barcode_handler,
+                                            n_iterations=5,
+                                            p_genotype_clip=0.01,
+                                            doublet_prior=0.35,
+                                            shares=None,
+                                            share_log_weights=None,
+                                            min_pair_posterior=1e-3,
+                                            barcode2pool=None,
+                                            pool2donors=None) -> Tuple[object, DoubletSharePosteriors]:
+        """(not in the reference) learn_genotypes_from_doublets for doublets of unequal shares: its loop with the E-step of
+        predict_posteriors_with_doublet_shares - every pair option the marginal over a grid of mixing shares, so that an 80 / 20
+        doublet is recognised at all - and an M-step that credits the donors of a pair 'A+B' at the pair's posterior mean share w of
+        A: r_A = prob[A] w / (prob[A] w + prob[B] (1 - w)), r_B the rest, in place of the even mixture's prob[A] / (prob[A] + prob[B]),
+        which hands the minor donor too much of the major donor's signal.  With shares=[0.5] and
+        share_log_weights=[0.0] the result is learn_genotypes_from_doublets' bit for bit.  The whole loop runs on the GPU
+        (dmx_em_doublet_shares); its sums are float64 in the reference's order whatever DEMUXALOT_AMD_ESTEP says.
+        :param shares, share_log_weights: the grid and the prior over it, as predict_posteriors_with_doublet_shares takes them
+            (None: 0.1 .. 0.9 under the uniform prior)
+        :param min_pair_posterior, barcode2pool, pool2donors: as learn_genotypes_from_doublets takes them
+        :return: learnt genotypes (betas = raw betas + the addition used by the last E-step) and the DoubletSharePosteriors of the
+            last iteration.
+        ValueError: what predict_posteriors_with_doublet_shares and learn_genotypes_from_doublets raise."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        grid, log_weights = resolve_shares(shares, share_log_weights)
+        setup = Demultiplexer._doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors,
+                                                      'learn_genotypes_with_doublet_shares')
+        with shared_context_lock:
+            ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
+                                          fetch_betas=False)
+            out = ctx.em_doublet_shares(n_iterations, p_genotype_clip, setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0,
+                                        setup.pair_penalty, grid, log_weights, min_pair_posterior,
+                                        contribution_power=Demultiplexer.contribution_power, fetch_addition=False)
+            learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
+        return genotypes._with_betas(learnt_betas, _take=True), Demultiplexer._share_posteriors(setup, genotypes, barcode_handler, grid, log_weights, out)
+
+    @staticmethod
+    def staged_genotype_learning_with_doublet_shares(chromosome2compressed_snp_calls,
+                                                     genotypes,
+                                                     barcode_handler,
+                                                     n_iterations=5,
+                                                     p_genotype_clip=0.01,
+                                                     doublet_prior=0.35,
+                                                     shares=None,
+                                                     share_log_weights=None,
+                                                     min_pair_posterior=1e-3,
+                                                     barcode2pool=None,
+                                                     pool2donors=None):
+        """Generator over the iterations of learn_genotypes_with_doublet_shares, shaped like staged_genotype_learning_from_doublets:
+        yields (DoubletSharePosteriors, debug dict with 'genotype_prior', 'genotype_addition'); the yielded addition is the one the
+        iteration's E-step used.  The EM state lives on the GPU between yields, in a device context private to this generator."""
+        grid, log_weights = resolve_shares(shares, share_log_weights)
+        setup = Demultiplexer._doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors,
+                                                      'staged_genotype_learning_with_doublet_shares')
+        pools = (setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty)
+
+        with _generator_context() as ctx:
+            _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
+            genotype_addition = np.zeros_like(prior_betas)
+            ctx.set_addition(None)
+            for _iteration in range(n_iterations):
+                ctx.probs_from_betas(p_genotype_clip, fetch=False)
+                out = ctx.estep_pair_shares(*pools, grid, log_weights, resident=True)
+                yield Demultiplexer._share_posteriors(setup, genotypes, barcode_handler, grid, log_weights, out), {
+                    'genotype_prior': prior_betas,
+                    'genotype_addition': genotype_addition,
+                }
+                genotype_addition = ctx.mstep_doublet_shares(*pools, out['probs'], out['share_mean'], min_pair_posterior,
+                                                             Demultiplexer.contribution_power)
+
     # ------------------------------------------------------------------------------------
     @staticmethod
     def _doublet_penalties(n_genotypes: int, doublet_prior: float) -> np.ndarray:

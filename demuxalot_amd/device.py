@@ -877,8 +877,62 @@ class DeviceContext:
         return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, ambient=True, more=more,
                                  tail=tail)
 
+    def _shares_arguments(self, shares, log_weights):
+        """(shares float32[n], log_weights float32[n] or None) as the entries over a grid of mixing shares take them."""
+        shares = as_c(shares, np.float32)
+        assert shares.ndim == 1, 'the grid is one-dimensional'
+        if log_weights is not None:
+            log_weights = as_c(log_weights, np.float32)
+            assert log_weights.shape == shares.shape, 'one log weight per share'
+        return shares, log_weights
+
+    def _shares_results(self, shares, fetch_share_index, fetch_share_mean):
+        """more(n) of _pooled_call for the share outputs, and the pointers to them in the entries' order."""
+        def more(n):
+            return dict(shares=shares, share_index=np.full(n, -1, np.int32) if fetch_share_index else None,
+                        share_mean=np.full(n, np.nan, np.float32) if fetch_share_mean else None,
+                        best_share_index=np.full(self.B, -1, np.int32), best_share_mean=np.full(self.B, np.nan, np.float32))
+
+        def pointers(out):
+            return (ptr(out['share_index']), ptr(out['share_mean']), ptr(out['best_share_index']), ptr(out['best_share_mean']))
+
+        return more, pointers
+
+    def em_doublet_shares(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, shares, log_weights=None,
+                          min_pair_posterior=1e-3, contribution_power=2., fetch_logits=True, fetch_probs=True, fetch_addition=True,
+                          fetch_share_index=True, fetch_share_mean=True):
+        """n_iterations of P-step, the dense E-step over a grid of mixing shares and the M-step that credits a live pair's donors at
+        the pair's posterior mean share, on the device (include/demux_hip_debug.h: dmx_em_doublet_shares): em_doublets() with
+        estep_pair_shares() as its E-step and r = own w_own / (own w_own + other w_other) as a donor's responsibility.  Returns
+        em_doublets()'s dict with estep_pair_shares()'s share keys of the last E-step.  get_learnt_betas() and get_probs() (the dense
+        [B, G] singlet posteriors) work afterwards."""
+        shares, log_weights = self._shares_arguments(shares, log_weights)
+        more, pointers = self._shares_results(shares, fetch_share_index, fetch_share_mean)
+        return self._pooled_call(self._lib.dmx_em_doublet_shares, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 head=(int(n_iterations), *self.clip_bounds(p_genotype_clip)),
+                                 middle=(float(contribution_power), float(min_pair_posterior), len(shares), ptr(shares), ptr(log_weights)),
+                                 tail=lambda out: (ptr(out['addition']), *pointers(out)), fetch_addition=bool(fetch_addition), more=more,
+                                 dense=True)
+
+    def mstep_doublet_shares(self, pools, pool_of_barcode, with_doublets, pair_penalty, post_rows, share_rows, min_pair_posterior=1e-3,
+                             contribution_power=2., fetch=True):
+        """The M-step that learns from doublets of unequal shares (include/demux_hip_debug.h: dmx_mstep_doublet_shares) on the resident
+        dense posteriors and the table of the last P-step: post_rows and share_rows are the compact 'probs' and 'share_mean'
+        estep_pair_shares(..., resident=True) returned for the same pools.  Returns the addition float32[V, G] (None without fetch);
+        it becomes the context's, as after mstep()."""
+        pool_args, _keep, out = self._pools_arguments(pools, pool_of_barcode, with_doublets, pair_penalty, False, False)
+        post_rows = as_c(post_rows, np.float32)
+        assert post_rows.ndim == 1, 'the compact rows are one-dimensional'
+        if share_rows is not None:
+            share_rows = as_c(share_rows, np.float32)
+            assert share_rows.shape == post_rows.shape, 'one share per posterior of the rows'
+        addition = np.empty((self.V, self.G), dtype=np.float32) if fetch else None
+        check(self._lib.dmx_mstep_doublet_shares(self._h, float(contribution_power), float(min_pair_posterior), int(bool(with_doublets)),
+                                                 *pool_args, ptr(post_rows), ptr(share_rows), len(post_rows), ptr(addition)))
+        return addition
+
     def estep_pair_shares(self, pools, pool_of_barcode, with_doublets, pair_penalty, shares, log_weights=None, fetch_logits=True,
-                          fetch_probs=True, fetch_share_index=True, fetch_share_mean=True):
+                          fetch_probs=True, fetch_share_index=True, fetch_share_mean=True, resident=False):
         """The pooled E-step with every pair option summed over a grid of mixing shares (include/demux_hip_debug.h:
         dmx_estep_pair_shares): estep_pools() with a pair (d1, d2) scored as prob[d1] w + prob[d2] (1 - w) at every w of `shares`
         (float32, 1 .. 64 values in [0, 1], any order) and its logit the log of the sum over the grid of exp(its logit there +
@@ -887,24 +941,14 @@ class DeviceContext:
         'share_index' int32[row_ptr[B]], the grid point of every pair's largest term (-1: a singlet; None without fetch_share_index);
         'share_mean' float32[row_ptr[B]], every pair's posterior mean share of its first donor (NaN: a singlet; None without
         fetch_share_mean); 'best_share_index' int32[B] and 'best_share_mean' float32[B], those of best_option (-1 / NaN: a singlet
-        or none).  The resident results of the last E-step are left as they are."""
-        shares = as_c(shares, np.float32)
-        assert shares.ndim == 1, 'the grid is one-dimensional'
-        if log_weights is not None:
-            log_weights = as_c(log_weights, np.float32)
-            assert log_weights.shape == shares.shape, 'one log weight per share'
-
-        def more(n):
-            return dict(shares=shares, share_index=np.full(n, -1, np.int32) if fetch_share_index else None,
-                        share_mean=np.full(n, np.nan, np.float32) if fetch_share_mean else None,
-                        best_share_index=np.full(self.B, -1, np.int32), best_share_mean=np.full(self.B, np.nan, np.float32))
-
-        def tail(out):
-            return (len(shares), ptr(shares), ptr(log_weights), ptr(out['share_index']), ptr(out['share_mean']), ptr(out['best_share_index']),
-                    ptr(out['best_share_mean']))
-
-        return self._pooled_call(self._lib.dmx_estep_pair_shares, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
-                                 more=more, tail=tail)
+        or none).  The resident results of the last E-step are left as they are - unless resident=True
+        (dmx_estep_pair_shares_resident): then the singlet posteriors are left in the context as a dense [B, G] matrix, zero outside a
+        barcode's pool, so that mstep_doublet_shares() or mstep() may follow and get_probs() returns it."""
+        shares, log_weights = self._shares_arguments(shares, log_weights)
+        more, pointers = self._shares_results(shares, fetch_share_index, fetch_share_mean)
+        entry = self._lib.dmx_estep_pair_shares_resident if resident else self._lib.dmx_estep_pair_shares
+        return self._pooled_call(entry, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs, more=more,
+                                 tail=lambda out: (len(shares), ptr(shares), ptr(log_weights), *pointers(out)), dense=resident)
 
     # ---- pooled results kept resident (include/demux_hip_debug.h "Pooled results kept resident"; csrc/pooled_readout.hip) ----
     def set_keep_pooled(self, keep):

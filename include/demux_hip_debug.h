@@ -804,6 +804,60 @@ int dmx_mstep_doublets(dmx_ctx *ctx, float power, float min_pair_posterior, int 
                        const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
                        const float *post_rows /* [n_rows] */, int64_t n_rows, float *addition_out /* nullable, float32[V, G] */);
 
+/* ------------------------------------------------------------------------- *
+ * Learning from doublets of unequal shares (product API; csrc/mstep_doublet_shares.hip, csrc/estep_pair_shares.hip: the DENSE form;
+ * DESIGN.md 4.17).  "Learning from doublet posteriors" above with two changes per iteration: the E-step is dmx_estep_pair_shares'
+ * pass - its contract of logits, posteriors, share_index and share_mean, word for word - which also leaves dense[B, G], and the
+ * M-step credits a live pair's donors at the pair's posterior mean share.  Let k = (d1, d2) be a pair option of b's row with
+ * post[k] >= min_pair_posterior, d1 ahead of d2 in the pool's option order, and w = share_mean[b, k]; float32, every operation rounded:
+ *     w_own = w for g == d1;  w_own = 1.0f - w for g == d2 (rounded once);  w_other = the other of the two
+ *     a = prob[v, g] * w_own;  o = prob[v, h] * w_other
+ *     r = a == 0 ? 0.0f : a / (a + o)                               IEEE float32 division, correctly rounded
+ *     credit = credit + post[k] * r
+ * Everything else - the live dense credit, the threshold, the row's option order, w = (credit * keep_c) ^ power, the one float64
+ * accumulator per (v, g) in call order, ONE arithmetic whatever dmx_set_estep_mode says - is dmx_mstep_doublets'.  A live pair's
+ * share_mean lies in [0, 1] (u is a monotone float32 sum of terms fl(e_j share_j) <= e_j, so u <= s); nothing is clamped.
+ * Identities, bit for bit: (D1) shares = {0.5}, log_weights NULL or {0}: every output and every iteration's addition is
+ * dmx_em_doublets' - share_mean is exactly 0.5, halving is exact on a clipped table and (own / 2) / fl(own / 2 + other / 2) =
+ * own / fl(own + other); (D2) the same grid with a threshold above 1, or any grid with with_doublets == 0, is dmx_em_pools with exact additions (without doublets no
+ * grid kernel is launched); (D3) shares = {1}: a live pair credits its first donor post[k] where prob[v, d1] > 0 and its second
+ * donor nothing; shares = {0} is the mirror image.
+ *   dmx_em_doublet_shares   dmx_em_doublets' arguments, loop and outputs with the grid (n_shares, shares, log_weights: as
+ *               dmx_estep_pair_shares takes them) and, each nullable, share_index / share_mean / best_share_index / best_share_mean
+ *               of the last E-step.  Everything stays on the device between the steps; one read-back.
+ *   dmx_estep_pair_shares_resident   the arguments, the pass and the results of dmx_estep_pair_shares.  It also leaves `dense` as the
+ *               context's resident posteriors with K = G (and their bitmaps and codes), as dmx_estep_pools_resident does.
+ *   dmx_mstep_doublet_shares   stateless: dmx_mstep_doublets with share_rows float32[n_rows] beside post_rows, the compact share_mean
+ *               that E-step returned.  Only the entries of pair options are read.
+ * Checked on the host before anything is uploaded or launched (csrc/doublet_shares_learning_plan.h): what dmx_estep_pair_shares
+ * refuses, then what dmx_em_doublets / dmx_mstep_doublets refuse, with their codes and words; dmx_mstep_doublet_shares also gives
+ * DMX_ERR_INVALID for null share_rows (whatever n_rows) and for a pair entry of share_rows that is not finite or outside [0, 1], with its
+ * index.  The timer slots are dmx_em_doublets'.  The pooled slot (dmx_set_keep_pooled) is left as it is.
+ * ------------------------------------------------------------------------- */
+int dmx_em_doublet_shares(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools,
+                          const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                          const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */, float power,
+                          float min_pair_posterior, int32_t n_shares, const float *shares /* [n_shares] */,
+                          const float *log_weights /* nullable, [n_shares] */,
+                          float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                          int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                          float *addition_out /* nullable, float32[V, G] */,
+                          int32_t *share_index /* nullable, int32[row_ptr[B]] */, float *share_mean /* nullable, float32[row_ptr[B]] */,
+                          int32_t *best_share_index /* nullable, [B] */, float *best_share_mean /* nullable, [B] */);
+int dmx_estep_pair_shares_resident(dmx_ctx *ctx, int with_doublets, int32_t n_pools, const int64_t *pool_start /* [n_pools+1] */,
+                                   const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                                   const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                                   float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                                   int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                                   int32_t n_shares, const float *shares /* [n_shares] */, const float *log_weights /* nullable, [n_shares] */,
+                                   int32_t *share_index /* nullable, int32[row_ptr[B]] */, float *share_mean /* nullable, float32[row_ptr[B]] */,
+                                   int32_t *best_share_index /* nullable, [B] */, float *best_share_mean /* nullable, [B] */);
+int dmx_mstep_doublet_shares(dmx_ctx *ctx, float power, float min_pair_posterior, int with_doublets, int32_t n_pools,
+                             const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                             const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */,
+                             const float *post_rows /* [n_rows] */, const float *share_rows /* [n_rows] */, int64_t n_rows,
+                             float *addition_out /* nullable, float32[V, G] */);
+
 #ifdef __cplusplus
 }
 #endif
