@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "device_scratch.h"
+#include "pairwise_sum.h"
 
 namespace {
 
@@ -197,30 +198,8 @@ __device__ __forceinline__ unsigned long long descending_key(double x)
     return ~ascending;
 }
 
-// numpy's pairwise_sum of n float64 (np.add.reduce over a contiguous row, n <= 128 << DEPTH; np_math.h)
-template <int DEPTH>
-__device__ double pairwise_sum(const double *a, long long n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (long long i = 0; i < n; i++) res += a[i];
-        return res;
-    }
-    if (DEPTH == 0 || n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; j++) r[j] = a[j];
-        long long i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    long long n2 = n / 2;
-    n2 -= n2 % 8;
-    return pairwise_sum<DEPTH ? DEPTH - 1 : 0>(a, n2) + pairwise_sum<DEPTH ? DEPTH - 1 : 0>(a + n2, n - n2);
-}
-constexpr int MAX_DONORS = 8192;  // 128 << 6
+// the overall ranking's row sum: np.sum of a row of importances, bit for bit, for every n_donors up to MAX_DONORS (pairwise_sum.h)
+using dmx::rowsum::MAX_DONORS;
 
 // column-major keys of the per-donor rankings: entry d * P + p
 __global__ __launch_bounds__(256) void k_sd_donor_keys(const double *__restrict__ importance, long long P, int D,
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(256) void k_sd_row_keys(const double *__restrict__ 
 {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    key[p] = descending_key(pairwise_sum<6>(importance + p * D, D));
+    key[p] = descending_key(dmx::rowsum::pairwise_sum(importance + p * D, D));
     idx[p] = (unsigned)p;
 }
 

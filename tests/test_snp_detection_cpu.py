@@ -11,10 +11,13 @@ from tests import fixture_io as fio
 P_BELOW = np.float32(0.01)
 
 
-def flat_calls(candidate_calls):
-    """(chrom number, position, base, barcode, p) of every call, in container order."""
+def flat_calls(candidate_calls, parts=None):
+    """(chrom number, position, base, barcode, p) of every call, in container order.  `parts`: an explicit list of
+    (chrom number, CompressedSNPCalls) instead of the dict, whose containers are numbered 0, 1, 2, ... in its order."""
+    if parts is None:
+        parts = list(enumerate(candidate_calls.values()))
     cols = [[], [], [], [], []]
-    for k, calls in enumerate(candidate_calls.values()):
+    for k, calls in parts:
         sc = calls.snp_calls[:calls.n_snp_calls]
         mol = calls.molecules[:calls.n_molecules]
         cols[0].append(np.full(len(sc), k, dtype=np.int64))
@@ -22,14 +25,15 @@ def flat_calls(candidate_calls):
         cols[2].append(sc['base_index'].astype(np.int64))
         cols[3].append(mol['compressed_cb'][sc['molecule_index']].astype(np.int64))
         cols[4].append(sc['p_base_wrong'])
-    return [np.concatenate(c) if c else np.zeros(0) for c in cols]
+    return [np.concatenate(c) if c else np.zeros(0, dtype=np.float32 if i == 4 else np.int64) for i, c in enumerate(cols)]
 
 
-def count(candidate_calls, donor_of_barcode, n_donors, cap=3):
-    """(chrom int32[P], pos int32[P], counts int32[P, D, 4]) in the canonical order."""
-    chrom, pos, base, cb, p = flat_calls(candidate_calls)
+def count(candidate_calls, donor_of_barcode, n_donors, cap=3, parts=None, p_below=P_BELOW):
+    """(chrom int32[P], pos int32[P], counts int32[P, D, 4]) in the canonical order: chrom value, then position; parts of
+    equal chrom merge.  `parts` as for flat_calls; `p_below`: the threshold, compared in float32."""
+    chrom, pos, base, cb, p = flat_calls(candidate_calls, parts)
     donor_of_barcode = np.asarray(donor_of_barcode)
-    keep = (p < P_BELOW) & (base < 4) & (donor_of_barcode[cb] >= 0)
+    keep = (p < np.float32(p_below)) & (base < 4) & (donor_of_barcode[cb] >= 0)
     chrom, pos, base, cb = chrom[keep], pos[keep], base[keep], cb[keep]
     pos_key = chrom << 32 | (pos + 2 ** 31)
     positions, rank = np.unique(pos_key, return_inverse=True)
@@ -60,10 +64,14 @@ def score(counts, regularization=3.):
     return importances, bases, np.stack([totals[rows, ref], totals[rows, alt]], axis=1)
 
 
-def select(importances, n_best, n_additional):
-    """_select_top_snps with stable rankings: selected indices, ascending."""
-    best_for_donors = np.argsort(-importances, axis=0, kind='stable')[:n_best]
-    overall = np.argsort(-importances.sum(axis=1), kind='stable')
+def select(importances, n_best, n_additional, row_sum=None):
+    """_select_top_snps with stable rankings: selected indices, ascending.  `row_sum`: what stands in for
+    importances.sum(axis=1) (tests/snp_detection_problems.py: the wrong associations)."""
+    if n_best:
+        best_for_donors = np.argsort(-importances, axis=0, kind='stable')[:n_best]
+    else:  # (what [:0] leaves of the sort, without sorting)
+        best_for_donors = np.zeros((0, importances.shape[1]), dtype=np.intp)
+    overall = np.argsort(-(importances.sum(axis=1) if row_sum is None else row_sum(importances)), kind='stable')
     is_new = ~np.isin(overall, best_for_donors)
     overall = overall[:np.searchsorted(np.cumsum(is_new), n_additional, side='right')]
     return np.union1d(best_for_donors.flatten(), overall).astype(np.int64)
