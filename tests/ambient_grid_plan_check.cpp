@@ -4,38 +4,21 @@
 // check, the supplied profile; tests/ambient_scoring_plan_check.cpp and tests/pools_plan_check.cpp walk those in depth) are asked
 // at all and in their place -, the boundaries of the grid's length and values, and the order of the checks.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "ambient_grid_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::agplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+// the shared pooled call (plan_check.h) with a grid and a profile
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> grid{0.0f, 0.5f, 1.0f, 0.25f, 0.5f};  // any order, duplicates allowed
     std::vector<float> soup{0.0f, 1.0f, 0.5f};
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
     Verdict verdict(const Facts &f, bool with_soup = false) const { return check(f, pools(), (long long)grid.size(), grid.data(), with_soup ? soup.data() : nullptr); }
 };
+}  // namespace
 
 int main()
 {
@@ -209,6 +192,5 @@ int main()
             EXPECT(first.status == INVALID && first.at == 3 && first.what[2] == 'g');
         }
 
-    std::printf("ambient grid plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("ambient grid plan");
 }

@@ -4,37 +4,20 @@
 // dmx_estep_ambient refuses (asplan::check, composed here; tests/ambient_scoring_plan_check.cpp walks it on its own), the fractions, the
 // profile -, the boundaries, the order of the checks, and whose fraction is read.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "ambient_learning_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::alplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+// the shared pooled call (plan_check.h) with the barcodes' fractions and a profile
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> alpha{0.0f, 0.5f, 1.0f, 0.25f};
     std::vector<float> soup{0.0f, 1.0f, 0.5f};
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
 };
+}  // namespace
 
 int main()
 {
@@ -198,6 +181,5 @@ int main()
         EXPECT(em(good, c, 3, -1.0f).what[0] == 't' && mstep(good, c, true, -1.0f).what[0] == 't');
     }
 
-    std::printf("ambient learning plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("ambient learning plan");
 }

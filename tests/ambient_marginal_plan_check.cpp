@@ -4,45 +4,26 @@
 // every one of its refusals is met once, to see that it is asked at all, with its code and ahead of the weights - and the rule of the
 // log weights: absent or every value finite, read only when everything else is in order, the first bad value reported.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "ambient_grid_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::agplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+// the shared pooled call (plan_check.h) with a grid, a profile and the grid's log weights
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> grid{0.0f, 0.5f, 1.0f, 0.25f, 0.5f};
     std::vector<float> soup{0.0f, 1.0f, 0.5f};
     std::vector<float> weights{0.0f, -1.5f, -30.0f, 2.0f, 0.0f};
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
     Verdict verdict(const Facts &f, bool with_soup = false, bool with_weights = true) const
     {
         return check_marginal(f, pools(), (long long)grid.size(), grid.data(), with_soup ? soup.data() : nullptr, with_weights ? weights.data() : nullptr);
     }
     Verdict plain(const Facts &f, bool with_soup = false) const { return check(f, pools(), (long long)grid.size(), grid.data(), with_soup ? soup.data() : nullptr); }
 };
-
-static bool same(const Verdict &a, const Verdict &b) { return a.status == b.status && a.what == b.what && a.at == b.at && a.value == b.value; }
+}  // namespace
 
 int main()
 {
@@ -71,43 +52,8 @@ int main()
             calls.push_back(c);
             facts.push_back(f);
         };
-        Facts f = good;
-        f.have_problem = false;
-        add(ok, f);
-        f = good;
-        f.have_table = false;
-        add(ok, f);
-        f = good;
-        f.attached = true;
-        add(ok, f);
-        f = good;
-        f.nranks = 2;
-        add(ok, f);
-        f = good;
-        f.dense_table = false;
-        add(ok, f);
-        Call c;
-        c.with_doublets = 2;
-        add(c, good);
-        c = Call();
-        c.pool_start[0] = 1;
-        add(c, good);
-        c = Call();
-        c.pool_start = {0, 3, 3};
-        add(c, good);
-        c = Call();
-        c.donors = {0, 2, 2, 1, 3};
-        add(c, good);
-        c = Call();
-        c.donors[4] = G;
-        add(c, good);
-        c = Call();
-        c.pool_of[3] = 2;
-        add(c, good);
-        c = Call();
-        c.row_ptr[4] += 1;
-        add(c, good);
-        c = Call();
+        borrowed_refusals<Call>(good, G, INVALID, UNSUPPORTED, [&](const Call &c, const Facts &f, int) { add(c, f); });
+        Call c;  // ... and check()'s own: the grid, the profile
         c.grid[2] = 1.5f;
         add(c, good);
         c = Call();
@@ -209,6 +155,5 @@ int main()
         EXPECT(check_marginal(nobody, p, 1, grid.data(), nullptr, nullptr).status == OK);
     }
 
-    std::printf("ambient marginal plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("ambient marginal plan");
 }

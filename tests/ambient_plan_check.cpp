@@ -3,23 +3,12 @@
 // the boundaries of the grid width and of the donor rules, the order of the checks, the zero column, the count limit, and the exact
 // row division for every row width a table can have.
 #include <cmath>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "ambient_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::aplan;
-
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
 
 int main()
 {
@@ -140,6 +129,5 @@ int main()
             if (row <= last) EXPECT(row_of(row * row_bytes, d.shift, d.inverse) == row);
     }
 
-    std::printf("ambient plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("ambient plan");
 }

@@ -5,24 +5,13 @@
 //      fetch of the addition, another M-step; a foreign writer of the addition between two incremental M-steps; a caller's
 //      table between two P-steps;
 //   3. seeded random sequences of those compositions against a model of what the buffers hold: the invariants of DESIGN.md 4.15.
-#include <cstdio>
 #include <functional>
 #include <random>
-#include <vector>
 
 #include "ctx_state.h"
+#include "plan_check.h"
 
 using dmx::CtxState;
-
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            if (failures < 40) std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
 
 static bool same(const CtxState &a, const CtxState &b)
 {

@@ -4,36 +4,19 @@
 // what the pooled entries refuse of the pools (pplan::check, composed here; tests/pools_plan_check.cpp walks it on its own), the length
 // and the values of the posterior rows -, the boundaries, the order of the checks, and the bound of the list's length.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "doublet_learning_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::dlplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool; rows of 6, 0, 3 and 6 options
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+// the shared pooled call (plan_check.h) with the posterior rows of its 15 options
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> rows = std::vector<float>(15, 0.125f);
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
 };
+}  // namespace
 
 int main()
 {
@@ -210,6 +193,5 @@ int main()
         EXPECT(pair_options(B, c.pools()) == 0);
     }
 
-    std::printf("doublet learning plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("doublet learning plan");
 }

@@ -5,37 +5,20 @@
 // M-step's own arguments, in that order and with their words -, the share rows of the M-step - present, every pair entry finite and in
 // [0, 1] with its index, singlet entries not read -, and the boundaries.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <limits>
-#include <vector>
 
 #include "doublet_shares_learning_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::dslplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
 static bool says(const Verdict &verdict, const char *words) { return std::strstr(verdict.what, words) != nullptr; }
 
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool; rows of 6, 0, 3 and 6 options.
+// the shared pooled call (plan_check.h) with the posterior and the share rows of its 15 options, a grid of shares and its log weights.
 // The singlet entries of the share rows are NaN, as the E-step leaves them.
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> rows = std::vector<float>(15, 0.125f);
     std::vector<float> shares = std::vector<float>(15, 0.75f);
     std::vector<float> grid{0.7f, 0.1f, 0.5f, 1.0f, 0.1f, 0.0f};
@@ -47,8 +30,8 @@ struct Call {
     }
     static std::vector<size_t> singlets() { return {0, 1, 2, 6, 7, 9, 10, 11}; }
     static std::vector<size_t> pairs() { return {3, 4, 5, 8, 12, 13, 14}; }
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
 };
+}  // namespace
 
 int main()
 {
@@ -277,6 +260,5 @@ int main()
     }
     EXPECT(pair_options(B, ok.pools()) == 3 + 0 + 1 + 3);
 
-    std::printf("doublet shares learning plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("doublet shares learning plan");
 }

@@ -4,43 +4,24 @@
 // everything of the grid; then the grid's own rules in their order: the length below 1, null shares, a bad share with its index, a bad
 // weight with its index, and last the length above 64.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
 #include "pair_shares_plan.h"
+#include "plan_check.h"
 
 using namespace dmx::psplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
+// the shared pooled call (plan_check.h) with a grid of shares and its log weights
+namespace {  // (Pools is hidden from the library's exports; so is what derives from it)
+struct Call : PooledCall<Pools> {
     std::vector<float> grid{0.0f, 0.5f, 1.0f, 0.25f, 0.5f};
     std::vector<float> weights{0.0f, -1.5f, -30.0f, 2.0f, 0.0f};
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
     Verdict verdict(const Facts &f, bool with_weights = true) const
     {
         return check(f, pools(), (long long)grid.size(), grid.data(), with_weights ? weights.data() : nullptr);
     }
 };
-
-static bool same(const Verdict &a, const Verdict &b) { return a.status == b.status && a.what == b.what && a.at == b.at && a.value == b.value; }
+}  // namespace
 
 int main()
 {
@@ -66,47 +47,11 @@ int main()
         std::vector<Call> calls;
         std::vector<Facts> facts;
         std::vector<int> codes;
-        auto add = [&](const Call &c, const Facts &f, int code) {
+        borrowed_refusals<Call>(good, G, INVALID, UNSUPPORTED, [&](const Call &c, const Facts &f, int code) {
             calls.push_back(c);
             facts.push_back(f);
             codes.push_back(code);
-        };
-        Facts f = good;
-        f.have_problem = false;
-        add(ok, f, INVALID);
-        f = good;
-        f.have_table = false;
-        add(ok, f, INVALID);
-        f = good;
-        f.attached = true;
-        add(ok, f, UNSUPPORTED);
-        f = good;
-        f.nranks = 2;
-        add(ok, f, UNSUPPORTED);
-        f = good;
-        f.dense_table = false;
-        add(ok, f, UNSUPPORTED);
-        Call c;
-        c.with_doublets = 2;
-        add(c, good, INVALID);
-        c = Call();
-        c.pool_start[0] = 1;
-        add(c, good, INVALID);
-        c = Call();
-        c.pool_start = {0, 3, 3};
-        add(c, good, INVALID);
-        c = Call();
-        c.donors = {0, 2, 2, 1, 3};
-        add(c, good, INVALID);
-        c = Call();
-        c.donors[4] = G;
-        add(c, good, INVALID);
-        c = Call();
-        c.pool_of[3] = 2;
-        add(c, good, INVALID);
-        c = Call();
-        c.row_ptr[4] += 1;
-        add(c, good, INVALID);
+        });
         for (size_t i = 0; i < calls.size(); i++) {
             const Verdict want = dmx::asplan::check_context_and_pools(facts[i], calls[i].pools());
             EXPECT(want.status == codes[i]);
@@ -259,6 +204,5 @@ int main()
         EXPECT(check(nobody, p, 1, grid.data(), nullptr).status == OK);
     }
 
-    std::printf("pair shares plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("pair shares plan");
 }

@@ -3,24 +3,12 @@
 // pooled result refuse - the upload's pools (pools_plan.h's check, met refusal by refusal, and the rows), the allowed lists, the
 // ranges of dmx_pooled_get / _get_pool, k of the top options - and the layouts they derive: marg_ptr, the pools' barcode lists, the
 // slab bounds of the option sums.
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
-#include <vector>
 
+#include "plan_check.h"
 #include "pooled_readout_plan.h"
 
 using namespace dmx::prplan;
-
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
 
 // one upload's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5 and a third, {2}, without barcodes; five barcodes, the second and
 // the last in no pool
@@ -261,6 +249,5 @@ int main()
     EXPECT(slab(512, 511).first == 511 && slab(512, 511).last == 512);
     EXPECT(slab(1300, 433).first == 1299 && slab(1300, 433).last == 1300 && slab(1300, 434).first == 1300);
 
-    std::printf("pooled readout plan: %d checks, %d failures\n", checks, failures);
-    return failures != 0;
+    return finish("pooled readout plan");
 }

@@ -2,40 +2,14 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer and runs it as a plain program): every refusal of the pooled entries with its code
 // and the index it speaks of, the order of the refusals, the boundaries of the option limit and of an option's 16-bit column, that
 // nothing is read of what a call does not have, and the layout of the options, word for word.
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
-#include <vector>
 
+#include "plan_check.h"
 #include "pools_plan.h"
 
 using namespace dmx::pplan;
 
-static int failures = 0, checks = 0;
-#define EXPECT(cond)                                                 \
-    do {                                                             \
-        checks++;                                                    \
-        if (!(cond)) {                                               \
-            failures++;                                              \
-            std::printf("line %d: %s does not hold\n", __LINE__, #cond); \
-        }                                                            \
-    } while (0)
-
-// one call's arrays, owned: pools {0, 2, 4} and {1, 3} of G = 5, four barcodes, the second in no pool
-struct Call {
-    int with_doublets = 1;
-    std::vector<int64_t> pool_start{0, 3, 5};
-    std::vector<int32_t> donors{0, 2, 4, 1, 3};
-    std::vector<float> penalty{-1.5f, 0.25f};
-    std::vector<int32_t> pool_of{0, -1, 1, 0};
-    std::vector<int64_t> row_ptr{0, 6, 6, 9, 15};
-    Pools pools() const { return {with_doublets, (long long)pool_start.size() - 1, pool_start.data(), donors.data(), penalty.data(), pool_of.data(), row_ptr.data()}; }
-    void singlets_only()
-    {
-        with_doublets = 0;
-        row_ptr = {0, 3, 3, 5, 8};
-    }
-};
+using Call = PooledCall<Pools>;  // the shared pooled call (plan_check.h), as it is
 
 static bool says(const Verdict &verdict, const char *word) { return std::strstr(verdict.what, word) != nullptr; }
 static unsigned option(unsigned d1, unsigned d2) { return d1 | d2 << 16; }
@@ -290,6 +264,5 @@ int main()
         EXPECT(ordered);
     }
 
-    std::printf("pools plan: %d checks, %d failures\n", checks, failures);
-    return failures ? 1 : 0;
+    return finish("pools plan");
 }

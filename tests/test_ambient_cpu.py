@@ -6,10 +6,7 @@
    AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run as a plain program.
 3. The Python side - assignments to table columns, the summary frame - on the restatement's outputs.
 4. The model recovers known contamination on a seeded simulation."""
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pandas as pd
@@ -18,9 +15,9 @@ import pytest
 from demuxalot_amd import ambient as amb
 from demuxalot_amd.demux import _option_names
 from tests import ambient_restatement as restated
+from tests import check_program
 from tests import fixture_io as fio
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE_FIXTURES = ['f1_synthetic_default.npz', 'f2_synthetic_g4.npz', 'f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
 
 
@@ -56,17 +53,9 @@ def test_derived_profile_is_the_share_of_calls_within_the_snp():
 
 # ---- 2. the validation header ------------------------------------------------------------------------------------------------
 def test_validation_over_every_refusal(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the validation check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'ambient_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'ambient_plan_check.cpp'), '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'ambient plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) > 30000, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'ambient_plan_check')
+    walked = re.search(r'ambient plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == 42253, stdout  # (every EXPECT the program walks: one added or lost changes the count)
 
 
 # ---- 3. the Python side ---------------------------------------------------------------------------------------------------------

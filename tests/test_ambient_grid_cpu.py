@@ -11,8 +11,6 @@ include/demux_hip_debug.h: dmx_estep_ambient_grid).
 5. The simulation with true doublets: the joint pass calls them doublets, and leaves the contaminated singlets alone."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pandas as pd
@@ -22,6 +20,7 @@ from demuxalot_amd import ambient as amb
 from tests import ambient_grid_restatement as restated
 from tests import ambient_restatement as profile_restated
 from tests import ambient_scoring_restatement as scoring_restated
+from tests import check_program
 from tests import fixture_io as fio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,18 +95,9 @@ def test_duplicates_in_the_grid_resolve_to_the_lower_index():
 
 # ---- 3. the validation header ------------------------------------------------------------------------------------------------
 def test_validation_over_every_refusal(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the validation check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'ambient_grid_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'ambient_grid_plan_check.cpp'),
-                           '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'ambient grid plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) > 200, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'ambient_grid_plan_check')
+    walked = re.search(r'ambient grid plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == 245, stdout  # (every EXPECT the program walks: one added or lost changes the count)
 
 
 def test_the_entry_point_is_declared_bound_and_stubbed():

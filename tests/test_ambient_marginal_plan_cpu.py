@@ -3,25 +3,15 @@
 The validation is a pure host function (csrc/ambient_grid_plan.h: check_marginal - the max entry's check and the rule of the log
 weights): tests/ambient_marginal_plan_check.cpp walks it - every refusal it borrows, met once and ahead of the weights, and every
 boundary of the weights' rule - built with AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and
-run as a plain program."""
-import os
+run as a plain program (tests/check_program.py)."""
 import re
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import check_program
+
+CHECKS = 417  # EXPECTs the program walks; a check that is added or lost changes the count
 
 
 def test_validation_over_every_case(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the ambient marginal plan check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'ambient_marginal_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'ambient_marginal_plan_check.cpp'),
-                           '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'ambient marginal plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) > 300, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'ambient_marginal_plan_check')
+    walked = re.search(r'ambient marginal plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == CHECKS, stdout

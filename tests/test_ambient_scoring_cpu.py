@@ -8,10 +8,7 @@ predict_posteriors_decontaminated; include/demux_hip_debug.h: dmx_estep_ambient)
    it, built with AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run as a plain program.
 4. The Python side: fractions from a Series or mapping, AmbientEstimate.fractions(), the best singlet.
 5. The three-pass workflow on the seeded simulation: contaminated singlets are no longer called doublets."""
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pandas as pd
@@ -20,9 +17,9 @@ import pytest
 from demuxalot_amd import ambient as amb
 from tests import ambient_restatement as profile_restated
 from tests import ambient_scoring_restatement as restated
+from tests import check_program
 from tests import fixture_io as fio
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE_FIXTURES = ['f1_synthetic_default.npz', 'f2_synthetic_g4.npz', 'f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
 
 
@@ -63,18 +60,9 @@ def test_options_with_penalty_zero_are_the_profile_log_likelihoods(name):
 
 # ---- 3. the validation header ------------------------------------------------------------------------------------------------
 def test_validation_over_every_refusal(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the validation check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'ambient_scoring_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'ambient_scoring_plan_check.cpp'),
-                           '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'ambient scoring plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) > 150, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'ambient_scoring_plan_check')
+    walked = re.search(r'ambient scoring plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == 185, stdout  # (every EXPECT the program walks: one added or lost changes the count)
 
 
 # ---- 4. the Python side ---------------------------------------------------------------------------------------------------------

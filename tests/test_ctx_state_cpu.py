@@ -7,11 +7,10 @@ program.  The source test reads demuxalot_amd/csrc: no file but ctx_state.h assi
 import glob
 import os
 import re
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'demuxalot_amd', 'csrc')
+from tests import check_program
+
+CSRC = check_program.CSRC
 
 # Fields of OTHER structs that share a flag's name: (file, object, field).  estep_plan.h's Facts copies two flags for the plan to read
 # (estep_facts), kernels.h's EstepArgs carries the floor the kernels build the codes with (fill_estep_args).
@@ -35,17 +34,9 @@ def without_comments_and_strings(text):
 
 
 def test_transitions_sequences_and_invariants(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the context state check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'ctx_state_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + CSRC, os.path.join(ROOT, 'tests', 'ctx_state_check.cpp'), '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'ctx state: (\d+) flags compared, (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(2)) > 100_000, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'ctx_state_check')
+    walked = re.search(r'ctx state: (\d+) flags compared, (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(2)) > 100_000, stdout
     assert int(walked.group(1)) == len(header_flags()), 'a flag of ctx_state.h that the walker does not compare'
 
 

@@ -9,28 +9,17 @@ import numpy as np
 import pytest
 
 from tests import doublet_learning_restatement as learning
+from tests import pooled_helpers as helpers
 from tests import pools_learning_restatement as pooled
 
-F1 = 'f1_synthetic_default.npz'  # G = 20, B = 1000
-SMALL = ['f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
-POOLS_F1 = [list(range(8)), list(range(4, 12)), [0, 19], [3, 7, 11, 15, 18], list(range(5, 18)), [19]]
-
-
-def pool_of_f1(B=1000):
-    pool_of = (np.arange(B) * 5) % 7
-    return np.where(pool_of == 6, -1, pool_of).astype(np.int32)
-
-
-def pools_of(name, problem):
-    B, G = problem['B'], problem['betas'].shape[1]
-    return (POOLS_F1, pool_of_f1()) if name == F1 else ([list(range(G))], np.zeros(B, np.int32))
+F1, SMALL = helpers.F1, helpers.F3_SMALL  # f1: G = 20, B = 1000
 
 
 @pytest.mark.parametrize('dp, threshold', [(0.35, 2.0), (0.35, np.nextafter(np.float32(1), np.float32(2))), (0.0, 1e-3)])
 @pytest.mark.parametrize('name', SMALL + ['f2_synthetic_g4.npz', F1])
 def test_no_credited_pair_is_the_pooled_loop(name, dp, threshold):
     problem = pooled.fixture_learning_problem(name)
-    pools, pool_of = pools_of(name, problem)
+    pools, pool_of = helpers.pools_of(name, problem['B'], problem['betas'].shape[1])
     n = 3
     want = pooled.learn(problem, pools, pool_of, n, 0.01, dp)
     got = learning.learn(problem, pools, pool_of, n, 0.01, dp, threshold=threshold)
@@ -43,7 +32,7 @@ def test_no_credited_pair_is_the_pooled_loop(name, dp, threshold):
 @pytest.mark.parametrize('name', SMALL + [F1])
 def test_a_credited_run_differs_where_pairs_are_live(name):
     problem = pooled.fixture_learning_problem(name)
-    pools, pool_of = pools_of(name, problem)
+    pools, pool_of = helpers.pools_of(name, problem['B'], problem['betas'].shape[1])
     plain = pooled.learn(problem, pools, pool_of, 2, 0.01, 0.35)
     credited = learning.learn(problem, pools, pool_of, 2, 0.01, 0.35, threshold=1e-3)
     live = learning.live_pairs(credited[0], pools, pool_of, True, 1e-3)
@@ -104,7 +93,7 @@ def test_the_contract_call_by_call(name, power, threshold):
 
 def test_by_items_summation_differs_in_rounding_ties_only():
     problem = pooled.fixture_learning_problem(F1)
-    pools, pool_of = pools_of(F1, problem)
+    pools, pool_of = helpers.pools_of(F1, problem['B'], problem['betas'].shape[1])
     rec = learning.learn(problem, pools, pool_of, 1, 0.01, 0.35)[0]
     args = (problem['v'], problem['cb'], problem['e'], rec['dense'], rec, pools, pool_of, True, rec['prob_table'])
     in_order = learning.doublet_addition(*args)

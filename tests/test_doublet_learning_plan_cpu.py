@@ -3,25 +3,16 @@
 The validation is a pure host function (csrc/doublet_learning_plan.h, built on pools_plan.h's check):
 tests/doublet_learning_plan_check.cpp walks it - every refusal with the index it speaks of, the order of the refusals, the boundaries of
 the iteration count, the power, the threshold and the unit range of the rows, and the bound of the list's length - built with
-AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run as a plain program."""
-import os
+AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run as a plain program
+(tests/check_program.py)."""
 import re
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import check_program
+
+CHECKS = 615  # EXPECTs the program walks; a check that is added or lost changes the count
 
 
 def test_validation_over_every_case(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the doublet learning plan check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'doublet_learning_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'doublet_learning_plan_check.cpp'),
-                           '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'doublet learning plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) > 100, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'doublet_learning_plan_check')
+    walked = re.search(r'doublet learning plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == CHECKS, stdout

@@ -12,24 +12,12 @@ import pytest
 
 from tests import doublet_learning_restatement as even
 from tests import doublet_shares_learning_restatement as learning
+from tests import pooled_helpers as helpers
 from tests import pools_learning_restatement as pooled
 
-F1 = 'f1_synthetic_default.npz'  # G = 20, B = 1000
-F2 = 'f2_synthetic_g4.npz'
-SMALL = ['f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
-POOLS_F1 = [list(range(8)), list(range(4, 12)), [0, 19], [3, 7, 11, 15, 18], list(range(5, 18)), [19]]
+F1, F2, SMALL = helpers.F1, helpers.F2, helpers.F3_SMALL  # f1: G = 20, B = 1000
 HALF, ZERO = np.array([0.5], np.float32), np.array([0.0], np.float32)
 GRID = np.array([0.7, 0.1, 0.5, 1.0, 0.1, 0.0, 0.35], np.float32)  # unsorted, a duplicate, both ends
-
-
-def pool_of_f1(B=1000):
-    pool_of = (np.arange(B) * 5) % 7
-    return np.where(pool_of == 6, -1, pool_of).astype(np.int32)
-
-
-def pools_of(name, problem):
-    B, G = problem['B'], problem['betas'].shape[1]
-    return (POOLS_F1, pool_of_f1()) if name == F1 else ([list(range(G))], np.zeros(B, np.int32))
 
 
 def assert_records(got, want, what):
@@ -42,7 +30,7 @@ def assert_records(got, want, what):
 @pytest.mark.parametrize('name', SMALL + [F2, F1])
 def test_d1_the_even_grid_is_the_even_loop(name, dp):
     problem = pooled.fixture_learning_problem(name)
-    pools, pool_of = pools_of(name, problem)
+    pools, pool_of = helpers.pools_of(name, problem['B'], problem['betas'].shape[1])
     n = 3
     want = even.learn(problem, pools, pool_of, n, 0.01, dp)
     for log_weights in (ZERO, None):
@@ -60,7 +48,7 @@ def test_d1_the_even_grid_is_the_even_loop(name, dp):
 @pytest.mark.parametrize('name', SMALL + [F2, F1])
 def test_d2_no_credited_pair_is_the_pooled_loop(name, dp, threshold, shares):
     problem = pooled.fixture_learning_problem(name)
-    pools, pool_of = pools_of(name, problem)
+    pools, pool_of = helpers.pools_of(name, problem['B'], problem['betas'].shape[1])
     n = 3
     want = pooled.learn(problem, pools, pool_of, n, 0.01, dp)
     got = learning.learn(problem, pools, pool_of, n, 0.01, dp, shares, threshold=threshold)
@@ -73,7 +61,7 @@ def test_d2_no_credited_pair_is_the_pooled_loop(name, dp, threshold, shares):
 @pytest.mark.parametrize('name', SMALL + [F2])
 def test_d3_a_grid_of_one_end_credits_one_donor(name, end):
     problem = pooled.fixture_learning_problem(name)
-    pools, pool_of = pools_of(name, problem)
+    pools, pool_of = helpers.pools_of(name, problem['B'], problem['betas'].shape[1])
     donors, threshold = pools[0], 1e-3
     n = len(donors)
     history = learning.learn(problem, pools, pool_of, 2, 0.01, 0.35, np.array([end], np.float32), threshold=threshold)
@@ -157,7 +145,7 @@ def test_the_contract_call_by_call(name, power, threshold):
 
 def test_by_items_summation_differs_in_rounding_ties_only():
     problem = pooled.fixture_learning_problem(F1)
-    pools, pool_of = pools_of(F1, problem)
+    pools, pool_of = helpers.pools_of(F1, problem['B'], problem['betas'].shape[1])
     rec = learning.learn(problem, pools, pool_of, 1, 0.01, 0.35, GRID)[0]
     args = (problem['v'], problem['cb'], problem['e'], rec['dense'], rec, pools, pool_of, True, rec['prob_table'])
     in_order = learning.share_addition(*args)

@@ -12,32 +12,21 @@ import pytest
 
 from tests import ambient_restatement as restated
 from tests import fixture_io as fio
+from tests import pooled_helpers as helpers
+from tests.pooled_helpers import at
 
 pytestmark = pytest.mark.gpu
 
-DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
-F1, SMALL = 'f1_synthetic_default.npz', 'f3_small_2.npz'  # G = 20; G = 5
-REFERENCE_FIXTURES = [F1, 'f2_synthetic_g4.npz', 'f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
+DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = helpers.DMX_ERR_INVALID, helpers.DMX_ERR_UNSUPPORTED
+F1, SMALL = helpers.F1, helpers.F3_SMALL[2]  # G = 20; G = 5
+REFERENCE_FIXTURES = [F1, helpers.F2] + helpers.F3_SMALL
+_resident = functools.lru_cache(maxsize=None)(helpers.new_resident)  # the contexts this module's own
 
 
 def resident(name, clip=0.01, extra_barcodes=0):
-    """(ctx, v, cb, e, prob, B, v2snp): a fixture's packed problem and its genotype table resident on a context of its own;
-    extra_barcodes: that many barcodes without any call behind the fixture's."""
+    """(ctx, v, cb, e, prob, B, v2snp): a fixture's packed problem and its genotype table resident on a context of its own, one per
+    (name, clip, extra_barcodes) however the call spells them; extra_barcodes: that many barcodes without any call behind the fixture's."""
     return _resident(name, float(clip), int(extra_barcodes))
-
-
-@functools.lru_cache(maxsize=None)
-def _resident(name, clip, extra_barcodes):
-    from demuxalot_amd.device import DeviceContext
-    fx = fio.load(name)
-    v, cb, e, prob, B, v2snp = restated.fixture_problem(name, clip)
-    B += extra_barcodes
-    ctx = DeviceContext(0)
-    ctx.set_problem(B, len(v2snp), prob.shape[1], v, cb, e, v2snp)
-    ctx.set_betas(fx['pack0_betas'])
-    ctx.set_addition(None)
-    fio.assert_bitwise(ctx.probs_from_betas(clip), prob, f'{name}: genotype table')
-    return ctx, v, cb, e, prob, B, v2snp
 
 
 def soup_of(name, clip=0.01):
@@ -248,12 +237,6 @@ def test_refusals_return_their_code_and_write_nothing():
     soup = soup_of(SMALL)
     status, _text, written = raw_call(ctx, grid, d1, d2)
     assert status == 0 and written
-
-    def at(array, index, value):
-        out = np.array(array, copy=True)
-        out[index] = value
-        return out
-
     singlet = int(np.flatnonzero((d1 >= 0) & (d2 < 0))[0])
     cases = [
         (dict(alphas=[]), DMX_ERR_INVALID, 'at least one'),
@@ -289,25 +272,9 @@ def test_refusals_return_their_code_and_write_nothing():
 
 
 def test_needs_a_problem_a_table_and_no_communicator():
-    from demuxalot_amd.device import DeviceContext
-    v, cb, e, prob, B, v2snp = restated.fixture_problem('f3_small_0.npz')
-    V, G = prob.shape
-    args = dict(alphas=[0.0, 0.5], d1=np.zeros(B, np.int32), d2=np.full(B, -1, np.int32), B=B, V=V)
-    with DeviceContext(0) as ctx:
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and not written
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and not written
-        ctx.set_probs(prob)
-        status, _text, written = raw_call(ctx, **args)
-        assert status == 0 and written
-    with DeviceContext(0) as ctx:
-        ctx.comm_init_emulated(0, 1)
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        ctx.set_probs(prob)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_UNSUPPORTED and 'communicator' in text and not written
+    _v, _cb, _e, prob, B, _v2snp = restated.fixture_problem('f3_small_0.npz')
+    args = dict(alphas=[0.0, 0.5], d1=np.zeros(B, np.int32), d2=np.full(B, -1, np.int32), B=B, V=len(prob))
+    helpers.check_needs_problem_table_no_communicator(raw_call, 'dmx_ambient_profile', args)
 
 
 # ---- 8. the read-outs alone -----------------------------------------------------------------------------------------------------

@@ -14,75 +14,27 @@ from tests import ambient_learning_problems as problems
 from tests import ambient_learning_restatement as learning
 from tests import ambient_restatement
 from tests import fixture_io as fio
+from tests import pooled_helpers as helpers
 from tests import pools_learning_restatement as pooled
 from tests import pools_restatement as restated
+from tests.pooled_helpers import assert_iteration, exact_mode, install, install_designed, pair_penalty, pool_of_f1  # noqa: F401 (exact_mode is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
-F1 = 'f1_synthetic_default.npz'  # G = 20, B = 1000
-SMALL = ['f3_small_0.npz', 'f3_small_1.npz', 'f3_small_2.npz', 'f3_small_3.npz']
-POOLS_F1 = [list(range(8)), list(range(4, 12)), [0, 19], [3, 7, 11, 15, 18], list(range(5, 18)), [19]]
+DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = helpers.DMX_ERR_INVALID, helpers.DMX_ERR_UNSUPPORTED
+F1, SMALL, POOLS_F1 = helpers.F1, helpers.F3_SMALL, helpers.POOLS_F1  # f1: G = 20, B = 1000
 FRACTIONS = np.array([0.0, 0.1, 0.37, 0.63, 1.0, 0.0, 0.25], dtype=np.float32)  # 0, grid values and exactly 1
-
-
-def pool_of_f1(B=1000):
-    pool_of = (np.arange(B) * 5) % 7
-    return np.where(pool_of == 6, -1, pool_of).astype(np.int32)
-
-
-def install(ctx, name):
-    """The fixture's packed problem and its prior betas (raw betas + the data prior: learn_genotypes's own) on a context."""
-    fx = fio.load(name)
-    problem = pooled.fixture_learning_problem(name)
-    V, G = problem['betas'].shape
-    ctx.set_problem(problem['B'], V, G, problem['v'], problem['cb'], problem['e'], problem['v2snp'])
-    molecules = np.bincount(problem['v'], weights=fx['pack_bc_variant_count'], minlength=V).astype(np.int64)
-    betas = ctx.set_prior_betas(problem['raw_betas'], float(fx['default_prior']), True, mol_per_variant=molecules)
-    fio.assert_bitwise(betas, problem['betas'], f'{name}: prior betas')
-    return ctx
-
-
-@functools.lru_cache(maxsize=None)
-def learner(name):
-    from demuxalot_amd.device import DeviceContext
-    return install(DeviceContext(0), name)
-
-
-def install_designed(ctx, problem):
-    V, G = problem['betas'].shape
-    ctx.set_problem(problem['B'], V, G, problem['v'], problem['cb'], problem['e'], problem['v2snp'])
-    ctx.set_betas(problem['betas'])
-    return ctx
-
-
-def pair_penalty(pools, dp):
-    return np.array([restated.demux_oracle.doublet_penalties(len(d), dp)[-1] if len(d) > 1 and dp != 0 else 0.0 for d in pools], dtype=np.float32)
+learner = functools.lru_cache(maxsize=None)(helpers.new_learner)  # a fixture installed for learning, the contexts this module's own
 
 
 def fractions(B, shift=0):
     return FRACTIONS[(np.arange(B) + shift) % len(FRACTIONS)].copy()
 
 
-def assert_iteration(ctx, got, want, what, addition=None):
-    """One E-step's results against a record of the restatement; the dense matrix is the context's resident posteriors."""
-    restated.assert_same(got, want, what)
-    fio.assert_bitwise(ctx.get_probs(), want['dense'], f'{what}: get_probs()')
-    if 'ambient' in got:
-        fio.assert_bitwise(got['ambient'], want['ambient'], f'{what}: the soup profile')
-    if addition is not None:
-        fio.assert_bitwise(addition, want['addition'], f'{what}: addition')
-
-
 def staged(ctx, n, clip, pools, pool_of, with_doublets, penalty, alpha, soup, power=2.):
-    """The step-wise path: per iteration (E-step results, the addition its table was made with)."""
-    ctx.set_addition(None)
-    addition = np.zeros((ctx.V, ctx.G), np.float32)
-    for it in range(n):
-        ctx.probs_from_betas(clip, fetch=False)
-        yield ctx.estep_ambient(pools, pool_of, with_doublets, penalty, alpha, clip, ambient=soup, resident=True), addition
-        if it + 1 < n:
-            addition = ctx.mstep_ambient(alpha, power, clip, ambient=soup)
+    """The step-wise path under the fractions: the resident ambient E-step, dmx_mstep_ambient behind it."""
+    return helpers.staged(ctx, n, clip, lambda: ctx.estep_ambient(pools, pool_of, with_doublets, penalty, alpha, clip, ambient=soup, resident=True),
+                          lambda _out: ctx.mstep_ambient(alpha, power, clip, ambient=soup))
 
 
 # ---- 1. every fraction 0: dmx_em_pools with exact additions, and the restatement ---------------------------------
@@ -334,44 +286,12 @@ def test_refusals_launch_nothing():
                 call()
 
 
-# ---- 7. end to end -----------------------------------------------------------------------------------------------
-@pytest.fixture
-def exact_mode():
-    """The pooled loop in the exact arithmetic: what the loop at fraction 0 is compared with bit for bit."""
-    import os
-    from demuxalot_amd.device import get_context
-    previous = os.environ.get('DEMUXALOT_AMD_ESTEP')
-    os.environ['DEMUXALOT_AMD_ESTEP'] = 'exact'
-    get_context().apply_environment()
-    try:
-        yield
-    finally:
-        if previous is None:
-            os.environ.pop('DEMUXALOT_AMD_ESTEP', None)
-        else:
-            os.environ['DEMUXALOT_AMD_ESTEP'] = previous
-        get_context().apply_environment()
-
-
-def simulation_inputs(seed=0):
-    """tests/ambient_learning_restatement.simulated_problem() as a user holds it: one molecule per call on one chromosome, the reference
-    allele 'A' and the alternative 'C' at position s + 1 of SNP s, genotypes with the problem's betas and default prior 0 - the prior
-    betas of the learning loop are then those betas themselves."""
-    from demuxalot_amd import BarcodeHandler, CompressedSNPCalls, ProbabilisticGenotypes
-    problem, sim = learning.simulated_problem(seed)
-    n = len(sim['v'])
-    calls = {'chr1': CompressedSNPCalls.from_arrays(sim['cb'], np.arange(n), sim['v'] // 2 + 1, sim['v'] % 2, sim['e'])}
-    genotypes = ProbabilisticGenotypes([f'donor{g}' for g in range(sim['prob'].shape[1])], default_prior=0.0)
-    genotypes.var2varid = {('chr1', int(row) // 2 + 1, 'AC'[int(row) % 2]): int(row) for row in range(len(sim['v2snp']))}
-    genotypes.variant_betas = problem['betas'].copy()
-    handler = BarcodeHandler([f'BC{b:03d}-1' for b in range(sim['B'])])
-    assert handler.ordered_barcodes == [f'BC{b:03d}-1' for b in range(sim['B'])]
-    return problem, sim, calls, genotypes, handler
-
-
+# ---- 7. end to end (exact_mode: the pooled loop in the exact arithmetic, what the loop at fraction 0 is compared with) ------------
 def test_learn_genotypes_with_ambient_end_to_end(exact_mode):
     from demuxalot_amd import Demultiplexer, PooledPosteriors
-    problem, sim, calls, genotypes, handler = simulation_inputs()
+    problem, sim = learning.simulated_problem(0)
+    # (genotypes with the problem's betas and default prior 0: the prior betas of the learning loop are then those betas themselves)
+    calls, genotypes, handler = helpers.user_inputs(sim, problem['betas'], default_prior=0.0)
     B, G = sim['B'], sim['prob'].shape[1]
     barcodes, donors = handler.ordered_barcodes, list(genotypes.genotype_names)
     alpha = sim['truth'].astype(np.float32)

@@ -7,7 +7,6 @@ is the intersection of: dmx_estep_pools at alpha = 0, dmx_ambient_profile for an
 at which the kernels can go wrong: option counts on either side of every slot boundary, rows on either side of the 8-call padding and
 of the prologue's 64-call chunk, pools of several buckets and barcodes in no pool in one call, barcodes without calls."""
 import functools
-import os
 
 import numpy as np
 import pandas as pd
@@ -16,28 +15,17 @@ import pytest
 from tests import ambient_restatement as profile_restated
 from tests import ambient_scoring_restatement as restated
 from tests import fixture_io as fio
+from tests import pooled_helpers as helpers
 from tests import pools_restatement
+from tests.pooled_helpers import at, exact_mode, spread_columns  # noqa: F401 (exact_mode is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
-F1, F2, SMALL = 'f1_synthetic_default.npz', 'f2_synthetic_g4.npz', 'f3_small_2.npz'  # G = 20, 4, 5
+DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = helpers.DMX_ERR_INVALID, helpers.DMX_ERR_UNSUPPORTED
+F1, F2, SMALL = helpers.F1, helpers.F2, helpers.F3_SMALL[2]  # G = 20, 4, 5
 FRACTIONS = np.array([0.0, 1.0, 0.01, 0.37, 0.63], dtype=np.float32)
 KEYS = ('row_ptr', 'logits', 'probs', 'best_option', 'best_prob', 'doublet_mass')
-
-
-@functools.lru_cache(maxsize=None)
-def resident(name, clip=0.01):
-    """(ctx, v, cb, e, prob, B, v2snp): a fixture's packed problem and its genotype table resident on a context of its own."""
-    from demuxalot_amd.device import DeviceContext
-    fx = fio.load(name)
-    v, cb, e, prob, B, v2snp = profile_restated.fixture_problem(name, clip)
-    ctx = DeviceContext(0)
-    ctx.set_problem(B, len(v2snp), prob.shape[1], v, cb, e, v2snp)
-    ctx.set_betas(fx['pack0_betas'])
-    ctx.set_addition(None)
-    fio.assert_bitwise(ctx.probs_from_betas(clip), prob, f'{name}: genotype table')
-    return ctx, v, cb, e, prob, B, v2snp
+resident = functools.lru_cache(maxsize=None)(helpers.new_resident)  # (ctx, v, cb, e, prob, B, v2snp), the contexts this module's own
 
 
 def mixed_fractions(B):
@@ -110,33 +98,14 @@ SINGLET_WIDTHS = [1, 63, 64, 65, 128, 129, 256, 257, 512, 513, 1024]  # options 
 DOUBLET_SIZES = [1, 2, 10, 11, 16, 22, 23, 31, 32, 44]  # donors: 1, 3, 55 | 66 | 136, 253 | 276, 496 | 528, 990 options
 
 
+DESIGNED = dict(lengths=LENGTHS, V=160, B=12 * len(LENGTHS), seed=11)
+
+
 @functools.lru_cache(maxsize=None)
 def designed():
     """144 barcodes, barcode i with LENGTHS[i % 12] calls, on 1024 donors and 80 biallelic SNPs; error probabilities at both ends of
     their range among them.  Group i // 12 of the barcodes is what the tests put into one pool (or into none)."""
-    from demuxalot_amd.device import DeviceContext
-    rng = np.random.default_rng(11)
-    V, G, B = 160, 1024, 12 * len(LENGTHS)
-    lengths = [LENGTHS[i % len(LENGTHS)] for i in range(B)]
-    v2snp = np.repeat(np.arange(V // 2, dtype=np.int32), 2)
-    v = np.concatenate([np.sort(rng.choice(V, size=n, replace=False)) for n in lengths]).astype(np.int32)
-    cb = np.repeat(np.arange(B), lengths).astype(np.int32)
-    e = rng.choice(np.array([0.0, 1e-5, 1e-4, 0.01, 0.3, 1.0], dtype=np.float32), size=len(v))
-    order = np.lexsort((cb, v))
-    v, cb, e = v[order], cb[order], e[order]
-    prob = rng.uniform(0.01, 0.99, size=(V, G)).astype(np.float32)
-    prob[0, :3] = [0.0, 1.0, 0.5]  # (row 0 is what the padding calls point at; the ends of the range)
-    soup = rng.uniform(0, 1, size=V).astype(np.float32)
-    soup[:3] = [1.0, 0.0, 0.5]
-    ctx = DeviceContext(0)
-    ctx.set_problem(B, V, G, v, cb, e, v2snp)
-    ctx.set_probs(prob)
-    assert np.bincount(cb, minlength=B).tolist() == lengths
-    return ctx, v, cb, e, prob, B, v2snp, soup, np.asarray(lengths)
-
-
-def spread_columns(rng, n, G):
-    return sorted(int(d) for d in rng.choice(G, size=n, replace=False))
+    return helpers.install_arrays(*helpers.designed_arrays(**DESIGNED))
 
 
 def check_designed(pools, with_doublets, penalty, what):
@@ -229,32 +198,16 @@ def test_refusals_return_their_code_and_write_nothing():
     good = dict(with_doublets=1, pool_start=[0, 2, 5], donors=[0, 1, 1, 2, 4], penalty=penalty, pool_of=pool_of, row_ptr=want['row_ptr'], alpha=alpha)
     status, _text, written = raw_call(ctx, **good)
     assert status == 0 and written
-
-    def at(array, index, value):
-        out = np.array(array, copy=True)
-        out[index] = value
-        return out
-
     pooled, outside = int(np.flatnonzero(pool_of >= 0)[3]), int(np.flatnonzero(pool_of < 0)[0])
-    bad_rows = want['row_ptr'].copy()
-    bad_rows[1:] += 1
     short_rows = want['row_ptr'].copy()
     short_rows[-1] -= 1
-    cases = [
-        (dict(pool_start=[1, 2, 5]), DMX_ERR_INVALID, 'pool_start[0]'),
+    cases = helpers.pool_refusal_cases(good, pool_of) + [
         (dict(pool_start=[0, 3, 2], donors=[0, 1, 2, 4, 4]), DMX_ERR_INVALID, 'decreases'),
-        (dict(pool_start=[0, 2, 2, 5], penalty=[0, 0, 0]), DMX_ERR_INVALID, 'empty'),
-        (dict(donors=[0, 1, 2, 1, 4]), DMX_ERR_INVALID, 'ascending'),
         (dict(donors=[0, 0, 1, 2, 4]), DMX_ERR_INVALID, 'ascending'),
-        (dict(donors=[0, 1, 1, 2, 5]), DMX_ERR_INVALID, 'outside'),
         (dict(donors=[-1, 1, 1, 2, 4]), DMX_ERR_INVALID, 'outside'),
-        (dict(pool_of=at(pool_of, 1, 2)), DMX_ERR_INVALID, 'pool_of_barcode'),
         (dict(pool_of=at(pool_of, 1, -2)), DMX_ERR_INVALID, 'pool_of_barcode'),
-        (dict(row_ptr=bad_rows), DMX_ERR_INVALID, 'row_ptr'),
         (dict(row_ptr=short_rows), DMX_ERR_INVALID, 'row_ptr'),
         (dict(with_doublets=0), DMX_ERR_INVALID, 'row_ptr'),  # (the rows were laid out for the pairs)
-        (dict(with_doublets=2), DMX_ERR_INVALID, 'with_doublets'),
-        (dict(n_pools=-1), DMX_ERR_INVALID, 'n_pools'),
         (dict(alpha=None), DMX_ERR_INVALID, 'null alpha'),
         (dict(alpha=at(alpha, pooled, np.nan)), DMX_ERR_INVALID, 'alpha of a barcode'),
         (dict(alpha=at(alpha, pooled, np.inf)), DMX_ERR_INVALID, 'alpha of a barcode'),
@@ -291,26 +244,10 @@ def test_more_than_1024_options_are_refused():
 
 
 def test_needs_a_problem_a_table_and_no_communicator():
-    from demuxalot_amd.device import DeviceContext
-    v, cb, e, prob, B, v2snp = profile_restated.fixture_problem('f3_small_0.npz')
-    V, G = prob.shape
+    _v, _cb, _e, prob, B, _v2snp = profile_restated.fixture_problem('f3_small_0.npz')
     args = dict(with_doublets=1, pool_start=[0, 2], donors=[0, 1], penalty=[0.0], pool_of=np.zeros(B, np.int32), row_ptr=np.arange(B + 1) * 3,
-                alpha=np.full(B, 0.25, np.float32), B=B, V=V)
-    with DeviceContext(0) as ctx:
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and not written
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and not written
-        ctx.set_probs(prob)
-        status, _text, written = raw_call(ctx, **args)
-        assert status == 0 and written
-    with DeviceContext(0) as ctx:
-        ctx.comm_init_emulated(0, 1)
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        ctx.set_probs(prob)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_UNSUPPORTED and 'communicator' in text and not written
+                alpha=np.full(B, 0.25, np.float32), B=B, V=len(prob))
+    helpers.check_needs_problem_table_no_communicator(raw_call, 'dmx_estep_ambient', args)
 
 
 # ---- 6. the resident results of an E-step are none of this pass's business ------------------------------------------------------
@@ -328,24 +265,7 @@ def test_leaves_the_resident_results_alone():
         assert first[key].tobytes() == again[key].tobytes(), f'{key}: two runs differ'
 
 
-# ---- 7. the front door ----------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def exact_mode():
-    """predict_posteriors in the exact arithmetic: what the new passes are compared with bit for bit."""
-    from demuxalot_amd.device import get_context
-    previous = os.environ.get('DEMUXALOT_AMD_ESTEP')
-    os.environ['DEMUXALOT_AMD_ESTEP'] = 'exact'
-    get_context().apply_environment()
-    try:
-        yield
-    finally:
-        if previous is None:
-            os.environ.pop('DEMUXALOT_AMD_ESTEP', None)
-        else:
-            os.environ['DEMUXALOT_AMD_ESTEP'] = previous
-        get_context().apply_environment()
-
-
+# ---- 7. the front door (exact_mode: predict_posteriors in the exact arithmetic, what the new passes are compared with) ------------
 @pytest.mark.parametrize('doublet_prior', [0.35, 0.0])
 def test_predict_posteriors_with_ambient_end_to_end(doublet_prior, exact_mode):
     from demuxalot_amd import Demultiplexer
@@ -424,24 +344,10 @@ def test_too_many_donors_point_to_the_pools():
             entry({}, genotypes, handler, *extra)
 
 
-def simulation_inputs():
-    """tests/ambient_restatement.simulate() as a user holds it: one molecule per call on one chromosome, the reference allele 'A'
-    and the alternative 'C' at position s + 1 of SNP s, genotypes whose betas are the allele probabilities times 1000."""
-    from demuxalot_amd import BarcodeHandler, CompressedSNPCalls, ProbabilisticGenotypes
-    sim, _ = profile_restated.simulated()
-    n = len(sim['v'])
-    calls = {'chr1': CompressedSNPCalls.from_arrays(sim['cb'], np.arange(n), sim['v'] // 2 + 1, sim['v'] % 2, sim['e'])}
-    genotypes = ProbabilisticGenotypes([f'donor{g}' for g in range(sim['prob'].shape[1])], default_prior=1.0)
-    genotypes.var2varid = {('chr1', int(row) // 2 + 1, 'AC'[int(row) % 2]): int(row) for row in range(len(sim['v2snp']))}
-    genotypes.variant_betas = (sim['prob'] * np.float32(1000)).astype(np.float32)
-    handler = BarcodeHandler([f'BC{b:03d}-1' for b in range(sim['B'])])
-    assert handler.ordered_barcodes == [f'BC{b:03d}-1' for b in range(sim['B'])]
-    return sim, calls, genotypes, handler
-
-
 def test_decontaminated_posteriors_on_the_simulation(exact_mode):
     from demuxalot_amd import AmbientEstimate, Demultiplexer
-    sim, calls, genotypes, handler = simulation_inputs()
+    sim, _ = profile_restated.simulated()  # (genotypes whose betas are the allele probabilities times 1000)
+    calls, genotypes, handler = helpers.user_inputs(sim, helpers.table_betas(sim), default_prior=1.0)
     G, B = sim['prob'].shape[1], sim['B']
     barcodes = handler.ordered_barcodes
     donors = list(genotypes.genotype_names)

@@ -14,13 +14,13 @@ from tests import doublet_learning_problems as problems
 from tests import doublet_shares_learning_restatement as learning
 from tests import fixture_io as fio
 from tests import pair_shares_restatement as shares_restated
+from tests import pooled_helpers as helpers
 from tests import pools_learning_restatement as pooled
+from tests.pooled_helpers import install, install_designed, pools_of
 
 pytestmark = pytest.mark.gpu
 
-F1 = 'f1_synthetic_default.npz'  # G = 20, B = 1000
-F2 = 'f2_synthetic_g4.npz'
-POOLS_F1 = [list(range(8)), list(range(4, 12)), [0, 19], [3, 7, 11, 15, 18], list(range(5, 18)), [19]]
+F1, F2 = helpers.F1, helpers.F2  # f1: G = 20, B = 1000
 HALF, ZERO = np.array([0.5], np.float32), np.array([0.0], np.float32)
 GRIDS = {  # unsorted, with duplicates and both ends
     1: np.array([0.8], np.float32),
@@ -37,58 +37,15 @@ def weights_of(n):
     return np.linspace(-2.0, 0.5, n).astype(np.float32)[np.random.default_rng(n).permutation(n)]
 
 
-def pool_of_f1(B=1000):
-    pool_of = (np.arange(B) * 5) % 7
-    return np.where(pool_of == 6, -1, pool_of).astype(np.int32)
-
-
-def pools_of(name, B, G):
-    return (POOLS_F1, pool_of_f1()) if name == F1 else ([list(range(G))], np.zeros(B, np.int32))
-
-
-def install(ctx, name):
-    """The fixture's packed problem and its prior betas (raw betas + the data prior: learn_genotypes's own) on a context."""
-    fx = fio.load(name)
-    problem = pooled.fixture_learning_problem(name)
-    V, G = problem['betas'].shape
-    ctx.set_problem(problem['B'], V, G, problem['v'], problem['cb'], problem['e'], problem['v2snp'])
-    molecules = np.bincount(problem['v'], weights=fx['pack_bc_variant_count'], minlength=V).astype(np.int64)
-    betas = ctx.set_prior_betas(problem['raw_betas'], float(fx['default_prior']), True, mol_per_variant=molecules)
-    fio.assert_bitwise(betas, problem['betas'], f'{name}: prior betas')
-    return ctx
-
-
-@functools.lru_cache(maxsize=None)
-def learner(name):
-    from demuxalot_amd.device import DeviceContext
-    return install(DeviceContext(0), name)
-
-
-def install_designed(ctx, problem):
-    V, G = problem['betas'].shape
-    ctx.set_problem(problem['B'], V, G, problem['v'], problem['cb'], problem['e'], problem['v2snp'])
-    ctx.set_betas(problem['betas'])
-    return ctx
-
-
-def assert_iteration(ctx, got, want, what, addition=None):
-    """One E-step's results against a record of the restatement; the dense matrix is the context's resident posteriors."""
-    learning.assert_same(got, want, what)
-    fio.assert_bitwise(ctx.get_probs(), want['dense'], f'{what}: get_probs()')
-    if addition is not None:
-        fio.assert_bitwise(addition, want['addition'], f'{what}: addition')
+learner = functools.lru_cache(maxsize=None)(helpers.new_learner)  # a fixture installed for learning, the contexts this module's own
+assert_iteration = functools.partial(helpers.assert_iteration, same=learning.assert_same)  # (the E-step's outputs with its shares)
 
 
 def staged(ctx, n, clip, pools, pool_of, with_doublets, penalty, shares, log_weights, threshold, power=2.):
-    """The step-wise path: per iteration (E-step results, the addition its table was made with)."""
-    ctx.set_addition(None)
-    addition = np.zeros((ctx.V, ctx.G), np.float32)
-    for it in range(n):
-        ctx.probs_from_betas(clip, fetch=False)
-        out = ctx.estep_pair_shares(pools, pool_of, with_doublets, penalty, shares, log_weights, resident=True)
-        yield out, addition
-        if it + 1 < n:
-            addition = ctx.mstep_doublet_shares(pools, pool_of, with_doublets, penalty, out['probs'], out['share_mean'], threshold, power)
+    """The step-wise path over the shares: the resident E-step over the grid, dmx_mstep_doublet_shares on its rows and means behind it."""
+    return helpers.staged(
+        ctx, n, clip, lambda: ctx.estep_pair_shares(pools, pool_of, with_doublets, penalty, shares, log_weights, resident=True),
+        lambda out: ctx.mstep_doublet_shares(pools, pool_of, with_doublets, penalty, out['probs'], out['share_mean'], threshold, power))
 
 
 # ---- D1: the grid {0.5} is dmx_em_doublets, every output and every iteration's addition --------------------------------------------
@@ -454,17 +411,10 @@ def test_refusals_launch_nothing():
 
 # ---- the front door, and "does it help?" on the device ---------------------------------------------------------------------------
 def simulation_inputs(share, seed=0):
-    """tests/doublet_shares_learning_restatement.simulated() as a user holds it (tests/test_gpu_doublet_learning.py: simulation_inputs)."""
-    from demuxalot_amd import BarcodeHandler, CompressedSNPCalls, ProbabilisticGenotypes
+    """tests/doublet_shares_learning_restatement.simulated() and what a user holds of it: genotypes with the problem's betas and default
+    prior 0 - the prior betas of the learning loop are then those betas themselves."""
     problem, sim, yardstick, history = learning.simulated(share, seed)
-    n = len(sim['v'])
-    calls = {'chr1': CompressedSNPCalls.from_arrays(sim['cb'], np.arange(n), sim['v'] // 2 + 1, sim['v'] % 2, sim['e'])}
-    genotypes = ProbabilisticGenotypes([f'donor{g}' for g in range(sim['prob'].shape[1])], default_prior=0.0)
-    genotypes.var2varid = {('chr1', int(row) // 2 + 1, 'AC'[int(row) % 2]): int(row) for row in range(len(sim['v2snp']))}
-    genotypes.variant_betas = problem['betas'].copy()
-    handler = BarcodeHandler([f'BC{b:03d}-1' for b in range(sim['B'])])
-    assert handler.ordered_barcodes == [f'BC{b:03d}-1' for b in range(sim['B'])]
-    return problem, sim, yardstick, history, calls, genotypes, handler
+    return (problem, sim, yardstick, history) + helpers.user_inputs(sim, problem['betas'], default_prior=0.0)
 
 
 def test_even_doublets_through_the_front_door_lose_no_more_than_the_half_gain():

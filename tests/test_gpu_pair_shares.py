@@ -6,42 +6,24 @@ tests/test_pair_shares_cpu.py) and with the pooled pass through the identities S
 can go wrong: pools on either side of every slot boundary, so that all five forms run, grid lengths on either side of the grid points a
 form takes per walk, unsorted grids with duplicates and both ends, a barcode without calls, barcodes in no pool."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
 from tests import fixture_io as fio
 from tests import pair_shares_restatement as restated
+from tests import pooled_helpers as helpers
 from tests import pools_restatement
+from tests.pooled_helpers import at, exact_mode, same_bytes, spread_columns  # noqa: F401 (exact_mode is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
-F1, F2, SMALL = 'f1_synthetic_default.npz', 'f2_synthetic_g4.npz', 'f3_small_2.npz'  # G = 20, 4, 5
+DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = helpers.DMX_ERR_INVALID, helpers.DMX_ERR_UNSUPPORTED
+F1, F2, SMALL = helpers.F1, helpers.F2, helpers.F3_SMALL[2]  # G = 20, 4, 5
 SHARED, OWN = restated.SHARED, restated.OWN
 GRID = np.array([1.0, 0.0, 0.2, 0.63, 0.2], dtype=np.float32)
 WEIGHTS = np.array([-0.5, -7.0, 0.25, -1.0, -2.5], dtype=np.float32)
-
-
-def same_bytes(got, want, keys, what):
-    for key in keys:
-        assert got[key].dtype == want[key].dtype and got[key].tobytes() == want[key].tobytes(), f'{what}: {key}'
-
-
-@functools.lru_cache(maxsize=None)
-def resident(name, clip=0.01):
-    """(ctx, v, cb, e, prob, B, v2snp): a fixture's packed problem and its genotype table resident on a context of its own."""
-    from demuxalot_amd.device import DeviceContext
-    fx = fio.load(name)
-    v, cb, e, prob, B = pools_restatement.fixture_problem(name, clip)
-    v2snp = fx['pack_v2snp']
-    ctx = DeviceContext(0)
-    ctx.set_problem(B, len(v2snp), prob.shape[1], v, cb, e, v2snp)
-    ctx.set_betas(fx['pack0_betas'])
-    ctx.set_addition(None)
-    fio.assert_bitwise(ctx.probs_from_betas(clip), prob, f'{name}: genotype table')
-    return ctx, v, cb, e, prob, B, v2snp
+resident = functools.lru_cache(maxsize=None)(helpers.new_resident)  # (ctx, v, cb, e, prob, B, v2snp), the contexts this module's own
 
 
 # ---- 1. S1 and S2 on the fixtures -----------------------------------------------------------------------------------------------------
@@ -86,20 +68,7 @@ def designed():
     return ctx, v, cb, e, prob, B, lengths
 
 
-def spread_columns(rng, n, G=1024):
-    return sorted(int(d) for d in rng.choice(G, size=n, replace=False))
-
-
-def designed_grid(n):
-    """n shares: unsorted, with both ends 1 and 0 (from two values on) and duplicated values (from three on)."""
-    values = np.random.default_rng(300 + n).uniform(0, 1, size=n).astype(np.float32)
-    if n >= 2:
-        values[0], values[-1] = 1.0, 0.0
-    if n >= 3:
-        values[1] = 0.0
-    if n >= 8:
-        values[n // 2], values[n - 3] = values[3], values[2]
-    return values
+designed_grid = functools.partial(helpers.designed_grid, seed_base=300)  # n shares: a draw of its own, apart from the ambient grids'
 
 
 def steep_weights(n):
@@ -269,25 +238,9 @@ def test_refusals_return_their_code_and_write_nothing():
                 weights=WEIGHTS)
     status, _text, written = raw_call(ctx, **good)
     assert status == 0 and written
-
-    def at(array, index, value):
-        out = np.array(array, copy=True)
-        out[index] = value
-        return out
-
-    bad_rows = want['row_ptr'].copy()
-    bad_rows[1:] += 1
     long_grid = np.linspace(0, 1, 65)
-    cases = [
-        (dict(pool_start=[1, 2, 5]), DMX_ERR_INVALID, 'pool_start[0]'),
-        (dict(pool_start=[0, 2, 2, 5], penalty=[0, 0, 0]), DMX_ERR_INVALID, 'empty'),
-        (dict(donors=[0, 1, 2, 1, 4]), DMX_ERR_INVALID, 'ascending'),
-        (dict(donors=[0, 1, 1, 2, 5]), DMX_ERR_INVALID, 'outside'),
-        (dict(pool_of=at(pool_of, 1, 2)), DMX_ERR_INVALID, 'pool_of_barcode'),
-        (dict(row_ptr=bad_rows), DMX_ERR_INVALID, 'row_ptr'),
+    cases = helpers.pool_refusal_cases(good, pool_of) + [
         (dict(with_doublets=0), DMX_ERR_INVALID, 'row_ptr'),  # (the rows were laid out for the pairs)
-        (dict(with_doublets=2), DMX_ERR_INVALID, 'with_doublets'),
-        (dict(n_pools=-1), DMX_ERR_INVALID, 'n_pools'),
         (dict(shares=[], weights=None), DMX_ERR_INVALID, 'at least one value'),
         (dict(n_shares=0), DMX_ERR_INVALID, 'at least one value'),
         (dict(n_shares=-3), DMX_ERR_INVALID, 'at least one value'),
@@ -320,30 +273,13 @@ def test_refusals_return_their_code_and_write_nothing():
 
 
 def test_more_than_1024_options_a_missing_table_and_a_communicator_are_refused():
-    from demuxalot_amd.device import DeviceContext
     ctx, *_rest, B, _lengths = designed()
     status, text, written = raw_call(ctx, 1, [0, 45], np.arange(45), [0.0], np.zeros(B, np.int32), np.arange(B + 1) * 1035, [0.5], weights=[0.0])
     assert status == DMX_ERR_UNSUPPORTED and 'more than 1024 options' in text and 'dmx_estep_pair_shares' in text and not written, (status, text)
-    v, cb, e, prob, B = pools_restatement.fixture_problem('f3_small_0.npz')
-    v2snp = fio.load('f3_small_0.npz')['pack_v2snp']
-    V, G = prob.shape
+    B = pools_restatement.fixture_problem('f3_small_0.npz')[4]
     args = dict(with_doublets=1, pool_start=[0, 2], donors=[0, 1], penalty=[0.0], pool_of=np.zeros(B, np.int32), row_ptr=np.arange(B + 1) * 3,
                 shares=[0.25, 1.0], weights=[0.0, -1.0], B=B)
-    with DeviceContext(0) as ctx:
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and 'dmx_estep_pair_shares' in text and not written
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_INVALID and 'call order' in text and not written
-        ctx.set_probs(prob)
-        status, _text, written = raw_call(ctx, **args)
-        assert status == 0 and written
-    with DeviceContext(0) as ctx:
-        ctx.comm_init_emulated(0, 1)
-        ctx.set_problem(B, V, G, v, cb, e, v2snp)
-        ctx.set_probs(prob)
-        status, text, written = raw_call(ctx, **args)
-        assert status == DMX_ERR_UNSUPPORTED and 'communicator' in text and 'dmx_estep_pair_shares' in text and not written
+    helpers.check_needs_problem_table_no_communicator(raw_call, 'dmx_estep_pair_shares', args)
 
 
 # ---- 4. the resident results of an E-step are none of this pass's business ------------------------------------------------------------
@@ -361,24 +297,7 @@ def test_leaves_the_resident_results_alone():
     same_bytes(again, first, SHARED + OWN, 'two runs')
 
 
-# ---- 5. the front door ------------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def exact_mode():
-    """predict_posteriors in the exact arithmetic: what the new pass is compared with bit for bit."""
-    from demuxalot_amd.device import get_context
-    previous = os.environ.get('DEMUXALOT_AMD_ESTEP')
-    os.environ['DEMUXALOT_AMD_ESTEP'] = 'exact'
-    get_context().apply_environment()
-    try:
-        yield
-    finally:
-        if previous is None:
-            os.environ.pop('DEMUXALOT_AMD_ESTEP', None)
-        else:
-            os.environ['DEMUXALOT_AMD_ESTEP'] = previous
-        get_context().apply_environment()
-
-
+# ---- 5. the front door (exact_mode: predict_posteriors in the exact arithmetic, what the new pass is compared with) ----------------------
 @pytest.mark.parametrize('doublet_prior', [0.35, 0.0])
 def test_the_front_door_without_pools(doublet_prior, exact_mode):
     from demuxalot_amd import Demultiplexer, DoubletSharePosteriors
@@ -441,14 +360,9 @@ def test_the_front_door_with_pools():
 
 @pytest.mark.parametrize('share', [0.8, 0.5])
 def test_the_value_conditions_hold_through_the_front_door(share):
-    from demuxalot_amd import BarcodeHandler, CompressedSNPCalls, Demultiplexer, ProbabilisticGenotypes
+    from demuxalot_amd import Demultiplexer
     sim, want_fixed, want_grid, _out = restated.simulated(share, 128, 0)
-    n = len(sim['v'])
-    calls = {'chr1': CompressedSNPCalls.from_arrays(sim['cb'], np.arange(n), sim['v'] // 2 + 1, sim['v'] % 2, sim['e'])}
-    genotypes = ProbabilisticGenotypes([f'donor{g}' for g in range(sim['prob'].shape[1])], default_prior=1.0)
-    genotypes.var2varid = {('chr1', int(row) // 2 + 1, 'AC'[int(row) % 2]): int(row) for row in range(len(sim['v2snp']))}
-    genotypes.variant_betas = (sim['prob'] * np.float32(1000)).astype(np.float32)
-    handler = BarcodeHandler([f'BC{b:03d}-1' for b in range(sim['B'])])
+    calls, genotypes, handler = helpers.user_inputs(sim, helpers.table_betas(sim), default_prior=1.0)
     _logits, probs = Demultiplexer.predict_posteriors(calls, genotypes, handler, doublet_prior=0.35)
     G = sim['prob'].shape[1]
     fixed = restated.counts_of(sim, probs.values[:, G:].astype(np.float64).sum(axis=1), probs.values.argmax(axis=1))

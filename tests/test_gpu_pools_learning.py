@@ -10,59 +10,26 @@ import numpy as np
 import pytest
 
 from tests import fixture_io as fio
+from tests import pooled_helpers as helpers
 from tests import pools_learning_restatement as learning
 from tests import pools_restatement as restated
+from tests.pooled_helpers import assert_iteration, install, pair_penalty, pool_of_f1
 
 pytestmark = pytest.mark.gpu
 
-DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = -1, -5
-F1 = 'f1_synthetic_default.npz'  # G = 20, B = 1000
-WIDE = 'f3_small_4.npz'  # G = 70, B = 24: two nz words per row, no `first` codes
-
-
-def install(ctx, name):
-    """The fixture's packed problem and its prior betas (raw betas + the data prior: learn_genotypes's own) on a context."""
-    fx = fio.load(name)
-    problem = learning.fixture_learning_problem(name)
-    V, G = problem['betas'].shape
-    ctx.set_problem(problem['B'], V, G, problem['v'], problem['cb'], problem['e'], problem['v2snp'])
-    molecules = np.bincount(problem['v'], weights=fx['pack_bc_variant_count'], minlength=V).astype(np.int64)
-    betas = ctx.set_prior_betas(problem['raw_betas'], float(fx['default_prior']), True, mol_per_variant=molecules)
-    fio.assert_bitwise(betas, problem['betas'], f'{name}: prior betas')
-    return ctx
-
-
-@functools.lru_cache(maxsize=None)
-def learner(name):
-    from demuxalot_amd.device import DeviceContext
-    return install(DeviceContext(0), name)
+DMX_ERR_INVALID, DMX_ERR_UNSUPPORTED = helpers.DMX_ERR_INVALID, helpers.DMX_ERR_UNSUPPORTED
+F1 = helpers.F1  # G = 20, B = 1000
+WIDE = helpers.WIDE  # G = 70, B = 24: two nz words per row, no `first` codes
+learner = functools.lru_cache(maxsize=None)(helpers.new_learner)  # a fixture installed for learning, the contexts this module's own
 
 
 def all_donor_penalty(G, dp):
     return [restated.demux_oracle.doublet_penalties(G, dp)[-1] if dp != 0 else 0.0]
 
 
-def pair_penalty(pools, dp):
-    return np.array([restated.demux_oracle.doublet_penalties(len(d), dp)[-1] if len(d) > 1 and dp != 0 else 0.0 for d in pools], dtype=np.float32)
-
-
-def assert_iteration(ctx, got, want, what, addition=None):
-    """One pooled E-step's results against a record of the restatement; the dense matrix is the context's resident posteriors."""
-    restated.assert_same(got, want, what)
-    fio.assert_bitwise(ctx.get_probs(), want['dense'], f'{what}: get_probs()')
-    if addition is not None:
-        fio.assert_bitwise(addition, want['addition'], f'{what}: addition')
-
-
 def staged(ctx, n, clip, pools, pool_of, with_doublets, penalty):
-    """The step-wise path: per iteration (E-step results, the addition its table was made with)."""
-    ctx.set_addition(None)
-    addition = np.zeros((ctx.V, ctx.G), np.float32)
-    for it in range(n):
-        ctx.probs_from_betas(clip, fetch=False)
-        yield ctx.estep_pools(pools, pool_of, with_doublets, penalty, resident=True), addition
-        if it + 1 < n:
-            addition = ctx.mstep()
+    """The step-wise path of the pooled loop: the resident pooled E-step, dmx_mstep behind it."""
+    return helpers.staged(ctx, n, clip, lambda: ctx.estep_pools(pools, pool_of, with_doublets, penalty, resident=True), lambda _out: ctx.mstep())
 
 
 # ---- 1. one all-donor pool is the reference's learn_genotypes ---------------------------------------------------
@@ -100,13 +67,8 @@ def test_all_donor_pool_is_the_reference(name):
 
 
 # ---- 2. overlapping pools, barcodes and nobody's donors ---------------------------------------------------------
-POOLS = [list(range(8)), list(range(4, 12)), [0, 19], [3, 7, 11, 15, 18], list(range(5, 18)), [19]]
+POOLS = helpers.POOLS_F1
 ITERATIONS = 4
-
-
-def pool_of_f1(B=1000):
-    pool_of = (np.arange(B) * 5) % 7
-    return np.where(pool_of == 6, -1, pool_of).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)

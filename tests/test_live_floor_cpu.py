@@ -2,29 +2,19 @@
 fixed_point.h the very conversion the kernels add with) and csrc/mstep_plan.h, walks the plan asked ahead of an M-step (sums_on_grid) against
 the form launch() then yields over the fact space, and runs every float32 posterior in [2^-27, 2^-25] x 5 keep factors x shifts 0 .. 50 through
 fixed_of: at or below the floor the added integer is 0.  Built with AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into
-the program, and run as a plain program (as tests/test_mstep_plan_cpu.py does)."""
+the program, and run as a plain program (tests/check_program.py, as tests/test_mstep_plan_cpu.py does)."""
 import os
 import re
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import check_program
 
 
 def test_live_floor_plan_and_proof(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the live-floor check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'live_floor_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O3', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra', '-pthread', '-D__HIP_PLATFORM_AMD__',
-                           '-I' + os.path.join(ROOT, 'include'), '-I/opt/rocm/include', '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'live_floor_check.cpp'), '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=600)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
+    flags = ['-pthread', '-D__HIP_PLATFORM_AMD__', '-I' + os.path.join(check_program.ROOT, 'include'), '-I/opt/rocm/include']
+    stdout = check_program.build_and_run(tmp_path, 'live_floor_check', '-O3', flags, timeout=600)
     said = re.search(r'live floor: (\d+) plan combinations walked, (\d+) conversions tried, first non-zero posterior (\S+) \(floor (\S+)\), 0 failures',
-                     done.stdout)
-    assert said, done.stdout
+                     stdout)
+    assert said, stdout
     # 12 booleans x 3 x 3 switches x 3 genotype counts x 3 powers x 7 M-step counts x 3 horizons x 2 announced horizons
     assert int(said.group(1)) == 2 ** 12 * 3 * 3 * 3 * 3 * 7 * 3 * 2
     # every float32 of two binades (and 2^-25 itself) x 5 keep factors x 51 shifts

@@ -2,27 +2,17 @@
 k_sd_row_keys) is plain C++ and needs no GPU: tests/pairwise_sum_check.cpp includes that header alone, sums the rows this test writes
 and writes the sums back; they must equal np.sum of each row bit for bit.  numpy is the reference: nothing here restates how the sum is
 associated.  Built with AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run as a plain
-program, as tests/test_mstep_plan_cpu.py does.  Without g++ (or ASAN_CXX) this test fails."""
-import os
-import shutil
-import subprocess
-
+program (tests/check_program.py), as tests/test_mstep_plan_cpu.py does.  Without g++ (or ASAN_CXX) this test fails."""
 import numpy as np
 
+from tests import check_program
 from tests import fixture_io as fio
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # every leaf and the first splits, and every length around the ones whose halves stay above 128 elements after six splits (7689..8191)
 LENGTHS = list(range(1, 301)) + list(range(7600, 8193))
 
 
 def test_row_sum_equals_numpy_bit_for_bit(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the row sum check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'pairwise_sum_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O3', '-g', '-ffp-contract=off', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'pairwise_sum_check.cpp'), '-o', program])
     rng = np.random.default_rng(20)
     rows = [np.square(rng.uniform(-1., 1., n)) for n in LENGTHS]  # squares of uniform numbers, as the importances are
     with open(tmp_path / 'rows.bin', 'wb') as f:
@@ -30,10 +20,9 @@ def test_row_sum_equals_numpy_bit_for_bit(tmp_path):
         for row in rows:
             f.write(np.int64(len(row)).tobytes())
             f.write(row.astype('<f8').tobytes())
-    done = subprocess.run([program, str(tmp_path / 'rows.bin'), str(tmp_path / 'sums.bin')], capture_output=True, text=True, timeout=600)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    assert f'pairwise sum: {len(rows)} rows' in done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'pairwise_sum_check', '-O3', ['-ffp-contract=off'],
+                                         [tmp_path / 'rows.bin', tmp_path / 'sums.bin'], timeout=600)
+    assert f'pairwise sum: {len(rows)} rows' in stdout
     sums = np.fromfile(tmp_path / 'sums.bin', dtype='<f8')
     want = np.array([np.sum(row) for row in rows])
     assert sums.shape == want.shape

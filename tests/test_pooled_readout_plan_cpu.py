@@ -3,29 +3,20 @@
 The validation is pure host code (csrc/pooled_readout_plan.h): tests/pooled_readout_plan_check.cpp walks every refusal and boundary -
 the upload's pools and rows, the allowed lists, the ranges of dmx_pooled_get / _get_pool, marg_ptr, the pools' barcode lists, the slab
 bounds of the option sums - built with AddressSanitizer + UndefinedBehaviorSanitizer, their runtimes linked into the program, and run
-as a plain program."""
+as a plain program (tests/check_program.py)."""
 import os
 import re
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import check_program
+
+ROOT = check_program.ROOT
 CHECKS = 134  # EXPECTs the program walks; a check that is added or lost changes the count
 
 
 def test_validation_over_every_case(tmp_path):
-    compiler = shutil.which(os.environ.get('ASAN_CXX', 'g++'))
-    assert compiler is not None, 'the pooled readout plan check needs g++ (or ASAN_CXX)'
-    program = str(tmp_path / 'pooled_readout_plan_check')
-    subprocess.check_call([compiler, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-Wextra',
-                           '-I' + os.path.join(ROOT, 'demuxalot_amd', 'csrc'), os.path.join(ROOT, 'tests', 'pooled_readout_plan_check.cpp'),
-                           '-o', program])
-    done = subprocess.run([program], capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0, (done.stdout[-1500:], done.stderr[-4000:])
-    assert 'ERROR: AddressSanitizer' not in done.stderr and 'runtime error:' not in done.stderr, done.stderr[-4000:]
-    walked = re.search(r'pooled readout plan: (\d+) checks, 0 failures', done.stdout)
-    assert walked and int(walked.group(1)) == CHECKS, done.stdout
+    stdout = check_program.build_and_run(tmp_path, 'pooled_readout_plan_check')
+    walked = re.search(r'pooled readout plan: (\d+) checks, 0 failures', stdout)
+    assert walked and int(walked.group(1)) == CHECKS, stdout
 
 
 def test_entries_are_declared_as_product_api():
