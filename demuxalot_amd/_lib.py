@@ -170,6 +170,9 @@ DEBUG_SIGNATURES = {
     'dmx_mstep_ambient': (c_int, [_P, c_float, _P, _P, c_float, c_float, _P]),
     'dmx_em_ambient': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P,
                                _P]),
+    'dmx_mstep_soup': (c_int, [_P, _P, _P, c_float, c_float, c_float, _P, _P]),
+    'dmx_em_ambient_soup': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, _P, _P, c_float, _P, _P, _P, _P, _P,
+                                    _P, _P, _P]),
     'dmx_em_doublets': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
     'dmx_mstep_doublets': (c_int, [_P, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     'dmx_em_doublet_shares': (c_int, [_P, c_int, c_float, c_float, c_int, c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_int32, _P, _P,

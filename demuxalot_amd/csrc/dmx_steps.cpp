@@ -35,8 +35,10 @@
 #include "mstep_doublet_shares.h"
 #include "mstep_doublets.h"
 #include "mstep_plan.h"
+#include "mstep_soup.h"
 #include "pair_shares_plan.h"
 #include "pools_plan.h"
+#include "soup_learning_plan.h"
 
 using namespace dmx::host;
 
@@ -1223,6 +1225,52 @@ int dmx_em_ambient(dmx_ctx *c, int n_iterations, float lo, float hi, int with_do
     DMX_TRY(run_dense_em(
         c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_ambient_pass(c, *run, power); },
         [&](int) { return dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)); }));
+    return dmx::read_back_estep_ambient(c, *run);
+}
+
+// Learning the soup's profile (mstep_soup.hip).  soup_learning_plan.h refuses, on the host, before anything is uploaded
+// or launched.  The step writes its counts to scratch: the context's addition, posteriors and table stay as they are.
+int dmx_mstep_soup(dmx_ctx *c, const float *alpha, const float *ambient, float pseudo_count, float lo, float hi, float *ambient_out,
+                   float *counts_out)
+{
+    namespace lp = dmx::slplan;
+    DMX_TRY(bind(c));
+    const lp::Verdict verdict = lp::check_mstep(ambient_facts(c, c->have_probs), c->have_post, pseudo_count, alpha, ambient);
+    if (verdict.status != lp::OK) return refuse("dmx_mstep_soup", verdict.status, verdict.what, verdict.at, verdict.value);
+    return dmx::run_mstep_soup_from_host(c, alpha, ambient, pseudo_count, lo, hi, ambient_out, counts_out);
+}
+
+// dmx_em_ambient with the profile learnt: behind every E-step but the last the soup M-step and the ambient M-step, both with the
+// profile that E-step read; the new profile takes the run's place for the next E-step, whose pass rebuilds the soup's terms.  The
+// dense pass closes at the lower of the two M-steps' live floors - the soup step's 0 -, so no codes are rebuilt between the two.
+int dmx_em_ambient_soup(dmx_ctx *c, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools, const int64_t *pool_start,
+                        const int32_t *pool_donors, const float *pair_penalty, const int32_t *pool_of_barcode, const int64_t *row_ptr,
+                        float power, const float *alpha, const float *ambient, float pseudo_count, float *logits_out, float *probs_out,
+                        int32_t *best_option, float *best_prob, double *doublet_mass, float *addition_out, float *ambient_out,
+                        float *counts_out)
+{
+    namespace lp = dmx::slplan;
+    DMX_TRY(bind(c));
+    const lp::Pools pools{with_doublets, n_pools, pool_start, pool_donors, pair_penalty, pool_of_barcode, row_ptr};
+    dmx::PoolsPlan plan;
+    DMX_TRY(accept_pools("dmx_em_ambient_soup",
+                         lp::check_em(ambient_facts(c, c->have_betas), pools, n_iterations, power, pseudo_count, alpha, ambient), pools,
+                         {logits_out, probs_out, best_option, best_prob, doublet_mass}, plan));
+    const dmx::AmbientScoring scoring{lo, hi, alpha, ambient, ambient_out, "dmx_em_ambient_soup"};
+    DMX_TRY(begin_dense_pools(c));
+    DMX_TRY(begin_em_additions(c));
+    dmx::AmbientRunPtr run;
+    DMX_TRY(dmx::prepare_estep_ambient(c, plan, scoring, true, run));
+    dmx::SoupRunPtr soup;
+    DMX_TRY(dmx::prepare_soup_run(c, pseudo_count, lo, hi, soup));
+    DMX_TRY(run_dense_em(
+        c, n_iterations, lo, hi, addition_out, [&] { return dmx::launch_estep_ambient_pass(c, *run, lp::POWER); },
+        [&](int) {
+            DMX_TRY(dmx::run_mstep_soup(c, *soup, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)));
+            DMX_TRY(dmx::run_mstep_ambient(c, power, dmx::ambient_run_alpha(*run), dmx::ambient_run_soup(*run)));
+            return dmx::ambient_run_replace_soup(c, *run, dmx::soup_run_profile(*soup));
+        }));
+    DMX_TRY(dmx::read_back_soup_counts(c, *soup, counts_out));
     return dmx::read_back_estep_ambient(c, *run);
 }
 

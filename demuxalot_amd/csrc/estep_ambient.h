@@ -62,6 +62,9 @@ int read_back_estep_ambient(dmx_ctx *c, AmbientRun &run);
 // what the M-step under the same fractions reads of a run (mstep_ambient.hip): device pointers, [B] and [V + 1]
 const float *ambient_run_alpha(const AmbientRun &run);
 const float *ambient_run_soup(const AmbientRun &run);
+// A call that learns the profile (mstep_soup.hip) replaces the run's: d_profile [V + 1], device memory, copied on the stream behind
+// whatever still reads the old one; the next pass rebuilds the stream of the soup's terms.  ambient_out then gets the new profile.
+int ambient_run_replace_soup(dmx_ctx *c, AmbientRun &run, const float *d_profile);
 // the three in a row without the dense form: dmx_estep_ambient
 int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring);
 

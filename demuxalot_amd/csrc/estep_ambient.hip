@@ -197,7 +197,7 @@ int prepare_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScorin
 }
 
 // The soup's terms depend on the fractions, the profile and the records, not on the table: the first pass of a run builds the stream
-// (inside its span of the DMX_T_ESTEP slot), the later ones of an EM call find it.
+// (inside its span of the DMX_T_ESTEP slot), the later ones of an EM call find it - until ambient_run_replace_soup changes the profile.
 int launch_estep_ambient_pass(dmx_ctx *c, AmbientRun &r, float power)
 {
     using namespace dmx::host;
@@ -232,6 +232,13 @@ int read_back_estep_ambient(dmx_ctx *c, AmbientRun &r)
 
 const float *ambient_run_alpha(const AmbientRun &run) { return run.d_alpha; }
 const float *ambient_run_soup(const AmbientRun &run) { return run.d_soup; }
+
+int ambient_run_replace_soup(dmx_ctx *c, AmbientRun &r, const float *d_profile)
+{
+    HIP_TRY(hipMemcpyAsync(r.d_soup, d_profile, sizeof(float) * ((size_t)c->V + 1), hipMemcpyDeviceToDevice, c->stream));
+    r.terms_done = false;
+    return 0;
+}
 
 int run_estep_ambient(dmx_ctx *c, const PoolsPlan &plan, const AmbientScoring &scoring)
 {

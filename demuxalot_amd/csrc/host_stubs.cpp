@@ -23,6 +23,7 @@
 #include "estep_pools.h"
 #include "mstep_doublet_shares.h"
 #include "mstep_doublets.h"
+#include "mstep_soup.h"
 
 // ------------------------------------------------------------------------------------
 // HIP runtime
@@ -185,6 +186,18 @@ const float *ambient_run_alpha(const AmbientRun &) { return nullptr; }
 const float *ambient_run_soup(const AmbientRun &) { return nullptr; }
 int run_mstep_ambient(dmx_ctx *, float, const float *, const float *) { return 0; }  // (validated by dmx_mstep_ambient / dmx_em_ambient; nothing is written)
 int run_mstep_ambient_from_host(dmx_ctx *, float, const float *, const float *, float, float) { return 0; }
+int ambient_run_replace_soup(dmx_ctx *, AmbientRun &, const float *) { return 0; }
+struct SoupRun {};
+void SoupRunDeleter::operator()(SoupRun *run) const { delete run; }
+int prepare_soup_run(dmx_ctx *, float, float, float, SoupRunPtr &run)
+{
+    run.reset(new SoupRun);
+    return 0;
+}
+int run_mstep_soup(dmx_ctx *, SoupRun &, const float *, const float *) { return 0; }  // (validated by dmx_em_ambient_soup; nothing is written)
+const float *soup_run_profile(const SoupRun &) { return nullptr; }
+int read_back_soup_counts(dmx_ctx *, SoupRun &, float *) { return 0; }
+int run_mstep_soup_from_host(dmx_ctx *, const float *, const float *, float, float, float, float *, float *) { return 0; }  // (validated by dmx_mstep_soup)
 struct DoubletRun {};
 void DoubletRunDeleter::operator()(DoubletRun *run) const { delete run; }
 int prepare_doublet_run(dmx_ctx *, const PoolsRun &, long long, DoubletRunPtr &run)

@@ -1,5 +1,5 @@
 // mstep_weighted.h -- the frame of the M-steps whose per-call weight reads the table of the iteration (mstep_weighted.hip; the forms:
-// mstep_ambient.h, mstep_doublets.h, mstep_doublet_shares.h): the argument block they share, the host steps around their launches, and the
+// mstep_ambient.h, mstep_doublets.h, mstep_doublet_shares.h, mstep_soup.h): the argument block they share, the host steps around their launches, and the
 // combining pass of the variants that span several work items.  What a form's weight reads comes behind this block in the form's own.
 #pragma once
 #include <functional>
@@ -25,8 +25,9 @@ struct WeightedMstepArgs {
 // The context's half of such an M-step: the codes are rebuilt first when they were written above live_floor_float64(power) (a
 // fixed-point M-step may have asked the E-step for a higher floor), then `a` is filled from the context's posteriors (d_post, singlet
 // columns; d_nz), records, work items and table (d_prob), with d_add as the result; the context's flags:
-// ctx_state.h addition_written_by_other_form.
-int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a);
+// ctx_state.h addition_written_by_other_form.  out (mstep_soup.hip): [V, G] of the caller's that takes the sums in
+// place of d_add - the addition and its flags then stay as they are.
+int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a, float *out = nullptr);
 
 // k_mcombine_weighted over [V, G] behind the zeroing of the two counters; the form's redo over the queue follows it
 hipError_t launch_mcombine_weighted(hipStream_t st, const WeightedMstepArgs &a);

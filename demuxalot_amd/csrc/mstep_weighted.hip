@@ -53,7 +53,7 @@ hipError_t launch_mcombine_weighted(hipStream_t st, const WeightedMstepArgs &a)
     return hipGetLastError();
 }
 
-int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a)
+int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a, float *out)
 {
     // the codes and the bitmap at the floor of a float64 sum (a fixed-point M-step may have asked the E-step for a higher one)
     const float floor = live_floor_float64(power);
@@ -73,7 +73,7 @@ int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a)
     a.m.partial = c->d_partial.p;
     a.m.item_variant = c->d_item_variant.p;
     a.m.item_ptr = c->d_item_ptr.p;
-    a.m.out32 = c->d_add.p;
+    a.m.out32 = out ? out : c->d_add.p;
     a.m.n_items = c->n_items;
     a.m.G = c->G;
     a.m.square = (power == 2.0f);
@@ -83,7 +83,7 @@ int begin_weighted_mstep(dmx_ctx *c, float power, WeightedMstepArgs &a)
     a.V = c->V;
     a.redo = c->d_redo.p;
     a.n_redo = c->d_n_redo.p;
-    c->addition_written_by_other_form();
+    if (!out) c->addition_written_by_other_form();
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // mstep_weighted_device.h -- device inlines of the M-steps with a table-dependent weight (mstep_ambient.hip, mstep_doublets.hip,
-// mstep_doublet_shares.hip): the broadcast of a lane's value, the power of a contribution, the ends of a walk - which (work item, word) a
+// mstep_doublet_shares.hip, mstep_soup.hip): the broadcast of a lane's value, the power of a contribution, the ends of a walk - which (work item, word) a
 // wavefront has, where its sums go - and the redo of the queued sums around a form's weight object.  The walks' chunk loops are the forms'.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1210,7 +1210,7 @@ class Demultiplexer:
         r = own / (own + ambient[v] alpha_b) with own = genotype_prob[v, g] (1 - alpha_b) - at alpha = 0.4 four calls in ten come from
         the soup and would pull the donor's betas towards the population mean.  With every fraction 0 the result is
         learn_genotypes_in_pools' (exact mode) bit for bit.  The fractions and the soup's profile are fixed for the call (alternate
-        estimate_ambient and this call to refine them).  The whole loop runs on the GPU (dmx_em_ambient); its sums are float64 in the
+        estimate_ambient and this call to refine the fractions; learn_genotypes_and_ambient learns the profile along with the genotypes).  The whole loop runs on the GPU (dmx_em_ambient); its sums are float64 in the
         reference's order whatever DEMUXALOT_AMD_ESTEP says.
         :param ambient_fractions: Series or mapping barcode -> alpha in [0, 1] (AmbientEstimate.fractions() gives one); a barcode
             that is missing, None or NaN learns with 0
@@ -1266,6 +1266,117 @@ class Demultiplexer:
                     'ambient': ambient,
                 }
                 genotype_addition = ctx.mstep_ambient(alpha, Demultiplexer.contribution_power, p_genotype_clip, ambient=ambient)
+
+    @staticmethod
+    def learn_ambient_profile(chromosome2compressed_snp_calls,
+                              genotypes,
+                              barcode_handler,
+                              ambient_fractions,
+                              ambient=None,
+                              n_iterations=3,
+                              pseudo_count=1.,
+                              p_genotype_clip=0.01,
+                              doublet_prior=0.,
+                              barcode2pool=None,
+                              pool2donors=None) -> np.ndarray:
+        """(not in the reference) The soup's allele profile learnt from the calls, with the genotypes fixed: n_iterations of
+        predict_posteriors_with_ambient's E-step (resident) and the soup M-step behind it - every call counts for the soup with
+        the probability that it came from there and not from its donor, s = amb / (own + amb), amb = ambient[v] alpha_b,
+        own = genotype_prob[v, g] (1 - alpha_b); per variant the posterior-weighted sum of s gives the soup's expected calls, and
+        the new profile is their share within each SNP (one pseudo_count per variant, clipped as the genotype table is).  The derived
+        profile (ambient=None: every call of a SNP counted) is the soup only when the soup is the droplets' average; a soup
+        dominated by one lysed sample is pulled towards the population mean there, and this call pulls it back.
+        :param ambient_fractions: Series or mapping barcode -> alpha in [0, 1] (AmbientEstimate.fractions() gives one); a barcode
+            that is missing, None or NaN counts with 0 - and so not at all
+        :param ambient: float32[n_variants], the profile to start from, or None: derived from the calls as estimate_ambient does
+        :param barcode2pool, pool2donors: as predict_posteriors_in_pools takes them (both or neither)
+        :return: float32[n_variants], the profile after the last update.
+        ValueError: a fraction outside [0, 1], a barcode that is not the handler's, more than 1024 options without pools."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        assert np.isfinite(pseudo_count) and pseudo_count > 0, 'pseudo_count should be finite and positive'
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'learn_ambient_profile')
+        with shared_context_lock:
+            ctx = get_context()
+            _set_up_table(ctx, chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, p_genotype_clip)
+            for _iteration in range(n_iterations):
+                out = ctx.estep_ambient(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, alpha, p_genotype_clip,
+                                        ambient=ambient, fetch_logits=False, fetch_probs=False, resident=True)
+                ambient, _counts = ctx.mstep_soup(alpha, pseudo_count, p_genotype_clip, ambient=out['ambient'])
+        return ambient
+
+    @staticmethod
+    def learn_genotypes_and_ambient(chromosome2compressed_snp_calls,
+                                    genotypes,
+                                    barcode_handler,
+                                    ambient_fractions,
+                                    ambient=None,
+                                    n_iterations=5,
+                                    pseudo_count=1.,
+                                    p_genotype_clip=0.01,
+                                    doublet_prior=0.,
+                                    barcode2pool=None,
+                                    pool2donors=None):
+        """(not in the reference) learn_genotypes_with_ambient with the soup's profile learnt along with the genotypes: behind every
+        E-step but the last, learn_ambient_profile's soup M-step and the weighted genotype M-step, both with the profile that
+        E-step read; the new profile takes effect in the next iteration.  The fractions stay fixed (estimate_ambient gives them).
+        The whole loop runs on the GPU (dmx_em_ambient_soup).
+        :param ambient: float32[n_variants], the first iteration's profile, or None: derived from the calls
+        :param pseudo_count: added to every variant's expected soup calls before their share within the SNP is taken
+        :return: (learnt genotypes, the posteriors of the last iteration as learn_genotypes_with_ambient returns them, float32
+            [n_variants]: the profile the last E-step read).
+        ValueError: as learn_genotypes_with_ambient."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        assert np.isfinite(pseudo_count) and pseudo_count > 0, 'pseudo_count should be finite and positive'
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'learn_genotypes_and_ambient')
+        with shared_context_lock:
+            ctx, _betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True,
+                                          fetch_betas=False)
+            out = ctx.em_ambient_soup(n_iterations, p_genotype_clip, setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0,
+                                      setup.pair_penalty, alpha, ambient=ambient, pseudo_count=pseudo_count,
+                                      contribution_power=Demultiplexer.contribution_power, fetch_logits=setup.pooled, fetch_addition=False)
+            learnt_betas = ctx.get_learnt_betas()  # genotypes.get_betas() + addition (demux.py:65), added on the device
+        return genotypes._with_betas(learnt_betas, _take=True), _framed_posteriors(setup, barcode_handler, out, None), out['ambient']
+
+    @staticmethod
+    def staged_genotype_learning_and_ambient(chromosome2compressed_snp_calls,
+                                             genotypes,
+                                             barcode_handler,
+                                             ambient_fractions,
+                                             ambient=None,
+                                             n_iterations=5,
+                                             pseudo_count=1.,
+                                             p_genotype_clip=0.01,
+                                             doublet_prior=0.,
+                                             barcode2pool=None,
+                                             pool2donors=None):
+        """Generator over the iterations of learn_genotypes_and_ambient: yields what staged_genotype_learning_with_ambient yields -
+        (posteriors, debug dict with 'genotype_prior', 'genotype_addition', 'ambient') -, 'ambient' the profile that the
+        iteration's E-step read.  The EM state lives on the GPU between yields, in a device context private to this generator."""
+        assert n_iterations >= 1, 'n_iterations should be positive'
+        assert np.isfinite(pseudo_count) and pseudo_count > 0, 'pseudo_count should be finite and positive'
+        alpha, setup = Demultiplexer._ambient_setup(genotypes, barcode_handler, ambient_fractions, doublet_prior, barcode2pool, pool2donors,
+                                                    'staged_genotype_learning_and_ambient')
+
+        with _generator_context() as ctx:
+            _ctx, prior_betas = _pack_on_device(chromosome2compressed_snp_calls, genotypes, barcode_handler.n_barcodes, True, ctx=ctx)
+            genotype_addition = np.zeros_like(prior_betas)
+            ctx.set_addition(None)
+            for _iteration in range(n_iterations):
+                ctx.probs_from_betas(p_genotype_clip, fetch=False)
+                out = ctx.estep_ambient(setup.pool_columns, setup.pool_of_barcode, doublet_prior != 0, setup.pair_penalty, alpha, p_genotype_clip,
+                                        ambient=ambient, fetch_logits=setup.pooled, resident=True)
+                read = out['ambient']
+                yield _framed_posteriors(setup, barcode_handler, out, None), {
+                    'genotype_prior': prior_betas,
+                    'genotype_addition': genotype_addition,
+                    'ambient': read,
+                }
+                if _iteration + 1 == n_iterations:
+                    break  # (the M-steps after the last yield are dead)
+                ambient, _counts = ctx.mstep_soup(alpha, pseudo_count, p_genotype_clip, ambient=read)
+                genotype_addition = ctx.mstep_ambient(alpha, Demultiplexer.contribution_power, p_genotype_clip, ambient=read)
 
     @staticmethod
     def _doublet_learning_setup(genotypes, barcode_handler, doublet_prior, min_pair_posterior, barcode2pool, pool2donors, who):

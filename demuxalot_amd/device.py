@@ -802,6 +802,34 @@ class DeviceContext:
                                  tail=lambda out: (ptr(out['addition']), ptr(out['ambient'])), fetch_addition=bool(fetch_addition),
                                  ambient=True, dense=True)
 
+    def mstep_soup(self, alpha, pseudo_count=1., p_genotype_clip=0.01, ambient=None):
+        """The M-step of the soup's allele profile (include/demux_hip_debug.h: dmx_mstep_soup): every call counts for the soup with
+        the probability that it came from there, s = amb / (own + amb), amb = ambient[v] alpha[b], own = genotype_prob[v, g]
+        (1 - alpha[b]), on the resident posteriors and the table of the last P-step.  alpha: float32[B] in [0, 1], every barcode's is
+        read; ambient: float32[V] or None - the profile the posteriors were scored with (None: the derived one).  Returns
+        (ambient' float32[V], counts float32[V]): the new profile - the P-step's formula on counts + pseudo_count, clipped - and the
+        soup's expected calls per variant.  The context's addition, posteriors and table stay as they are."""
+        alpha, ambient = self._ambient_arguments(alpha, ambient)
+        lo, hi = self.clip_bounds(p_genotype_clip)
+        profile, counts = np.empty(self.V, np.float32), np.empty(self.V, np.float32)
+        check(self._lib.dmx_mstep_soup(self._h, ptr(alpha), ptr(ambient), float(pseudo_count), lo, hi, ptr(profile), ptr(counts)))
+        return profile, counts
+
+    def em_ambient_soup(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, alpha, ambient=None,
+                        pseudo_count=1., contribution_power=2., fetch_logits=True, fetch_probs=True, fetch_addition=True):
+        """em_ambient() with the soup's profile learnt (include/demux_hip_debug.h: dmx_em_ambient_soup): behind every E-step but the
+        last, mstep_soup() and mstep_ambient(), both with the profile that E-step read; the new profile takes effect in the next
+        iteration.  ambient: the first iteration's profile (None: the derived one).  Returns em_ambient()'s dict - 'ambient' is the
+        profile the LAST E-step read - with one more key, 'counts': float32[V], the totals that profile was formed from (zeros with
+        one iteration)."""
+        alpha, ambient = self._ambient_arguments(alpha, ambient)
+        return self._pooled_call(self._lib.dmx_em_ambient_soup, pools, pool_of_barcode, with_doublets, pair_penalty, fetch_logits, fetch_probs,
+                                 head=(int(n_iterations), *self.clip_bounds(p_genotype_clip)),
+                                 middle=(float(contribution_power), ptr(alpha), ptr(ambient), float(pseudo_count)),
+                                 tail=lambda out: (ptr(out['addition']), ptr(out['ambient']), ptr(out['counts'])),
+                                 fetch_addition=bool(fetch_addition), ambient=True, more=lambda _n: dict(counts=np.empty(self.V, np.float32)),
+                                 dense=True)
+
     def em_doublets(self, n_iterations, p_genotype_clip, pools, pool_of_barcode, with_doublets, pair_penalty, min_pair_posterior=1e-3,
                     contribution_power=2., fetch_logits=True, fetch_probs=True, fetch_addition=True):
         """n_iterations of P-step, dense pooled E-step and the M-step that also learns from doublet posteriors, on the device

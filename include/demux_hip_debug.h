@@ -758,6 +758,51 @@ int dmx_em_ambient(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_
                    float *addition_out /* nullable, float32[V, G] */, float *ambient_out /* nullable, [V] */);
 
 /* ------------------------------------------------------------------------- *
+ * Learning the soup's allele profile (product API; csrc/mstep_soup.hip): the third M-step of the ambient model.  The
+ * complement of the weight above, s = 1 - r in exact arithmetic, is the probability that a call came from the soup; summed per
+ * variant it gives the soup's expected allele counts.  For variant v, donor column g and the calls c of v in stored variant-major
+ * order, b = cb_c, in float32 without contraction:
+ *     amb = ambient[v] * alpha[b]
+ *     own = prob[v, g] * (1.0f - alpha[b])
+ *     mix = own + amb
+ *     s   = amb == 0 ? 0.0f : amb / mix                          IEEE float32 division, correctly rounded
+ *     t   = (dense[b, g] * keep_c) * s                           power 1: expected counts
+ *     count[v, g] = f32( sum over c of f64(t) )                  one float64 accumulator, in call order, over dense[b, g] != 0
+ *     total[v]    = f32( sum over g of f64(count[v, g]) )        one float64 accumulator, g ascending
+ *     beta[v]     = total[v] + pseudo_count
+ *     ambient'[v] = the P-step's formula on the one column beta, clipped to [lo, hi]   (as dmx_ambient_profile derives a profile)
+ * prob and ambient are the table and the profile the E-step of `dense` read.  alpha[b] == 0 gives s == 0 exactly: with every
+ * fraction 0 every count is +0 and ambient' is the pseudo-counts' uniform share within each SNP.  alpha[b] == 1 with
+ * ambient[v] != 0 gives s == 1 exactly.  Only the singlet columns are counted, with_doublets or not; a posterior is live when it is
+ * not 0.  One arithmetic, whatever dmx_set_estep_mode / dmx_set_exact_additions say.
+ *   dmx_mstep_soup   stateless: the step above on the context's resident posteriors and the table of the last P-step, with alpha
+ *               float32[B] (EVERY barcode's is read) and ambient float32[V] or NULL (derived, clipped to [lo, hi]).  ambient_out
+ *               (nullable, float32[V]) receives ambient', counts_out (nullable, float32[V]) total.  The counts live in scratch:
+ *               the context's addition, posteriors, table and dmx_get_learnt_betas are bit for bit what they were before the
+ *               call (the codes of the posteriors are rebuilt at floor 0 when they were written above it: additions that follow
+ *               keep their bits).  dmx_get_redo_count returns the sums this step redid in call order.
+ *   dmx_em_ambient_soup   dmx_em_ambient with the profile learnt.  Per iteration: the P-step; the dense E-step under the fractions
+ *               with the current profile (the soup's terms are rebuilt whenever the profile has changed); except after the last
+ *               E-step the step above and dmx_mstep_ambient's, both with the profile that E-step read.  The new profile takes
+ *               effect in the next iteration.  Outputs (each nullable): what dmx_em_ambient returns - ambient_out the profile of
+ *               the LAST E-step - and counts_out float32[V], the totals that profile was formed from (+0 with one iteration: no
+ *               step ran).  With the profile unchanged the genotype additions are dmx_em_ambient's bit for bit.
+ * Checked on the host before anything is uploaded or launched (csrc/soup_learning_plan.h).  DMX_ERR_INVALID: a pseudo_count that is
+ * not finite or not above 0, and everything dmx_mstep_ambient / dmx_em_ambient refuse, with their codes.  The walk is counted in
+ * DMX_T_MSTEP, the combining pass and the redo in DMX_T_MCOMBINE, the totals and the profile in DMX_T_PSTEP.
+ * ------------------------------------------------------------------------- */
+int dmx_mstep_soup(dmx_ctx *ctx, const float *alpha /* [B] */, const float *ambient /* nullable, [V] */, float pseudo_count, float lo, float hi,
+                   float *ambient_out /* nullable, [V] */, float *counts_out /* nullable, [V] */);
+int dmx_em_ambient_soup(dmx_ctx *ctx, int n_iterations, float lo, float hi, int with_doublets, int32_t n_pools,
+                        const int64_t *pool_start /* [n_pools+1] */, const int32_t *pool_donors, const float *pair_penalty /* [n_pools] */,
+                        const int32_t *pool_of_barcode /* [B], -1: none */, const int64_t *row_ptr /* [B+1] */, float power,
+                        const float *alpha /* [B] */, const float *ambient /* nullable, [V] */, float pseudo_count,
+                        float *logits_out, float *probs_out,          /* nullable, float32[row_ptr[B]] */
+                        int32_t *best_option, float *best_prob, double *doublet_mass /* nullable, [B] */,
+                        float *addition_out /* nullable, float32[V, G] */, float *ambient_out /* nullable, [V] */,
+                        float *counts_out /* nullable, [V] */);
+
+/* ------------------------------------------------------------------------- *
  * Learning from doublet posteriors (product API; csrc/mstep_doublets.hip).  dmx_em_pools' loop with one change per
  * iteration: the M-step credits each donor of a pair option of the barcode's row with its share of every call.  The E-step is
  * dmx_em_pools' dense pooled pass; it leaves the compact rows post[row_ptr[b] ...] in pool-local option order (singlets, then the
